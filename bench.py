@@ -3,6 +3,7 @@
 (BASELINE.json configs[1]: batch 256 synthetic bf16 tiles per GPU, random-init weights).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py ... --dump-outputs DIR            (also writes what the last timed step returned: DIR/features.npy, float32)
     python bench.py --gpus N ...                      (starts the N ranks itself: re-executes under torch.distributed.run, one rank per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...        (the same, launched from outside)
 
@@ -131,6 +132,28 @@ def lib_sha16() -> str:
         return hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()[:16]
     except OSError:
         return "unknown"
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """Write each [rows, ...] tensor as out_dir/<name>.npy in float32.  Past DUMP_MAX_BYTES in all, every array keeps the same fixed, seeded
+    sample of its rows, and out_dir/<name>_rows.npy (float64) names the rows kept.  Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if total > DUMP_MAX_BYTES:
+            keep = max(1, int(a.shape[0] * DUMP_MAX_BYTES // total))
+            rows = torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = a[rows]
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.numpy().astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.numpy())
+        written[name] = list(a.shape)
+    return written
 
 
 def time_gpu(fn, dev, reps: int):
@@ -532,10 +555,15 @@ def main():
     ap.add_argument("--budget", default=None, choices=["ladder", "measured"], help="re-run KEEPModel.calibrate with this budget after loading")
     ap.add_argument("--plan", default=None, help="run this per-block plan instead of the calibrated one: the 'attn:<digits> mlp:<digits>' string a bench line "
                                                  "reports (profiling runs: KEEP_CALIBRATE=0 keeps the calibration's kernels out of the trace)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32): rank 0's features "
+                         "[batch, 768] and, over RCCL, the gathered [gpus x batch, 768]")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: keep_amd has no CPU execution path")
     launched = "WORLD_SIZE" in os.environ            # under torch.distributed.run (the documented N > 1 launch) the ranks already exist
@@ -588,11 +616,13 @@ def main():
     # keep_amd.distributed.StepExchange: double-buffered, so the RCCL all-gather of step i overlaps the encode of step i+1 (the same
     # class runs under gloo at world sizes 2 and 3 in tests/test_distributed_cpu.py)
     exchange = StepExchange(B, shape.projection_dim, dev) if use_dist else None
+    last = {}
 
     def step():
         f = model.encode_image(tiles)
         if use_dist:
-            exchange.submit(f)
+            last["gathered"] = exchange.buffers[exchange.submit(f)]
+        last["features"] = f
         return f
 
     def timed(n_steps, own=None):
@@ -633,6 +663,9 @@ def main():
     in_region = {t: model.profile_read(t) for t in DOMINANT_TAGS}
     model.profile_disable()
     log(f"timed region done: {elapsed / args.steps * 1e3:.2f} ms/step")
+    if args.dump_outputs and rank == 0:
+        # the timed region ended in a fence / device synchronisation: both arrays are final, and no later step has run yet
+        log(f"outputs of the last timed step -> {args.dump_outputs}: {dump_outputs(args.dump_outputs, last)}")
     per_rank = exchange_cost = None
     if use_dist:
         t = torch.tensor([own_elapsed[0]], device=dev, dtype=torch.float64)
@@ -807,7 +840,11 @@ def main():
             "roofline": roofline,
         }
         if model.calibration is not None:
-            line["calibration"] = model.calibration
+            # the walk over candidate plans and the per-block variance shares are 16 KB of the record and grow with the walk: they go to the
+            # log, so that the result line stays small enough for line-oriented readers
+            log(f"calibration record: {json.dumps(model.calibration)}")
+            line["calibration"] = {k: v for k, v in model.calibration.items() if k not in ("tried", "variance_shares")}
+            line["calibration"]["plans_tried"] = len(model.calibration["tried"])
         if sustained is not None:
             line["sustained"] = sustained
         if parity is not None:

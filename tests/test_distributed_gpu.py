@@ -9,6 +9,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -73,11 +74,12 @@ def test_rank0_plan_adoption_through_rccl(nccl_world1):
     assert len(assert_same_setting([m.get_option("precision")] + [float(v) for am in m.get_plan() for v in am], "plan", device=dev)) == 1
 
 
-def test_bench_distributed_leg_runs_on_nccl():
+def test_bench_distributed_leg_runs_on_nccl(tmp_path):
     env = dict(os.environ, KEEP_BENCH_FORCE_DIST="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))      # bench.py sets the RCCL environment itself (keep_amd.distributed.rccl_env)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64",
-                        "--no-cpu-baseline", "--no-breakdown", "--no-configs"], capture_output=True, text=True, env=env, timeout=600)
+                        "--no-cpu-baseline", "--no-breakdown", "--no-configs", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])          # the JSON line is the last thing on stdout, after RCCL's banner
     assert line["n_gpus"] == 1 and line["value"] > 0
@@ -86,6 +88,9 @@ def test_bench_distributed_leg_runs_on_nccl():
     assert len(line["per_rank_tiles_per_s"]) == 1 and line["per_rank_tiles_per_s"][0] > 0
     assert set(line["exchange"]) >= {"ms_per_step_with_exchange", "ms_per_step_encode_only", "exposed_ms_per_step", "bytes_gathered_per_step"}
     assert line["roofline"]["in_timed_region_two_lane"]["launches"] > 0
+    # --dump-outputs over RCCL: rank 0's features and the all-gathered matrix of the last timed step (one rank: the same rows)
+    feats, gathered = np.load(tmp_path / "features.npy"), np.load(tmp_path / "gathered.npy")
+    assert feats.shape == gathered.shape == (64, 768) and np.array_equal(feats, gathered)
 
 
 def _rccl_worker(rank, world, port, n_tiles, q):
