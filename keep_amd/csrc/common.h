@@ -115,13 +115,9 @@ struct GemmParams {
     const float* ls;                      // [N]   (EPI_RESID_LS)
     const float* pos;                     // [197][N] (EPI_PATCH)
     float* resid;                         // fp32 [M'][N]
-    float* resid_copy; int64_t resid_copy_ld;   // nullable (small-M reduce, EPI_RESID_LS only): row m of the updated residual is ALSO stored at resid_copy + m * resid_copy_ld
-                                          // (the CLS-row chain writes its rows back into the token stream from its last reduce: no scatter launch)
     float* out_f32;                       // EPI_RESID_F32
     f16* out_hi; f16* out_lo;             // fp16 outputs (lo optional)
     int out_kt;                           // > 0: fp16 output in blk layout with KT = out_kt (= N/32); 0: row-major [M][N]
-    int out_ld, out_col0;                 // row-major fp16 output (EPI_F16, 256x256 kernel only): leading dimension (0 = N) and first column of this GEMM's N columns
-                                          // inside a wider buffer (the K | V part of the last block's qkv)
     int patches_per_img;                  // EPI_PATCH: 196
     // optional LayerNorm of the updated row, fused into the split-K reduce (EPI_RESID_LS / EPI_RESID_F32, N <= 1024);
     // launch_gemm_f16 reports through its return value whether it was applied (bit 0) -- the big kernel never does
@@ -138,7 +134,6 @@ struct GemmParams {
 };
 
 int launch_gemm_f16(const GemmParams& p, int epi, hipStream_t s);             // blk-layout operands (product path); returns GEMM_DID_LN or 0
-constexpr int GEMM_NO_RESID_COPY = 2;   // launch_gemm_f16: GemmParams.resid_copy was NOT honoured (the call took a kernel without that epilogue: the caller scatters the rows)
 constexpr int GEMM_DID_LN = 1;
 // split-K scratch: 30 MiB cover every small-M shape (M <= SKINNY_MAX_M: <= 768 + 1024 partial tiles of 32 x 128 fp32);
 // the mid-size path (256x256 tiles x K slices when a GEMM has fewer tiles than CUs) needs <= 448 tiles of 256 KiB
@@ -155,8 +150,6 @@ struct AttnParams {
     const int64_t* mask;                  // [batch][ntok] (1 = attend) or nullptr
     int batch, ntok, heads;               // head_dim fixed at 64
     int q_rows;                           // > 0: only the first q_rows query rows of every image are computed (CLS-only last block)
-    const f16* q_hi; int q_ld;            // q_rows == 1 only, nullable: the ONE query row of image b at q_hi + b * q_ld (head-major, like the q part of a qkv row) instead of
-                                          // qkv_hi -- the last block computes Q for its CLS rows only
     int split;                            // 0/1
     // nullable (single-pass mode only): the attention output of query row 0 (the CLS row) of image b, from the fp32 accumulators, ALSO as hi + lo
     // planes into row b of a compact [batch][D] operand in the layout of `out_*` (KEEP_ATTN_PROJ_CLS: the CLS rows' proj runs again as a split product)

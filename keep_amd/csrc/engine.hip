@@ -156,43 +156,21 @@ struct keep_handle {
         cal.clear(); bias_ready = false;
     }
     int patch_split = 1;         // 0: the patch-embedding GEMM as one fp16 pass (experiments; measured in profiles/r05_patch_embed_plain.txt)
-    int cls_qkv = 0;             // 1: last ViT block (with cls_tail): the q part of the qkv GEMM for the CLS rows only (exact).  Measured (round 5, tools/ab_options.py):
-                                 // vit.qkv -0.09 ms per step on one stream, +0.02 ms of small launches, 6041 vs 6044 tiles/s end to end with two lanes: below the
-                                 // 0.3 % it would have to return -- off by default
     // 2128 (default): the plain proj GEMMs of the image tower on the 256x128 / 4-wave / two-workgroups-per-CU kernel (GemmParams.impl_hint) -- proj is the one GEMM whose
     // tile is 40 % fp32 residual read-modify-write epilogue, and with two workgroups on a CU one's epilogue runs under the other's K loop: -8.5 % on the proj launches,
     // +0.57 % end to end in a six-round rotated A/B on the round-5 plan (profiles/r05_ab_two_workgroups_per_cu.txt; qkv / fc1 / fc2 on the same kernel lose 1.6-4.3 %:
     // 1.5 x the operand bytes per FLOP).  0: the persistent 256x256 kernel.  Bit-identical results either way (same K order per output).
     int proj_impl = 2128;
-    int impl2128_mask = 0;       // experiments: the same kernel for the plain qkv (1) / fc1 (4) / fc2 (8) launches (2 = proj, same as proj_impl)
     // hipGraph replay of launch-bound calls (one prompt / one tile: ~100 dependent kernels of a few us each)
     struct GraphSlot { hipGraphExec_t exec; unsigned long long epoch; char* arena; };
     std::map<std::string, GraphSlot> graphs;
     int use_graphs = 1;
     unsigned long long opt_epoch = 0;   // bumped by keep_set_option / keep_finalize_weights: graphs captured under an older epoch are dropped
     hipStream_t cap_stream = nullptr;
-    int dbg_calls = 0;
-    int dbg_skip_ln = 0;         // diagnostics (takes effect from the 4th encode_image call, so the buffers hold real data): skip the ViT block LayerNorm launches (results wrong; bounds what fusing them away could gain)
     int lane_min_tiles = 16;     // a lane is only opened for at least this many tiles (32 tiles: 7.09 -> 6.50 ms as 2 x 16; 16 tiles as 2 x 8 loses)
-    int lane_skew = 0;           // >0: lane l starts after lane l-1 finished stage `lane_skew` of block 0 (1 qkv .. 5 fc2)
-    hipEvent_t ev_skew[4] = {nullptr, nullptr, nullptr, nullptr};
-    int lane0_permille = 500;    // share of a 2-lane chunk given to lane 0 (experiments with workgroup-round packing)
     int n_streams = 2;           // concurrent sub-batches inside keep_encode_image (1 = everything on the caller's stream)
     hipStream_t aux[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
-    // The CLS-row chain (KEEP_MLP_CLS, with KEEP_ATTN_PROJ_CLS in front of it) of a lane on a stream of its own: 7-8 small DEPENDENT launches per block.  In
-    // the lane's own stream each of them queues behind whatever persistent GEMM of the other lane holds the CUs, the lane advances one small kernel per big
-    // kernel of its neighbour, and the two lanes end up taking turns -- with the chain in all 24 blocks the two-lane step was the single-stream sum (round 6).
-    // Forked after the residual gather, joined before the next block: the chain runs under the lane's own LayerNorm-2 / fc1 / fc2.
-    // MEASURED NEGATIVE, off: 6 334 against 7 086 tiles/s on one box (tools/ab_options.py --calibrate --arm base --arm cls_side_stream=0, three rotated rounds,
-    // profiles/r06_ab_cls_side_stream.txt): the three cross-stream waits per block and lane (144 per step) cost more than the chain's exposure -- a
-    // cross-queue dependency is a barrier packet the next persistent GEMM sits behind.  The premise was wrong too: the kernel times of a step add up to
-    // 37.8 ms on one stream and the two-lane step takes 37.7 -- the lanes already pack the GPU back to back; what the chains cost is their own latency.
-    int cls_side_stream = 0;
-    int cls_chain_early = 1;     // 2: a chain that starts with the CLS-row proj is issued even before the plain proj; 1: the chain (own stream) is issued before the block's LayerNorm-2 and scattered behind its fc2; 0: all of it behind fc2, last reduce writes the rows back
-    hipStream_t aux_cls[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_cls[4][3] = {};
-    float* cls_splitk[4] = {nullptr, nullptr, nullptr, nullptr};     // the chain's own K-slice scratch (the lane's is in use by its main stream)
 
     // workspace arena
     char* arena = nullptr;
@@ -462,9 +440,7 @@ GemmParams gemm_params(const keep_handle* h, const f16* a_hi, const f16* a_lo, c
 // attention staging, GEMM epilogues, partial last rounds of workgroups) overlap the other lane's MFMA phases.
 struct VitLane {
     const void* pixels; int pix_dtype; int Bc; float* out; hipStream_t s; VitWs ws; bool cls_compact = false;
-    hipEvent_t skew_ev = nullptr; int skew_stage = 0;     // recorded after stage `skew_stage` of block 0 (lane_skew)
     bool xn_ready = false;                                // the previous block's fc2 already wrote this block's LayerNorm-1 output
-    hipStream_t cs = nullptr; hipEvent_t ce[3] = {nullptr, nullptr, nullptr}; float* cs_splitk = nullptr;      // side stream of the CLS-row chain (nullable)
     bool c_resid_live = false;                            // ws.c_resid holds the CLS rows of ws.resid as they are NOW (left there by the previous block's CLS-row chain): no gather
 };
 
@@ -493,7 +469,6 @@ int vit_begin(keep_handle* h, VitLane& L) {
 int vit_layer(keep_handle* h, VitLane& L, int i) {
     const int D = h->vit_D, Bc = L.Bc, M = Bc * 197;
     hipStream_t s = L.s; VitWs& ws = L.ws;
-    auto mark = [&](int stage) { if (i == 0 && L.skew_ev && L.skew_stage == stage) (void)hipEventRecord(L.skew_ev, s); };
     const VitBlock& b = h->vblocks[i];
     // mean-input compensation: a PLAIN launch of site k uses the bias with W_lo a_mean folded in; while calibrating, every site's input is summed
     auto site_bias = [&](int site, const float* orig, bool plain) {
@@ -516,11 +491,6 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
     const bool mlp_plain = mlp == KEEP_MLP_PLAIN || mlp_cls;
     // KEEP_ATTN_PROJ_CLS: every row plain; the attention kernel also writes the CLS rows' output hi + lo (compact), and their proj runs again as a split product
     const bool proj_cls = !sp && !cls_only && (h->plan_attn(i) == KEEP_ATTN_PROJ_CLS || h->plan_attn(i) == KEEP_ATTN_COMPQKV_PROJ_CLS) && i >= h->strict_blocks;
-#ifdef KEEP_DIAGNOSTICS
-    const bool skip_ln = h->dbg_skip_ln == 1 && h->dbg_calls > 3;
-#else
-    const bool skip_ln = false;
-#endif
     // qkv of a split-attention block in the compensated mode: fp16 pass + MX-fp4 correction terms instead of three fp16 passes (lanes
     // large enough for the 256x256 kernel; LayerNorm-1 then writes the fp4 planes of its output instead of the lo plane)
     const bool qkv_q = h->vit_qkv_comp(i, Bc) && b.qkv->q && ws.xn_q && !L.xn_ready;
@@ -529,36 +499,21 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
     ln.x = ws.resid; ln.x_stride = D; ln.rows = M; ln.D = D; ln.eps = 1e-6f;
     ln.out_hi = ws.xn_hi; ln.out_lo = (sp && !qkv_q) ? ws.xn_lo : nullptr; ln.out_kt = D / 32;
     ln.out_q = qkv_q ? ws.xn_q : nullptr; ln.out_sc = qkv_q ? ws.xn_sc : nullptr;
-    if (!L.xn_ready && !skip_ln) {
+    if (!L.xn_ready) {
         Scope sc(h, T_VIT_LN, s);
         ln.gamma = b.n1w; ln.beta = b.n1b;
         if (launch_layernorm(ln, s)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %d", D);
     }
     L.xn_ready = false;
-    // Last block, single-pass lanes: only the CLS row of every image is a query, so the q third of the qkv GEMM is computed for those Bc rows only
-    // (exact: the skipped rows' q is never read; the FLOPs it saves are not counted as done).  K and V still need every token.
-    const bool kv_only = cls_only && h->cls_qkv && !sp && !qkv_q && Bc >= 32 && !L.xn_ready && D % 256 == 0;
     {
         const int tag = (sp || qkv_q) ? T_VIT_QKV_X : T_VIT_QKV;
         Scope sc(h, tag, s);
         capture(0, ws.xn_hi, M, D);
         GemmParams p = gemm_params(h, ws.xn_hi, ws.xn_lo, b.qkv, M, sp && !qkv_q, site_bias(0, b.qkv_b, !sp && !qkv_q));
-        if (!sp && !qkv_q && (h->impl2128_mask & 1)) p.impl_hint = 2128;
-        if (kv_only) {          // weight rows D .. 3D-1 (n-tiles D/256 ..), written into columns D .. 3D-1 of the token-major qkv buffer
-            p.N = 2 * D; p.w_hi += (int64_t)(D / 256) * (D / 32) * 8192; p.bias += D; p.out_ld = 3 * D; p.out_col0 = D;
-        }
         p.out_hi = ws.qkv_hi; p.out_lo = sp ? ws.qkv_lo : nullptr;
         if (qkv_q) { p.comp = 2; p.a_q = ws.xn_q; p.a_sc = ws.xn_sc; p.w_q = b.qkv->q; p.w_sc = b.qkv->sc; }
         if (run_gemm(h, tag, p, EPI_F16, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "qkv GEMM launch failed");
     }
-    if (kv_only) {              // q of the CLS rows: gather their LayerNorm-1 rows, [Bc, D] x W_q^T on the small-M kernel, into a compact buffer (free until the MLP)
-        Scope sc(h, T_VIT_TAIL, s);
-        launch_gather_rows_blk(ws.xn_hi, 197, ws.c_xn_hi, Bc, D, s);
-        GemmParams p = gemm_params(h, ws.c_xn_hi, nullptr, b.qkv, Bc, false, site_bias(0, b.qkv_b, true));
-        p.N = D; p.out_hi = ws.c_mlp_hi;
-        if (run_gemm(h, T_VIT_TAIL, p, EPI_F16, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "CLS-query GEMM launch failed");
-    }
-    mark(1);
     {
         Scope sc(h, sp ? T_VIT_ATTN_X : T_VIT_ATTN, s);
         AttnParams a{};
@@ -566,14 +521,9 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
         a.qkv_hi = ws.qkv_hi; a.qkv_lo = ws.qkv_lo; a.out_hi = ws.att_hi; a.out_lo = sp ? ws.att_lo : nullptr;
         a.mask = nullptr; a.batch = Bc; a.ntok = 197; a.heads = h->vit_heads; a.split = sp; a.scale = 0.125f; a.out_kt = D / 32;
         a.q_rows = cls_only ? 1 : 0;
-        if (kv_only) { a.q_hi = ws.c_mlp_hi; a.q_ld = D; }
         if (proj_cls) { a.cls_hi = ws.c_att_hi; a.cls_lo = ws.c_att_lo; }
-#ifdef KEEP_DIAGNOSTICS
-        if (!(h->dbg_skip_ln == 2 && h->dbg_calls > 3))      // dbg_skip_ln = 2: skip the attention launches instead (bounds what a faster attention could gain)
-#endif
         if (launch_attention(a, s)) return h->fail(KEEP_EUNSUPPORTED, "attention launch failed");
     }
-    mark(2);
     const int Mr = cls_only ? Bc : M;
     float* resid = cls_only ? ws.c_resid : ws.resid;
     const f16 *att_hi = ws.att_hi, *att_lo = ws.att_lo;
@@ -594,36 +544,29 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
         launch_gather_rows_f32(ws.resid, (int64_t)197 * D, ws.c_resid, Bc, D, s);
     }
     int did = 0;
-    auto main_proj = [&]() -> int {
+    {
         const int tag = cls_only ? T_VIT_TAIL : sp ? T_VIT_PROJ_X : T_VIT_PROJ;
         Scope sc(h, tag, s);
         capture(1, att_hi, Mr, D);
         GemmParams p = gemm_params(h, att_hi, att_lo, b.proj, Mr, sp, site_bias(1, b.proj_b, !sp));
-        p.ls = b.ls1; p.resid = resid; p.impl_hint = (h->impl2128_mask & 2) ? 2128 : h->proj_impl;
+        p.ls = b.ls1; p.resid = resid; p.impl_hint = h->proj_impl;
         if (!mlp_q) offer_ln(p, ln);                 // the fused LayerNorm of the small-M path does not write fp4 planes
         did = run_gemm(h, tag, p, EPI_RESID_LS, s, ws.splitk);
         if (did < 0) return h->fail(KEEP_EUNSUPPORTED, "proj GEMM launch failed");
-        return KEEP_OK;
-    };
-    // cls_chain_early = 2: a chain that starts with the CLS-row proj needs nothing of the plain proj (its residual is the one in FRONT of it): issued before it
-    const bool chain_first = proj_cls && mlp_cls && h->cls_chain_early == 2 && L.cs == nullptr;
-    if (!chain_first) { const int rcp = main_proj(); if (rcp) return rcp; }
-    mark(3);
-    bool cls_ln_done = false;   // LayerNorm-2 of the compact CLS rows already written (hi + lo) by the CLS-row proj's epilogue
-    // The CLS-row chain of this block (KEEP_ATTN_PROJ_CLS and / or KEEP_MLP_CLS) on the compact [Bc, D] rows.  Its stream: the lane's own -- then the whole chain is
-    // issued BEHIND the plain fc2, and its last reduce writes the rows straight back into the token stream -- or the lane's side stream ("cls_side_stream", off:
-    // measured negative), forked here and joined by a scatter behind the plain fc2.
-    const bool side = mlp_cls && L.cs != nullptr;
-    hipStream_t cs = side ? L.cs : s;
-    float* c_splitk = side ? L.cs_splitk : ws.splitk;
+    }
+    // The CLS-row chain of this block (KEEP_ATTN_PROJ_CLS and / or KEEP_MLP_CLS) on the compact [Bc, D] rows, in the lane's own stream: issued here, between the
+    // plain proj and LayerNorm-2, and scattered behind the plain fc2 (whose rows it replaces).  The small kernels then sit between the lane's two light kernels
+    // instead of between two persistent GEMMs: +1.5 % against the whole chain behind fc2.  On a side stream of its own the chain cost 11 %: a cross-queue
+    // dependency is a barrier packet the next persistent GEMM sits behind (both measured in round 6: tools/experiments/README.md).
     if (mlp_cls && !proj_cls) { // the CLS rows' residual as it enters the MLP, i.e. BEHIND this block's proj (a live compact copy is the residual in front of it): always gathered
         Scope sc(h, T_VIT_TAIL, s);
         launch_gather_rows_f32(ws.resid, (int64_t)197 * D, ws.c_resid, Bc, D, s);
     }
-    auto cls_proj = [&]() -> int {
+    bool cls_ln_done = false;   // LayerNorm-2 of the compact CLS rows already written (hi + lo) by the CLS-row proj's epilogue
+    if (proj_cls) {
         // [Bc, D] x W_proj^T as a split product on the small-M kernels: the CLS rows' attention output from the fp32 accumulators (hi + lo) against W hi + lo,
         // + LayerScale + the residual.  With KEEP_MLP_CLS in the same block the chain continues on the compact rows (its LayerNorm-2 is fused into this GEMM's reduce)
-        Scope sc(h, T_VIT_TAIL, cs);
+        Scope sc(h, T_VIT_TAIL, s);
         GemmParams r = gemm_params(h, ws.c_att_hi, ws.c_att_lo, b.proj, Bc, true, b.proj_b);
         r.ls = b.ls1; r.resid = ws.c_resid;
         LnParams cl{};
@@ -633,45 +576,29 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
             cl.out_hi = ws.c_xn_hi; cl.out_lo = ws.c_xn_lo; cl.out_kt = D / 32;
             offer_ln(r, cl);
         }
-        const int rc = run_gemm(h, T_VIT_TAIL, r, EPI_RESID_LS, cs, c_splitk);
+        const int rc = run_gemm(h, T_VIT_TAIL, r, EPI_RESID_LS, s, ws.splitk);
         if (rc < 0) return h->fail(KEEP_EUNSUPPORTED, "CLS-row proj GEMM launch failed");
         cls_ln_done = mlp_cls && (rc & GEMM_DID_LN);
-        return KEEP_OK;
-    };
-    auto cls_mlp = [&](bool write_back) -> int {
-        // LayerNorm-2 -> fc1 + GELU -> fc2 + LayerScale + residual as split products on the compact rows; `write_back`: the last reduce also stores the rows into the
-        // token stream (they replace what the plain fc2 wrote there: the caller orders this behind it).  0.5 % of the rows; the feature is pooled from them.
-        Scope sc(h, T_VIT_TAIL, cs);
+    }
+    if (mlp_cls) {
+        // LayerNorm-2 -> fc1 + GELU -> fc2 + LayerScale + residual as split products on the compact rows.  0.5 % of the rows; the feature is pooled from them.
+        Scope sc(h, T_VIT_TAIL, s);
         LnParams cl{};
         cl.tune = &h->tune;
         cl.x = ws.c_resid; cl.x_stride = D; cl.rows = Bc; cl.D = D; cl.eps = 1e-6f; cl.gamma = b.n2w; cl.beta = b.n2b;
         cl.out_hi = ws.c_xn_hi; cl.out_lo = ws.c_xn_lo; cl.out_kt = D / 32;
-        if (!cls_ln_done && launch_layernorm(cl, cs)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %d", D);
+        if (!cls_ln_done && launch_layernorm(cl, s)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %d", D);
         GemmParams p = gemm_params(h, ws.c_xn_hi, ws.c_xn_lo, b.fc1, Bc, true, b.fc1_b);
         p.out_hi = ws.c_mlp_hi; p.out_lo = ws.c_mlp_lo; p.out_kt = h->vit_F / 32;
-        if (run_gemm(h, T_VIT_TAIL, p, EPI_GELU_F16, cs, c_splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "CLS-row fc1 GEMM launch failed");
+        if (run_gemm(h, T_VIT_TAIL, p, EPI_GELU_F16, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "CLS-row fc1 GEMM launch failed");
         GemmParams r = gemm_params(h, ws.c_mlp_hi, ws.c_mlp_lo, b.fc2, Bc, true, b.fc2_b);
         r.ls = b.ls2; r.resid = ws.c_resid;
-        if (write_back) { r.resid_copy = ws.resid; r.resid_copy_ld = (int64_t)197 * D; }
-        const int rc = run_gemm(h, T_VIT_TAIL, r, EPI_RESID_LS, cs, c_splitk);
-        if (rc < 0) return h->fail(KEEP_EUNSUPPORTED, "CLS-row fc2 GEMM launch failed");
-        if (write_back && (rc & GEMM_NO_RESID_COPY)) launch_scatter_rows_f32(ws.c_resid, ws.resid, (int64_t)197 * D, Bc, D, cs);      // (kernel-selection experiments only)
-        return KEEP_OK;
-    };
-    const bool early = mlp_cls && !side && h->cls_chain_early;      // in the lane's own stream, but issued HERE (before LayerNorm-2; = 2: even before the plain proj) and scattered behind the plain fc2
-    if (side || early) {        // fork: everything the chain reads (the gathered residual, the CLS rows' attention output) is queued on the lane's stream before this point
-        if (side && (hipEventRecord(L.ce[0], s) != hipSuccess || hipStreamWaitEvent(cs, L.ce[0], 0) != hipSuccess)) return h->fail(KEEP_EHIP, "CLS-row chain: fork failed");
-        int rc2 = proj_cls ? cls_proj() : KEEP_OK;
-        if (!rc2) rc2 = cls_mlp(false);
-        if (rc2) return rc2;
-        if (chain_first && (rc2 = main_proj())) return rc2;
-    } else if (proj_cls && !mlp_cls) {      // no CLS-row MLP behind it: the rows go back before LayerNorm-2 reads them
-        const int rc2 = cls_proj();
-        if (rc2) return rc2;
+        if (run_gemm(h, T_VIT_TAIL, r, EPI_RESID_LS, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "CLS-row fc2 GEMM launch failed");
+    } else if (proj_cls) {      // no CLS-row MLP behind it: the rows go back before LayerNorm-2 reads them
         Scope sc(h, T_VIT_TAIL, s);
         launch_scatter_rows_f32(ws.c_resid, ws.resid, (int64_t)197 * D, Bc, D, s);
     }
-    if (!(did & GEMM_DID_LN) && !skip_ln) {
+    if (!(did & GEMM_DID_LN)) {
         Scope sc(h, T_VIT_LN, s);
         if (launch_layernorm(ln, s)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %d", D);
     }
@@ -681,21 +608,18 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
         capture(2, xn_hi, Mr, D);
         GemmParams p = gemm_params(h, xn_hi, xn_lo, b.fc1, Mr, mlp_lo, site_bias(2, b.fc1_b, mlp_plain));
         p.out_hi = mlp_hi; p.out_lo = mlp_lo ? mlp_lo_p : nullptr; p.out_kt = h->vit_F / 32;
-        if (mlp_plain && (h->impl2128_mask & 4)) p.impl_hint = 2128;
         if (mlp_q) {
             p.comp = mlp_comp; p.a_q = ws.xn_q; p.a_sc = ws.xn_sc; p.w_q = b.fc1->q; p.w_sc = b.fc1->sc;
             p.out_q = ws.mlp_q; p.out_sc = ws.mlp_sc;
         }
         if (run_gemm(h, tag, p, EPI_GELU_F16, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "fc1 GEMM launch failed");
     }
-    mark(4);
     {
         const int tag = cls_only ? T_VIT_TAIL : !mlp_plain ? T_VIT_FC2_X : T_VIT_FC2;
         Scope sc(h, tag, s);
         capture(3, mlp_hi, Mr, h->vit_F);
         GemmParams p = gemm_params(h, mlp_hi, mlp_lo_p, b.fc2, Mr, mlp_lo, site_bias(3, b.fc2_b, mlp_plain));
         p.ls = b.ls2; p.resid = resid;
-        if (mlp_plain && (h->impl2128_mask & 8)) p.impl_hint = 2128;
         if (mlp_q) { p.comp = mlp_comp; p.a_q = ws.mlp_q; p.a_sc = ws.mlp_sc; p.w_q = b.fc2->q; p.w_sc = b.fc2->sc; }
         if (i + 1 < h->vit_depth && !cls_only && !mlp_cls) {        // next block's LayerNorm-1 reads exactly the rows written here (not when CLS rows are still to be replaced)
             const VitBlock& nb = h->vblocks[i + 1];
@@ -708,21 +632,11 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
         if (rc < 0) return h->fail(KEEP_EUNSUPPORTED, "fc2 GEMM launch failed");
         L.xn_ready = (rc & GEMM_DID_LN) != 0;
     }
-    if (mlp_cls && side) {      // the join: the chain's rows replace what the plain fc2 wrote (ordered after it), and the lane goes on behind the scatter
-        Scope sc(h, T_VIT_TAIL, cs);
-        if (hipEventRecord(L.ce[1], s) != hipSuccess || hipStreamWaitEvent(cs, L.ce[1], 0) != hipSuccess) return h->fail(KEEP_EHIP, "CLS-row chain: join failed");
-        launch_scatter_rows_f32(ws.c_resid, ws.resid, (int64_t)197 * D, Bc, D, cs);
-        if (hipEventRecord(L.ce[2], cs) != hipSuccess || hipStreamWaitEvent(s, L.ce[2], 0) != hipSuccess) return h->fail(KEEP_EHIP, "CLS-row chain: join failed");
-    } else if (early) {
+    if (mlp_cls) {              // the chain's rows replace what the plain fc2 wrote
         Scope sc(h, T_VIT_TAIL, s);
         launch_scatter_rows_f32(ws.c_resid, ws.resid, (int64_t)197 * D, Bc, D, s);
-    } else if (mlp_cls) {       // in the lane's own stream: the whole chain behind the plain fc2, the rows written back by its last reduce
-        int rc2 = proj_cls ? cls_proj() : KEEP_OK;
-        if (!rc2) rc2 = cls_mlp(true);
-        if (rc2) return rc2;
     }
     L.c_resid_live = mlp_cls;   // (any other block's proj / fc2 moved the CLS rows of the token stream on without the compact copy)
-    mark(5);
     return KEEP_OK;
 }
 
@@ -1116,7 +1030,6 @@ void planes_to_f32(const f16* hi, const f16* lo, float* out, int64_t n, hipStrea
 
 // the image tower on B tiles (arguments checked, device selected by the caller)
 int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, float* out, hipStream_t s) {
-    ++h->dbg_calls;
     if (h->use_graphs && !h->prof_mode && B * 197 <= SKINNY_MAX_M && B <= h->max_tiles) {
         const size_t pxb = pix_dtype == KEEP_PIX_F32 ? 4 : (pix_dtype == KEEP_PIX_U8_HWC ? 1 : 2);
         const bool sp = h->any_split();
@@ -1147,10 +1060,7 @@ int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t 
     int64_t per = (B + lanes - 1) / lanes;
     if (per > h->max_tiles) per = h->max_tiles;
     const bool split = h->any_split();
-    const int64_t chunk_max = per * lanes;
-    const bool uneven = lanes == 2 && h->lane0_permille != 500;
-    const int64_t lane_cap = uneven ? (chunk_max * (h->lane0_permille > 500 ? h->lane0_permille : 1000 - h->lane0_permille) + 999) / 1000 : per;
-    const size_t lane_bytes = align_up(vit_ws_bytes(h, lane_cap, split));
+    const size_t lane_bytes = align_up(vit_ws_bytes(h, per, split));
     int rc = ensure_arena(h, lane_bytes * lanes);
     if (rc) return rc;
     if (lanes > 1) {
@@ -1165,38 +1075,19 @@ int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t 
     for (int64_t b0 = 0; b0 < B; b0 += per * lanes) {
         VitLane L[4];
         int nl = 0;
-        const int64_t chunk = (B - b0) < chunk_max ? (B - b0) : chunk_max;
-        const int64_t n0 = uneven ? (chunk * h->lane0_permille + 500) / 1000 : per;
         for (int l = 0; l < lanes; ++l) {
-            const int64_t lo = b0 + (uneven ? (l ? n0 : 0) : l * per);
-            const int64_t cap = uneven ? (l ? chunk - n0 : n0) : per;
-            if (lo >= B || cap <= 0) break;
+            const int64_t lo = b0 + l * per;
+            if (lo >= B) break;
             VitLane& x = L[nl++];
-            x.Bc = (int)((B - lo) < cap ? (B - lo) : cap);
+            x.Bc = (int)((B - lo) < per ? (B - lo) : per);
             x.pixels = (const char*)pixels + (size_t)lo * 3 * 224 * 224 * px;
             x.pix_dtype = pix_dtype;
             x.out = out + lo * h->proj_dim;
             x.s = lanes > 1 ? h->aux[l] : s;
             x.ws = carve_vit(h, h->arena + (size_t)l * lane_bytes, x.Bc, split);
-            if (lanes > 1 && h->cls_side_stream && !h->capture && x.Bc >= h->lane_min_tiles) {
-                if (!h->aux_cls[l]) HIPCHK(h, hipStreamCreateWithFlags(&h->aux_cls[l], hipStreamNonBlocking));
-                for (int e = 0; e < 3; ++e) if (!h->ev_cls[l][e]) HIPCHK(h, hipEventCreateWithFlags(&h->ev_cls[l][e], hipEventDisableTiming));
-                if (!h->cls_splitk[l]) HIPCHK(h, hipMalloc(&h->cls_splitk[l], SKINNY_WS_BYTES));
-                x.cs = h->aux_cls[l]; x.cs_splitk = h->cls_splitk[l];
-                for (int e = 0; e < 3; ++e) x.ce[e] = h->ev_cls[l][e];
-            }
         }
-        const bool skew = nl > 1 && h->lane_skew > 0;
-        for (int l = 0; l < nl; ++l) {
-            if (skew) {
-                if (!h->ev_skew[l]) HIPCHK(h, hipEventCreateWithFlags(&h->ev_skew[l], hipEventDisableTiming));
-                L[l].skew_ev = h->ev_skew[l]; L[l].skew_stage = h->lane_skew;
-                if (l > 0) HIPCHK(h, hipStreamWaitEvent(L[l].s, h->ev_skew[l - 1], 0));
-            }
-            if ((rc = vit_begin(h, L[l]))) return rc;
-            if (skew && (rc = vit_layer(h, L[l], 0))) return rc;
-        }
-        for (int i = skew ? 1 : 0; i < h->vit_depth; ++i)
+        for (int l = 0; l < nl; ++l) if ((rc = vit_begin(h, L[l]))) return rc;
+        for (int i = 0; i < h->vit_depth; ++i)
             for (int l = 0; l < nl; ++l) if ((rc = vit_layer(h, L[l], i))) return rc;
         for (int l = 0; l < nl; ++l) if ((rc = vit_end(h, L[l]))) return rc;
     }
@@ -1284,11 +1175,6 @@ int keep_destroy(keep_handle* h) {
     if (h->cls_buf) hipFree(h->cls_buf);
     if (h->err_flag) hipFree(h->err_flag);
     for (int l = 0; l < 4; ++l) { if (h->aux[l]) hipStreamDestroy(h->aux[l]); if (h->ev_join[l]) hipEventDestroy(h->ev_join[l]); }
-    for (int l = 0; l < 4; ++l) {
-        if (h->aux_cls[l]) hipStreamDestroy(h->aux_cls[l]);
-        for (int e = 0; e < 3; ++e) if (h->ev_cls[l][e]) hipEventDestroy(h->ev_cls[l][e]);
-        if (h->cls_splitk[l]) (void)hipFree(h->cls_splitk[l]);
-    }
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     delete h;
     return KEEP_OK;
@@ -1365,12 +1251,8 @@ int keep_set_option(keep_handle* h, const char* name, double value) {
     else if (n == "max_tiles") { if (v < 1) return h->fail(KEEP_EINVAL, "max_tiles < 1"); h->max_tiles = v; }
     else if (n == "max_prompts") { if (v < 1) return h->fail(KEEP_EINVAL, "max_prompts < 1"); h->max_prompts = v; }
     else if (n == "cls_tail") { h->cls_tail = v ? 1 : 0; if (h->bias_ready && h->cal_cls_tail != h->cls_tail) h->bias_ready = false; }   // (the mean-input biases of the last block were averaged under the other setting: recalibrate)
-    else if (n == "cls_qkv") { h->cls_qkv = v ? 1 : 0; }
-    else if (n == "cls_side_stream") { h->cls_side_stream = v ? 1 : 0; }
-    else if (n == "cls_chain_early") { if (v < 0 || v > 2) return h->fail(KEEP_EINVAL, "cls_chain_early must be 0..2"); h->cls_chain_early = v; }
     else if (n == "patch_split") { h->patch_split = v ? 1 : 0; }
     else if (n == "bias_correction") { h->bias_correction = v ? 1 : 0; }
-    else if (n == "impl2128_mask") { if (v < 0 || v > 15) return h->fail(KEEP_EINVAL, "impl2128_mask must be 0..15"); h->impl2128_mask = v; }
     else if (n == "proj_impl") { if (v != 0 && v != 2128) return h->fail(KEEP_EINVAL, "proj_impl must be 0 or 2128"); h->proj_impl = v; }
     else if (n == "streams") { if (v < 1 || v > 4) return h->fail(KEEP_EINVAL, "streams must be 1..4"); h->n_streams = v; }
     else if (n == "gemm_persistent") { if (v < 0 || v > 1024) return h->fail(KEEP_EINVAL, "gemm_persistent must be 0..1024"); t.gemm_persistent = v; }
@@ -1379,8 +1261,6 @@ int keep_set_option(keep_handle* h, const char* name, double value) {
     else if (n == "skinny_wide") { t.skinny_wide = v ? 1 : 0; }
     else if (n == "gemm_skinny_m") { if (v < 0 || v > SKINNY_MAX_M) return h->fail(KEEP_EINVAL, "gemm_skinny_m must be 0..%d", SKINNY_MAX_M); t.gemm_skinny_m = v; }
     else if (n == "lane_min_tiles") { if (v < 6) return h->fail(KEEP_EINVAL, "lane_min_tiles must be >= 6"); h->lane_min_tiles = v; }
-    else if (n == "lane_skew") { if (v < 0 || v > 5) return h->fail(KEEP_EINVAL, "lane_skew must be 0..5"); h->lane_skew = v; }
-    else if (n == "lane0_permille") { if (v < 100 || v > 900) return h->fail(KEEP_EINVAL, "lane0_permille must be 100..900"); h->lane0_permille = v; }
     else if (n == "ln_impl") { if (v < 0 || v > 2) return h->fail(KEEP_EINVAL, "ln_impl must be 0, 1 or 2"); t.ln_impl = v; }
     else if (n == "attn_waves") { if (v != 4 && v != 8 && v != 16) return h->fail(KEEP_EINVAL, "attn_waves must be 4, 8 or 16 (16: persistent double-buffered kernel for the image tower)"); t.attn_waves = v; }
     else if (n == "gemm_impl") {
@@ -1390,7 +1270,6 @@ int keep_set_option(keep_handle* h, const char* name, double value) {
     }
 #ifdef KEEP_DIAGNOSTICS
     // result-changing / timing diagnostics exist only in -DKEEP_DIAGNOSTICS builds (tools/gemm_timeline.py, tools/attn_timeline.py)
-    else if (n == "dbg_skip_ln") h->dbg_skip_ln = v;
     else if (n == "gemm_ablate") { t.gemm_ablate = v; }
     else if (n == "gemm_dbg") {
         if (v && !t.dbg) { HIPCHK(h, hipMalloc(&t.dbg, (size_t)65536 * 4 * sizeof(long long))); HIPCHK(h, hipMemset(t.dbg, 0, (size_t)65536 * 4 * sizeof(long long))); }
@@ -1425,14 +1304,8 @@ double keep_get_option(keep_handle* h, const char* name) {
     if (n == "gemm_persistent") return t.gemm_persistent;
     if (n == "ln_impl") return t.ln_impl;
     if (n == "attn_waves") return t.attn_waves;
-    if (n == "lane_skew") return h->lane_skew;
-    if (n == "lane0_permille") return h->lane0_permille;
     if (n == "cls_tail") return h->cls_tail;
     if (n == "proj_impl") return h->proj_impl;
-    if (n == "impl2128_mask") return h->impl2128_mask;
-    if (n == "cls_qkv") return h->cls_qkv;
-    if (n == "cls_side_stream") return h->cls_side_stream;
-    if (n == "cls_chain_early") return h->cls_chain_early;
     if (n == "patch_split") return h->patch_split;
     if (n == "bias_correction") return h->bias_correction;
     if (n == "bias_ready") return h->bias_ready ? 1 : 0;

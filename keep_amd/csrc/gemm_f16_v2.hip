@@ -626,10 +626,9 @@ void gemm_f16_v2_kernel(GemmParams p) {
     // fp16 outputs go to the blk layout (the consumer is a GEMM) or row-major (attention): ONE address form, offset(m) = (m / 256) * out_sa +
     // (m % 256) * out_sb + out_g, with the three constants picked here -- a "which layout" test per store was two scalar branches in front of each
     // of a tile's 16 stores
-    const int out_ld = p.out_ld > 0 ? p.out_ld : p.N;
-    const int64_t out_sa = p.out_kt > 0 ? (int64_t)p.out_kt * 8192 : (int64_t)256 * out_ld;
-    const int out_sb = p.out_kt > 0 ? 32 : out_ld;
-    const int out_g = p.out_kt > 0 ? ((ncol >> 5) * 8192 + (ncol & 31)) : ncol + p.out_col0;
+    const int64_t out_sa = p.out_kt > 0 ? (int64_t)p.out_kt * 8192 : (int64_t)256 * p.N;
+    const int out_sb = p.out_kt > 0 ? 32 : p.N;
+    const int out_g = p.out_kt > 0 ? ((ncol >> 5) * 8192 + (ncol & 31)) : ncol;
 #pragma unroll
     for (int j = 0; j < TM; ++j) {
         const int mbase = m0 + wm * (TM * 32) + j * 32;

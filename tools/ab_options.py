@@ -3,7 +3,7 @@
 HIP-event times of one single-stream pass per arm (so a change is visible in the operator it touches).  The part runs at its power cap: only
 same-box, same-minute comparisons mean anything.
 
-    python tools/ab_options.py --arm base --arm proj_impl=2128 --arm cls_qkv=0 [--plan 1,8 | --calibrate] [--steps 20] [--rounds 3]
+    python tools/ab_options.py --arm base --arm proj_impl=0 --arm attn_waves=8 [--plan 1,8 | --calibrate] [--steps 20] [--rounds 3]
 """
 import argparse
 import os
