@@ -202,6 +202,23 @@ int64_t keep_workspace_bytes(keep_handle* h);
  *   L2-normalised (F.normalize semantics). */
 int keep_encode_image(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, float* out, void* stream);
 
+/* Replaces: KEEPModel.encode_image on tiles of any size  (quick_start/keep_inference.py:32-40 builds the ViT with
+ *   timm.create_model(..., dynamic_img_size=True): the patch embedding runs on any H, W divisible by 16 and the position
+ *   embedding is resampled to the gh x gw = H/16 x W/16 patch grid by timm's resample_abs_pos_embed -- bicubic, antialiased,
+ *   the CLS row kept; unchanged at 14 x 14 only).  pixels: [B,3,H,W] NCHW (or uint8 [B,H,W,3] with KEEP_PIX_U8_HWC), one size
+ *   per call; out: fp32 [B,768].  KEEP_EINVAL unless H and W are positive multiples of 16.  At 224 x 224 the same computation as
+ *   keep_encode_image, bit for bit.  KEEP_PREC_COMP keeps its per-block plan (calibrated on 224 x 224 tiles) for
+ *   197 to 1025 tokens per tile, the band its tolerance was measured in, and runs other grids as KEEP_PREC_STRICT (option
+ *   "grid_plan": 1 default, 0 every non-224 grid strict, 2 the plan everywhere -- measurements only). */
+int keep_encode_image_hw(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, int64_t H, int64_t W, float* out,
+                         void* stream);
+
+/* Replaces: timm.layers.resample_abs_pos_embed(visual.pos_embed, new_size=(gh, gw), old_size=(14, 14), num_prefix_tokens=1)
+ *   (the step timm's dynamic_img_size takes per forward, quick_start/keep_inference.py:32-40).  out: fp32 [gh*gw+1, D], the table
+ *   keep_encode_image_hw uses for that grid: visual.pos_embed itself at 14 x 14, else the CLS row + the patch rows through
+ *   F.interpolate(mode="bicubic", antialias=True, align_corners=False).  Cached per grid inside the handle. */
+int keep_vit_pos_embed(keep_handle* h, int gh, int gw, float* out, void* stream);
+
 /* Replaces: KEEPModel.encode_text  (quick_start/keep_inference.py:60-62)
  *   input_ids / token_type_ids / attention_mask: int64 [P,T] (the tokenizer's return_tensors='pt'
  *   layout, keep_inference.py:99); token_type_ids and attention_mask may be NULL (zeros / ones, as
@@ -309,6 +326,11 @@ int keep_op_mlp(keep_handle* h, const float* x, const float* ln_w, const float* 
 /* qkv fp32 [B*T, 3*heads*64] (q|k|v), mask int64 [B,T] or NULL -> out fp32 [B*T, heads*64] */
 int keep_op_attention(keep_handle* h, const float* qkv, const int64_t* mask, int64_t B, int64_t T, int heads,
                       int split, float* out, void* stream);
+/* The image tower's attention beyond 512 tokens (timm Attention.forward, scaled_dot_product_attention without a mask, at the
+ * sequence lengths of quick_start/keep_inference.py:32-40 with dynamic_img_size): key-blocked online softmax, any T >= 1.
+ * qkv fp32 [B*T, 3*heads*64] -> out fp32 [B*T, heads*64]; q_rows > 0: only the first q_rows queries of every sequence (other rows 0) */
+int keep_op_attention_long(keep_handle* h, const float* qkv, int64_t B, int64_t T, int heads, int split, int q_rows,
+                           float* out, void* stream);
 int keep_op_layernorm(keep_handle* h, const float* x, const float* add, const float* gamma, const float* beta,
                       int64_t rows, int64_t D, float eps, float* out, void* stream);
 /* out[M,N] = act(scale * A[M,K] @ B[N,K]^T + bias); act 0 none, 1 gelu, 2 tanh (exact fp32 MFMA) */

@@ -42,6 +42,8 @@ SIGNATURES = {
     "keep_reserve": (_i32, [_vp, _i64, _i64, _i64]),
     "keep_workspace_bytes": (_i64, [_vp]),
     "keep_encode_image": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp]),
+    "keep_encode_image_hw": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp]),
+    "keep_vit_pos_embed": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "keep_encode_text": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "keep_resize_crop_u8": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp]),
     "keep_token_error": (_i32, [_vp, _vp]),
@@ -58,6 +60,7 @@ SIGNATURES = {
     "keep_op_linear": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp]),
     "keep_op_mlp": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp]),
     "keep_op_attention": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
+    "keep_op_attention_long": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
     "keep_op_layernorm": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp]),
     "keep_op_sgemm": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _vp]),
     "keep_op_l2norm": (_i32, [_vp, _vp, _i64, _i64, _vp]),

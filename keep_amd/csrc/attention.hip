@@ -559,6 +559,181 @@ int launch_one(const AttnParams& p, hipStream_t s) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Long sequences (ntok > 512: the image tower at 384 x 384 and beyond), where one head's K and V no longer fit the LDS of a CU (1025 keys:
+// 256 KiB single, 512 KiB as hi + lo).  One 4-wave workgroup per (query block of 64 rows, image, head); K and V stream through an LDS double
+// buffer in blocks of 64 keys (LDS-DMA through stage_kv<4>: block kb + 1 is in flight while block kb is computed), and each wave keeps the
+// online-softmax state of its 16 queries in registers -- running maximum m and a lane-partial sum l per query, O^T in the fragments of the
+// whole-sequence kernels.  Per key block, in the textbook order (no deferred maximum): scores, block maximum, new maximum, O and l scaled by
+// 2^(m_old - m_new) exactly once, and only THEN the block's P exponentiated against the new maximum and accumulated -- nothing at the old scale
+// is left unscaled and nothing at the new one is scaled.  Same S^T = K Q^T mapping, LDS swizzles and hi / lo products as attention_kernel.
+constexpr int ATL_KB = 64;                 // keys per staged block (4 key tiles)
+constexpr int ATL_QB = 64;                 // query rows per workgroup (one 16-row tile per wave)
+constexpr int ATL_PLANE = ATL_KB * HD * 2; // f16 elements of one staged plane: K image + V image (stage_kv<4> layout)
+__host__ __device__ constexpr size_t atl_lds_bytes(bool split) { return (size_t)2 * (split ? 2 : 1) * ATL_PLANE * 2; }
+
+template <bool SPLIT>
+__global__ __launch_bounds__(256, 2)
+void attention_long_kernel(AttnParams p) {
+    constexpr int NW = 4, NTB = ATL_KB / 16, NU = NTB / 2, NPL = SPLIT ? 2 : 1;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    f16* sBuf = reinterpret_cast<f16*>(smem);            // [buffer][plane: hi, lo][K image | V image]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.y / p.heads, h = blockIdx.y - b * p.heads;
+    const int ntok = p.ntok, D = p.heads * HD, D3 = 3 * D;
+    const int64_t tok0 = (int64_t)b * ntok;
+    const f16* base_hi = p.qkv_hi + tok0 * D3;
+    const f16* base_lo = SPLIT ? p.qkv_lo + tok0 * D3 : nullptr;
+    const int nq = (p.q_rows > 0 && p.q_rows < ntok) ? p.q_rows : ntok;
+    const int qt = blockIdx.x * NW + wave;
+    const bool active = qt * 16 < nq;                    // wave-uniform: a wave past the last query tile only stages
+    const int nkb = (ntok + ATL_KB - 1) / ATL_KB;
+    auto stage = [&](int kb, int buf) {
+        const int key0 = kb * ATL_KB, kc = ntok - key0 < ATL_KB ? ntok - key0 : ATL_KB;     // rows >= kc are copies of the last key (masked below)
+        f16* dh = sBuf + (size_t)(buf * NPL) * ATL_PLANE;
+        stage_kv<NTB, NW * 64>(base_hi + (int64_t)key0 * D3, kc, D3, D + h * HD, 2 * D + h * HD, dh, dh + ATL_KB * HD, tid, wave);
+        if (SPLIT) {
+            f16* dl = dh + ATL_PLANE;
+            stage_kv<NTB, NW * 64>(base_lo + (int64_t)key0 * D3, kc, D3, D + h * HD, 2 * D + h * HD, dl, dl + ATL_KB * HD, tid, wave);
+        }
+    };
+
+    const int qi = lane & 15, g = lane >> 4;
+    const int q = qt * 16 + qi;
+    f16x8 qf[2], ql[2];
+    {
+        const int qc = q < ntok ? q : ntok - 1;
+        const unsigned qo = (unsigned)qc * (unsigned)D3 + (unsigned)(h * HD + g * 8);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            qf[ks] = *reinterpret_cast<const f16x8*>(base_hi + (qo + ks * 32));
+            if (SPLIT) ql[ks] = *reinterpret_cast<const f16x8*>(base_lo + (qo + ks * 32));
+        }
+    }
+    const float sc2 = p.scale * 1.4426950408889634f;
+    float m_run = -INFINITY, l_run = 0.f;                // l_run: this lane's share of the sum (keys 4g..4g+3 of every tile)
+    f32x4 o[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    stage(0, 0);
+    for (int kb = 0; kb < nkb; ++kb) {
+        const int cur = kb & 1;
+        // block kb has landed (this wave's DMA by vmcnt, the others' by the barrier); nobody reads buffer cur ^ 1 (block kb - 1) any more
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (kb + 1 < nkb) stage(kb + 1, cur ^ 1);
+        if (!active) continue;
+        const f16* sK = sBuf + (size_t)(cur * NPL) * ATL_PLANE;
+        const f16* sV = sK + ATL_KB * HD;
+        const f16* sKl = sK + ATL_PLANE;
+        const f16* sVl = sV + ATL_PLANE;
+        // ---- S^T = K Q^T for the block's 4 key tiles
+        f32x4 s[NTB];
+#pragma unroll
+        for (int kt = 0; kt < NTB; ++kt) {
+            const int row = kt * 16 + qi;
+            s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const int off = row * HD + (((ks * 4 + g) ^ ((row >> 1) & 7)) << 3);
+                const f16x8 kf = *reinterpret_cast<const f16x8*>(sK + off);
+                if (SPLIT) {
+                    const f16x8 kl = *reinterpret_cast<const f16x8*>(sKl + off);
+                    s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl, qf[ks], s[kt], 0, 0, 0);
+                    s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, ql[ks], s[kt], 0, 0, 0);
+                }
+                s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[ks], s[kt], 0, 0, 0);
+            }
+        }
+        // ---- the block's maximum, then the rescale of everything accumulated at the old maximum (once), then P at the new one
+        const int key0 = kb * ATL_KB;
+        float mb = -INFINITY;
+#pragma unroll
+        for (int kt = 0; kt < NTB; ++kt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                s[kt][r] = (key0 + kt * 16 + g * 4 + r < ntok) ? s[kt][r] * sc2 : -INFINITY;     // log2-domain score; keys past the end: P = 0
+                mb = fmaxf(mb, s[kt][r]);
+            }
+        mb = fmaxf(mb, __shfl_xor(mb, 16));
+        mb = fmaxf(mb, __shfl_xor(mb, 32));
+        const float m_new = fmaxf(m_run, mb);            // finite from block 0 on (key 0 is valid)
+        const float f = __builtin_amdgcn_exp2f(m_run - m_new);     // 0 at block 0 (m_run = -inf, O = l = 0), 1 when the maximum did not move
+        l_run *= f;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[dt][r] *= f;
+        m_run = m_new;
+        f16x8 ph[NU], pl[SPLIT ? NU : 1];
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float a0 = __builtin_amdgcn_exp2f(s[2 * u][r] - m_run), a1 = __builtin_amdgcn_exp2f(s[2 * u + 1][r] - m_run);
+                l_run += a0;
+                l_run += a1;
+                const f16 h0 = (f16)a0, h1 = (f16)a1;
+                ph[u][r] = h0; ph[u][4 + r] = h1;
+                if (SPLIT) { pl[u][r] = (f16)(a0 - (float)h0); pl[u][4 + r] = (f16)(a1 - (float)h1); }
+            }
+        }
+        // ---- O^T += V^T P^T (V^T fragments by the transpose read, as in attention_kernel)
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int vrow = 32 * u + 4 * g + (qi >> 2);
+            const int vsw = (2 * g + (qi >> 3)) & 3;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                const int voff = vrow * HD + ((dt ^ vsw) << 4) + ((qi & 3) << 2);
+                const f16x4 v0 = tr_read4(sV + voff), v1 = tr_read4(sV + voff + 16 * HD);
+                const f16x8 vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                if (SPLIT) {
+                    const f16x4 w0 = tr_read4(sVl + voff), w1 = tr_read4(sVl + voff + 16 * HD);
+                    const f16x8 vl = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
+                    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl, ph[u], o[dt], 0, 0, 0);
+                    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pl[u], o[dt], 0, 0, 0);
+                }
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, ph[u], o[dt], 0, 0, 0);
+            }
+        }
+    }
+    if (!active) return;
+    l_run += __shfl_xor(l_run, 16);
+    l_run += __shfl_xor(l_run, 32);
+    const float inv = 1.0f / l_run;
+    if (q < nq) {
+        const bool o_blk = p.out_kt > 0;
+        const unsigned o_sa = o_blk ? (unsigned)p.out_kt * 8192u : 256u * (unsigned)D, o_sb = o_blk ? 32u : (unsigned)D;
+        const unsigned o_ga = o_blk ? 8192u : 32u, o_g0 = (o_blk ? (unsigned)(h * 2) * 8192u : (unsigned)(h * HD)) + (unsigned)(g * 4);
+        const int mrow = (int)(tok0 + q);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            f16x4 oh, ol;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { f16 hh, ll; split_f16(o[dt][r] * inv, hh, ll); oh[r] = hh; ol[r] = ll; }
+            const unsigned oo = (unsigned)(mrow >> 8) * o_sa + (unsigned)(mrow & 255) * o_sb + o_g0 + (unsigned)(dt >> 1) * o_ga + (unsigned)(dt & 1) * 16u;
+            *reinterpret_cast<f16x4*>(p.out_hi + oo) = oh;
+            if (SPLIT) *reinterpret_cast<f16x4*>(p.out_lo + oo) = ol;
+            if (!SPLIT && p.cls_hi && q == 0) {          // KEEP_ATTN_PROJ_CLS: the CLS row once more, hi + lo, into row b of the compact operand
+                const unsigned oc = (unsigned)(b >> 8) * o_sa + (unsigned)(b & 255) * o_sb + o_g0 + (unsigned)(dt >> 1) * o_ga + (unsigned)(dt & 1) * 16u;
+                *reinterpret_cast<f16x4*>(p.cls_hi + oc) = oh;
+                *reinterpret_cast<f16x4*>(p.cls_lo + oc) = ol;
+            }
+        }
+    }
+}
+
+template <bool SPLIT>
+int launch_long(const AttnParams& p, int qblocks, hipStream_t s) {
+    constexpr size_t bytes = atl_lds_bytes(SPLIT);
+    if (bytes > 65536 && !keep_lds_opt_in(reinterpret_cast<const void*>(&attention_long_kernel<SPLIT>), bytes)) return -1;
+    hipLaunchKernelGGL((attention_long_kernel<SPLIT>), dim3(qblocks, p.batch * p.heads), dim3(256), bytes, s, p);
+    return 0;
+}
+
 }  // namespace keepk
 
 int launch_attention(const AttnParams& p_in, hipStream_t s) {
@@ -599,4 +774,19 @@ int launch_attention(const AttnParams& p_in, hipStream_t s) {
     if (nt <= 16) return g_attn_waves == 4 ? launch_one<16, false, 4>(p, s) : launch_one<16, false, 8>(p, s);
     if (nt <= 32) return launch_one<32, false, 4>(p, s);
     return -1;
+}
+
+int launch_attention_long(const AttnParams& p_in, hipStream_t s) {
+    using namespace keepk;
+    AttnParams p = p_in;
+    p.key0 = 0; p.kcount = 0; p.part_out = nullptr; p.part_in = nullptr; p.dbg = nullptr;
+    if (p.ntok < 1 || p.batch < 1 || p.heads < 1 || p.mask) return -1;
+    if ((p.cls_hi != nullptr) != (p.cls_lo != nullptr) || (p.cls_hi && p.split)) return -1;      // CLS-row hi + lo copy: both planes, single pass only
+    if (p.split && !p.qkv_lo) return -1;
+    // 32-bit lane offsets, as in launch_attention
+    if ((int64_t)p.ntok * 3 * p.heads * HD >= (1ll << 31) || ((int64_t)p.batch * p.ntok + 255) / 256 * 256 * p.heads * HD >= (1ll << 31)) return -1;
+    if ((int64_t)p.batch * p.heads > 65535) return -1;     // grid y
+    const int nq = (p.q_rows > 0 && p.q_rows < p.ntok) ? p.q_rows : p.ntok;
+    const int qblocks = (nq + ATL_QB - 1) / ATL_QB;
+    return p.split ? launch_long<true>(p, qblocks, s) : launch_long<false>(p, qblocks, s);
 }

@@ -88,7 +88,7 @@ enum GemmEpi : int {
     EPI_F16      = 0,   // out_f16 = acc + bias                                   (QKV)
     EPI_GELU_F16 = 1,   // out_f16 = gelu(acc + bias)                             (fc1)
     EPI_RESID_LS = 2,   // resid  += ls[n] * (acc + bias)   fp32, in place        (proj / fc2, ViT)
-    EPI_PATCH    = 3,   // resid[b*197+1+p] = acc + bias + pos[1+p]               (patch embed)
+    EPI_PATCH    = 3,   // resid[b*(P+1)+1+p] = acc + bias + pos[1+p], P = patches_per_img  (patch embed)
     EPI_RESID_F32= 4,   // out_f32 = acc + bias + resid      (BERT pre-LN sum; may alias resid)
     EPI_PARTIAL  = 5,   // internal: fp32 partial sums of one K slice -> splitk_ws[slice][M][N] (no bias); the
                         // split-K reduce kernel of gemm_f16_skinny.hip then applies the real epilogue
@@ -113,12 +113,12 @@ struct GemmParams {
     unsigned char* out_q; unsigned char* out_sc;   // EPI_GELU_F16 with out_kt > 0: also emit the fp4 planes of the output (K = N of this GEMM)
     const float* bias;                    // [N]
     const float* ls;                      // [N]   (EPI_RESID_LS)
-    const float* pos;                     // [197][N] (EPI_PATCH)
+    const float* pos;                     // [patches_per_img + 1][N] (EPI_PATCH)
     float* resid;                         // fp32 [M'][N]
     float* out_f32;                       // EPI_RESID_F32
     f16* out_hi; f16* out_lo;             // fp16 outputs (lo optional)
     int out_kt;                           // > 0: fp16 output in blk layout with KT = out_kt (= N/32); 0: row-major [M][N]
-    int patches_per_img;                  // EPI_PATCH: 196
+    int patches_per_img;                  // EPI_PATCH: gh * gw (196 at 224 x 224)
     // optional LayerNorm of the updated row, fused into the split-K reduce (EPI_RESID_LS / EPI_RESID_F32, N <= 1024);
     // launch_gemm_f16 reports through its return value whether it was applied (bit 0) -- the big kernel never does
     const float* ln_gamma; const float* ln_beta; float ln_eps;
@@ -165,6 +165,10 @@ struct AttnParams {
     const KeepTune* tune;
 };
 int launch_attention(const AttnParams& p, hipStream_t s);   // returns 0 or -1 (unsupported ntok)
+// Key-blocked online-softmax attention for ntok > 512 (the image tower at grids beyond 22 x 22 patches): K / V stream through an LDS double
+// buffer, so the sequence length is bounded only by the 32-bit offsets.  No key mask; split, q_rows, cls_hi / cls_lo and out_kt as above
+// (part_ws is not used).  A separate entry point: launch_attention's own dispatch is unchanged.  Returns 0 or -1.
+int launch_attention_long(const AttnParams& p, hipStream_t s);
 constexpr int ATT_PART_FLOATS = 66;       // 64 output features + maximum + sum
 
 // LayerNorm over rows of D in {768,1024}; fp32 in, fp16 (hi[,lo]) and/or fp32 out.
@@ -196,8 +200,13 @@ struct SgemmParams {
 int launch_sgemm_f32(const SgemmParams& p, hipStream_t s);
 
 // Row-wise helpers (rowops.hip)
-void launch_im2col(const void* pixels, int dtype, int B, f16* out_hi, f16* out_lo,      // out in blk layout (KT = 24)
+// pixels [B,3,16 gh,16 gw] (or uint8 [B,16 gh,16 gw,3]) -> patches [B * gh * gw][768], row-major (y, x) patch order; CLS rows of resid
+void launch_im2col(const void* pixels, int dtype, int B, int gh, int gw, f16* out_hi, f16* out_lo,      // out in blk layout (KT = 24)
                    const float* cls, const float* pos, float* resid, int D, hipStream_t s);
+// position-embedding resample: out[1 + y gw + x][d] = sum_ij wy[y][i] wx[x][j] pos[1 + (y0[y] + i) gs + x0[x] + j][d], out[0] = pos[0];
+// ybeg / xbeg: first input index per output row / column, wy / wx: ytaps / xtaps weights each (zero-padded), gs: source grid side
+void launch_pos_resample(const float* pos, int gs, int D, int gh, int gw, const int* ybeg, const double* wy, int ytaps,
+                         const int* xbeg, const double* wx, int xtaps, float* out, hipStream_t s);
 // Pillow-exact bicubic Resize + CenterCrop of raw uint8 HWC images (weights / windows from keep_amd/preprocess.py)
 void launch_resize_crop_u8(const unsigned char* src, int B, int H, int W, const int* xb, const int* xk, int xks, int col0, int ncols,
                            const int* yb, const int* yk, int yks, int row0, int nrows, unsigned char* tmp, unsigned char* out, hipStream_t s);

@@ -8,6 +8,7 @@
 #include "quant4.h"
 #include "../../include/keep_hip.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -155,6 +156,25 @@ struct keep_handle {
         for (auto& c : cal) for (int k = 0; k < 4; ++k) { if (c.sum[k]) (void)hipFree(c.sum[k]); if (c.bias[k]) (void)hipFree(c.bias[k]); }
         cal.clear(); bias_ready = false;
     }
+    // Patch grids other than 14 x 14 (keep_encode_image_hw): the position table resampled to each grid (timm resample_abs_pos_embed), fp32
+    // [gh gw + 1][D] on the device, built outside any graph capture on first use; at most POS_CACHE grids, the oldest dropped first (with
+    // the captured graphs, which bake its address in); dropped whenever the image tower's weights are (re)finalised or pos_embed is reloaded.
+    struct PosSlot { int gh, gw; float* buf; };
+    static constexpr int POS_CACHE = 8;
+    std::vector<PosSlot> pos_cache;
+    void drop_pos_cache() {
+        if (pos_cache.empty()) return;
+        (void)hipDeviceSynchronize();
+        for (auto& e : pos_cache) (void)hipFree(e.buf);
+        pos_cache.clear();
+        ++opt_epoch;
+    }
+    // KEEP_PREC_COMP at grids other than 14 x 14: the per-block plan is calibrated on 197-token tiles.  Measured against strict on the bench weights
+    // (tools/grid_precision.py, 2 000 tiles per family) it stays at the 224 figure from 257 to 1025 tokens (worst 6.7e-5) and gets
+    // worse below 197 (7.1e-5 at 101 tokens, 8.1e-5 at 50).  1 (default): the plan for 197 <= tokens <= 1025, KEEP_PREC_STRICT outside that band;
+    // 0: every grid but 14 x 14 strict; 2: the plan at every grid (measurements only).
+    int grid_plan = 1;
+    bool grid_keeps_plan(int ntok) const { return grid_plan == 2 || (grid_plan == 1 && ntok >= 197 && ntok <= 1025); }
     int patch_split = 1;         // 0: the patch-embedding GEMM as one fp16 pass (experiments; measured in profiles/r05_patch_embed_plain.txt)
     // 2128 (default): the plain proj GEMMs of the image tower on the 256x128 / 4-wave / two-workgroups-per-CU kernel (GemmParams.impl_hint) -- proj is the one GEMM whose
     // tile is 40 % fp32 residual read-modify-write epilogue, and with two workgroups on a CU one's epilogue runs under the other's K loop: -8.5 % on the proj launches,
@@ -306,19 +326,25 @@ struct Carver {
 struct VitWs { float* splitk; float* resid; f16 *xn_hi, *xn_lo, *qkv_hi, *qkv_lo, *att_hi, *att_lo, *mlp_hi, *mlp_lo, *pat_hi, *pat_lo; float *cls, *h1;
                unsigned char *xn_q, *xn_sc, *mlp_q, *mlp_sc;     // MX-fp4 side planes of the LayerNorm-2 output and of the MLP hidden (compensated mode)
                // compact CLS-row buffers for the last block
-               float* c_resid; f16 *c_att_hi, *c_att_lo, *c_xn_hi, *c_xn_lo, *c_mlp_hi, *c_mlp_lo; };
+               float* c_resid; f16 *c_att_hi, *c_att_lo, *c_xn_hi, *c_xn_lo, *c_mlp_hi, *c_mlp_lo;
+               float* part; size_t part_bytes; };            // split attention's two-window state (256 < ntok <= 512 only)
 struct TxtWs { float* splitk; float* resid; f16 *xn_hi, *xn_lo, *qkv_hi, *qkv_lo, *att_hi, *att_lo, *mlp_hi, *mlp_lo; float* attn_part; size_t attn_part_bytes; };
 
-size_t vit_ws_bytes(const keep_handle* h, int64_t Bc, bool split) {
-    const size_t M = (size_t)Bc * 197, Mp = (size_t)Bc * 196, D = h->vit_D, F = h->vit_F, k = split ? 2 : 1;
+// split attention over 256 < ntok <= 512 keys parks a partial state per (tile, head, query) between its two key windows (launch_attention)
+size_t vit_part_bytes(const keep_handle* h, int64_t Bc, int ntok, bool split) {
+    return (split && ntok > 256 && ntok <= 512) ? (size_t)Bc * h->vit_heads * ntok * ATT_PART_FLOATS * sizeof(float) : 0;
+}
+size_t vit_ws_bytes(const keep_handle* h, int64_t Bc, bool split, int ntok = 197) {
+    const size_t M = (size_t)Bc * ntok, Mp = (size_t)Bc * (ntok - 1), D = h->vit_D, F = h->vit_F, k = split ? 2 : 1;
+    const size_t part = vit_part_bytes(h, Bc, ntok, split);
     const size_t comp = h->any_comp() ? align_up(keepk::q4_data_bytes(M, D)) + align_up(keepk::q4_scale_bytes(M, D)) +
                                         align_up(keepk::q4_data_bytes(M, F)) + align_up(keepk::q4_scale_bytes(M, F)) : 0;
     return comp + align_up(SKINNY_WS_BYTES) + align_up(M * D * 4) + k * (align_up(blk_elems(M, D) * 2) * 2 + align_up(M * 3 * D * 2) + align_up(blk_elems(M, F) * 2)) + 2 * align_up(blk_elems(Mp, 768) * 2) +
            align_up((size_t)Bc * D * 4) + align_up((size_t)Bc * h->proj_dim * 4) + 4096 +
-           align_up((size_t)Bc * D * 4) + 2 * (2 * align_up(blk_elems(Bc, D) * 2) + align_up(blk_elems(Bc, F) * 2));
+           align_up((size_t)Bc * D * 4) + 2 * (2 * align_up(blk_elems(Bc, D) * 2) + align_up(blk_elems(Bc, F) * 2)) + (part ? align_up(part) : 0);
 }
-VitWs carve_vit(const keep_handle* h, char* arena, int64_t Bc, bool split) {
-    const size_t M = (size_t)Bc * 197, Mp = (size_t)Bc * 196, D = h->vit_D, F = h->vit_F;
+VitWs carve_vit(const keep_handle* h, char* arena, int64_t Bc, bool split, int ntok = 197) {
+    const size_t M = (size_t)Bc * ntok, Mp = (size_t)Bc * (ntok - 1), D = h->vit_D, F = h->vit_F;
     Carver c(arena); VitWs w{};
     w.splitk = c.take<float>(SKINNY_WS_BYTES / 4);
     w.resid = c.take<float>(M * D);
@@ -337,6 +363,8 @@ VitWs carve_vit(const keep_handle* h, char* arena, int64_t Bc, bool split) {
         w.xn_q = c.take<unsigned char>(keepk::q4_data_bytes(M, D));  w.xn_sc = c.take<unsigned char>(keepk::q4_scale_bytes(M, D));
         w.mlp_q = c.take<unsigned char>(keepk::q4_data_bytes(M, F)); w.mlp_sc = c.take<unsigned char>(keepk::q4_scale_bytes(M, F));
     }
+    w.part_bytes = vit_part_bytes(h, Bc, ntok, split);
+    if (w.part_bytes) w.part = c.take<float>(w.part_bytes / sizeof(float));
     return w;
 }
 size_t txt_ws_bytes(const keep_handle* h, int64_t Pc, int64_t T, bool split) {
@@ -440,6 +468,8 @@ GemmParams gemm_params(const keep_handle* h, const f16* a_hi, const f16* a_lo, c
 // attention staging, GEMM epilogues, partial last rounds of workgroups) overlap the other lane's MFMA phases.
 struct VitLane {
     const void* pixels; int pix_dtype; int Bc; float* out; hipStream_t s; VitWs ws; bool cls_compact = false;
+    int gh = 14, gw = 14, ntok = 197;                     // patch grid and tokens per tile (gh gw + 1)
+    const float* pos = nullptr;                           // position table of that grid, [ntok][D] (vit_pos_table)
     bool xn_ready = false;                                // the previous block's fc2 already wrote this block's LayerNorm-1 output
     bool c_resid_live = false;                            // ws.c_resid holds the CLS rows of ws.resid as they are NOW (left there by the previous block's CLS-row chain): no gather
 };
@@ -452,14 +482,14 @@ int vit_begin(keep_handle* h, VitLane& L) {
     const bool sp0 = h->patch_split || h->precision == KEEP_PREC_STRICT || h->strict_blocks > 0;
     {
         Scope sc(h, T_VIT_IM2COL, s);
-        launch_im2col(pixels, pix_dtype, Bc, ws.pat_hi, sp0 ? ws.pat_lo : nullptr,
-                      find(h, "visual.cls_token")->f32, find(h, "visual.pos_embed")->f32, ws.resid, D, s);
+        launch_im2col(pixels, pix_dtype, Bc, L.gh, L.gw, ws.pat_hi, sp0 ? ws.pat_lo : nullptr,
+                      find(h, "visual.cls_token")->f32, L.pos, ws.resid, D, s);
     }
     {
         Scope sc(h, T_VIT_PATCH, s);
-        GemmParams p = gemm_params(h, ws.pat_hi, ws.pat_lo, find(h, "visual.patch_embed.proj.weight"), Bc * 196, sp0,
+        GemmParams p = gemm_params(h, ws.pat_hi, ws.pat_lo, find(h, "visual.patch_embed.proj.weight"), Bc * (L.ntok - 1), sp0,
                                    find(h, "visual.patch_embed.proj.bias")->f32);
-        p.pos = find(h, "visual.pos_embed")->f32;
+        p.pos = L.pos; p.patches_per_img = L.ntok - 1;
         p.resid = ws.resid;
         if (run_gemm(h, T_VIT_PATCH, p, EPI_PATCH, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "patch-embedding GEMM launch failed");
     }
@@ -467,7 +497,7 @@ int vit_begin(keep_handle* h, VitLane& L) {
 }
 
 int vit_layer(keep_handle* h, VitLane& L, int i) {
-    const int D = h->vit_D, Bc = L.Bc, M = Bc * 197;
+    const int D = h->vit_D, Bc = L.Bc, ntok = L.ntok, M = Bc * ntok;
     hipStream_t s = L.s; VitWs& ws = L.ws;
     const VitBlock& b = h->vblocks[i];
     // mean-input compensation: a PLAIN launch of site k uses the bias with W_lo a_mean folded in; while calibrating, every site's input is summed
@@ -519,10 +549,12 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
         AttnParams a{};
         a.tune = &h->tune;
         a.qkv_hi = ws.qkv_hi; a.qkv_lo = ws.qkv_lo; a.out_hi = ws.att_hi; a.out_lo = sp ? ws.att_lo : nullptr;
-        a.mask = nullptr; a.batch = Bc; a.ntok = 197; a.heads = h->vit_heads; a.split = sp; a.scale = 0.125f; a.out_kt = D / 32;
+        a.mask = nullptr; a.batch = Bc; a.ntok = ntok; a.heads = h->vit_heads; a.split = sp; a.scale = 0.125f; a.out_kt = D / 32;
         a.q_rows = cls_only ? 1 : 0;
         if (proj_cls) { a.cls_hi = ws.c_att_hi; a.cls_lo = ws.c_att_lo; }
-        if (launch_attention(a, s)) return h->fail(KEEP_EUNSUPPORTED, "attention launch failed");
+        a.part_ws = ws.part; a.part_bytes = ws.part_bytes;
+        // beyond 512 tokens (grids past 22 x 22 patches) the key-blocked kernel; up to 512 the whole-sequence kernels of the 224 path
+        if ((ntok > 512 ? launch_attention_long(a, s) : launch_attention(a, s))) return h->fail(KEEP_EUNSUPPORTED, "attention launch failed (%d tokens)", ntok);
     }
     const int Mr = cls_only ? Bc : M;
     float* resid = cls_only ? ws.c_resid : ws.resid;
@@ -530,9 +562,9 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
     f16 *xn_hi = ws.xn_hi, *xn_lo = ws.xn_lo, *mlp_hi = ws.mlp_hi, *mlp_lo_p = ws.mlp_lo;
     if (cls_only) {
         Scope sc(h, T_VIT_HEAD, s);
-        launch_gather_rows_f32(ws.resid, (int64_t)197 * D, ws.c_resid, Bc, D, s);
-        launch_gather_rows_blk(ws.att_hi, 197, ws.c_att_hi, Bc, D, s);
-        if (sp) launch_gather_rows_blk(ws.att_lo, 197, ws.c_att_lo, Bc, D, s);
+        launch_gather_rows_f32(ws.resid, (int64_t)ntok * D, ws.c_resid, Bc, D, s);
+        launch_gather_rows_blk(ws.att_hi, ntok, ws.c_att_hi, Bc, D, s);
+        if (sp) launch_gather_rows_blk(ws.att_lo, ntok, ws.c_att_lo, Bc, D, s);
         att_hi = ws.c_att_hi; att_lo = ws.c_att_lo; xn_hi = ws.c_xn_hi; xn_lo = ws.c_xn_lo; mlp_hi = ws.c_mlp_hi; mlp_lo_p = ws.c_mlp_lo;
         L.cls_compact = true;
     }
@@ -541,7 +573,7 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
     ln.gamma = b.n2w; ln.beta = b.n2b;
     if (proj_cls && !L.c_resid_live) {      // the CLS rows' residual as it enters proj (the plain proj below updates these rows too; the split result replaces that)
         Scope sc(h, T_VIT_TAIL, s);
-        launch_gather_rows_f32(ws.resid, (int64_t)197 * D, ws.c_resid, Bc, D, s);
+        launch_gather_rows_f32(ws.resid, (int64_t)ntok * D, ws.c_resid, Bc, D, s);
     }
     int did = 0;
     {
@@ -560,7 +592,7 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
     // dependency is a barrier packet the next persistent GEMM sits behind (both measured in round 6: tools/experiments/README.md).
     if (mlp_cls && !proj_cls) { // the CLS rows' residual as it enters the MLP, i.e. BEHIND this block's proj (a live compact copy is the residual in front of it): always gathered
         Scope sc(h, T_VIT_TAIL, s);
-        launch_gather_rows_f32(ws.resid, (int64_t)197 * D, ws.c_resid, Bc, D, s);
+        launch_gather_rows_f32(ws.resid, (int64_t)ntok * D, ws.c_resid, Bc, D, s);
     }
     bool cls_ln_done = false;   // LayerNorm-2 of the compact CLS rows already written (hi + lo) by the CLS-row proj's epilogue
     if (proj_cls) {
@@ -596,7 +628,7 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
         if (run_gemm(h, T_VIT_TAIL, r, EPI_RESID_LS, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "CLS-row fc2 GEMM launch failed");
     } else if (proj_cls) {      // no CLS-row MLP behind it: the rows go back before LayerNorm-2 reads them
         Scope sc(h, T_VIT_TAIL, s);
-        launch_scatter_rows_f32(ws.c_resid, ws.resid, (int64_t)197 * D, Bc, D, s);
+        launch_scatter_rows_f32(ws.c_resid, ws.resid, (int64_t)ntok * D, Bc, D, s);
     }
     if (!(did & GEMM_DID_LN)) {
         Scope sc(h, T_VIT_LN, s);
@@ -634,7 +666,7 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
     }
     if (mlp_cls) {              // the chain's rows replace what the plain fc2 wrote
         Scope sc(h, T_VIT_TAIL, s);
-        launch_scatter_rows_f32(ws.c_resid, ws.resid, (int64_t)197 * D, Bc, D, s);
+        launch_scatter_rows_f32(ws.c_resid, ws.resid, (int64_t)ntok * D, Bc, D, s);
     }
     L.c_resid_live = mlp_cls;   // (any other block's proj / fc2 moved the CLS rows of the token stream on without the compact copy)
     return KEEP_OK;
@@ -648,7 +680,7 @@ int vit_end(keep_handle* h, VitLane& L) {
         Scope sc(h, T_VIT_HEAD, s);
         LnParams ln{};
         ln.tune = &h->tune;
-        ln.x = L.cls_compact ? ws.c_resid : ws.resid; ln.x_stride = L.cls_compact ? (int64_t)D : (int64_t)197 * D;
+        ln.x = L.cls_compact ? ws.c_resid : ws.resid; ln.x_stride = L.cls_compact ? (int64_t)D : (int64_t)L.ntok * D;
         ln.rows = Bc; ln.D = D; ln.eps = 1e-6f;
         ln.gamma = find(h, "visual.norm.weight")->f32; ln.beta = find(h, "visual.norm.bias")->f32;
         ln.out_f32 = ws.cls; ln.out_f32_stride = D;
@@ -840,6 +872,7 @@ const WTensor* need_mat(keep_handle* h, const std::string& key, int64_t n, int64
 int finalize_vit(keep_handle* h) {
     h->vblocks.clear(); h->vit_depth = 0;
     h->free_cal();               // corrected biases belong to the weights they were calibrated on
+    h->drop_pos_cache();         // so do the resampled position tables
     for (float* v : h->owned_vecs) (void)hipFree(v);
     h->owned_vecs.clear();
     const WTensor* pe = find(h, "visual.patch_embed.proj.weight");
@@ -1028,23 +1061,99 @@ void planes_to_f32(const f16* hi, const f16* lo, float* out, int64_t n, hipStrea
     hipLaunchKernelGGL(f16_planes_to_f32_kernel, dim3(blocks), dim3(256), 0, s, hi, lo, out, n);
 }
 
-// the image tower on B tiles (arguments checked, device selected by the caller)
-int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, float* out, hipStream_t s) {
-    if (h->use_graphs && !h->prof_mode && B * 197 <= SKINNY_MAX_M && B <= h->max_tiles) {
-        const size_t pxb = pix_dtype == KEEP_PIX_F32 ? 4 : (pix_dtype == KEEP_PIX_U8_HWC ? 1 : 2);
+// ATen's antialiased bicubic resample (F.interpolate(mode="bicubic", antialias=True, align_corners=False), what timm's
+// resample_abs_pos_embed calls) as a weight table, in double: Keys cubic with a = -0.5, support 2 max(in / out, 1), window clipped at the
+// edges (not edge-replicated), weights normalised per output.  beg[o]: first input index of output o; w[o][0..taps): its weights (zero-padded).
+void aa_bicubic_table(int in, int out, std::vector<int>& beg, std::vector<double>& w, int& taps) {
+    const double scale = (double)in / out;
+    const double support = scale >= 1.0 ? 2.0 * scale : 2.0;
+    const double invscale = scale >= 1.0 ? 1.0 / scale : 1.0;
+    taps = (int)std::ceil(support) * 2 + 1;
+    beg.assign(out, 0); w.assign((size_t)out * taps, 0.0);
+    auto cubic = [](double x) {
+        const double a = -0.5;
+        x = std::fabs(x);
+        if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0;
+        if (x < 2.0) return (((x - 5.0) * x + 8.0) * x - 4.0) * a;
+        return 0.0;
+    };
+    for (int o = 0; o < out; ++o) {
+        const double center = scale * (o + 0.5);
+        const int64_t lo = std::max<int64_t>((int64_t)(center - support + 0.5), 0);      // (int64_t) truncates, as ATen's cast does
+        const int64_t n = std::min<int64_t>((int64_t)(center + support + 0.5), in) - lo;
+        double total = 0.0;
+        for (int64_t j = 0; j < n && j < taps; ++j) { const double v = cubic(((double)(j + lo) - center + 0.5) * invscale); w[(size_t)o * taps + j] = v; total += v; }
+        if (total != 0.0)
+            for (int j = 0; j < taps; ++j) w[(size_t)o * taps + j] /= total;
+        beg[o] = (int)lo;
+    }
+}
+
+// The position table of a gh x gw grid: the checkpoint's own at 14 x 14 (timm returns it unchanged there and only there), otherwise the
+// CLS row as it is + the 14 x 14 patch table resampled to gh x gw (cached per grid, POS_CACHE grids).  Allocates and synchronises: never
+// called inside a graph capture (encode_image_run asks for it before graph_run).
+int vit_pos_table(keep_handle* h, int gh, int gw, const float** out) {
+    const float* pos = find(h, "visual.pos_embed")->f32;
+    if (gh == 14 && gw == 14) { *out = pos; return KEEP_OK; }
+    for (const auto& e : h->pos_cache) if (e.gh == gh && e.gw == gw) { *out = e.buf; return KEEP_OK; }
+    if ((int)h->pos_cache.size() >= keep_handle::POS_CACHE) {
+        HIPCHK(h, hipDeviceSynchronize());
+        (void)hipFree(h->pos_cache.front().buf);
+        h->pos_cache.erase(h->pos_cache.begin());
+        ++h->opt_epoch;                          // a captured graph may hold the freed table's address
+    }
+    const int D = h->vit_D;
+    std::vector<int> yb, xb;
+    std::vector<double> wy, wx;
+    int ty = 0, tx = 0;
+    aa_bicubic_table(14, gh, yb, wy, ty);
+    aa_bicubic_table(14, gw, xb, wx, tx);
+    float* buf = nullptr;
+    HIPCHK(h, hipMalloc(&buf, (size_t)(gh * gw + 1) * D * sizeof(float)));
+    Tmp t;
+    int* d_yb = t.get<int>(yb.size()); int* d_xb = t.get<int>(xb.size());
+    double* d_wy = t.get<double>(wy.size()); double* d_wx = t.get<double>(wx.size());
+    if (!d_yb || !d_xb || !d_wy || !d_wx) { (void)hipFree(buf); return h->fail(KEEP_ENOMEM, "position table: temp alloc"); }
+    hipError_t e = hipMemcpy(d_yb, yb.data(), yb.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_xb, xb.data(), xb.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_wy, wy.data(), wy.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_wx, wx.data(), wx.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_pos_resample(pos, 14, D, gh, gw, d_yb, d_wy, ty, d_xb, d_wx, tx, buf, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();         // the tables above are freed on return
+    if (e != hipSuccess) { (void)hipFree(buf); return h->fail(KEEP_EHIP, "position table: %s", hipGetErrorString(e)); }
+    h->pos_cache.push_back({gh, gw, buf});
+    *out = buf;
+    return KEEP_OK;
+}
+
+// the image tower on B tiles of a gh x gw patch grid (arguments checked, device selected by the caller)
+int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, float* out, hipStream_t s, int gh = 14, int gw = 14) {
+    const int ntok = gh * gw + 1;
+    const bool g14 = gh == 14 && gw == 14;
+    const float* pos = nullptr;
+    int rc = vit_pos_table(h, gh, gw, &pos);            // outside any capture: it may allocate
+    if (rc) return rc;
+    const size_t px = pix_dtype == KEEP_PIX_F32 ? 4 : (pix_dtype == KEEP_PIX_U8_HWC ? 1 : 2);    // bytes per value; 3 * 16 gh * 16 gw values per tile in every layout
+    const size_t tile_vals = (size_t)3 * (gh * 16) * (gw * 16);
+    if (h->use_graphs && !h->prof_mode && B * ntok <= SKINNY_MAX_M && B <= h->max_tiles) {
         const bool sp = h->any_split();
-        const size_t ws_bytes = align_up(vit_ws_bytes(h, B, sp)), ib = (size_t)B * 3 * 224 * 224 * pxb, ob = (size_t)B * h->proj_dim * sizeof(float);
-        int rc = ensure_arena(h, ws_bytes + align_up(ib) + align_up(ob));
+        const size_t ws_bytes = align_up(vit_ws_bytes(h, B, sp, ntok)), ib = (size_t)B * tile_vals * px, ob = (size_t)B * h->proj_dim * sizeof(float);
+        rc = ensure_arena(h, ws_bytes + align_up(ib) + align_up(ob));
         if (rc) return rc;
         char* st_pix = h->arena + ws_bytes;
         float* st_out = (float*)(h->arena + ws_bytes + align_up(ib));
         HIPCHK(h, hipMemcpyAsync(st_pix, pixels, ib, hipMemcpyDeviceToDevice, s));
         char key[96];
-        snprintf(key, sizeof key, "img|%lld|%d|%d", (long long)B, pix_dtype, h->precision);     // (keep_classify switches the precision per call, without an option epoch)
+        if (g14) snprintf(key, sizeof key, "img|%lld|%d|%d", (long long)B, pix_dtype, h->precision);     // (keep_classify switches the precision per call, without an option epoch)
+        else snprintf(key, sizeof key, "img|%lld|%d|%d|%dx%d", (long long)B, pix_dtype, h->precision, gh, gw);
         rc = graph_run(h, key, s, [&](hipStream_t cs) {
             VitLane L{};
             L.Bc = (int)B; L.pixels = st_pix; L.pix_dtype = pix_dtype; L.out = st_out; L.s = cs;
-            L.ws = carve_vit(h, h->arena, L.Bc, sp);
+            L.gh = gh; L.gw = gw; L.ntok = ntok; L.pos = pos;
+            L.ws = carve_vit(h, h->arena, L.Bc, sp, ntok);
             int r = vit_begin(h, L);
             for (int i = 0; !r && i < h->vit_depth; ++i) r = vit_layer(h, L, i);
             return r ? r : vit_end(h, L);
@@ -1053,15 +1162,16 @@ int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t 
         HIPCHK(h, hipMemcpyAsync(out, st_out, ob, hipMemcpyDeviceToDevice, s));
         return KEEP_OK;
     }
-    const size_t px = pix_dtype == KEEP_PIX_F32 ? 4 : (pix_dtype == KEEP_PIX_U8_HWC ? 1 : 2);    // bytes per value; 3*224*224 values per tile in every layout
-    // lanes: split the batch over n_streams concurrent sub-batches once there is enough work for each
+    // lanes: split the batch over n_streams concurrent sub-batches once there is enough work for each (in 197-token tile equivalents)
     int lanes = h->n_streams;
-    while (lanes > 1 && B < (int64_t)lanes * h->lane_min_tiles) --lanes;
+    while (lanes > 1 && B * ntok < (int64_t)lanes * h->lane_min_tiles * 197) --lanes;
     int64_t per = (B + lanes - 1) / lanes;
-    if (per > h->max_tiles) per = h->max_tiles;
+    // sub-batches are bounded in tokens: per * ntok <= max_tiles * 197 (a 512 x 512 call needs the arena of a 224 x 224 one)
+    const int64_t per_max = std::max<int64_t>((int64_t)h->max_tiles * 197 / ntok, 1);
+    if (per > per_max) per = per_max;
     const bool split = h->any_split();
-    const size_t lane_bytes = align_up(vit_ws_bytes(h, per, split));
-    int rc = ensure_arena(h, lane_bytes * lanes);
+    const size_t lane_bytes = align_up(vit_ws_bytes(h, per, split, ntok));
+    rc = ensure_arena(h, lane_bytes * lanes);
     if (rc) return rc;
     if (lanes > 1) {
         if (!h->ev_fork) HIPCHK(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
@@ -1080,11 +1190,12 @@ int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t 
             if (lo >= B) break;
             VitLane& x = L[nl++];
             x.Bc = (int)((B - lo) < per ? (B - lo) : per);
-            x.pixels = (const char*)pixels + (size_t)lo * 3 * 224 * 224 * px;
+            x.pixels = (const char*)pixels + (size_t)lo * tile_vals * px;
             x.pix_dtype = pix_dtype;
             x.out = out + lo * h->proj_dim;
             x.s = lanes > 1 ? h->aux[l] : s;
-            x.ws = carve_vit(h, h->arena + (size_t)l * lane_bytes, x.Bc, split);
+            x.gh = gh; x.gw = gw; x.ntok = ntok; x.pos = pos;
+            x.ws = carve_vit(h, h->arena + (size_t)l * lane_bytes, x.Bc, split, ntok);
         }
         for (int l = 0; l < nl; ++l) if ((rc = vit_begin(h, L[l]))) return rc;
         for (int i = 0; i < h->vit_depth; ++i)
@@ -1168,6 +1279,7 @@ int keep_destroy(keep_handle* h) {
     if (h->tune.dbg) hipFree(h->tune.dbg);
     for (float* v : h->owned_vecs) hipFree(v);
     h->free_cal();
+    h->drop_pos_cache();
     for (auto& l : h->blayers) { if (l.qkv.hi) hipFree(l.qkv.hi); if (l.qkv.lo) hipFree(l.qkv.lo); if (l.qkv_b) hipFree(l.qkv_b); }
     drop_graphs(h);
     if (h->cap_stream) hipStreamDestroy(h->cap_stream);
@@ -1196,6 +1308,7 @@ int keep_load_tensor(keep_handle* h, const char* key, const float* data, int ndi
     const std::string k(key);
     if (k == "text.embeddings.position_ids" || k == "text.embeddings.token_type_ids") return KEEP_OK;   // buffers of older checkpoints
     if (!known_key(k)) return h->fail(KEEP_EKEY, "unexpected key %s", key);
+    if (k == "visual.pos_embed") h->drop_pos_cache();
     std::vector<int64_t> shp(shape, shape + ndim);
     if (ndim == 0) shp = {1};
     const int64_t n = numel_of(shp);
@@ -1252,6 +1365,7 @@ int keep_set_option(keep_handle* h, const char* name, double value) {
     else if (n == "max_prompts") { if (v < 1) return h->fail(KEEP_EINVAL, "max_prompts < 1"); h->max_prompts = v; }
     else if (n == "cls_tail") { h->cls_tail = v ? 1 : 0; if (h->bias_ready && h->cal_cls_tail != h->cls_tail) h->bias_ready = false; }   // (the mean-input biases of the last block were averaged under the other setting: recalibrate)
     else if (n == "patch_split") { h->patch_split = v ? 1 : 0; }
+    else if (n == "grid_plan") { if (v < 0 || v > 2) return h->fail(KEEP_EINVAL, "grid_plan must be 0, 1 or 2"); h->grid_plan = v; }
     else if (n == "bias_correction") { h->bias_correction = v ? 1 : 0; }
     else if (n == "proj_impl") { if (v != 0 && v != 2128) return h->fail(KEEP_EINVAL, "proj_impl must be 0 or 2128"); h->proj_impl = v; }
     else if (n == "streams") { if (v < 1 || v > 4) return h->fail(KEEP_EINVAL, "streams must be 1..4"); h->n_streams = v; }
@@ -1307,6 +1421,7 @@ double keep_get_option(keep_handle* h, const char* name) {
     if (n == "cls_tail") return h->cls_tail;
     if (n == "proj_impl") return h->proj_impl;
     if (n == "patch_split") return h->patch_split;
+    if (n == "grid_plan") return h->grid_plan;
     if (n == "bias_correction") return h->bias_correction;
     if (n == "bias_ready") return h->bias_ready ? 1 : 0;
     return -1;
@@ -1362,6 +1477,37 @@ int keep_encode_image(keep_handle* h, const void* pixels, int pix_dtype, int64_t
     if (B == 0) return KEEP_OK;
     KEEP_ON_DEVICE(h);
     return encode_image_run(h, pixels, pix_dtype, B, out, (hipStream_t)stream);
+}
+
+int keep_encode_image_hw(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, int64_t H, int64_t W, float* out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!h->finalized || !h->vit_depth) return h->fail(KEEP_ESTATE, "image tower not loaded / finalised");
+    if (!pixels || !out || B < 0) return h->fail(KEEP_EINVAL, "null pointer or negative batch");
+    if (pix_dtype < KEEP_PIX_F32 || pix_dtype > KEEP_PIX_U8_HWC) return h->fail(KEEP_EINVAL, "pixel dtype %d", pix_dtype);
+    if (H < 16 || W < 16 || H % 16 || W % 16) return h->fail(KEEP_EINVAL, "image size %lldx%lld: H and W must be positive multiples of 16", (long long)H, (long long)W);
+    const int64_t gh = H / 16, gw = W / 16;
+    // 32-bit offsets of the kernels: the qkv rows of one tile (launch_attention_long) and a tile's pixels
+    if (gh * gw + 1 > 65536) return h->fail(KEEP_EUNSUPPORTED, "image size %lldx%lld: more than 65536 patches", (long long)H, (long long)W);
+    if (B == 0) return KEEP_OK;
+    KEEP_ON_DEVICE(h);
+    // the compensated plan is calibrated on 197-token tiles: outside the band its tolerance was measured in, the grid runs strict
+    const int prec = h->precision;
+    if (!(gh == 14 && gw == 14) && !h->grid_keeps_plan((int)(gh * gw + 1)) && prec == KEEP_PREC_COMP) h->precision = KEEP_PREC_STRICT;
+    const int rc = encode_image_run(h, pixels, pix_dtype, B, out, (hipStream_t)stream, (int)gh, (int)gw);
+    h->precision = prec;
+    return rc;
+}
+
+int keep_vit_pos_embed(keep_handle* h, int gh, int gw, float* out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!h->finalized || !h->vit_depth) return h->fail(KEEP_ESTATE, "image tower not loaded / finalised");
+    if (!out || gh < 1 || gw < 1 || (int64_t)gh * gw + 1 > 65536) return h->fail(KEEP_EINVAL, "bad position-table arguments (grid %dx%d)", gh, gw);
+    KEEP_ON_DEVICE(h);
+    const float* pos = nullptr;
+    const int rc = vit_pos_table(h, gh, gw, &pos);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(out, pos, (size_t)(gh * gw + 1) * h->vit_D * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return KEEP_OK;
 }
 
 int keep_encode_text(keep_handle* h, const int64_t* ids, const int64_t* types, const int64_t* mask, int64_t P, int64_t T,
@@ -1874,6 +2020,29 @@ int keep_op_attention(keep_handle* h, const float* qkv, const int64_t* mask, int
     launch_unblockify_f32(o_hi, split ? o_lo : nullptr, out, (int)M, (int)D, s);
     HIPCHK(h, hipStreamSynchronize(s));
     return check_launch(h, "op_attention");
+}
+
+int keep_op_attention_long(keep_handle* h, const float* qkv, int64_t B, int64_t T, int heads, int split, int q_rows, float* out, void* stream) {
+    if (!h || !qkv || !out || B < 1 || T < 1 || heads < 1 || q_rows < 0) return h ? h->fail(KEEP_EINVAL, "bad attention arguments") : KEEP_EINVAL;
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t M = B * T, D = (int64_t)heads * 64;
+    Tmp t;
+    f16* q_hi = t.get<f16>(M * 3 * D); f16* q_lo = t.get<f16>(M * 3 * D);
+    const size_t oe = blk_elems(M, D);
+    f16* o_hi = t.get<f16>(oe); f16* o_lo = t.get<f16>(oe);
+    if (!q_hi || !q_lo || !o_hi || !o_lo) return h->fail(KEEP_ENOMEM, "temp alloc");
+    HIPCHK(h, hipMemsetAsync(o_hi, 0, oe * sizeof(f16), s));      // rows past q_rows read back as 0
+    HIPCHK(h, hipMemsetAsync(o_lo, 0, oe * sizeof(f16), s));
+    launch_split_f16(qkv, q_hi, q_lo, M * 3 * D, s);
+    AttnParams a{};
+    a.tune = &h->tune;
+    a.qkv_hi = q_hi; a.qkv_lo = q_lo; a.out_hi = o_hi; a.out_lo = split ? o_lo : nullptr; a.mask = nullptr;
+    a.batch = (int)B; a.ntok = (int)T; a.heads = heads; a.split = split; a.scale = 0.125f; a.out_kt = (int)(D / 32); a.q_rows = q_rows;
+    if (launch_attention_long(a, s)) return h->fail(KEEP_EUNSUPPORTED, "long attention: B %lld, T %lld, heads %d unsupported", (long long)B, (long long)T, heads);
+    launch_unblockify_f32(o_hi, split ? o_lo : nullptr, out, (int)M, (int)D, s);
+    HIPCHK(h, hipStreamSynchronize(s));
+    return check_launch(h, "op_attention_long");
 }
 
 // Matrix-pipe ceiling probe (keep_mfma_probe): no memory traffic inside the loop; every wave holds 2 A and 4 B fragments of the caller's data in registers and

@@ -141,18 +141,20 @@ void layernorm_blk_kernel(LnParams p) {
 // ------------------------------------------------------------------ im2col for the patch embed
 __device__ __forceinline__ float bf16_to_f32(unsigned short u) { return __uint_as_float((unsigned)u << 16); }
 
-template <int DT>
+// G = 14: the 224 x 224 grid with compile-time extents; G = 0: a gh x gw patch grid (H = 16 gh, W = 16 gw) from the arguments
+template <int DT, int G>
 __global__ __launch_bounds__(256)
-void im2col_kernel(const void* __restrict__ pixels, int B, f16* __restrict__ out_hi, f16* __restrict__ out_lo) {
-    // one work item = 8 consecutive pixels of one image row: (b, c, y, xc) with xc in [0,28)
-    const int64_t total = (int64_t)B * 3 * 224 * 28;
+void im2col_kernel(const void* __restrict__ pixels, int B, int gh_, int gw_, f16* __restrict__ out_hi, f16* __restrict__ out_lo) {
+    const int gh = G ? G : gh_, gw = G ? G : gw_, H = gh * 16, W = gw * 16, XC = gw * 2;
+    // one work item = 8 consecutive pixels of one image row: (b, c, y, xc) with xc in [0, W / 8)
+    const int64_t total = (int64_t)B * 3 * H * XC;
     for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < total; it += (int64_t)gridDim.x * 256) {
-        const int xc = (int)(it % 28);
-        int64_t r = it / 28;
-        const int y = (int)(r % 224); r /= 224;
+        const int xc = (int)(it % XC);
+        int64_t r = it / XC;
+        const int y = (int)(r % H); r /= H;
         const int c = (int)(r % 3);
         const int b = (int)(r / 3);
-        const int64_t src = (((int64_t)b * 3 + c) * 224 + y) * 224 + xc * 8;
+        const int64_t src = (((int64_t)b * 3 + c) * H + y) * W + xc * 8;
         float v[8];
         if (DT == PIX_F32) {
             const f32x4 a = *reinterpret_cast<const f32x4*>((const float*)pixels + src);
@@ -173,7 +175,7 @@ void im2col_kernel(const void* __restrict__ pixels, int B, f16* __restrict__ out
             }
         }
         const int py = y >> 4, ph = y & 15, px = xc >> 1, half = xc & 1;
-        const int64_t dst = blk_off(b * 196 + py * 14 + px, c * 256 + ph * 16 + half * 8, 24);
+        const int64_t dst = blk_off(b * (gh * gw) + py * gw + px, c * 256 + ph * 16 + half * 8, 24);
         f16x8 h, l;
 #pragma unroll
         for (int e = 0; e < 8; ++e) { f16 hh, ll; split_f16(v[e], hh, ll); h[e] = hh; l[e] = ll; }
@@ -182,19 +184,21 @@ void im2col_kernel(const void* __restrict__ pixels, int B, f16* __restrict__ out
     }
 }
 
-// uint8 HWC tiles [B,224,224,3] (what a tile extractor / PIL delivers after resize + crop): ToTensor (/255) and
+// uint8 HWC tiles [B,H,W,3] ([B,224,224,3] at the default grid; what a tile extractor / PIL delivers after resize + crop): ToTensor (/255) and
 // Normalize(ImageNet mean/std) of the reference transform (keep_inference.py:91-92) are applied on the fly,
 // in the same operation order as torchvision: (x / 255 - mean) / std in fp32.
+template <int G>
 __global__ __launch_bounds__(256)
-void im2col_u8_kernel(const unsigned char* __restrict__ pixels, int B, f16* __restrict__ out_hi, f16* __restrict__ out_lo) {
+void im2col_u8_kernel(const unsigned char* __restrict__ pixels, int B, int gh_, int gw_, f16* __restrict__ out_hi, f16* __restrict__ out_lo) {
+    const int gh = G ? G : gh_, gw = G ? G : gw_, H = gh * 16, W = gw * 16, XC = gw * 2;
     // one work item = 8 consecutive pixels (24 bytes) of one image row: (b, y, xc)
-    const int64_t total = (int64_t)B * 224 * 28;
+    const int64_t total = (int64_t)B * H * XC;
     const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
     for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < total; it += (int64_t)gridDim.x * 256) {
-        const int xc = (int)(it % 28);
-        const int64_t r = it / 28;
-        const int y = (int)(r % 224), b = (int)(r / 224);
-        const unsigned char* src = pixels + (((int64_t)b * 224 + y) * 224 + xc * 8) * 3;
+        const int xc = (int)(it % XC);
+        const int64_t r = it / XC;
+        const int y = (int)(r % H), b = (int)(r / H);
+        const unsigned char* src = pixels + (((int64_t)b * H + y) * W + xc * 8) * 3;
         const uint2 w0 = *reinterpret_cast<const uint2*>(src);          // 24 bytes = 3 x 8-byte loads (8-byte aligned: 24 | offset)
         const uint2 w1 = *reinterpret_cast<const uint2*>(src + 8);
         const uint2 w2 = *reinterpret_cast<const uint2*>(src + 16);
@@ -210,7 +214,7 @@ void im2col_u8_kernel(const unsigned char* __restrict__ pixels, int B, f16* __re
                 const float v = (u / 255.0f - mean[c]) / stdv[c];
                 f16 hh, ll; split_f16(v, hh, ll); h[e] = hh; l[e] = ll;
             }
-            const int64_t dst = blk_off(b * 196 + py * 14 + px, c * 256 + ph * 16 + half * 8, 24);
+            const int64_t dst = blk_off(b * (gh * gw) + py * gw + px, c * 256 + ph * 16 + half * 8, 24);
             *reinterpret_cast<f16x8*>(out_hi + dst) = h;
             if (out_lo) *reinterpret_cast<f16x8*>(out_lo + dst) = l;
         }
@@ -584,20 +588,62 @@ int launch_layernorm(const LnParams& p, hipStream_t s) {
     return 0;
 }
 
-void launch_im2col(const void* pixels, int dtype, int B, f16* out_hi, f16* out_lo,
+void launch_im2col(const void* pixels, int dtype, int B, int gh, int gw, f16* out_hi, f16* out_lo,
                    const float* cls, const float* pos, float* resid, int D, hipStream_t s) {
-    const int64_t total = (int64_t)B * 3 * 224 * 28;
+    const bool g14 = gh == 14 && gw == 14;        // the 224 x 224 grid keeps its compile-time kernels
+    const int64_t total = (int64_t)B * 3 * (gh * 16) * (gw * 2);
     int blocks = (int)((total + 255) / 256);
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (dtype == PIX_U8_HWC) {
-        const int64_t t8 = (int64_t)B * 224 * 28;
+        const int64_t t8 = (int64_t)B * (gh * 16) * (gw * 2);
         int b8 = (int)((t8 + 255) / 256); if (b8 > 256 * 16) b8 = 256 * 16;
-        hipLaunchKernelGGL(im2col_u8_kernel, dim3(b8), dim3(256), 0, s, (const unsigned char*)pixels, B, out_hi, out_lo);
-    } else if (dtype == PIX_F32) hipLaunchKernelGGL(im2col_kernel<PIX_F32>, dim3(blocks), dim3(256), 0, s, pixels, B, out_hi, out_lo);
-    else if (dtype == PIX_F16) hipLaunchKernelGGL(im2col_kernel<PIX_F16>, dim3(blocks), dim3(256), 0, s, pixels, B, out_hi, out_lo);
-    else hipLaunchKernelGGL(im2col_kernel<PIX_BF16>, dim3(blocks), dim3(256), 0, s, pixels, B, out_hi, out_lo);
+        if (g14) hipLaunchKernelGGL(im2col_u8_kernel<14>, dim3(b8), dim3(256), 0, s, (const unsigned char*)pixels, B, gh, gw, out_hi, out_lo);
+        else hipLaunchKernelGGL(im2col_u8_kernel<0>, dim3(b8), dim3(256), 0, s, (const unsigned char*)pixels, B, gh, gw, out_hi, out_lo);
+    } else if (g14) {
+        if (dtype == PIX_F32) hipLaunchKernelGGL((im2col_kernel<PIX_F32, 14>), dim3(blocks), dim3(256), 0, s, pixels, B, gh, gw, out_hi, out_lo);
+        else if (dtype == PIX_F16) hipLaunchKernelGGL((im2col_kernel<PIX_F16, 14>), dim3(blocks), dim3(256), 0, s, pixels, B, gh, gw, out_hi, out_lo);
+        else hipLaunchKernelGGL((im2col_kernel<PIX_BF16, 14>), dim3(blocks), dim3(256), 0, s, pixels, B, gh, gw, out_hi, out_lo);
+    } else {
+        if (dtype == PIX_F32) hipLaunchKernelGGL((im2col_kernel<PIX_F32, 0>), dim3(blocks), dim3(256), 0, s, pixels, B, gh, gw, out_hi, out_lo);
+        else if (dtype == PIX_F16) hipLaunchKernelGGL((im2col_kernel<PIX_F16, 0>), dim3(blocks), dim3(256), 0, s, pixels, B, gh, gw, out_hi, out_lo);
+        else hipLaunchKernelGGL((im2col_kernel<PIX_BF16, 0>), dim3(blocks), dim3(256), 0, s, pixels, B, gh, gw, out_hi, out_lo);
+    }
     const int64_t n = (int64_t)B * D;
-    hipLaunchKernelGGL(cls_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, cls, pos, resid, B, D, 197);
+    hipLaunchKernelGGL(cls_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, cls, pos, resid, B, D, gh * gw + 1);
+}
+
+// timm resample_abs_pos_embed (bicubic, antialias) as two separable weight tables built on the host in double precision (engine.hip:
+// vit_pos_table); one thread per output element, accumulated in double and rounded once.  Load-time work: off the hot path.
+__global__ __launch_bounds__(256)
+void pos_resample_kernel(const float* __restrict__ pos, int gs, int D, int gh, int gw, const int* __restrict__ ybeg, const double* __restrict__ wy,
+                         int ytaps, const int* __restrict__ xbeg, const double* __restrict__ wx, int xtaps, float* __restrict__ out) {
+    const int64_t total = (int64_t)(gh * gw + 1) * D;
+    for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < total; it += (int64_t)gridDim.x * 256) {
+        const int d = (int)(it % D), row = (int)(it / D);
+        if (row == 0) { out[it] = pos[d]; continue; }
+        const int y = (row - 1) / gw, x = (row - 1) - y * gw;
+        double acc = 0.0;
+        for (int i = 0; i < ytaps; ++i) {
+            const double a = wy[(int64_t)y * ytaps + i];
+            if (a == 0.0) continue;
+            const int sy = ybeg[y] + i;
+            double rsum = 0.0;
+            for (int j = 0; j < xtaps; ++j) {
+                const double b = wx[(int64_t)x * xtaps + j];
+                if (b != 0.0) rsum += b * (double)pos[(int64_t)(1 + sy * gs + xbeg[x] + j) * D + d];
+            }
+            acc += a * rsum;
+        }
+        out[it] = (float)acc;
+    }
+}
+
+void launch_pos_resample(const float* pos, int gs, int D, int gh, int gw, const int* ybeg, const double* wy, int ytaps,
+                         const int* xbeg, const double* wx, int xtaps, float* out, hipStream_t s) {
+    const int64_t total = (int64_t)(gh * gw + 1) * D;
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(pos_resample_kernel, dim3(blocks), dim3(256), 0, s, pos, gs, D, gh, gw, ybeg, wy, ytaps, xbeg, wx, xtaps, out);
 }
 
 void launch_resize_crop_u8(const unsigned char* src, int B, int H, int W, const int* xb, const int* xk, int xks, int col0, int ncols,

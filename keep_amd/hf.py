@@ -43,7 +43,8 @@ def _from_config(cls, config, **kwargs):
     kwargs.pop("torch_dtype", None)
     kwargs.pop("dtype", None)
     shape = config.to_shape() if isinstance(config, KEEPConfig) else KEEPShape.from_config_json(config.to_dict())
-    model = cls(shape, precision=kwargs.pop("precision", DEFAULT_PRECISION), towers=kwargs.pop("towers", ("image", "text")))
+    model = cls(shape, precision=kwargs.pop("precision", DEFAULT_PRECISION), towers=kwargs.pop("towers", ("image", "text")),
+                dynamic_img_size=kwargs.pop("dynamic_img_size", False))
     model.hf_config = config
     return model
 

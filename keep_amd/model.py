@@ -171,12 +171,16 @@ class KEEPModel:
     _live: "List[weakref.ref]" = []
 
     def __init__(self, config: Optional[Union[KEEPShape, Mapping, str]] = None, precision: str = DEFAULT_PRECISION,
-                 towers=("image", "text")):
+                 towers=("image", "text"), dynamic_img_size: bool = False):
         if config is None:
             config = KEEPShape()
         elif not isinstance(config, KEEPShape):
             config = KEEPShape.from_config_json(config)
         self.config = config
+        # timm's dynamic_img_size (keep_inference.py:32-40 builds the ViT with it): True = encode_image / encode_image_uint8 / forward take tiles of
+        # any H, W that are multiples of 16 (one size per call; the position embedding is resampled to the patch grid, keep_encode_image_hw).
+        # False (default) = 224 x 224 only, as before.  classify, encode_image_raw and the WSI functions stay 224-only either way.
+        self.dynamic_img_size = bool(dynamic_img_size)
         # nn.Parameter(torch.ones([]) * log(1/0.04)) -- keep_inference.py:52 (never applied at inference)
         self.logit_scale = torch.tensor(config.logit_scale_init, dtype=torch.float32)
         self.training = False
@@ -369,7 +373,8 @@ class KEEPModel:
         the local-files equivalent of ``AutoModel.from_pretrained`` at zeroshot_subtyping_WSI.py:44."""
         cfg_path = os.path.join(path, "config.json")
         config = KEEPShape.from_config_json(cfg_path) if os.path.exists(cfg_path) else KEEPShape()
-        model = cls(config, precision=precision, towers=_ignored.pop("towers", ("image", "text")))
+        model = cls(config, precision=precision, towers=_ignored.pop("towers", ("image", "text")),
+                    dynamic_img_size=_ignored.pop("dynamic_img_size", False))
         st = os.path.join(path, "model.safetensors")
         pt = os.path.join(path, "pytorch_model.bin")
         if os.path.exists(st):
@@ -834,16 +839,25 @@ class KEEPModel:
                 raise _lib.KeepHipError("no weights loaded: call load_state_dict / from_pretrained first")
 
     # ------------------------------------------------------------------ the hot path
+    def _check_hw(self, H: int, W: int, layout: str):
+        """The tile-size rule: 224 x 224, or with dynamic_img_size any positive multiple of 16 in both directions."""
+        if self.dynamic_img_size:
+            if H < 16 or W < 16 or H % 16 or W % 16:
+                raise ValueError(f"dynamic_img_size: H and W must be positive multiples of 16 (the patch size), got {layout} with "
+                                 f"H={H}, W={W}")
+        elif H != 224 or W != 224:
+            raise ValueError(f"only 224x224 tiles are supported, got {layout} (KEEPModel(..., dynamic_img_size=True) accepts any "
+                             "multiple of 16, as the reference's timm dynamic_img_size does)")
+
     @torch.no_grad()
     def encode_image(self, image_inputs: torch.Tensor) -> torch.Tensor:
-        """keep_inference.py:54-58: normalize(visual_head(visual(x)), dim=-1) -> [B, 768] fp32."""
+        """keep_inference.py:54-58: normalize(visual_head(visual(x)), dim=-1) -> [B, 768] fp32.
+        x: [B,3,224,224]; with ``dynamic_img_size`` [B,3,H,W], H and W multiples of 16."""
         self._ready()
         x = image_inputs
         if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError(f"expected [B,3,224,224], got {tuple(x.shape)}")
-        if x.shape[2] != 224 or x.shape[3] != 224:
-            raise ValueError("only 224x224 tiles are supported (the reference would resample pos_embed via "
-                             "timm dynamic_img_size; every reference caller feeds 224x224)")
+            raise ValueError(f"expected [B,3,H,W], got {tuple(x.shape)}")
+        self._check_hw(int(x.shape[2]), int(x.shape[3]), f"[B,3,H,W] = {tuple(x.shape)}")
         if x.dtype not in _PIX:
             x = x.to(torch.float32)
         src_dev = x.device
@@ -851,15 +865,19 @@ class KEEPModel:
             return torch.empty((0, self.config.projection_dim), dtype=torch.float32, device=src_dev)
         xd = x.to(self._device, non_blocking=True).contiguous()
         out = torch.empty((xd.shape[0], self.config.projection_dim), dtype=torch.float32, device=self._device)
-        lib = _lib.load()
-        _lib.check(self._handle, lib.keep_encode_image(self._handle, _ptr(xd), _PIX[xd.dtype], xd.shape[0], _ptr(out),
-                                                       _stream(self._device)), "encode_image")
+        _lib.check(self._handle, self._encode(xd, _PIX[xd.dtype], xd.shape[2], xd.shape[3], out), "encode_image")
         self._queue_flag_check(_stream(self._device))
         if src_dev == self._device:
             return out
         res = out.to(src_dev)
         self.check_errors(wait=True)
         return res
+
+    def _encode(self, xd: torch.Tensor, pix: int, H: int, W: int, out: torch.Tensor) -> int:
+        lib = _lib.load()
+        if H == 224 and W == 224:          # the entry point every 224 x 224 call has always taken
+            return lib.keep_encode_image(self._handle, _ptr(xd), pix, xd.shape[0], _ptr(out), _stream(self._device))
+        return lib.keep_encode_image_hw(self._handle, _ptr(xd), pix, xd.shape[0], H, W, _ptr(out), _stream(self._device))
 
     @torch.no_grad()
     def encode_image_uint8(self, tiles_u8: torch.Tensor) -> torch.Tensor:
@@ -868,15 +886,15 @@ class KEEPModel:
         150 KB per tile.  Same result as ``encode_image(normalised_float_tiles)`` up to fp32 rounding."""
         self._ready()
         x = tiles_u8
-        if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (224, 224, 3):
-            raise ValueError(f"expected uint8 [B,224,224,3], got {x.dtype} {tuple(x.shape)}")
+        if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+            raise ValueError(f"expected uint8 [B,H,W,3], got {x.dtype} {tuple(x.shape)}")
+        self._check_hw(int(x.shape[1]), int(x.shape[2]), f"uint8 [B,H,W,3] = {tuple(x.shape)}")
         src_dev = x.device
         if x.shape[0] == 0:
             return torch.empty((0, self.config.projection_dim), dtype=torch.float32, device=src_dev)
         xd = x.to(self._device, non_blocking=True).contiguous()
         out = torch.empty((xd.shape[0], self.config.projection_dim), dtype=torch.float32, device=self._device)
-        _lib.check(self._handle, _lib.load().keep_encode_image(self._handle, _ptr(xd), _lib.PIX_U8_HWC, xd.shape[0], _ptr(out),
-                                                               _stream(self._device)), "encode_image_uint8")
+        _lib.check(self._handle, self._encode(xd, _lib.PIX_U8_HWC, xd.shape[1], xd.shape[2], out), "encode_image_uint8")
         self._queue_flag_check(_stream(self._device))
         if src_dev == self._device:
             return out

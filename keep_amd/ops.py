@@ -80,6 +80,15 @@ class Ops:
         _lib.check(self._h, rc, "op_attention")
         return out
 
+    def attention_long(self, qkv, B, T, heads, split=False, q_rows=0):
+        """The key-blocked attention kernel the image tower runs beyond 512 tokens (any T; no key mask)."""
+        qkv = self._f(qkv)
+        out = torch.empty((B * T, heads * 64), dtype=torch.float32, device=self.device)
+        rc = _lib.load().keep_op_attention_long(self._h, _ptr(qkv), B, T, heads, int(split), int(q_rows), _ptr(out),
+                                                _stream(self.device))
+        _lib.check(self._h, rc, "op_attention_long")
+        return out
+
     def layernorm(self, x, gamma, beta, eps, add=None):
         x, gamma, beta, add = map(self._f, (x, gamma, beta, add))
         out = torch.empty_like(x)
