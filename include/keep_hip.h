@@ -191,6 +191,28 @@ int keep_resize_crop_u8(keep_handle* h, const unsigned char* src, int64_t B, int
                         const int32_t* xweights, int xksize, int64_t out_w, const int32_t* ybounds, const int32_t* yweights, int yksize,
                         int64_t out_h, int64_t crop_left, int64_t crop_top, int64_t size, unsigned char* out, void* stream);
 
+/* ---- slide regions on the device ------------------------------------------
+ * region: uint8 [H,W,C] RGB (pix_stride 3) or RGBA (pix_stride 4, alpha ignored), rows row_stride_bytes apart (>= W * pix_stride,
+ * so a cropped view of a larger image needs no copy).  Grid cells of side `patch` (>= 16) sit at (gx * step, gy * step) for every
+ * cell that lies wholly inside the region, row-major (y outer, x inner).
+ *
+ * Replaces: the CLAM patching + segmentation step the reference's README (README.md:74) runs before any WSI script, i.e. the
+ * tile grid and coords of the CLAM .h5 files.  A pixel is tissue iff max(r,g,b) > 0 and 255 (max - min) >= sat_min max (HSV
+ * saturation >= sat_min, integer-exact); a cell is kept iff it holds >= min_pixels tissue pixels (min_pixels = 0: every cell).
+ * cell_xy_out: int32 [gx * gy, 2] device buffer; its first *n_out rows receive the kept cells' (x, y) pixel offsets in grid order
+ * (stable compaction, deterministic).  n_out: ONE int64 on the device. */
+int keep_region_grid(keep_handle* h, const unsigned char* region, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
+                     int64_t patch, int64_t step, int sat_min, int64_t min_pixels, int32_t* cell_xy_out, int64_t* n_out, void* stream);
+/* Replaces: the host patch cut (openslide read_region per coord + PIL convert("RGB")) and transforms.Resize(224, BICUBIC) +
+ * CenterCrop((224,224)) (quick_start/keep_inference.py:88-90) of every patch.  out: uint8 [B,224,224,3] for
+ * keep_encode_image(..., KEEP_PIX_U8_HWC, ...).  patch == 224: the patches themselves (tables may be NULL); otherwise Pillow's
+ * bicubic resize of the patch to 224 x 224 with the tables of keep_resize_crop_u8 (pil_bicubic_coeffs(patch, 224) for both
+ * axes), bit-identical to PIL.  A cell outside the region is KEEP_EINVAL: the cells are checked on the device and the flag read
+ * back before any pixel is read (one stream synchronisation per call). */
+int keep_region_patches_u8(keep_handle* h, const unsigned char* region, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
+                           const int32_t* cell_xy, int64_t B, int64_t patch, const int32_t* xbounds, const int32_t* xweights, int xksize,
+                           const int32_t* ybounds, const int32_t* yweights, int yksize, unsigned char* out, void* stream);
+
 /* Pre-allocate workspace for calls of up to `tiles` tiles and `prompts` x `seq` tokens. */
 int keep_reserve(keep_handle* h, int64_t tiles, int64_t prompts, int64_t seq);
 int64_t keep_workspace_bytes(keep_handle* h);

@@ -10,6 +10,7 @@
     segment_utils.py:16-42 softmax(10*logits)); ``keep_amd/wsi_evaluation/*_utils.py`` export each of them as ``run``.
   * ``save_slide_features`` writes what ``encode_image`` produced in the same on-disk formats, so feature
     files can be regenerated with this engine instead of the offline CLAM extraction (README.md:74).
+  * ``extract_slide_features`` is that extraction: slide pixels in bands -> ``KEEPModel.encode_region`` -> the feature file.
 """
 from __future__ import annotations
 
@@ -78,6 +79,42 @@ def save_slide_features(data_source: str, slide_id: str, features: torch.Tensor,
         path = os.path.join(data_source, "pt_files", slide_id + ".pt")
         torch.save(f, path)
     return path
+
+
+@torch.no_grad()
+def extract_slide_features(read_region, width: int, height: int, slide_id: str, data_source: str, patch_size: int = 256,
+                           step: Optional[int] = None, tissue=None, band_rows: int = 8, coord_scale: int = 1, use_h5: bool = False,
+                           model=None) -> str:
+    """The feature files the WSI scripts read, made on the device (replaces the CLAM extraction step of README.md:74).
+
+    ``read_region(x, y, w, h)`` returns uint8 [h, w, 3 | 4] pixels of the slide level being tiled, ``width`` x ``height`` pixels
+    in all; with openslide, for example::
+
+        ds = int(slide.level_downsamples[level])
+        read_region = lambda x, y, w, h: np.asarray(slide.read_region((x * ds, y * ds), level, (w, h)))   # RGBA; alpha is ignored
+        extract_slide_features(read_region, *slide.level_dimensions[level], slide_id, out_dir, coord_scale=ds, model=m)
+
+    The slide is walked in horizontal bands of ``band_rows`` grid rows (keep_amd.region.plan_bands); each band goes through
+    ``model.encode_region(band, patch_size, step, tissue, origin=(0, y0), coord_scale)``, so every grid cell is encoded exactly once
+    and the rows come out in the slide's row-major grid order.  The features (and, with ``use_h5``, the level-0 coords) are
+    written by :func:`save_slide_features`; returns its path."""
+    from .model import engine_for
+    from .region import check_grid_args, plan_bands
+    patch, step, _, coord_scale = check_grid_args(patch_size, step, (0, 0), coord_scale)
+    bands = plan_bands(width, height, patch, step, band_rows)
+    m = engine_for(model=model)
+    feats, coords = [], []
+    for _, _, y0, h in bands:
+        band = read_region(0, y0, width, h)
+        band = torch.from_numpy(np.ascontiguousarray(band)) if not isinstance(band, torch.Tensor) else band
+        if band.dim() != 3 or tuple(band.shape[:2]) != (h, width):
+            raise ValueError(f"read_region(0, {y0}, {width}, {h}) returned {tuple(band.shape)}, expected [{h}, {width}, 3|4]")
+        f, c = m.encode_region(band, patch, step, tissue, origin=(0, y0), coord_scale=coord_scale)
+        feats.append(f.cpu())
+        coords.append(c.cpu())
+    features = torch.cat(feats) if feats else torch.empty((0, m.config.projection_dim), dtype=torch.float32)
+    xy = torch.cat(coords) if coords else torch.empty((0, 2), dtype=torch.int64)
+    return save_slide_features(data_source, slide_id, features, xy.numpy(), use_h5=use_h5)
 
 
 def _loop(model, classifier: torch.Tensor, dataloader, device, softmax: bool, want_targets: bool):

@@ -30,6 +30,11 @@ __device__ __forceinline__ void split_f16(float x, f16& hi, f16& lo) {
 }
 
 // Exact (erf) GELU: timm nn.GELU and HF hidden_act="gelu".
+// Pillow's 8-bit resample: 22-bit fixed-point accumulator (started at 1 << 21 for rounding) -> uint8 (rowops.hip, region.hip)
+__device__ __forceinline__ unsigned char clip8_fixed(int v) {
+    v >>= 22;
+    return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
 __device__ __forceinline__ float gelu_erf(float x) {
     return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
 }
@@ -199,6 +204,17 @@ struct SgemmParams {
 };
 int launch_sgemm_f32(const SgemmParams& p, hipStream_t s);
 
+// Slide-region front end (region.hip): patch grid + tissue rule + stable compaction, patch gather.
+// keep: ncells bytes, counts / offsets: ceil(ncells / 2048) ints each; tmp (patch != 224): B * patch * 224 * 3 bytes
+void launch_region_grid(const unsigned char* region, int64_t row_stride, int ps, int gx, int64_t ncells, int patch, int step, int sat_min,
+                        int min_pixels, unsigned char* keep, int* counts, int* offsets, int32_t* cell_xy, int64_t* n_out, hipStream_t s);
+void launch_region_check_cells(const int32_t* cell_xy, int B, int64_t H, int64_t W, int patch, int* bad, hipStream_t s);   // *bad = 1 if a cell is outside
+void launch_region_patches_u8(const unsigned char* region, int64_t row_stride, int ps, const int32_t* cell_xy, int B, int patch,
+                              const int* xb, const int* xk, int xks, const int* yb, const int* yk, int yks, unsigned char* tmp,
+                              unsigned char* out, hipStream_t s);
+constexpr int REGION_MAX_PATCH = 32768;
+constexpr int REGION_GRID_CHUNK = 2048;                 // cells per block of the compaction
+
 // Row-wise helpers (rowops.hip)
 // pixels [B,3,16 gh,16 gw] (or uint8 [B,16 gh,16 gw,3]) -> patches [B * gh * gw][768], row-major (y, x) patch order; CLS rows of resid
 void launch_im2col(const void* pixels, int dtype, int B, int gh, int gw, f16* out_hi, f16* out_lo,      // out in blk layout (KT = 24)
@@ -210,6 +226,9 @@ void launch_pos_resample(const float* pos, int gs, int D, int gh, int gw, const 
 // Pillow-exact bicubic Resize + CenterCrop of raw uint8 HWC images (weights / windows from keep_amd/preprocess.py)
 void launch_resize_crop_u8(const unsigned char* src, int B, int H, int W, const int* xb, const int* xk, int xks, int col0, int ncols,
                            const int* yb, const int* yk, int yks, int row0, int nrows, unsigned char* tmp, unsigned char* out, hipStream_t s);
+// the vertical pass alone: tmp [B,H,ncols,3] (already resized horizontally) -> out [B,nrows,ncols,3], output rows row0.. of the table
+void launch_resize_v_u8(const unsigned char* tmp, int B, int H, int ncols, const int* yb, const int* yk, int yks, int row0, int nrows,
+                        unsigned char* out, hipStream_t s);
 void launch_split_f16(const float* src, f16* hi, f16* lo, int64_t n, hipStream_t s);
 // row-major fp32 [M][K] -> blk-layout fp16 hi (+lo); rows M..pad are zero-filled
 void launch_split_blockify(const float* src, f16* hi, f16* lo, int M, int K, hipStream_t s);

@@ -1635,6 +1635,79 @@ int keep_resize_crop_u8(keep_handle* h, const unsigned char* src, int64_t B, int
     return check_launch(h, "resize_crop_u8");
 }
 
+static int region_view_check(keep_handle* h, const unsigned char* region, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
+                             int64_t patch) {
+    if (!region || H < 1 || W < 1) return h->fail(KEEP_EINVAL, "region: null pointer or empty shape %lldx%lld", (long long)H, (long long)W);
+    if (pix_stride != 3 && pix_stride != 4) return h->fail(KEEP_EINVAL, "region: pixel stride %d (3 = RGB, 4 = RGBA)", pix_stride);
+    if (W > INT32_MAX || H > INT32_MAX || row_stride_bytes < W * pix_stride)
+        return h->fail(KEEP_EINVAL, "region: row stride %lld bytes < width %lld x pixel stride %d (or a side >= 2^31)", (long long)row_stride_bytes,
+                       (long long)W, pix_stride);
+    if (patch < 16 || patch > REGION_MAX_PATCH) return h->fail(KEEP_EINVAL, "region: patch %lld outside [16, %d]", (long long)patch, REGION_MAX_PATCH);
+    return KEEP_OK;
+}
+
+int keep_region_grid(keep_handle* h, const unsigned char* region, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride, int64_t patch,
+                     int64_t step, int sat_min, int64_t min_pixels, int32_t* cell_xy_out, int64_t* n_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    int rc = region_view_check(h, region, H, W, row_stride_bytes, pix_stride, patch);
+    if (rc) return rc;
+    if (step < 1) return h->fail(KEEP_EINVAL, "region_grid: step %lld < 1", (long long)step);
+    if (sat_min < 0 || sat_min > 255) return h->fail(KEEP_EINVAL, "region_grid: sat_min %d outside [0, 255]", sat_min);
+    if (min_pixels < 0 || min_pixels > patch * patch)
+        return h->fail(KEEP_EINVAL, "region_grid: min_pixels %lld outside [0, patch^2 = %lld]", (long long)min_pixels, (long long)(patch * patch));
+    if (!cell_xy_out || !n_out) return h->fail(KEEP_EINVAL, "region_grid: null output");
+    const int64_t gx = W >= patch ? (W - patch) / step + 1 : 0, gy = H >= patch ? (H - patch) / step + 1 : 0;
+    const int64_t ncells = gx * gy;
+    if (ncells > INT32_MAX) return h->fail(KEEP_EINVAL, "region_grid: %lld cells (limit 2^31 - 1)", (long long)ncells);
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (ncells == 0) {
+        HIPCHK(h, hipMemsetAsync(n_out, 0, sizeof(int64_t), s));
+        return KEEP_OK;
+    }
+    const int64_t nb = (ncells + REGION_GRID_CHUNK - 1) / REGION_GRID_CHUNK;
+    const size_t b_keep = align_up((size_t)ncells), b_counts = align_up((size_t)nb * 4);
+    rc = ensure_arena(h, b_keep + 2 * b_counts);
+    if (rc) return rc;
+    launch_region_grid(region, row_stride_bytes, pix_stride, (int)gx, ncells, (int)patch, (int)step, sat_min, (int)min_pixels,
+                       (unsigned char*)h->arena, (int*)(h->arena + b_keep), (int*)(h->arena + b_keep + b_counts), cell_xy_out, n_out, s);
+    return check_launch(h, "region_grid");
+}
+
+int keep_region_patches_u8(keep_handle* h, const unsigned char* region, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
+                           const int32_t* cell_xy, int64_t B, int64_t patch, const int32_t* xbounds, const int32_t* xweights, int xksize,
+                           const int32_t* ybounds, const int32_t* yweights, int yksize, unsigned char* out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    int rc = region_view_check(h, region, H, W, row_stride_bytes, pix_stride, patch);
+    if (rc) return rc;
+    if (B < 0 || B > INT32_MAX / 224 || (B > 0 && (!cell_xy || !out))) return h->fail(KEEP_EINVAL, "region_patches: bad B %lld or null pointer", (long long)B);
+    if (patch != 224 && (!xbounds || !xweights || !ybounds || !yweights || xksize < 1 || yksize < 1))
+        return h->fail(KEEP_EINVAL, "region_patches: patch %lld needs the Resize(224) tables", (long long)patch);
+    if (patch > H || patch > W) return h->fail(KEEP_EINVAL, "region_patches: patch %lld larger than the region %lldx%lld", (long long)patch,
+                                               (long long)W, (long long)H);
+    if (B == 0) return KEEP_OK;
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    // [flag][horizontally resized rows]: the flag is read back before any pixel is touched (the one synchronisation of this call),
+    // so a cell outside the region is an error, not an out-of-bounds read
+    const size_t b_flag = align_up(sizeof(int)), b_tmp = patch == 224 ? 0 : align_up((size_t)B * patch * 224 * 3);
+    rc = ensure_arena(h, b_flag + b_tmp);
+    if (rc) return rc;
+    int* bad = (int*)h->arena;
+    HIPCHK(h, hipMemsetAsync(bad, 0, sizeof(int), s));
+    launch_region_check_cells(cell_xy, (int)B, H, W, (int)patch, bad, s);
+    rc = check_launch(h, "region_check_cells");
+    if (rc) return rc;
+    int bad_h = 0;
+    HIPCHK(h, hipMemcpyAsync(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (bad_h) return h->fail(KEEP_EINVAL, "region_patches: a cell (x, y) has x < 0, y < 0, x + %lld > %lld or y + %lld > %lld", (long long)patch,
+                              (long long)W, (long long)patch, (long long)H);
+    launch_region_patches_u8(region, row_stride_bytes, pix_stride, cell_xy, (int)B, (int)patch, xbounds, xweights, xksize, ybounds, yweights,
+                             yksize, (unsigned char*)h->arena + b_flag, out, s);
+    return check_launch(h, "region_patches_u8");
+}
+
 int keep_token_error(keep_handle* h, void* stream) {
     if (!h) return KEEP_EINVAL;
     KEEP_ON_DEVICE(h);

@@ -445,10 +445,6 @@ void bert_embed_ln_kernel(const int64_t* __restrict__ ids, const int64_t* __rest
 // Pillow's 8-bit resample (what torchvision's Resize runs on PIL inputs, keep_inference.py:88-90): 22-bit fixed-point weights
 // (built on the host in float64 exactly as libImaging does, keep_amd/preprocess.py), horizontal pass -> uint8 -> vertical
 // pass -> uint8; only the columns / rows that survive the centre crop are computed.  Bit-identical to PIL.
-__device__ __forceinline__ unsigned char clip8_fixed(int v) {
-    v >>= 22;
-    return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
 // tmp[b][y][xx][c] = sum_x src[b][y][x0 + x][c] * k[x]     for xx in the cropped column range
 __global__ __launch_bounds__(256)
 void resize_h_u8_kernel(const unsigned char* __restrict__ src, int B, int H, int W, const int* __restrict__ bounds,
@@ -651,6 +647,12 @@ void launch_resize_crop_u8(const unsigned char* src, int B, int H, int W, const 
     auto blocks = [](int64_t n) { int64_t b = (n + 255) / 256; return (unsigned)(b > 65536 ? 65536 : (b < 1 ? 1 : b)); };
     hipLaunchKernelGGL(resize_h_u8_kernel, dim3(blocks((int64_t)B * H * ncols)), dim3(256), 0, s, src, B, H, W, xb, xk, xks, col0, ncols, tmp);
     hipLaunchKernelGGL(resize_v_u8_kernel, dim3(blocks((int64_t)B * nrows * ncols)), dim3(256), 0, s, tmp, B, H, ncols, yb, yk, yks, row0, nrows, out);
+}
+void launch_resize_v_u8(const unsigned char* tmp, int B, int H, int ncols, const int* yb, const int* yk, int yks, int row0, int nrows,
+                        unsigned char* out, hipStream_t s) {
+    int64_t b = ((int64_t)B * nrows * ncols + 255) / 256;
+    b = b > 65536 ? 65536 : (b < 1 ? 1 : b);
+    hipLaunchKernelGGL(resize_v_u8_kernel, dim3((unsigned)b), dim3(256), 0, s, tmp, B, H, ncols, yb, yk, yks, row0, nrows, out);
 }
 void launch_split_f16(const float* src, f16* hi, f16* lo, int64_t n, hipStream_t s) {
     int blocks = (int)((n + 255) / 256);

@@ -942,6 +942,120 @@ class KEEPModel:
         out = self.encode_image_uint8(self.resize_crop_uint8(images_u8.to(self._device)))
         return out if dev_in == self._device else out.to(dev_in)
 
+    # ------------------------------------------------------------------ slide regions
+    @staticmethod
+    def _region_tensor(region) -> torch.Tensor:
+        """uint8 [H,W,3|4] tensor or numpy array, checked on the host (shape / dtype / pixel-stride errors before any device work)."""
+        from .region import region_layout
+        x = torch.from_numpy(region) if not isinstance(region, torch.Tensor) else region
+        region_layout(x)
+        return x
+
+    def _region_on_device(self, x: torch.Tensor) -> Tuple[torch.Tensor, int, int, int, int]:
+        """-> (device view, H, W, C, row_stride_bytes); a device region of any row stride is used in place."""
+        from .region import region_layout
+        if x.device != self._device:
+            x = x.to(self._device)                                 # a cropped host view arrives contiguous
+        H, W, C, row = region_layout(x)
+        return x, H, W, C, row
+
+    def _region_cells(self, xd: torch.Tensor, H: int, W: int, C: int, row: int, patch: int, step: int, sat_min: int,
+                      min_pixels: int) -> torch.Tensor:
+        """keep_region_grid -> the kept cells' (x, y) offsets in the region, int32 [N,2] on the device (reads N back: one sync)."""
+        from .region import grid_shape
+        gy, gx = grid_shape(H, W, patch, step)
+        if gy * gx == 0:
+            return torch.empty((0, 2), dtype=torch.int32, device=self._device)
+        cells = torch.empty((gy * gx, 2), dtype=torch.int32, device=self._device)
+        n = torch.empty((1,), dtype=torch.int64, device=self._device)
+        _lib.check(self._handle, _lib.load().keep_region_grid(self._handle, _ptr(xd), H, W, row, C, patch, step, sat_min, min_pixels,
+                                                              _ptr(cells), _ptr(n), _stream(self._device)), "region_grid")
+        return cells[:int(n.item())]
+
+    def _region_tiles(self, xd: torch.Tensor, H: int, W: int, C: int, row: int, cells: torch.Tensor, patch: int) -> torch.Tensor:
+        """keep_region_patches_u8: int32 [B,2] cells -> uint8 [B,224,224,3] tiles on the device."""
+        from .region import TILE, resize_tables
+        cells = cells.to(self._device, torch.int32).contiguous()
+        B = int(cells.shape[0])
+        out = torch.empty((B, TILE, TILE, 3), dtype=torch.uint8, device=self._device)
+        if patch == TILE:
+            xb = xk = None
+            xks = 0
+        else:
+            xb, xk, xks = resize_tables(patch, self._device)
+        _lib.check(self._handle, _lib.load().keep_region_patches_u8(self._handle, _ptr(xd), H, W, row, C, _ptr(cells), B, patch, _ptr(xb), _ptr(xk),
+                                                                    xks, _ptr(xb), _ptr(xk), xks, _ptr(out), _stream(self._device)),
+                   "region_patches_u8")
+        return out
+
+    @staticmethod
+    def _cells_to_coords(cells: torch.Tensor, origin, coord_scale: int) -> torch.Tensor:
+        o = torch.tensor(origin, dtype=torch.int64, device=cells.device)
+        return (cells.to(torch.int64) + o) * coord_scale
+
+    @torch.no_grad()
+    def region_grid(self, region, patch_size: int = 224, step: Optional[int] = None, tissue=None, origin=(0, 0),
+                    coord_scale: int = 1) -> torch.Tensor:
+        """Patch grid over a uint8 region [H,W,3] (RGB) or [H,W,4] (RGBA, alpha ignored as PIL's ``convert("RGB")`` drops it), host or
+        device, any row stride -> the level-0 coords int64 [N,2] ``(x, y)`` of the kept cells, on the region's device.
+
+        Cells of side ``patch_size`` sit at ``(gx step, gy step)`` (``step`` defaults to ``patch_size``) wherever they lie wholly inside
+        the region, in row-major order; coords are ``(origin + cell offset) * coord_scale`` (the convention of refine_seg / cood2str and
+        the CLAM .h5 files; ``coord_scale`` for a region read at a downsampled level).  ``tissue`` (default off: every cell) is an exact
+        integer rule (keep_amd.region.TissueRule): a pixel is tissue iff ``max(r,g,b) > 0`` and ``255 (max - min) >= sat_min max``, a cell
+        is kept iff it holds ``>= ceil(min_fraction patch^2)`` of them.  This is deliberately NOT CLAM's contour segmentation."""
+        from .region import check_grid_args, tissue_params
+        patch, step, origin, coord_scale = check_grid_args(patch_size, step, origin, coord_scale)
+        sat_min, min_pixels = tissue_params(tissue, patch)
+        x = self._region_tensor(region)
+        self._ready_device()
+        xd, H, W, C, row = self._region_on_device(x)
+        coords = self._cells_to_coords(self._region_cells(xd, H, W, C, row, patch, step, sat_min, min_pixels), origin, coord_scale)
+        return coords if x.device == self._device else coords.to(x.device)
+
+    @torch.no_grad()
+    def region_patches_uint8(self, region, coords: torch.Tensor, patch_size: int, origin=(0, 0), coord_scale: int = 1) -> torch.Tensor:
+        """The tiles of ``coords`` (as :meth:`region_grid` returns them, same ``origin`` / ``coord_scale``) cut from ``region`` on the
+        device -> uint8 [N,224,224,3]: the patches themselves at ``patch_size == 224``, else the reference transform's
+        ``Resize(224, BICUBIC)`` + ``CenterCrop(224)`` of each patch, bit-identical to PIL.  A coord outside the region is a ValueError."""
+        from .region import check_grid_args
+        patch, _, origin, coord_scale = check_grid_args(patch_size, None, origin, coord_scale)
+        coords = torch.as_tensor(coords)
+        if coords.dim() != 2 or coords.shape[1] != 2:
+            raise ValueError(f"coords must be [N,2] (x, y), got {tuple(coords.shape)}")
+        x = self._region_tensor(region)
+        self._ready_device()
+        xd, H, W, C, row = self._region_on_device(x)
+        c = coords.to(self._device, torch.int64)
+        cells = (torch.div(c, coord_scale, rounding_mode="floor") - torch.tensor(origin, dtype=torch.int64, device=self._device))
+        cells = cells.clamp(-(1 << 31), (1 << 31) - 1).to(torch.int32)          # out of int32 range stays outside the region
+        out = self._region_tiles(xd, H, W, C, row, cells, patch)
+        return out if x.device == self._device else out.to(x.device)
+
+    @torch.no_grad()
+    def encode_region(self, region, patch_size: int = 224, step: Optional[int] = None, tissue=None, origin=(0, 0), coord_scale: int = 1,
+                      batch: int = 256) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Slide pixels in, what the WSI functions take out: the grid of :meth:`region_grid`, the tiles of
+        :meth:`region_patches_uint8` and :meth:`encode_image_uint8`, ``batch`` tiles at a time -> (features fp32 [N,768],
+        coords int64 [N,2]) on the region's device; ``[0,768]`` / ``[0,2]`` when no cell is kept."""
+        from .region import check_grid_args, tissue_params
+        patch, step, origin, coord_scale = check_grid_args(patch_size, step, origin, coord_scale)
+        sat_min, min_pixels = tissue_params(tissue, patch)
+        if isinstance(batch, bool) or int(batch) != batch or batch < 1:
+            raise ValueError(f"batch must be an integer >= 1, got {batch!r}")
+        x = self._region_tensor(region)
+        self._ready()
+        xd, H, W, C, row = self._region_on_device(x)
+        cells = self._region_cells(xd, H, W, C, row, patch, step, sat_min, min_pixels)
+        N = int(cells.shape[0])
+        feats = torch.empty((N, self.config.projection_dim), dtype=torch.float32, device=self._device)
+        for i in range(0, N, int(batch)):
+            feats[i:i + batch] = self.encode_image_uint8(self._region_tiles(xd, H, W, C, row, cells[i:i + batch], patch))
+        coords = self._cells_to_coords(cells, origin, coord_scale)
+        if x.device == self._device:
+            return feats, coords
+        return feats.to(x.device), coords.to(x.device)
+
     @torch.no_grad()
     def encode_text(self, text_inputs: Mapping[str, torch.Tensor]) -> torch.Tensor:
         """keep_inference.py:60-62: normalize(text(**inputs).pooler_output, dim=-1) -> [P, 768] fp32."""
