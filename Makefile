@@ -13,7 +13,7 @@ test-gpu: build   ## HIP path vs oracle (needs an MI355X)
 	$(PY) -m pytest tests -q -m gpu
 
 bench: build      ## one JSON line: tiles/s + roofline + parity + CPU baseline
-	$(PY) bench.py
+	$(PY) bench.py --full
 
 smoke: build
 	$(PY) __graft_entry__.py --smoke

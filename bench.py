@@ -6,14 +6,19 @@
     python bench.py ... --dump-outputs DIR            (also writes what the last timed step returned: DIR/features.npy, float32)
     python bench.py --gpus N ...                      (starts the N ranks itself: re-executes under torch.distributed.run, one rank per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...        (the same, launched from outside)
+    python bench.py ... --full                        (also runs every other leg below; --no-<leg> leaves one out)
 
 One step = KEEPModel.encode_image on one batch of 256 device-resident tiles per rank (+ the RCCL
 all-gather of the [256,768] embeddings when N > 1: the slide-level pooling exchange of config 4).
 Rank 0 prints ONE JSON line.  `value` is measured over exactly --steps steps, in the DEFAULT precision mode
-('comp': the fastest mode whose cosines stay within the 1e-4 reference tolerance); on top of that contract the line carries
+('comp': the fastest mode whose cosines stay within the 1e-4 reference tolerance).  A plain run sets up (load-time calibration
+included), warms up, times the steps and prints the line: the contract, the settings, the calibration and, from inside the timed
+region, the dominant kernel's two-lane figures (`roofline.in_timed_region_two_lane`, `roofline.frac_end_to_end`).  With --full
+the line also carries
   sustained   the same step repeated for >= 10 s (the part runs at its power cap; a sub-second burst is not a sustained rate)
   roofline    the time-dominant kernel (the persistent fp32-residual GEMM: vit.proj + vit.fc2), HIP-event timed on one stream with nothing
-              else on the GPU (a KERNEL figure); the same launches inside the two-lane timed region under a separate key; every other kernel
+              else on the GPU (a KERNEL figure); every other kernel; the effective shader clock; what the matrix pipes alone sustain
+  breakdown   every profile tag's time in that single-stream pass (`breakdown_ms_per_step_single_stream`)
   parity      BASELINE config 3 (4096 tiles x 64 prompts through both towers, similarity + argmax) against the committed
               fp32-oracle fixture tests/golden/c3_dual_tower.npz: 262 144 cosines, match-rate, argmax agreement
   configs     c3 (dual tower), c4 (100 000-tile slides: every cosine of the benched setting against the split-product mode, screening scores,
@@ -21,6 +26,7 @@ Rank 0 prints ONE JSON line.  `value` is measured over exactly --steps steps, in
               background -- not the N(0,1) pixels the headline is timed on) and c5 (100 000-tile x 2-class fp16 probability map, all of it
               against the oracle)
   cpu_baseline  the oracle's encode_image and encode_text on the host cores (bounded samples)
+  exchange    at N > 1: the same steps timed without the all-gather, i.e. what the exchange costs on the critical path
 """
 from __future__ import annotations
 
@@ -539,6 +545,9 @@ def main():
     ap.add_argument("--precision", default="comp", choices=["comp", "fp16", "strict"])
     ap.add_argument("--pixel-dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--opt", action="append", default=[], help="engine option name=value (e.g. comp_mlp_blocks=8)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every other leg: sustained rate and shader clock, single-stream breakdown and "
+                                                        "roofline, matrix-pipe ceiling, configs 3 / 4 / 5 with their parity checks, CPU baseline, the exchange cost at "
+                                                        "N > 1 (the --no-* options below leave legs of a --full run out)")
     ap.add_argument("--sustain-seconds", type=float, default=10.0)
     ap.add_argument("--no-sustained", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -589,7 +598,7 @@ def main():
     log(f"start: world={world} cpus={usable_cpus()} (os.cpu_count={os.cpu_count()})")
     torch.set_num_threads(min(usable_cpus(), 16))
     shape = KEEPShape()
-    want_configs = rank == 0 and world == 1 and not args.no_configs      # the config-3 parity / c3 / c5 legs belong to the 1-GPU line; scaling runs stay lean
+    want_configs = args.full and rank == 0 and world == 1 and not args.no_configs      # the config-3 parity / c3 / c5 legs belong to the 1-GPU line; scaling runs stay lean
     # identical weights on every rank, BOTH towers everywhere: the load-time calibration measures its cosines against prompts through the loaded text
     # tower (an image-only engine falls back to random unit vectors, a harsher yardstick that picks a slower setting) -- every rank of every world
     # size must run the same setting for the scaling figures to compare like with like
@@ -672,6 +681,7 @@ def main():
         rows = [torch.empty_like(t) for _ in range(world)]
         dist.all_gather(rows, t)
         per_rank = [round(B * args.steps / float(r.item()), 1) for r in rows]
+    if use_dist and args.full:
         # what the exchange costs on the critical path: the same steps without it, same fences
         def bare():
             model.encode_image(tiles)
@@ -688,42 +698,43 @@ def main():
             raise SystemExit(f"slide leg: the ranks disagree on the gathered embeddings / label / ratio: {slide}")
         model.reserve(tiles=args.batch)
 
-    # effective shader clock under this load: a one-wave probe (shader cycles against the 100 MHz reference counter) on a side stream, right after
-    # the timed region (the queue is still full of encodes: the probe lands between them) and again during the sustained region
-    side = torch.cuda.Stream(device=dev)
-    clock_buf = torch.zeros(16, 2, dtype=torch.int64, device=dev)     # allocated and settled before the probes' neighbours are queued
-    torch.cuda.synchronize(dev)
-    clock_samples = []
+    sustained = clock = None
+    if args.full:
+        # effective shader clock under this load: a one-wave probe (shader cycles against the 100 MHz reference counter) on a side stream, right after
+        # the timed region (the queue is still full of encodes: the probe lands between them) and again during the sustained region
+        side = torch.cuda.Stream(device=dev)
+        clock_buf = torch.zeros(16, 2, dtype=torch.int64, device=dev)     # allocated and settled before the probes' neighbours are queued
+        torch.cuda.synchronize(dev)
+        clock_samples = []
 
-    def sample_clock():
-        if len(clock_samples) < clock_buf.shape[0]:
-            clock_samples.append(clock_buf[len(clock_samples)])
-            model.clock_probe(clock_samples[-1], spin_us=300, stream=side)
+        def sample_clock():
+            if len(clock_samples) < clock_buf.shape[0]:
+                clock_samples.append(clock_buf[len(clock_samples)])
+                model.clock_probe(clock_samples[-1], spin_us=300, stream=side)
 
-    for _ in range(3):
-        step()
-        sample_clock()
-    sustained = None
-    if not args.no_sustained:
-        n_sus = max(args.steps, int(args.sustain_seconds / (elapsed / args.steps)) + 1)
-        el = timed(n_sus)
-        sustained = {"value": round(world * B * n_sus / el, 2), "unit": "tiles/s", "steps": n_sus, "seconds": round(el, 2),
-                     "ms_per_step": round(el / n_sus * 1e3, 3),
-                     "note": "same step, same barriers, timed for >= 10 s: the part sits at its power cap under this load, so this is the rate to plan with"}
-        for _ in range(8):                                          # (the timed regions themselves stay untouched: samples are taken around them)
+        for _ in range(3):
             step()
             sample_clock()
-        log(f"sustained region done: {n_sus} steps in {el:.1f} s")
-    torch.cuda.synchronize(dev)
-    mhz = sorted(100.0 * float(t[0]) / float(t[1]) for t in clock_buf[:len(clock_samples)].cpu() if float(t[1]) > 0)
-    clock = {"effective_shader_MHz_median": round(mhz[len(mhz) // 2], 0), "min": round(mhz[0], 0), "max": round(mhz[-1], 0), "samples": len(mhz),
-             "how": "keep_clock_probe: one wavefront counting shader cycles against the 100 MHz reference for 300 us on a side stream while encode steps run",
-             "peak_quoted_at_MHz": 2400} if mhz else None
+        if not args.no_sustained:
+            n_sus = max(args.steps, int(args.sustain_seconds / (elapsed / args.steps)) + 1)
+            el = timed(n_sus)
+            sustained = {"value": round(world * B * n_sus / el, 2), "unit": "tiles/s", "steps": n_sus, "seconds": round(el, 2),
+                         "ms_per_step": round(el / n_sus * 1e3, 3),
+                         "note": "same step, same barriers, timed for >= 10 s: the part sits at its power cap under this load, so this is the rate to plan with"}
+            for _ in range(8):                                          # (the timed regions themselves stay untouched: samples are taken around them)
+                step()
+                sample_clock()
+            log(f"sustained region done: {n_sus} steps in {el:.1f} s")
+        torch.cuda.synchronize(dev)
+        mhz = sorted(100.0 * float(t[0]) / float(t[1]) for t in clock_buf[:len(clock_samples)].cpu() if float(t[1]) > 0)
+        clock = {"effective_shader_MHz_median": round(mhz[len(mhz) // 2], 0), "min": round(mhz[0], 0), "max": round(mhz[-1], 0), "samples": len(mhz),
+                 "how": "keep_clock_probe: one wavefront counting shader cycles against the 100 MHz reference for 300 us on a side stream while encode steps run",
+                 "peak_quoted_at_MHz": 2400} if mhz else None
 
     # untimed pass on ONE internal stream: per-kernel times with nothing else on the GPU (lanes do not overlap): the breakdown, and the KERNEL figure
     # of the roofline block (HIP events around every launch, on the stream it is launched on)
     breakdown, single = None, {}
-    if not args.no_breakdown and rank == 0:
+    if args.full and not args.no_breakdown and rank == 0:
         streams_was = model._options.get("streams", 2)
         model.set_option("streams", 1)
         model.profile_enable(None)
@@ -743,7 +754,7 @@ def main():
 
     # context for the roofline fractions: what the matrix pipes ALONE sustain on this box at the socket's power cap, no memory traffic (keep_mfma_probe)
     pipe_ceiling = None
-    if rank == 0 and not args.no_breakdown:
+    if args.full and rank == 0 and not args.no_breakdown:
         rnd = model.mfma_ceiling()
         zer = model.mfma_ceiling(torch.zeros(1024, dtype=torch.float16, device=dev))
         pipe_ceiling = {"random_N01_fp16_operands_TFLOPs": round(rnd, 1), "frac_of_peak": round(rnd / PEAK_F16_TFLOPS, 4),
@@ -780,42 +791,45 @@ def main():
             return {"achieved": round(fl / (ms * 1e-3) / 1e12, 1) if ms > 0 else 0.0, "frac": round(fl / (ms * 1e-3) / 1e12 / PEAK_F16_TFLOPS, 4) if ms > 0 else 0.0,
                     "avg_launch_ms": round(ms / max(n, 1), 4), "launches": int(n), "flops_per_launch": round(fl / max(n, 1), 1)}
 
-        # HBM-side traffic of the dominant kernel: PMC counters need rocprofv3 around the process (separate FETCH_SIZE / WRITE_SIZE passes, the guide's
-        # gfx950 correction), so it is read from the committed summary of tools/refresh_profiles.sh and labelled with the library build it was taken on
-        traffic, traffic_src, traffic_tiles = None, None, None
-        for rnd in ("r06", "r05", "r04", "r03"):
-            tpath = os.path.join(ROOT, "profiles", f"{rnd}_hbm_traffic.json")
-            if os.path.exists(tpath):
-                try:
-                    tjs = json.load(open(tpath))
-                    tj = tjs.get("vit.fc2", tjs.get("vit.proj+fc2", {}))
-                    traffic = tj.get("bytes_per_launch")
-                    traffic_tiles = tj.get("tiles_per_launch", 128)      # the PMC passes run the two-lane bench: 128-tile launches
-                    sha_path = os.path.join(ROOT, "profiles", f"{rnd}_lib_sha16.txt")
-                    sha = open(sha_path).read().strip() if os.path.exists(sha_path) else "unrecorded"
-                    traffic_src = (f"profiles/{rnd}_hbm_traffic.json: rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + WRITE_SIZE per launch of this kernel "
-                                   f"({traffic_tiles}-tile launches; algorithmic: {tj.get('algorithmic_bytes_per_launch')}), measured on library build {sha}; "
-                                   f"this run's library is {lib_sha16()}")
-                    break
-                except (OSError, ValueError):
-                    traffic = None
-        dom = [single.get(t, (0.0, 0, 0.0)) for t in DOMINANT_TAGS]
-        dom_ms, dom_n, dom_fl = (sum(d[i] for d in dom) for i in range(3))
-        roofline = {"bound": "mfma", "kernel": DOMINANT_KERNEL, "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s", **rate(dom_ms, dom_n, dom_fl),
-                    "traffic": traffic, "traffic_tiles_per_launch": traffic_tiles, "flops_tiles_per_launch": B, "traffic_source": traffic_src,
-                    "timing": "single_stream_pass: HIP events around every launch of this kernel, on the stream it is launched on, 3 encode calls of 256 tiles with one "
-                              "internal stream (nothing else on the GPU): a kernel figure, comparable with profiles/r06_rocprofv3_kernel_stats_single_stream.csv",
-                    "share_of_single_stream_step": round(dom_ms / max(sum(v[0] for v in single.values()), 1e-9), 4) if single else None,
-                    "by_operator": {t: rate(*single[t]) for t in DOMINANT_TAGS if t in single},
+        roofline = {"bound": "mfma", "kernel": DOMINANT_KERNEL, "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s",
                     "in_timed_region_two_lane": {**rate(*(sum(in_region[t][i] for t in DOMINANT_TAGS) for i in range(3))),
                                                  "note": "the same kernel's launches INSIDE the timed region, where two 128-tile lanes share the GPU: a launch's "
                                                          "duration includes the time it spends beside the other lane's kernels -- not a kernel figure"},
-                    "other_kernels_single_stream": {t: rate(*single[t]) for t in ("vit.qkv", "vit.fc1", "vit.proj", "vit.fc1.x", "vit.fc2.x", "vit.qkv.x", "vit.proj.x", "vit.patch")
-                                                    if t in single},
                     "frac_end_to_end": round(frac_e2e, 4),
                     "note": "achieved / frac = ALGORITHMIC FLOPs (2*M*N*K per launch; correction passes are never counted) / summed launch durations; "
                             "frac_end_to_end = tiles/s x 123.11 GFLOP / peak over the whole encoder (the figure the driver can check against its own clock); "
                             "peak = 256 CU x 4096 FLOP/clk x 2.4 GHz dense fp16"}
+        if args.full:
+            # HBM-side traffic of the dominant kernel: PMC counters need rocprofv3 around the process (separate FETCH_SIZE / WRITE_SIZE passes, the guide's
+            # gfx950 correction), so it is read from the committed summary of tools/refresh_profiles.sh and labelled with the library build it was taken on
+            traffic, traffic_src, traffic_tiles = None, None, None
+            for rnd in ("r06", "r05", "r04", "r03"):
+                tpath = os.path.join(ROOT, "profiles", f"{rnd}_hbm_traffic.json")
+                if os.path.exists(tpath):
+                    try:
+                        tjs = json.load(open(tpath))
+                        tj = tjs.get("vit.fc2", tjs.get("vit.proj+fc2", {}))
+                        traffic = tj.get("bytes_per_launch")
+                        traffic_tiles = tj.get("tiles_per_launch", 128)      # the PMC passes run the two-lane bench: 128-tile launches
+                        sha_path = os.path.join(ROOT, "profiles", f"{rnd}_lib_sha16.txt")
+                        sha = open(sha_path).read().strip() if os.path.exists(sha_path) else "unrecorded"
+                        traffic_src = (f"profiles/{rnd}_hbm_traffic.json: rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + WRITE_SIZE per launch of this kernel "
+                                       f"({traffic_tiles}-tile launches; algorithmic: {tj.get('algorithmic_bytes_per_launch')}), measured on library build {sha}; "
+                                       f"this run's library is {lib_sha16()}")
+                        break
+                    except (OSError, ValueError):
+                        traffic = None
+            dom = [single.get(t, (0.0, 0, 0.0)) for t in DOMINANT_TAGS]
+            dom_ms, dom_n, dom_fl = (sum(d[i] for d in dom) for i in range(3))
+            roofline.update({**rate(dom_ms, dom_n, dom_fl),
+                             "traffic": traffic, "traffic_tiles_per_launch": traffic_tiles, "flops_tiles_per_launch": B, "traffic_source": traffic_src,
+                             "timing": "single_stream_pass: HIP events around every launch of this kernel, on the stream it is launched on, 3 encode calls of 256 tiles "
+                                       "with one internal stream (nothing else on the GPU): a kernel figure, comparable with "
+                                       "profiles/r06_rocprofv3_kernel_stats_single_stream.csv",
+                             "share_of_single_stream_step": round(dom_ms / max(sum(v[0] for v in single.values()), 1e-9), 4) if single else None,
+                             "by_operator": {t: rate(*single[t]) for t in DOMINANT_TAGS if t in single},
+                             "other_kernels_single_stream": {t: rate(*single[t]) for t in ("vit.qkv", "vit.fc1", "vit.proj", "vit.fc1.x", "vit.fc2.x", "vit.qkv.x",
+                                                                                           "vit.proj.x", "vit.patch") if t in single}})
         if pipe_ceiling is not None:
             roofline["matrix_pipe_ceiling_measured"] = pipe_ceiling
         if clock is not None:
@@ -855,12 +869,13 @@ def main():
             line["rccl_ranks_seen"] = rccl_ranks_seen      # sum of an all-reduced ones tensor over the nccl (= RCCL) group: must equal n_gpus
         if per_rank is not None:
             line["per_rank_tiles_per_s"] = per_rank
+        if exchange_cost is not None:
             line["exchange"] = exchange_cost
         if slide is not None:
             line["slide"] = slide
         if breakdown is not None:
             line["breakdown_ms_per_step_single_stream"] = breakdown
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("cpu baseline (oracle on host cores) ...")
             line["cpu_baseline"] = cpu_baseline(sd)
             log("cpu baseline done")

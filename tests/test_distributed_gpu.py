@@ -78,7 +78,7 @@ def test_bench_distributed_leg_runs_on_nccl(tmp_path):
     env = dict(os.environ, KEEP_BENCH_FORCE_DIST="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))      # bench.py sets the RCCL environment itself (keep_amd.distributed.rccl_env)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64",
-                        "--no-cpu-baseline", "--no-breakdown", "--no-configs", "--dump-outputs", str(tmp_path)],
+                        "--full", "--no-cpu-baseline", "--no-breakdown", "--no-configs", "--dump-outputs", str(tmp_path)],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])          # the JSON line is the last thing on stdout, after RCCL's banner

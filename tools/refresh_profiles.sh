@@ -5,10 +5,10 @@
 # chose given explicitly, so a trace holds encode steps only (not the calibration's strict / ladder passes).
 set -u
 REPO=$(pwd); OUT=$REPO/gpurun_out/prof; rm -rf "$OUT"; mkdir -p "$OUT"
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.log"
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.log"
 PLAN=$(python -c "import json;print(json.load(open('$OUT/bench.json'))['config']['comp_settings']['plan'])")
 SET=(--plan "$PLAN")
-LEAN="--no-cpu-baseline --no-configs --no-sustained"
+LEAN="--full --no-cpu-baseline --no-configs --no-sustained"
 export KEEP_CALIBRATE=0
 cd /tmp && export TMPDIR=/tmp
 # 1. per-kernel time summary of the bench command (two internal lanes, as the bench runs)
