@@ -213,6 +213,37 @@ int keep_region_patches_u8(keep_handle* h, const unsigned char* region, int64_t 
                            const int32_t* cell_xy, int64_t B, int64_t patch, const int32_t* xbounds, const int32_t* xweights, int xksize,
                            const int32_t* ybounds, const int32_t* yweights, int yksize, unsigned char* out, void* stream);
 
+/* ---- tissue mask from a thumbnail, and the grid decided by a mask -----------
+ * Replaces: the tissue segmentation of the CLAM step the reference's README (README.md:74) runs before any WSI script
+ * (CLAM's segmentTissue: HSV saturation, medianBlur, fixed or Otsu threshold, morphological closing, contour / hole area
+ * filters), restated on the pixel mask instead of on contour polygons; integer arithmetic, exact.
+ * thumb: uint8 [H,W,C] RGB / RGBA with the layout contract of keep_region_grid, H W <= 2^30.  ksize: odd, 1 (off) .. 15, border
+ * replicated.  median_out: uint8 [H,W]: the median of S = (2 * 255 (max - min) + max) / (2 max) (0 where max = 0).
+ * hist_out: int32 [256] on the device, zeroed here and filled with the histogram of median_out (for Otsu's threshold, which
+ * the caller picks: keep_amd.region.otsu_threshold). */
+int keep_tissue_median_hist(keep_handle* h, const unsigned char* thumb, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
+                            int ksize, unsigned char* median_out, int32_t* hist_out, void* stream);
+/* Replaces: the rest of segmentTissue.  median: uint8 [H,W] contiguous.  Foreground iff median > threshold (0..255); closing by a
+ * close x close box (0 = off, <= 31; anchor close / 2, OpenCV's constant borders); background 4-components that touch no border
+ * and hold <= min_hole pixels are filled; foreground 8-components of <= min_area pixels are dropped.  mask_out: uint8 {0,1}
+ * [H,W] (must not alias median).  A labelling loop that runs into its iteration cap sets bit 2 (value 4) of the handle's sticky
+ * error word (keep_token_error). */
+int keep_tissue_mask(keep_handle* h, const unsigned char* median, int64_t H, int64_t W, int threshold, int close, int64_t min_hole,
+                     int64_t min_area, unsigned char* mask_out, void* stream);
+
+/* how a grid cell is tested against a mask: CLAM's isInContour family */
+enum { KEEP_MASK_FOUR_PT = 0,       /* any of the four points (c.x +- patch / 4, c.y +- patch / 4), c = cell origin + patch / 2 */
+       KEEP_MASK_FOUR_PT_HARD = 1,  /* all four                                                                              */
+       KEEP_MASK_CENTER = 2 };      /* c itself                                                                              */
+/* Replaces: CLAM's patch-level contour test (isInContourV3_Easy / _Hard / V2) in the patching step of README.md:74.  mask: uint8
+ * [mh,mw] contiguous on the device, one pixel = downsample x downsample pixels of the level being tiled.  The grid is that of
+ * keep_region_grid over an H x W region whose first pixel sits at (origin_x, origin_y) of the level; a point (px, py) is tissue
+ * iff mask[py / downsample][px / downsample] != 0, outside the mask it is not.  No region pixel is read.  Outputs as
+ * keep_region_grid's. */
+int keep_region_grid_mask(keep_handle* h, const unsigned char* mask, int64_t mh, int64_t mw, int64_t downsample, int64_t H, int64_t W,
+                          int64_t patch, int64_t step, int64_t origin_x, int64_t origin_y, int mode, int32_t* cell_xy_out, int64_t* n_out,
+                          void* stream);
+
 /* Pre-allocate workspace for calls of up to `tiles` tiles and `prompts` x `seq` tokens. */
 int keep_reserve(keep_handle* h, int64_t tiles, int64_t prompts, int64_t seq);
 int64_t keep_workspace_bytes(keep_handle* h);
@@ -254,7 +285,9 @@ int keep_encode_text(keep_handle* h, const int64_t* input_ids, const int64_t* to
  *              would raise IndexError);
  *   bit 1 (2): an output feature row of keep_encode_image / keep_encode_text was not finite: an activation left the fp16 range
  *              (|x| > 65504 in a qkv / MLP-hidden store -- conversions do not saturate, so the overflow reaches the output as NaN
- *              instead of as plausible garbage; the fp32 reference would not overflow).
+ *              instead of as plausible garbage; the fp32 reference would not overflow);
+ *   bit 2 (4): a component-labelling loop of keep_tissue_mask ran into its iteration cap (cannot happen unless the labels were
+ *              corrupted: a chain of strictly decreasing pixel indices is shorter than the image); the mask is not valid.
  * Encode calls only ever SET bits; they are cleared here, once the host has seen them, so an error can not be lost between calls.
  * Synchronises `stream`. */
 int keep_token_error(keep_handle* h, void* stream);

@@ -84,7 +84,7 @@ def save_slide_features(data_source: str, slide_id: str, features: torch.Tensor,
 @torch.no_grad()
 def extract_slide_features(read_region, width: int, height: int, slide_id: str, data_source: str, patch_size: int = 256,
                            step: Optional[int] = None, tissue=None, band_rows: int = 8, coord_scale: int = 1, use_h5: bool = False,
-                           model=None) -> str:
+                           model=None, thumbnail=None, thumbnail_downsample: Optional[int] = None, segmentation=None) -> str:
     """The feature files the WSI scripts read, made on the device (replaces the CLAM extraction step of README.md:74).
 
     ``read_region(x, y, w, h)`` returns uint8 [h, w, 3 | 4] pixels of the slide level being tiled, ``width`` x ``height`` pixels
@@ -97,21 +97,66 @@ def extract_slide_features(read_region, width: int, height: int, slide_id: str, 
     The slide is walked in horizontal bands of ``band_rows`` grid rows (keep_amd.region.plan_bands); each band goes through
     ``model.encode_region(band, patch_size, step, tissue, origin=(0, y0), coord_scale)``, so every grid cell is encoded exactly once
     and the rows come out in the slide's row-major grid order.  The features (and, with ``use_h5``, the level-0 coords) are
-    written by :func:`save_slide_features`; returns its path."""
+    written by :func:`save_slide_features`; returns its path.
+
+    ``tissue`` may also be a ``keep_amd.region.TissueMask`` (``model.tissue_mask(...)`` or a caller's own mask), or one is made
+    first from ``thumbnail`` (uint8 [h,w,3|4] of the whole slide, one pixel = ``thumbnail_downsample`` pixels of the level being
+    tiled per side) with ``segmentation`` (a ``TissueSegmentation``)::
+
+        thumb = np.asarray(slide.read_region((0, 0), top, slide.level_dimensions[top]))         # the smallest pyramid level
+        extract_slide_features(read_region, ..., thumbnail=thumb,
+                               thumbnail_downsample=int(slide.level_downsamples[top] / slide.level_downsamples[level]), model=m)
+
+    With a mask the cells of every band are decided BEFORE ``read_region``: a band with no kept cell is not read at all, of the
+    others only the columns ``[min kept x, max kept x + patch_size)`` (keep_amd.region.plan_mask_reads), and that window is cut
+    with ``origin=(x0, y0)``.  Rows and coords come out in the same slide row-major order, and the tiles are encoded in the batches
+    ``encode_region(whole slide, tissue=mask)`` would form, so the features equal its features exactly."""
     from .model import engine_for
-    from .region import check_grid_args, plan_bands
+    from .region import TissueMask, check_grid_args, plan_bands, plan_mask_reads
     patch, step, _, coord_scale = check_grid_args(patch_size, step, (0, 0), coord_scale)
     bands = plan_bands(width, height, patch, step, band_rows)
+    if thumbnail is not None and (tissue is not None or thumbnail_downsample is None):
+        raise ValueError("thumbnail= needs thumbnail_downsample= and replaces tissue=: give one of the two")
+    if thumbnail is None and (thumbnail_downsample is not None or segmentation is not None):
+        raise ValueError("thumbnail_downsample= / segmentation= need thumbnail=")
     m = engine_for(model=model)
+    if thumbnail is not None:
+        tissue = m.tissue_mask(thumbnail, thumbnail_downsample, segmentation)
     feats, coords = [], []
-    for _, _, y0, h in bands:
-        band = read_region(0, y0, width, h)
-        band = torch.from_numpy(np.ascontiguousarray(band)) if not isinstance(band, torch.Tensor) else band
-        if band.dim() != 3 or tuple(band.shape[:2]) != (h, width):
-            raise ValueError(f"read_region(0, {y0}, {width}, {h}) returned {tuple(band.shape)}, expected [{h}, {width}, 3|4]")
-        f, c = m.encode_region(band, patch, step, tissue, origin=(0, y0), coord_scale=coord_scale)
-        feats.append(f.cpu())
-        coords.append(c.cpu())
+    if isinstance(tissue, TissueMask):
+        # every kept cell of the slide, decided on the mask alone; then per band only the window that holds kept cells is read.
+        # Tiles are encoded ``batch`` consecutive kept cells at a time ACROSS bands: the batches of one encode_region over the
+        # whole slide, so the features equal it bit for bit (and a band with three kept cells does not cost a launch of three)
+        m._ready()
+        cells = m._mask_cells(tissue, height, width, patch, step, (0, 0)).cpu().numpy().astype(np.int64)
+        pending, n_pending, batch = [], 0, 256
+
+        def encode(final):
+            nonlocal pending, n_pending
+            while n_pending >= batch or (final and n_pending):
+                tiles = torch.cat(pending) if len(pending) > 1 else pending[0]
+                feats.append(m.encode_image_uint8(tiles[:batch]).cpu())
+                pending, n_pending = ([tiles[batch:]], n_pending - batch) if n_pending > batch else ([], 0)
+        for x0, y0, w, h in plan_mask_reads(cells, bands, patch, step):
+            band = read_region(x0, y0, w, h)
+            band = torch.from_numpy(np.ascontiguousarray(band)) if not isinstance(band, torch.Tensor) else band
+            if band.dim() != 3 or tuple(band.shape[:2]) != (h, w):
+                raise ValueError(f"read_region({x0}, {y0}, {w}, {h}) returned {tuple(band.shape)}, expected [{h}, {w}, 3|4]")
+            xy = torch.from_numpy(cells[(cells[:, 1] >= y0) & (cells[:, 1] + patch <= y0 + h)] * coord_scale)
+            pending.append(m.region_patches_uint8(band.to(m._device), xy, patch, origin=(x0, y0), coord_scale=coord_scale))
+            n_pending += len(xy)
+            coords.append(xy)
+            encode(final=False)
+        encode(final=True)
+    else:
+        for _, _, y0, h in bands:
+            band = read_region(0, y0, width, h)
+            band = torch.from_numpy(np.ascontiguousarray(band)) if not isinstance(band, torch.Tensor) else band
+            if band.dim() != 3 or tuple(band.shape[:2]) != (h, width):
+                raise ValueError(f"read_region(0, {y0}, {width}, {h}) returned {tuple(band.shape)}, expected [{h}, {width}, 3|4]")
+            f, c = m.encode_region(band, patch, step, tissue, origin=(0, y0), coord_scale=coord_scale)
+            feats.append(f.cpu())
+            coords.append(c.cpu())
     features = torch.cat(feats) if feats else torch.empty((0, m.config.projection_dim), dtype=torch.float32)
     xy = torch.cat(coords) if coords else torch.empty((0, 2), dtype=torch.int64)
     return save_slide_features(data_source, slide_id, features, xy.numpy(), use_h5=use_h5)

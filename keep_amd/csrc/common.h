@@ -212,8 +212,23 @@ void launch_region_check_cells(const int32_t* cell_xy, int B, int64_t H, int64_t
 void launch_region_patches_u8(const unsigned char* region, int64_t row_stride, int ps, const int32_t* cell_xy, int B, int patch,
                               const int* xb, const int* xk, int xks, const int* yb, const int* yk, int yks, unsigned char* tmp,
                               unsigned char* out, hipStream_t s);
+// the stable compaction alone: keep [ncells] flags (null: every cell) -> the kept cells' (x, y) in grid order + the device count
+void launch_region_compact(const unsigned char* keep, int gx, int64_t ncells, int step, int* counts, int* offsets, int32_t* cell_xy,
+                           int64_t* n_out, hipStream_t s);
 constexpr int REGION_MAX_PATCH = 32768;
 constexpr int REGION_GRID_CHUNK = 2048;                 // cells per block of the compaction
+
+// Thumbnail tissue segmentation and the grid on a mask (tissue.hip)
+constexpr int64_t TISSUE_MAX_PIXELS = (int64_t)1 << 30;   // int32 pixel indices and areas
+// uint8 RGB / RGBA thumbnail -> ksize x ksize median of the saturation (bytes) and its histogram (added into hist: the caller zeroes it); -1: ksize unsupported
+int launch_tissue_median_hist(const unsigned char* thumb, int64_t row_stride, int ps, int h, int w, int ksize, unsigned char* med, int* hist,
+                              hipStream_t s);
+// median bytes -> {0,1} mask: > thr, closing, holes <= min_hole filled, components <= min_area dropped.  tmp: h w bytes; labels, info:
+// h w int32 each; err: the handle's sticky error word (value 4: a labelling loop hit its cap)
+void launch_tissue_mask(const unsigned char* med, int h, int w, int thr, int close, int min_hole, int min_area, unsigned char* tmp, int* labels,
+                        int* info, int* err, unsigned char* mask, hipStream_t s);
+void launch_tissue_grid_cells(const unsigned char* mask, int64_t mh, int64_t mw, int64_t ds, int gx, int64_t ncells, int patch, int step,
+                              int64_t ox, int64_t oy, int mode, unsigned char* keep, hipStream_t s);
 
 // Row-wise helpers (rowops.hip)
 // pixels [B,3,16 gh,16 gw] (or uint8 [B,16 gh,16 gw,3]) -> patches [B * gh * gw][768], row-major (y, x) patch order; CLS rows of resid

@@ -195,7 +195,7 @@ struct keep_handle {
     // workspace arena
     char* arena = nullptr;
     size_t arena_bytes = 0;
-    int* err_flag = nullptr;     // device int, sticky: bit 0 out-of-range token ids, bit 1 non-finite output features (fp16 range exceeded)
+    int* err_flag = nullptr;     // device int, sticky: bit 0 out-of-range token ids, bit 1 non-finite output features (fp16 range exceeded), bit 2 (value 4) a tissue-labelling loop hit its cap
 
     // profiling
     int prof_mode = 0;           // 0 off, 1 the tags of prof_mask, 2 all
@@ -1708,6 +1708,82 @@ int keep_region_patches_u8(keep_handle* h, const unsigned char* region, int64_t 
     return check_launch(h, "region_patches_u8");
 }
 
+int keep_tissue_median_hist(keep_handle* h, const unsigned char* thumb, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
+                            int ksize, unsigned char* median_out, int32_t* hist_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!thumb || H < 1 || W < 1) return h->fail(KEEP_EINVAL, "tissue_median_hist: null pointer or empty shape %lldx%lld", (long long)H, (long long)W);
+    if (pix_stride != 3 && pix_stride != 4) return h->fail(KEEP_EINVAL, "tissue_median_hist: pixel stride %d (3 = RGB, 4 = RGBA)", pix_stride);
+    if (H > TISSUE_MAX_PIXELS || W > TISSUE_MAX_PIXELS || H * W > TISSUE_MAX_PIXELS)
+        return h->fail(KEEP_EINVAL, "tissue_median_hist: %lldx%lld pixels (limit H W <= 2^30)", (long long)H, (long long)W);
+    if (row_stride_bytes < W * pix_stride)
+        return h->fail(KEEP_EINVAL, "tissue_median_hist: row stride %lld bytes < width %lld x pixel stride %d", (long long)row_stride_bytes,
+                       (long long)W, pix_stride);
+    if (ksize < 1 || ksize > 15 || ksize % 2 == 0) return h->fail(KEEP_EINVAL, "tissue_median_hist: ksize %d (odd, 1..15)", ksize);
+    if (!median_out || !hist_out) return h->fail(KEEP_EINVAL, "tissue_median_hist: null output");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(h, hipMemsetAsync(hist_out, 0, 256 * sizeof(int32_t), s));
+    if (launch_tissue_median_hist(thumb, row_stride_bytes, pix_stride, (int)H, (int)W, ksize, median_out, hist_out, s))
+        return h->fail(KEEP_EUNSUPPORTED, "tissue_median_hist: no kernel for ksize %d", ksize);
+    return check_launch(h, "tissue_median_hist");
+}
+
+int keep_tissue_mask(keep_handle* h, const unsigned char* median, int64_t H, int64_t W, int threshold, int close, int64_t min_hole,
+                     int64_t min_area, unsigned char* mask_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!median || !mask_out || median == mask_out) return h->fail(KEEP_EINVAL, "tissue_mask: null pointer, or mask_out aliases median");
+    if (H < 1 || W < 1 || H > TISSUE_MAX_PIXELS || W > TISSUE_MAX_PIXELS || H * W > TISSUE_MAX_PIXELS)
+        return h->fail(KEEP_EINVAL, "tissue_mask: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (threshold < 0 || threshold > 255) return h->fail(KEEP_EINVAL, "tissue_mask: threshold %d outside [0, 255]", threshold);
+    if (close < 0 || close > 31) return h->fail(KEEP_EINVAL, "tissue_mask: close %d outside [0, 31]", close);
+    if (min_hole < 0 || min_area < 0) return h->fail(KEEP_EINVAL, "tissue_mask: min_hole %lld / min_area %lld < 0", (long long)min_hole, (long long)min_area);
+    KEEP_ON_DEVICE(h);
+    const size_t n = (size_t)(H * W);
+    const bool label = min_hole > 0 || min_area > 0;
+    const size_t b_tmp = close > 0 ? align_up(n) : 0, b_lab = label ? align_up(n * 4) : 0;
+    int rc = ensure_arena(h, b_tmp + 2 * b_lab);
+    if (rc) return rc;
+    // an area never exceeds H W <= 2^30: larger bounds decide the same
+    launch_tissue_mask(median, (int)H, (int)W, threshold, close, (int)std::min<int64_t>(min_hole, TISSUE_MAX_PIXELS),
+                       (int)std::min<int64_t>(min_area, TISSUE_MAX_PIXELS), (unsigned char*)h->arena, (int*)(h->arena + b_tmp),
+                       (int*)(h->arena + b_tmp + b_lab), h->err_flag, mask_out, (hipStream_t)stream);
+    return check_launch(h, "tissue_mask");
+}
+
+int keep_region_grid_mask(keep_handle* h, const unsigned char* mask, int64_t mh, int64_t mw, int64_t downsample, int64_t H, int64_t W,
+                          int64_t patch, int64_t step, int64_t origin_x, int64_t origin_y, int mode, int32_t* cell_xy_out, int64_t* n_out,
+                          void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!mask || mh < 1 || mw < 1 || mh > INT32_MAX || mw > INT32_MAX)
+        return h->fail(KEEP_EINVAL, "region_grid_mask: null mask or bad mask shape %lldx%lld", (long long)mh, (long long)mw);
+    if (downsample < 1 || downsample > INT32_MAX) return h->fail(KEEP_EINVAL, "region_grid_mask: downsample %lld < 1", (long long)downsample);
+    if (H < 1 || W < 1 || H > INT32_MAX || W > INT32_MAX) return h->fail(KEEP_EINVAL, "region_grid_mask: region shape %lldx%lld", (long long)H, (long long)W);
+    if (patch < 16 || patch > REGION_MAX_PATCH) return h->fail(KEEP_EINVAL, "region_grid_mask: patch %lld outside [16, %d]", (long long)patch, REGION_MAX_PATCH);
+    if (step < 1) return h->fail(KEEP_EINVAL, "region_grid_mask: step %lld < 1", (long long)step);
+    constexpr int64_t omax = (int64_t)1 << 40;
+    if (origin_x < -omax || origin_x > omax || origin_y < -omax || origin_y > omax)
+        return h->fail(KEEP_EINVAL, "region_grid_mask: origin (%lld, %lld) outside +-2^40", (long long)origin_x, (long long)origin_y);
+    if (mode < KEEP_MASK_FOUR_PT || mode > KEEP_MASK_CENTER) return h->fail(KEEP_EINVAL, "region_grid_mask: mode %d (0 four_pt, 1 four_pt_hard, 2 center)", mode);
+    if (!cell_xy_out || !n_out) return h->fail(KEEP_EINVAL, "region_grid_mask: null output");
+    const int64_t gx = W >= patch ? (W - patch) / step + 1 : 0, gy = H >= patch ? (H - patch) / step + 1 : 0;
+    const int64_t ncells = gx * gy;
+    if (ncells > INT32_MAX) return h->fail(KEEP_EINVAL, "region_grid_mask: %lld cells (limit 2^31 - 1)", (long long)ncells);
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (ncells == 0) {
+        HIPCHK(h, hipMemsetAsync(n_out, 0, sizeof(int64_t), s));
+        return KEEP_OK;
+    }
+    const int64_t nb = (ncells + REGION_GRID_CHUNK - 1) / REGION_GRID_CHUNK;
+    const size_t b_keep = align_up((size_t)ncells), b_counts = align_up((size_t)nb * 4);
+    int rc = ensure_arena(h, b_keep + 2 * b_counts);
+    if (rc) return rc;
+    unsigned char* keep = (unsigned char*)h->arena;
+    launch_tissue_grid_cells(mask, mh, mw, downsample, (int)gx, ncells, (int)patch, (int)step, origin_x, origin_y, mode, keep, s);
+    launch_region_compact(keep, (int)gx, ncells, (int)step, (int*)(h->arena + b_keep), (int*)(h->arena + b_keep + b_counts), cell_xy_out, n_out, s);
+    return check_launch(h, "region_grid_mask");
+}
+
 int keep_token_error(keep_handle* h, void* stream) {
     if (!h) return KEEP_EINVAL;
     KEEP_ON_DEVICE(h);
@@ -1715,7 +1791,7 @@ int keep_token_error(keep_handle* h, void* stream) {
     HIPCHK(h, hipMemcpyAsync(&flag, h->err_flag, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
     if (flag) HIPCHK(h, hipMemsetAsync(h->err_flag, 0, sizeof(int), (hipStream_t)stream));     // seen by the host: re-arm
-    return flag & 3;
+    return flag & 7;
 }
 
 int keep_token_error_async(keep_handle* h, int32_t* host_flag, void* stream) {

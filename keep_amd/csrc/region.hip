@@ -190,6 +190,11 @@ void launch_region_grid(const unsigned char* region, int64_t row_stride, int ps,
                            step, (unsigned)sat_min, min_pixels, keep);
     else
         keep = nullptr;                                           // count >= 0 holds for every cell: no pass over the pixels
+    launch_region_compact(keep, gx, ncells, step, counts, offsets, cell_xy, n_out, s);
+}
+
+void launch_region_compact(const unsigned char* keep, int gx, int64_t ncells, int step, int* counts, int* offsets, int32_t* cell_xy,
+                           int64_t* n_out, hipStream_t s) {
     const int nb = (int)((ncells + REGION_CELLS_PER_BLOCK - 1) / REGION_CELLS_PER_BLOCK);
     hipLaunchKernelGGL(region_block_count_kernel, dim3(nb), dim3(256), 0, s, keep, ncells, counts);
     hipLaunchKernelGGL(region_scan_kernel, dim3(1), dim3(256), 0, s, counts, nb, offsets, n_out);

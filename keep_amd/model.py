@@ -988,6 +988,56 @@ class KEEPModel:
                    "region_patches_u8")
         return out
 
+    def _mask_cells(self, mask, H: int, W: int, patch: int, step: int, origin) -> torch.Tensor:
+        """keep_region_grid_mask -> the kept cells' (x, y) offsets in an H x W region at ``origin``, int32 [N,2] on the device (reads N
+        back: one sync).  The region's pixels play no part."""
+        from .region import MASK_MODES, grid_shape
+        gy, gx = grid_shape(H, W, patch, step)
+        if gy * gx == 0:
+            return torch.empty((0, 2), dtype=torch.int32, device=self._device)
+        md = mask.mask.to(self._device)
+        cells = torch.empty((gy * gx, 2), dtype=torch.int32, device=self._device)
+        n = torch.empty((1,), dtype=torch.int64, device=self._device)
+        _lib.check(self._handle, _lib.load().keep_region_grid_mask(self._handle, _ptr(md), int(md.shape[0]), int(md.shape[1]), mask.downsample, H, W,
+                                                                   patch, step, origin[0], origin[1], MASK_MODES.index(mask.mode), _ptr(cells),
+                                                                   _ptr(n), _stream(self._device)), "region_grid_mask")
+        return cells[:int(n.item())]
+
+    @torch.no_grad()
+    def tissue_mask(self, thumbnail, downsample: int, params=None):
+        """Tissue segmentation of a slide thumbnail on the device -> ``keep_amd.region.TissueMask``.
+
+        ``thumbnail``: uint8 [h,w,3] (RGB) or [h,w,4] (RGBA, alpha ignored), host or device, numpy or torch, any row stride,
+        ``h w <= 2^30``; one pixel of it covers ``downsample`` x ``downsample`` pixels of the level that will be tiled.  ``params``: a
+        ``keep_amd.region.TissueSegmentation`` (default: its defaults).  Stages, after CLAM's ``segmentTissue`` but on the pixel mask
+        instead of contour polygons, all in integers and equal to ``keep_amd.region.tissue_mask_numpy`` bit for bit: HSV saturation,
+        k x k median, fixed or Otsu threshold (the histogram is made on the device, the 256-candidate choice on the host; the
+        threshold used is ``.threshold`` of the result), closing, small holes filled, small fragments dropped.  The mask stays on
+        the engine's device; hand the result to ``region_grid`` / ``encode_region`` / ``extract_slide_features`` as ``tissue=``."""
+        from .region import TissueMask, TissueSegmentation, check_downsample, otsu_threshold, thumbnail_layout
+        params = TissueSegmentation() if params is None else params
+        if not isinstance(params, TissueSegmentation):
+            raise ValueError(f"params must be a TissueSegmentation, got {params!r}")
+        downsample = check_downsample(downsample)
+        x = torch.from_numpy(thumbnail) if not isinstance(thumbnail, torch.Tensor) else thumbnail
+        thumbnail_layout(x)
+        self._ready_device()
+        if x.device != self._device:
+            x = x.to(self._device)
+        h, w, C, row = thumbnail_layout(x)
+        lib, st = _lib.load(), _stream(self._device)
+        med = torch.empty((h, w), dtype=torch.uint8, device=self._device)
+        hist = torch.empty((256,), dtype=torch.int32, device=self._device)
+        _lib.check(self._handle, lib.keep_tissue_median_hist(self._handle, _ptr(x), h, w, row, C, params.mthresh, _ptr(med), _ptr(hist), st),
+                   "tissue_median_hist")
+        t = otsu_threshold(hist.cpu().tolist()) if params.use_otsu else int(params.sthresh)
+        mask = torch.empty((h, w), dtype=torch.uint8, device=self._device)
+        _lib.check(self._handle, lib.keep_tissue_mask(self._handle, _ptr(med), h, w, t, params.close, params.min_hole, params.min_area,
+                                                      _ptr(mask), st), "tissue_mask")
+        self._queue_flag_check(st)
+        self.last_tissue_median, self.last_tissue_hist = med, hist                  # the intermediates, for inspection and tests
+        return TissueMask(mask, downsample, params.mode, t)
+
     @staticmethod
     def _cells_to_coords(cells: torch.Tensor, origin, coord_scale: int) -> torch.Tensor:
         o = torch.tensor(origin, dtype=torch.int64, device=cells.device)
@@ -1003,14 +1053,23 @@ class KEEPModel:
         the region, in row-major order; coords are ``(origin + cell offset) * coord_scale`` (the convention of refine_seg / cood2str and
         the CLAM .h5 files; ``coord_scale`` for a region read at a downsampled level).  ``tissue`` (default off: every cell) is an exact
         integer rule (keep_amd.region.TissueRule): a pixel is tissue iff ``max(r,g,b) > 0`` and ``255 (max - min) >= sat_min max``, a cell
-        is kept iff it holds ``>= ceil(min_fraction patch^2)`` of them.  This is deliberately NOT CLAM's contour segmentation."""
-        from .region import check_grid_args, tissue_params
+        is kept iff it holds ``>= ceil(min_fraction patch^2)`` of them.  That rule is deliberately NOT CLAM's contour segmentation;
+        a ``keep_amd.region.TissueMask`` (from :meth:`tissue_mask`, or a caller's own) is the other choice: a cell is then tested at
+        CLAM's ``four_pt`` / ``four_pt_hard`` / ``center`` points, in level coordinates including ``origin``, against the mask
+        (DESIGN.md section 11), and the region's pixels are not read."""
+        from .region import TissueMask, check_grid_args, region_layout, tissue_params
         patch, step, origin, coord_scale = check_grid_args(patch_size, step, origin, coord_scale)
-        sat_min, min_pixels = tissue_params(tissue, patch)
         x = self._region_tensor(region)
-        self._ready_device()
-        xd, H, W, C, row = self._region_on_device(x)
-        coords = self._cells_to_coords(self._region_cells(xd, H, W, C, row, patch, step, sat_min, min_pixels), origin, coord_scale)
+        if isinstance(tissue, TissueMask):                         # decided by the mask: the region gives its shape, no pixel is read
+            self._ready_device()
+            H, W, _, _ = region_layout(x)
+            cells = self._mask_cells(tissue, H, W, patch, step, origin)
+        else:
+            sat_min, min_pixels = tissue_params(tissue, patch)
+            self._ready_device()
+            xd, H, W, C, row = self._region_on_device(x)
+            cells = self._region_cells(xd, H, W, C, row, patch, step, sat_min, min_pixels)
+        coords = self._cells_to_coords(cells, origin, coord_scale)
         return coords if x.device == self._device else coords.to(x.device)
 
     @torch.no_grad()
@@ -1037,16 +1096,19 @@ class KEEPModel:
                       batch: int = 256) -> Tuple[torch.Tensor, torch.Tensor]:
         """Slide pixels in, what the WSI functions take out: the grid of :meth:`region_grid`, the tiles of
         :meth:`region_patches_uint8` and :meth:`encode_image_uint8`, ``batch`` tiles at a time -> (features fp32 [N,768],
-        coords int64 [N,2]) on the region's device; ``[0,768]`` / ``[0,2]`` when no cell is kept."""
-        from .region import check_grid_args, tissue_params
+        coords int64 [N,2]) on the region's device; ``[0,768]`` / ``[0,2]`` when no cell is kept.  ``tissue`` as in
+        :meth:`region_grid`: off, the per-pixel rule, or a ``TissueMask``."""
+        from .region import TissueMask, check_grid_args, tissue_params
         patch, step, origin, coord_scale = check_grid_args(patch_size, step, origin, coord_scale)
-        sat_min, min_pixels = tissue_params(tissue, patch)
+        by_mask = isinstance(tissue, TissueMask)
+        sat_min, min_pixels = (0, 0) if by_mask else tissue_params(tissue, patch)
         if isinstance(batch, bool) or int(batch) != batch or batch < 1:
             raise ValueError(f"batch must be an integer >= 1, got {batch!r}")
         x = self._region_tensor(region)
         self._ready()
         xd, H, W, C, row = self._region_on_device(x)
-        cells = self._region_cells(xd, H, W, C, row, patch, step, sat_min, min_pixels)
+        cells = self._mask_cells(tissue, H, W, patch, step, origin) if by_mask else \
+            self._region_cells(xd, H, W, C, row, patch, step, sat_min, min_pixels)
         N = int(cells.shape[0])
         feats = torch.empty((N, self.config.projection_dim), dtype=torch.float32, device=self._device)
         for i in range(0, N, int(batch)):
@@ -1134,6 +1196,8 @@ class KEEPModel:
         when = " of an earlier call" if earlier else ""
         if bits & 1:
             raise IndexError(f"index out of range in self (input_ids / token_type_ids{when} were outside the embedding tables)")
+        if bits & 4:
+            raise _lib.KeepHipError(f"tissue_mask{when}: a component-labelling loop ran into its iteration cap (the mask is not valid)")
         if bits & 2:
             raise FloatingPointError(f"non-finite output features{when}: an activation exceeded the fp16 range (65504) of the engine's qkv / "
                                      "MLP-hidden stores; these weights need the fp32 reference path")

@@ -385,3 +385,31 @@ def calibration_probe(n_per_family: int, device, seed: int = 20250929, families=
         parts.append(x)
         groups.append(torch.full((n_per_family,), gi, dtype=torch.int64))
     return torch.cat(parts, 0), torch.cat(groups, 0), tuple(families)
+
+
+def synth_thumbnail(h: int = 384, w: int = 512, seed: int = 3):
+    """A slide thumbnail for the tissue segmentation, uint8 [h,w,3] numpy: grey glass with noise, one stained
+    blob with a large hole, a medium one, three of radius 6-7 and three of radius 1-2, four specks, a second mid-sized fragment
+    and 1 % single saturated pixels.  The layout is drawn for 384 x 512 and scaled by min(h / 384, w / 512)."""
+    import numpy as np
+    g = np.random.default_rng(seed)
+    s = min(h / 384.0, w / 512.0)
+    img = (238 + g.integers(-6, 7, (h, w, 3), dtype=np.int16)).astype(np.int16)
+    yy, xx = np.mgrid[:h, :w].astype(np.float32) / np.float32(s)
+
+    def stain(m):
+        img[m] = np.array([200, 120, 170], np.int16) + g.integers(-25, 26, (int(m.sum()), 3), dtype=np.int16)
+
+    def glass(m):
+        img[m] = 238 + g.integers(-6, 7, (int(m.sum()), 3), dtype=np.int16)
+
+    def disc(cy, cx, r):
+        return (yy - cy) ** 2 + (xx - cx) ** 2 <= r * r
+    stain(((yy - 190) / 120.0) ** 2 + ((xx - 250) / 170.0) ** 2 < 1)
+    for cy, cx, r in ((150, 200, 30), (230, 330, 12), (120, 300, 7), (260, 180, 6), (250, 270, 7), (200, 150, 2), (180, 300, 1), (240, 220, 2)):
+        glass(disc(cy, cx, r))
+    for cy, cx, r in ((30, 40, 4), (40, 450, 3), (350, 60, 5), (20, 250, 2)):
+        stain(disc(cy, cx, r))
+    stain((abs(yy - 340) < 14) & (abs(xx - 430) < 20))
+    img[g.random((h, w), dtype=np.float32) < 0.01] = np.array([90, 20, 140], np.int16)
+    return np.clip(img, 0, 255).astype(np.uint8)
