@@ -244,6 +244,37 @@ int keep_region_grid_mask(keep_handle* h, const unsigned char* mask, int64_t mh,
                           int64_t patch, int64_t step, int64_t origin_x, int64_t origin_y, int mode, int32_t* cell_xy_out, int64_t* n_out,
                           void* stream);
 
+/* ---- tile scores rasterised onto the slide thumbnail -------------------------
+ * The accumulator `acc` is int64 [H,W] contiguous on the device, 8-byte aligned, H W <= 2^30, one word per raster pixel read as
+ * unsigned: bits 0..39 hold the sum of q over the tiles that cover the pixel, bits 40..63 their number, q = rint(clip(value, 0, 1) *
+ * 65535) (round half to even).  At most 2^24 - 1 tiles may ever be added into one accumulator (the caller counts them), so that
+ * neither field can overflow; integer sums do not depend on the order, so a raster is the same however its tiles are split
+ * over calls.
+ *
+ * Replaces: the pred-mask painting of eval_seg_coarse (WSI_evaluation/segment_utils.py:134-140: every tile above the threshold
+ * painted into a level-16 array) and, with keep_heat_render, the heatmap that closes CLAM's step of README.md:74.
+ * coords: int64 [N,2] level-0 (x, y); values: fp32 [N]; a tile covers raster columns [floor((x - origin_x) / downsample),
+ * floor((x - origin_x + patch) / downsample)) and rows likewise, clipped to the raster; a NaN value skips its tile.  1 <= downsample
+ * <= patch <= 2^30, origin a multiple of downsample within +-2^40, 0 <= N <= 2^24 - 1.  zero_first != 0 starts a new raster, 0 adds
+ * into the one in acc. */
+int keep_heat_accumulate(keep_handle* h, const int64_t* coords, const float* values, int64_t N, int64_t patch, int64_t downsample,
+                         int64_t H, int64_t W, int64_t origin_x, int64_t origin_y, int zero_first, int64_t* acc, void* stream);
+/* Replaces: reading the raster back as numbers (the probability map in slide geometry; the {0,255} pred_mask of
+ * segment_utils.py:134-140 when the values were p > thd).  mean_out: fp32 [H,W] = float(double(sum) / double(65535 count)) where
+ * count > 0, else `uncovered`; count_out: int32 [H,W]; pred_out: uint8 [H,W], 255 where sum > 0.  Any of the three may be null, not
+ * all. */
+int keep_heat_mean(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, float uncovered, float* mean_out, int32_t* count_out,
+                   unsigned char* pred_out, void* stream);
+/* Replaces: the heatmap blended over the thumbnail that closes CLAM's step of README.md:74 (no blur, no percentile ranks).
+ * thumb: uint8 [H,W,C] RGB / RGBA with the layout contract of keep_region_grid, or null for the constant background_rgb
+ * (R | G << 8 | B << 16).  mask: uint8 [H,W] contiguous (non-zero = show), or null.  lut: uint8 [256,3].  With S = sum, c = count a
+ * pixel is shown iff c > 0, the mask is set and S >= min16 c; its colour index is clamp((2 255 (S - lo16 c) + (hi16 - lo16) c) /
+ * (2 (hi16 - lo16) c), 0, 255) (0 when S < lo16 c) and out = (alpha lut[idx] + (256 - alpha) under + 128) >> 8 per channel; other
+ * pixels pass `under` through.  0 <= alpha <= 256, 0 <= lo16 < hi16 <= 65535, 0 <= min16 <= 65535.  out: uint8 [H,W,3] contiguous. */
+int keep_heat_render(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, const unsigned char* thumb, int64_t row_stride_bytes,
+                     int pix_stride, int background_rgb, const unsigned char* mask, const unsigned char* lut, int alpha, int lo16, int hi16,
+                     int min16, unsigned char* out, void* stream);
+
 /* Pre-allocate workspace for calls of up to `tiles` tiles and `prompts` x `seq` tokens. */
 int keep_reserve(keep_handle* h, int64_t tiles, int64_t prompts, int64_t seq);
 int64_t keep_workspace_bytes(keep_handle* h);

@@ -52,6 +52,9 @@ SIGNATURES = {
     "keep_tissue_median_hist": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "keep_tissue_mask": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i64, _i64, _vp, _vp]),
     "keep_region_grid_mask": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "keep_heat_accumulate": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp]),
+    "keep_heat_mean": (_i32, [_vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "keep_heat_render": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "keep_token_error": (_i32, [_vp, _vp]),
     "keep_token_error_async": (_i32, [_vp, _vp, _vp]),
     "keep_similarity": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _vp, _vp]),

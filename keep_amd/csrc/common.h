@@ -230,6 +230,21 @@ void launch_tissue_mask(const unsigned char* med, int h, int w, int thr, int clo
 void launch_tissue_grid_cells(const unsigned char* mask, int64_t mh, int64_t mw, int64_t ds, int gx, int64_t ncells, int patch, int step,
                               int64_t ox, int64_t oy, int mode, unsigned char* keep, hipStream_t s);
 
+// Tile scores rasterised onto the thumbnail (heatmap.hip).  acc: one 64-bit word per raster pixel, bits 0..39 the sum
+// of the 16-bit fixed-point values of the covering tiles, bits 40..63 their number
+constexpr int64_t HEAT_MAX_PIXELS = (int64_t)1 << 30;     // int32 pixel indices
+constexpr int64_t HEAT_MAX_TILES = ((int64_t)1 << 24) - 1;  // the count field; (2^24 - 1) 65535 < 2^40, so neither field can overflow
+constexpr int64_t HEAT_MAX_PATCH = (int64_t)1 << 30;
+// adds every tile's footprint into acc (integer atomics; the caller zeroes acc when it starts a raster)
+void launch_heat_accumulate(const int64_t* coords, const float* values, int64_t n, int64_t patch, int64_t d, int h, int w, int64_t ox,
+                            int64_t oy, int64_t* acc, hipStream_t s);
+// any of mean / count / pred may be null
+void launch_heat_mean(const int64_t* acc, int h, int w, float uncovered, float* mean, int* count, unsigned char* pred, hipStream_t s);
+// thumb null: the constant bg (R | G << 8 | B << 16); mask null: every pixel
+void launch_heat_render(const int64_t* acc, int h, int w, const unsigned char* thumb, int64_t row_stride, int ps, unsigned bg,
+                        const unsigned char* mask, const unsigned char* lut, int alpha, int lo16, int hi16, int min16, unsigned char* out,
+                        hipStream_t s);
+
 // Row-wise helpers (rowops.hip)
 // pixels [B,3,16 gh,16 gw] (or uint8 [B,16 gh,16 gw,3]) -> patches [B * gh * gw][768], row-major (y, x) patch order; CLS rows of resid
 void launch_im2col(const void* pixels, int dtype, int B, int gh, int gw, f16* out_hi, f16* out_lo,      // out in blk layout (KT = 24)

@@ -1784,6 +1784,69 @@ int keep_region_grid_mask(keep_handle* h, const unsigned char* mask, int64_t mh,
     return check_launch(h, "region_grid_mask");
 }
 
+static const char* heat_shape_error(int64_t H, int64_t W) {
+    return (H < 1 || W < 1 || H > HEAT_MAX_PIXELS || W > HEAT_MAX_PIXELS || H * W > HEAT_MAX_PIXELS) ? "raster shape (1 <= H W <= 2^30)" : nullptr;
+}
+
+int keep_heat_accumulate(keep_handle* h, const int64_t* coords, const float* values, int64_t N, int64_t patch, int64_t downsample,
+                         int64_t H, int64_t W, int64_t origin_x, int64_t origin_y, int zero_first, int64_t* acc, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "heat_accumulate: acc is null or not 8-byte aligned");
+    if (N < 0 || N > HEAT_MAX_TILES) return h->fail(KEEP_EINVAL, "heat_accumulate: %lld tiles (0 .. 2^24 - 1)", (long long)N);
+    if (N > 0 && (!coords || !values)) return h->fail(KEEP_EINVAL, "heat_accumulate: null coords or values");
+    if (heat_shape_error(H, W)) return h->fail(KEEP_EINVAL, "heat_accumulate: %lldx%lld: %s", (long long)H, (long long)W, heat_shape_error(H, W));
+    if (patch < 1 || patch > HEAT_MAX_PATCH) return h->fail(KEEP_EINVAL, "heat_accumulate: patch %lld outside [1, 2^30]", (long long)patch);
+    if (downsample < 1 || downsample > patch)
+        return h->fail(KEEP_EINVAL, "heat_accumulate: downsample %lld outside [1, patch = %lld]", (long long)downsample, (long long)patch);
+    constexpr int64_t omax = (int64_t)1 << 40;
+    if (origin_x < -omax || origin_x > omax || origin_y < -omax || origin_y > omax)
+        return h->fail(KEEP_EINVAL, "heat_accumulate: origin (%lld, %lld) outside +-2^40", (long long)origin_x, (long long)origin_y);
+    if (origin_x % downsample || origin_y % downsample)
+        return h->fail(KEEP_EINVAL, "heat_accumulate: origin (%lld, %lld) is not a multiple of downsample %lld", (long long)origin_x,
+                       (long long)origin_y, (long long)downsample);
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (zero_first) HIPCHK(h, hipMemsetAsync(acc, 0, (size_t)(H * W) * sizeof(int64_t), s));
+    launch_heat_accumulate(coords, values, N, patch, downsample, (int)H, (int)W, origin_x, origin_y, acc, s);
+    return check_launch(h, "heat_accumulate");
+}
+
+int keep_heat_mean(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, float uncovered, float* mean_out, int32_t* count_out,
+                   unsigned char* pred_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "heat_mean: acc is null or not 8-byte aligned");
+    if (heat_shape_error(H, W)) return h->fail(KEEP_EINVAL, "heat_mean: %lldx%lld: %s", (long long)H, (long long)W, heat_shape_error(H, W));
+    if (!mean_out && !count_out && !pred_out) return h->fail(KEEP_EINVAL, "heat_mean: no output");
+    if (((uintptr_t)mean_out & 3) || ((uintptr_t)count_out & 3)) return h->fail(KEEP_EINVAL, "heat_mean: mean_out / count_out not 4-byte aligned");
+    KEEP_ON_DEVICE(h);
+    launch_heat_mean(acc, (int)H, (int)W, uncovered, mean_out, count_out, pred_out, (hipStream_t)stream);
+    return check_launch(h, "heat_mean");
+}
+
+int keep_heat_render(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, const unsigned char* thumb, int64_t row_stride_bytes,
+                     int pix_stride, int background_rgb, const unsigned char* mask, const unsigned char* lut, int alpha, int lo16, int hi16,
+                     int min16, unsigned char* out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "heat_render: acc is null or not 8-byte aligned");
+    if (!lut || !out) return h->fail(KEEP_EINVAL, "heat_render: null lut or output");
+    if (heat_shape_error(H, W)) return h->fail(KEEP_EINVAL, "heat_render: %lldx%lld: %s", (long long)H, (long long)W, heat_shape_error(H, W));
+    if (thumb) {
+        if (pix_stride != 3 && pix_stride != 4) return h->fail(KEEP_EINVAL, "heat_render: pixel stride %d (3 = RGB, 4 = RGBA)", pix_stride);
+        if (row_stride_bytes < W * pix_stride)
+            return h->fail(KEEP_EINVAL, "heat_render: row stride %lld bytes < width %lld x pixel stride %d", (long long)row_stride_bytes,
+                           (long long)W, pix_stride);
+    } else if (background_rgb < 0 || background_rgb > 0xFFFFFF) {
+        return h->fail(KEEP_EINVAL, "heat_render: background 0x%x outside [0, 0xFFFFFF]", background_rgb);
+    }
+    if (alpha < 0 || alpha > 256) return h->fail(KEEP_EINVAL, "heat_render: alpha %d outside [0, 256]", alpha);
+    if (lo16 < 0 || hi16 > 65535 || lo16 >= hi16) return h->fail(KEEP_EINVAL, "heat_render: window [%d, %d] (0 <= lo16 < hi16 <= 65535)", lo16, hi16);
+    if (min16 < 0 || min16 > 65535) return h->fail(KEEP_EINVAL, "heat_render: min16 %d outside [0, 65535]", min16);
+    KEEP_ON_DEVICE(h);
+    launch_heat_render(acc, (int)H, (int)W, thumb, row_stride_bytes, pix_stride, (unsigned)background_rgb, mask, lut, alpha, lo16, hi16, min16,
+                       out, (hipStream_t)stream);
+    return check_launch(h, "heat_render");
+}
+
 int keep_token_error(keep_handle* h, void* stream) {
     if (!h) return KEEP_EINVAL;
     KEEP_ON_DEVICE(h);

@@ -1,0 +1,264 @@
+"""Tile scores rasterised onto the slide thumbnail: the last stage of the slide flow.
+
+``KEEPModel.tile_raster`` scatters per-tile values (the tumour probabilities of ``keep_amd.wsi.refine``) into a raster whose pixel
+covers ``downsample`` x ``downsample`` level-0 pixels -- the geometry of ``KEEPModel.tissue_mask`` and of the thumbnail it was given --
+and ``KEEPModel.render_heatmap`` blends the coloured mean over that thumbnail.  It replaces the pred-mask painting inside the
+reference's ``eval_seg_coarse`` (``WSI_evaluation/segment_utils.py:134-140``) and the heatmap that closes CLAM's step of the
+reference's ``README.md:74``.
+
+Everything is integer arithmetic.  A value becomes ``q = rint(clip(float32(v), 0, 1) * 65535)`` (round half to even; NaN skips the
+tile) and one uint64 per raster pixel holds the sum of q over the covering tiles in bits 0..39 and their number in bits 40..63.
+The device kernels (``csrc/heatmap.hip``) equal the numpy restatements below exactly, and integer sums do not depend on the order, so
+a raster is the same however its tiles are split over calls.
+
+This module holds the host side: argument checks (ValueError before any device call), :class:`TileRaster`, the colour tables and
+the restatements ``raster_numpy`` / ``mean_numpy`` / ``pred_numpy`` / ``render_numpy``."""
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+COUNT_SHIFT = 40
+SUM_MASK = (1 << COUNT_SHIFT) - 1
+Q_ONE = 65535
+MAX_TILES = (1 << 24) - 1                      # the count field; (2^24 - 1) * 65535 < 2^40, so neither field can overflow
+MAX_PIXELS = 1 << 30
+MAX_PATCH = 1 << 30
+MAX_ORIGIN = 1 << 40
+COLORMAPS = ("jet", "gray")
+
+
+def _integer(v, name: str) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer, float)) or int(v) != v:
+        raise ValueError(f"{name} must be an integer, got {v!r}")
+    return int(v)
+
+
+def check_raster_args(patch, downsample, shape, origin=(0, 0)) -> Tuple[int, int, Tuple[int, int], Tuple[int, int]]:
+    """Validate the raster geometry on the host -> (patch, downsample, (h, w), (ox, oy))."""
+    patch, d = _integer(patch, "patch_size"), _integer(downsample, "downsample")
+    if patch < 1 or patch > MAX_PATCH:
+        raise ValueError(f"patch_size must lie in [1, 2^30], got {patch}")
+    if d < 1 or d > patch:
+        raise ValueError(f"downsample must lie in [1, patch_size = {patch}], got {d}")
+    if len(shape) != 2:
+        raise ValueError(f"shape must be (h, w), got {shape!r}")
+    h, w = _integer(shape[0], "shape[0]"), _integer(shape[1], "shape[1]")
+    if h < 1 or w < 1 or h * w > MAX_PIXELS:
+        raise ValueError(f"raster of {h}x{w} pixels: need 1 <= h * w <= 2^30")
+    if len(origin) != 2:
+        raise ValueError(f"origin must be two integers (x, y), got {origin!r}")
+    ox, oy = _integer(origin[0], "origin[0]"), _integer(origin[1], "origin[1]")
+    if ox % d or oy % d:
+        raise ValueError(f"origin {(ox, oy)} must be a multiple of downsample {d}: raster pixel (0, 0) starts on the pixel lattice")
+    if abs(ox) > MAX_ORIGIN or abs(oy) > MAX_ORIGIN:
+        raise ValueError(f"origin {(ox, oy)} outside +-2^40")
+    return patch, d, (h, w), (ox, oy)
+
+
+def check_tiles(coords, values) -> int:
+    """Shapes of one call's tiles: coords [N,2] of an integer type, values [N] of a floating type -> N."""
+    cs, vs = tuple(coords.shape), tuple(values.shape)
+    if len(cs) != 2 or cs[1] != 2 or len(vs) != 1 or vs[0] != cs[0]:
+        raise ValueError(f"coords must be [N,2] and values [N], got {cs} and {vs}")
+    cd = coords.dtype
+    if cd in (torch.bool, np.dtype(bool)) or (cd.is_floating_point if isinstance(cd, torch.dtype) else cd.kind not in "iu"):
+        raise ValueError(f"coords must hold integers, got {cd}")
+    vd = values.dtype
+    if not (vd.is_floating_point if isinstance(vd, torch.dtype) else vd.kind == "f"):
+        raise ValueError(f"values must be floating point, got {vd}")
+    return int(cs[0])
+
+
+def quantize(value) -> int:
+    """One value in the raster's fixed point: rint(clip(float32(v), 0, 1) * 65535); NaN is an error here."""
+    v = np.float32(value)
+    if np.isnan(v):
+        raise ValueError("a window / threshold value must not be NaN")
+    return int(np.rint(np.clip(v, np.float32(0), np.float32(1)) * np.float32(Q_ONE)))
+
+
+def render_args(alpha, window, min_value, background) -> Tuple[int, int, int, int, Tuple[int, int, int]]:
+    """The display arguments as the integers the kernel takes -> (a, lo16, hi16, min16, (R, G, B))."""
+    if isinstance(alpha, bool) or not (0.0 <= float(alpha) <= 1.0):
+        raise ValueError(f"alpha must lie in [0, 1], got {alpha!r}")
+    a = int(round(256 * float(alpha)))
+    if len(window) != 2:
+        raise ValueError(f"window must be (low, high), got {window!r}")
+    lo16, hi16 = quantize(window[0]), quantize(window[1])
+    if lo16 >= hi16:
+        raise ValueError(f"window {tuple(window)!r} is empty in 16-bit fixed point ({lo16} >= {hi16})")
+    bg = tuple(_integer(c, "background") for c in background)
+    if len(bg) != 3 or any(c < 0 or c > 255 for c in bg):
+        raise ValueError(f"background must be three integers in 0..255, got {background!r}")
+    return a, lo16, hi16, quantize(min_value), bg
+
+
+def colormap(name) -> np.ndarray:
+    """A colour table, uint8 [256,3], built in integer arithmetic from the formulas below; a caller's own [256,3] uint8 array is
+    checked and passed through.  No parity with matplotlib's tables of the same names is claimed: "jet" is the piecewise-linear
+    blue -> cyan -> yellow -> red ramp ``channel(i) = clamp((765 - 2 |4 i - 255 k| + 1) // 2, 0, 255)`` with k = 3 / 2 / 1 for
+    R / G / B (1.5 - |4 t - k| at t = i / 255, scaled to 0..255 and rounded half up), "gray" is ``(i, i, i)``."""
+    if isinstance(name, str):
+        i = np.arange(256, dtype=np.int64)
+        if name == "jet":
+            return np.stack([np.clip((765 - 2 * np.abs(4 * i - 255 * k) + 1) // 2, 0, 255) for k in (3, 2, 1)], axis=1).astype(np.uint8)
+        if name == "gray":
+            return np.stack([i, i, i], axis=1).astype(np.uint8)
+        raise ValueError(f"colormap must be one of {COLORMAPS} or a uint8 [256,3] array, got {name!r}")
+    lut = name.cpu().numpy() if isinstance(name, torch.Tensor) else np.asarray(name)
+    if lut.dtype != np.uint8 or lut.shape != (256, 3):
+        raise ValueError(f"a colour table must be uint8 [256,3], got {lut.dtype} {lut.shape}")
+    return np.ascontiguousarray(lut)
+
+
+_table = colormap                              # the name `colormap` is also the keyword of the render functions
+
+
+class TileRaster:
+    """An accumulator and its geometry: ``acc`` int64 ``[h,w]`` (bits 0..39 the sum of the fixed-point values of the tiles covering
+    the pixel, bits 40..63 their number), ``downsample`` (level-0 pixels per raster pixel), ``patch`` (a tile's footprint in level-0
+    units), ``origin`` (the level-0 position of raster pixel (0, 0)) and ``tiles``, the number of tiles added so far (NaN tiles
+    included: the cap of 2^24 - 1 is enforced by counting on the host).  ``KEEPModel.tile_raster`` makes and extends one."""
+
+    def __init__(self, acc: torch.Tensor, downsample: int, patch: int, origin=(0, 0), tiles: int = 0, model=None):
+        if not isinstance(acc, torch.Tensor) or acc.dtype != torch.int64 or acc.dim() != 2 or not acc.is_contiguous():
+            raise ValueError("acc must be a contiguous int64 [h,w] tensor")
+        self.patch, self.downsample, _, self.origin = check_raster_args(patch, downsample, acc.shape, origin)
+        self.acc = acc
+        self.tiles = 0
+        self._model = model
+        self.claim(tiles)
+
+    @property
+    def shape(self) -> Tuple[int, int]:
+        return int(self.acc.shape[0]), int(self.acc.shape[1])
+
+    def __repr__(self):
+        return (f"TileRaster({self.shape} on {self.acc.device}, downsample={self.downsample}, patch={self.patch}, origin={self.origin}, "
+                f"tiles={self.tiles})")
+
+    def claim(self, n: int) -> None:
+        """Count ``n`` more tiles against the cap, before they are added; ValueError beyond 2^24 - 1."""
+        n = _integer(n, "the number of tiles")
+        if n < 0 or self.tiles + n > MAX_TILES:
+            raise ValueError(f"a raster takes at most 2^24 - 1 = {MAX_TILES} tiles in all (its count field is 24 bits): {self.tiles} added, "
+                             f"{n} more asked for")
+        self.tiles += n
+
+    def check_geometry(self, patch: int, downsample: int, shape, origin) -> None:
+        if (self.patch, self.downsample, self.shape, self.origin) != (patch, downsample, tuple(shape), tuple(origin)):
+            raise ValueError(f"into= raster has patch {self.patch}, downsample {self.downsample}, shape {self.shape}, origin {self.origin}; "
+                             f"the call has {patch}, {downsample}, {tuple(shape)}, {tuple(origin)}")
+
+    def _engine(self):
+        from .model import engine_for
+        if self.acc.device.type != "cuda":
+            raise ValueError("this raster lives on the host: use the numpy restatements (mean_numpy, pred_numpy, render_numpy)")
+        return engine_for(device=self.acc.device, model=self._model)
+
+    def _read(self, uncovered: float, mean: bool, count: bool, pred: bool):
+        return self._engine()._heat_read(self, float(uncovered), mean, count, pred)
+
+    @property
+    def sum(self) -> torch.Tensor:
+        """int64 [h,w]: the sum of the 16-bit fixed-point values of the covering tiles."""
+        return self.acc & SUM_MASK
+
+    @property
+    def count(self) -> torch.Tensor:
+        """int32 [h,w]: the number of covering tiles."""
+        return self._read(0.0, False, True, False)[1]
+
+    def mean(self, uncovered: float = 0.0) -> torch.Tensor:
+        """fp32 [h,w]: ``float32(float64(sum) / float64(65535 * count))`` where a tile covers the pixel, ``uncovered`` elsewhere."""
+        return self._read(uncovered, True, False, False)[0]
+
+    def pred(self) -> torch.Tensor:
+        """uint8 {0,255} [h,w]: 255 where sum > 0.  With values ``p > thd`` this is "any covering tile above the threshold", the
+        pred_mask of ``segment_utils.py:134-140``."""
+        return self._read(0.0, False, False, True)[2]
+
+
+# ------------------------------------------------------------------------------------------------ the restatements
+def footprints_numpy(coords: np.ndarray, patch: int, d: int, shape, origin) -> np.ndarray:
+    """int64 [N,4]: (c0, c1, r0, r1) of every tile, floor division (also below zero), clipped to the raster; empty when c1 <= c0 or
+    r1 <= r0."""
+    c = np.asarray(coords).astype(np.int64).reshape(-1, 2)
+    x, y = c[:, 0] - origin[0], c[:, 1] - origin[1]
+    h, w = shape
+    return np.stack([np.clip(x // d, 0, None), np.clip((x + patch) // d, None, w), np.clip(y // d, 0, None), np.clip((y + patch) // d, None, h)],
+                    axis=1)
+
+
+def quantize_numpy(values: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (q int64 [N], skip bool [N]): q = rint(clip(float32(v), 0, 1) * float32(65535)), skip where v is NaN."""
+    v = np.asarray(values).astype(np.float32).reshape(-1)
+    skip = np.isnan(v)
+    q = np.rint(np.clip(np.where(skip, np.float32(0), v), np.float32(0), np.float32(1)) * np.float32(Q_ONE)).astype(np.int64)
+    return q, skip
+
+
+def raster_numpy(coords, values, patch: int, downsample: int, shape, origin=(0, 0), into: Optional[np.ndarray] = None) -> np.ndarray:
+    """The accumulate step restated on the host -> the accumulator, int64 [h,w]; ``into`` adds to an earlier one (in place)."""
+    patch, d, (h, w), origin = check_raster_args(patch, downsample, shape, origin)
+    coords, values = np.asarray(coords), np.asarray(values)
+    check_tiles(coords, values)
+    if into is None:
+        into = np.zeros((h, w), np.int64)
+    elif into.dtype != np.int64 or into.shape != (h, w):
+        raise ValueError(f"into must be int64 {(h, w)}, got {into.dtype} {into.shape}")
+    acc = into.view(np.uint64)
+    q, skip = quantize_numpy(values)
+    fp = footprints_numpy(coords, patch, d, (h, w), origin)
+    for n in np.nonzero(~skip & (fp[:, 1] > fp[:, 0]) & (fp[:, 3] > fp[:, 2]))[0]:
+        c0, c1, r0, r1 = fp[n]
+        acc[r0:r1, c0:c1] += np.uint64((1 << COUNT_SHIFT) | int(q[n]))
+    return into
+
+
+def unpack_numpy(acc: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (sum int64 [h,w], count int32 [h,w])."""
+    a = np.asarray(acc).view(np.uint64)
+    return (a & np.uint64(SUM_MASK)).astype(np.int64), (a >> np.uint64(COUNT_SHIFT)).astype(np.int32)
+
+
+def mean_numpy(acc: np.ndarray, uncovered: float = 0.0) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (mean fp32 [h,w], count int32 [h,w]); the division is done in float64 and rounded to float32 once."""
+    s, c = unpack_numpy(acc)
+    out = np.full(s.shape, np.float32(uncovered), np.float32)
+    on = c > 0
+    out[on] = (s[on].astype(np.float64) / (Q_ONE * c[on].astype(np.int64)).astype(np.float64)).astype(np.float32)
+    return out, c
+
+
+def pred_numpy(acc: np.ndarray) -> np.ndarray:
+    """uint8 {0,255} [h,w]: 255 where sum > 0."""
+    return np.where(unpack_numpy(acc)[0] > 0, 255, 0).astype(np.uint8)
+
+
+def render_numpy(acc: np.ndarray, thumbnail: Optional[np.ndarray] = None, alpha: float = 0.4, colormap="jet", mask: Optional[np.ndarray] = None,
+                 window=(0.0, 1.0), min_value: float = 0.0, background=(255, 255, 255)) -> np.ndarray:
+    """The render step restated on the host -> uint8 [h,w,3].  ``thumbnail``: uint8 [h,w,3|4] (any strides; alpha ignored);
+    ``mask``: [h,w], non-zero = show."""
+    a, lo16, hi16, min16, bg = render_args(alpha, window, min_value, background)
+    lut = _table(colormap).astype(np.int64)
+    S, c = unpack_numpy(acc)
+    c = c.astype(np.int64)
+    h, w = S.shape
+    if thumbnail is None:
+        under = np.empty((h, w, 3), np.int64)
+        under[:] = bg
+    else:
+        if thumbnail.dtype != np.uint8 or thumbnail.ndim != 3 or thumbnail.shape[:2] != (h, w) or thumbnail.shape[2] not in (3, 4):
+            raise ValueError(f"thumbnail must be uint8 {(h, w)} x 3|4, got {thumbnail.dtype} {thumbnail.shape}")
+        under = thumbnail[..., :3].astype(np.int64)
+    shown = (c > 0) & (S >= min16 * c)
+    if mask is not None:
+        if mask.shape != (h, w):
+            raise ValueError(f"mask must be {(h, w)}, got {mask.shape}")
+        shown &= np.asarray(mask) != 0
+    span, cs = hi16 - lo16, np.maximum(c, 1)
+    idx = np.clip((2 * 255 * (S - lo16 * c) + span * c) // (2 * span * cs), 0, 255)
+    blend = (a * lut[idx] + (256 - a) * under + 128) >> 8
+    return np.where(shown[..., None], blend, under).astype(np.uint8)

@@ -186,6 +186,7 @@ class KEEPModel:
         self.training = False
         self._handle = C.c_void_p(0)
         self._device: Optional[torch.device] = None
+        self._heat_luts: Dict[str, torch.Tensor] = {}           # render_heatmap's named colour tables on the device
         self._host_sd: Optional[Dict[str, torch.Tensor]] = None
         self._loaded = False
         self._options = {"precision": _PRECISIONS[precision], "strict_blocks": 0}
@@ -1037,6 +1038,106 @@ class KEEPModel:
         self._queue_flag_check(st)
         self.last_tissue_median, self.last_tissue_hist = med, hist                  # the intermediates, for inspection and tests
         return TissueMask(mask, downsample, params.mode, t)
+
+    # ------------------------------------------------------------------ heatmap
+    @torch.no_grad()
+    def tile_raster(self, coords, values, patch_size: int, downsample: int, shape, origin=(0, 0), into=None):
+        """Per-tile values rasterised in slide geometry on the device -> ``keep_amd.heatmap.TileRaster``.
+
+        ``coords``: integers [N,2], level-0 ``(x, y)`` (the convention of ``wsi.refine`` / ``cood2str`` / ``region_grid``); ``values``:
+        floating point [N]; both host or device, numpy or torch.  ``patch_size``: a tile's footprint in the units of the coords
+        (``patch_size * coord_scale`` of ``encode_region``); one raster pixel covers ``downsample`` x ``downsample`` of them,
+        ``1 <= downsample <= patch_size``; ``shape``: the raster's ``(h, w)``, ``h w <= 2^30``; ``origin``: the level-0 position of raster
+        pixel (0, 0), a multiple of ``downsample``.  Tile n adds ``rint(clip(float32(v), 0, 1) * 65535)`` and a count of one to the
+        columns ``[(x - ox) // d, (x - ox + P) // d)`` and the rows likewise (floor division, clipped to the raster); a NaN value skips
+        its tile; duplicate coords each count (pass the output of ``wsi.refine`` for first-occurrence-wins).  Coordinates must stay
+        within +-2^62 (they are not read on the host).  ``into``: an earlier raster of the same geometry to add to; the result is the
+        same however the tiles are split over calls.  At most 2^24 - 1 tiles go into one raster.  No host synchronisation."""
+        from .heatmap import MAX_TILES, TileRaster, check_raster_args, check_tiles
+        patch, d, (h, w), origin = check_raster_args(patch_size, downsample, shape, origin)
+        c = coords if isinstance(coords, torch.Tensor) else torch.as_tensor(coords)
+        v = values if isinstance(values, torch.Tensor) else torch.as_tensor(values)
+        N = check_tiles(c, v)
+        if into is not None:
+            if not isinstance(into, TileRaster):
+                raise ValueError(f"into must be a TileRaster, got {type(into).__name__}")
+            into.check_geometry(patch, d, (h, w), origin)
+            into.claim(N)                                           # raises beyond the cap, before any device work
+        elif N > MAX_TILES:
+            raise ValueError(f"a raster takes at most 2^24 - 1 = {MAX_TILES} tiles in all, got {N}")
+        self._ready_device()
+        if into is None:
+            into, zero = TileRaster(torch.empty((h, w), dtype=torch.int64, device=self._device), d, patch, origin, N, self), 1
+        elif into.acc.device != self._device:
+            into.tiles -= N
+            raise ValueError(f"into= raster lives on {into.acc.device}, this engine on {self._device}")
+        else:
+            zero = 0
+        c = c.to(self._device, torch.int64).contiguous()
+        v = v.to(self._device, torch.float32).contiguous()
+        _lib.check(self._handle, _lib.load().keep_heat_accumulate(self._handle, _ptr(c), _ptr(v), N, patch, d, h, w, origin[0], origin[1], zero,
+                                                                  _ptr(into.acc), _stream(self._device)), "heat_accumulate")
+        return into
+
+    def _heat_read(self, raster, uncovered: float, mean: bool, count: bool, pred: bool):
+        """keep_heat_mean -> (mean fp32 | None, count int32 | None, pred uint8 | None), each [h,w] on the device."""
+        h, w = raster.shape
+        outs = [torch.empty((h, w), dtype=dt, device=self._device) if on else None
+                for on, dt in ((mean, torch.float32), (count, torch.int32), (pred, torch.uint8))]
+        _lib.check(self._handle, _lib.load().keep_heat_mean(self._handle, _ptr(raster.acc), h, w, uncovered, _ptr(outs[0]), _ptr(outs[1]),
+                                                            _ptr(outs[2]), _stream(self._device)), "heat_mean")
+        return tuple(outs)
+
+    @torch.no_grad()
+    def render_heatmap(self, raster, thumbnail=None, alpha: float = 0.4, colormap="jet", tissue=None, window=(0.0, 1.0),
+                       min_value: float = 0.0, background=(255, 255, 255)) -> torch.Tensor:
+        """The raster's mean, coloured and blended over the thumbnail -> uint8 [h,w,3] on the device.
+
+        ``thumbnail``: uint8 [h,w,3|4] of the raster's shape (the layout contract of :meth:`tissue_mask`: any row stride, alpha
+        ignored; host or device), or None for the constant ``background``.  ``tissue``: a ``TissueMask`` of the raster's downsample
+        and shape; pixels outside it are not painted.  ``colormap``: "jet", "gray" or a uint8 [256,3] table
+        (``keep_amd.heatmap.colormap``).  ``window``: the values mapped to the ends of the table; ``min_value``: pixels whose mean
+        is below it are not painted; ``alpha``: the weight of the colour, used as ``round(256 alpha)``.  All in integers on the
+        16-bit fixed-point sums, equal to ``keep_amd.heatmap.render_numpy`` bit for bit.  No blur and no percentile ranks (CLAM has
+        both)."""
+        from .heatmap import TileRaster, colormap as table, render_args
+        from .region import TissueMask, region_layout
+        if not isinstance(raster, TileRaster):
+            raise ValueError(f"raster must be a TileRaster, got {type(raster).__name__}")
+        a, lo16, hi16, min16, bg = render_args(alpha, window, min_value, background)
+        h, w = raster.shape
+        key = colormap if isinstance(colormap, str) else None
+        lut_host = table(colormap)
+        x = None
+        if thumbnail is not None:
+            x = torch.from_numpy(thumbnail) if not isinstance(thumbnail, torch.Tensor) else thumbnail
+            if region_layout(x)[:2] != (h, w):
+                raise ValueError(f"thumbnail is {tuple(x.shape[:2])}, the raster {(h, w)}")
+        if tissue is not None:
+            if not isinstance(tissue, TissueMask):
+                raise ValueError(f"tissue must be a TissueMask, got {type(tissue).__name__}")
+            if tissue.downsample != raster.downsample or tuple(tissue.mask.shape) != (h, w):
+                raise ValueError(f"tissue mask has downsample {tissue.downsample} and shape {tuple(tissue.mask.shape)}, the raster "
+                                 f"{raster.downsample} and {(h, w)}")
+        self._ready_device()
+        if raster.acc.device != self._device:
+            raise ValueError(f"the raster lives on {raster.acc.device}, this engine on {self._device}")
+        lut = self._heat_luts.get(key)
+        if lut is None or lut.device != self._device:
+            lut = torch.from_numpy(lut_host).to(self._device)
+            if key is not None:
+                self._heat_luts[key] = lut                              # the named tables are uploaded once
+        ps, row = 3, 0
+        if x is not None:
+            if x.device != self._device:
+                x = x.to(self._device)
+            _, _, ps, row = region_layout(x)
+        md = None if tissue is None else tissue.mask.to(self._device)
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=self._device)
+        _lib.check(self._handle, _lib.load().keep_heat_render(self._handle, _ptr(raster.acc), h, w, _ptr(x), row, ps, bg[0] | bg[1] << 8 | bg[2] << 16,
+                                                              _ptr(md), _ptr(lut), a, lo16, hi16, min16, _ptr(out), _stream(self._device)),
+                   "heat_render")
+        return out
 
     @staticmethod
     def _cells_to_coords(cells: torch.Tensor, origin, coord_scale: int) -> torch.Tensor:

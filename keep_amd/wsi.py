@@ -328,3 +328,40 @@ def zero_shot_segment(classifier, tile_features, tile_coords, mask_path, patch_s
         return probs_all_refined
     raise NotImplementedError("AUC / Dice against an openslide mask (segment_utils.py:91-152) is outside the hot path; "
                               "call with mask_path=None and feed the returned map to the reference's eval_seg_auc / eval_seg_coarse")
+
+
+# ------------------------------------------------------------------------------------------------ heatmap
+def segment_heatmap(classifier, tile_features, tile_coords, downsample, shape, patch_size=224, overlap=True, cls=1, origin=(0, 0), model=None):
+    """The segmentation flow ending in slide geometry instead of a dict: ``_probs`` -> :func:`refine` -> ``KEEPModel.tile_raster`` on
+    device tensors -> ``keep_amd.heatmap.TileRaster`` of class ``cls``'s refined probability (``.mean()`` is the probability map,
+    ``KEEPModel.render_heatmap`` the picture).  No dict is built and the host is visited only where :func:`refine` already does.
+    ``downsample`` / ``shape`` / ``origin``: the raster's geometry, that of the thumbnail and of ``KEEPModel.tissue_mask``."""
+    from .heatmap import check_raster_args
+    check_raster_args(patch_size, downsample, shape, origin)
+    m = _engine(model, tile_features, classifier)
+    if isinstance(tile_coords, torch.Tensor):
+        tile_coords = tile_coords.cpu()                             # refine checks the coordinate range on the host
+    coords, mean, _ = refine(_probs(m, classifier, tile_features), tile_coords, patch_size, overlap, model=m)
+    if not -mean.shape[1] <= int(cls) < mean.shape[1]:
+        raise ValueError(f"cls {cls!r} outside the classifier's {mean.shape[1]} classes")
+    return m.tile_raster(coords, mean[:, int(cls)].contiguous(), patch_size, downsample, shape, origin)
+
+
+def segment_pred_mask(probs, thd, downsample, shape, patch_size=224, origin=(0, 0), model=None) -> torch.Tensor:
+    """The ``pred_mask`` that ``eval_seg_coarse`` paints (segment_utils.py:134-140), at any integer ``downsample`` (the reference's
+    level 16 is ``downsample=16``): uint8 {0,255} [h,w] on the device, 255 where any covering tile has ``p > thd``, overlapping tiles
+    included.  ``probs``: the ``{"x_y": probability}`` dict of ``zero_shot_segment(mask_path=None)`` / ``refine_seg_segment``, or a
+    ``(coords [N,2], p [N])`` pair (host or device).  The comparison is made in float32 (``float32(p) > float32(thd)``) on the values as
+    given, before rasterising."""
+    from .heatmap import check_raster_args
+    check_raster_args(patch_size, downsample, shape, origin)
+    if isinstance(probs, Mapping):
+        coords = torch.tensor([str2cood(k) for k in probs], dtype=torch.int64).reshape(-1, 2)
+        p = torch.tensor(list(probs.values()), dtype=torch.float64)
+    else:
+        coords, p = probs
+        coords = torch.as_tensor(np.asarray(coords)) if not isinstance(coords, torch.Tensor) else coords
+        p = torch.as_tensor(np.asarray(p)) if not isinstance(p, torch.Tensor) else p
+    m = _engine(model, p, coords)
+    above = (p.to(m._device).to(torch.float32) > torch.tensor(float(thd), dtype=torch.float32, device=m._device)).to(torch.float32)
+    return m.tile_raster(coords, above, patch_size, downsample, shape, origin).pred()
