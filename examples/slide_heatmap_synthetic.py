@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Slide pixels in, heatmap out, on one GPU (DESIGN.md sections 10-12): a synthetic slide and its thumbnail -> tissue_mask ->
-encode_region with half-overlapping tiles -> wsi.segment_heatmap -> render_heatmap -> a PNG.
+"""Slide pixels in, heatmap and lesion table out, on one GPU (DESIGN.md sections 10-13): a synthetic slide and its thumbnail ->
+tissue_mask -> encode_region with half-overlapping tiles -> wsi.segment_heatmap -> render_heatmap -> a PNG; wsi.segment_regions -> the
+regions above the median score, largest first.
 
     python examples/slide_heatmap_synthetic.py [--rows 8] [--cols 10] [--depth 2] [--out slide_heatmap.png]
 
@@ -65,6 +66,17 @@ def main():
     print(f"{a.rows} x {a.cols} cells of {PATCH}: {int(tissue.mask.sum())} of {tissue.mask.numel()} thumbnail pixels are tissue, {feats.shape[0]} tiles "
           f"encoded (step {PATCH // 2}), {raster}, up to {int(raster.count.max())} tiles per pixel, mean in [{lo:.4f}, {hi:.4f}]; "
           f"heatmap {tuple(picture.shape)} in {dt * 1e3:.1f} ms")
+    thd = float(raster.mean()[raster.count > 0].median())
+    lesions = wsi.segment_regions(raster, thd, tissue=tissue, min_area=4, model=model)
+    tissue_regions = model.mask_regions(tissue, labels=False)
+    print(f"{tissue_regions.n} tissue region(s); {lesions.n} region(s) of >= 4 pixels with mean score > {thd:.4f}:")
+    print("   id  area px  area mm2 @0.25um  box level-0 (x0, y0, x1, y1)    centroid level-0      mean    peak  border")
+    top = lesions.sort("area")
+    l0 = top.to_level0()
+    for i in range(min(top.n, 10)):
+        box, (cx, cy) = [int(v) for v in l0["box"][i]], l0["centroid"][i]
+        print(f"  {int(top.ids[i]):3d}  {int(top.area[i]):7d}  {top.area_mm2(0.25)[i]:16.4f}  {str(tuple(box)):30s}  ({cx:8.1f}, {cy:8.1f})  "
+              f"{top.mean_score()[i]:.4f}  {top.peak_score()[i]:.4f}  {int(top.border[i])}")
     from PIL import Image
     Image.fromarray(picture.cpu().numpy()).save(a.out)
     print(f"wrote {a.out}")

@@ -275,6 +275,33 @@ int keep_heat_render(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, c
                      int pix_stride, int background_rgb, const unsigned char* mask, const unsigned char* lut, int alpha, int lo16, int hi16,
                      int min16, unsigned char* out, void* stream);
 
+/* Region table: the connected regions of a mask, numbered, with geometry and scores.
+ * Replaces: the list of tissue contours with areas and boxes that CLAM's segmentTissue hands back (the step of README.md:74), and
+ * the per-lesion reading of a tumour-probability map that follows WSI_evaluation/segment_utils.py's pred_mask; restated on the
+ * pixel mask, integer arithmetic, exact.
+ * keep_regions_label: mask uint8 [H,W] contiguous, non-zero = foreground, 1 <= H W <= 2^30.  Components are 4- or 8-connected
+ * (connectivity); one is KEPT iff it holds >= min_area pixels (min_area >= 1; keep_tissue_mask's rule is the other way round:
+ * DROPPED iff <= min_area).  The kept components are numbered 1..n in the row-major order of their first pixels, which is
+ * scipy.ndimage.label's numbering with the dropped ones removed.  labels_out: int32 [H,W], 0 = background or dropped; n_out: one
+ * int64 ON THE DEVICE.  Workspace (8 bytes per pixel) comes from the handle's arena.  A labelling loop that runs into its
+ * iteration cap sets bit 2 (value 4) of the handle's sticky error word (keep_token_error).
+ * keep_regions_table: labels int32 [H,W] with values 0..n (a value outside 1..n counts as background), n >= 0 as read back from
+ * n_out; acc: the int64 [H,W] accumulator of keep_heat_accumulate (bits 0..39 the sum S, bits 40..63 the count c), 8-byte aligned,
+ * or NULL.  table_out: int64 [n,14] (may be NULL when n = 0), row i - 1 for label i:
+ *   0 first_x, 1 first_y  the region's first pixel in row-major order     7 sum_x, 8 sum_y  sums of the pixels' column / row indices
+ *   2 area                pixels                                           9 border          1 iff a pixel lies in row 0 / H - 1 or column 0 / W - 1
+ *   3 x0, 4 y0, 5 x1, 6 y1  bounding box, x1 / y1 exclusive               10 covered         pixels with c > 0
+ *  11 sum_c, 12 sum_s     sums of c and of S over the region              13 peak16          max over covered pixels of (2 S + c) / (2 c)
+ * Columns 10..13 are 0 without acc.  sum_s must fit: the caller checks tiles * (patch / downsample + 1)^2 * 65535 < 2^63.
+ * PRECONDITION on acc: every word satisfies S <= 65535 c, as every word keep_heat_accumulate writes does (each tile adds at most
+ * 65535 to S and 1 to c).  The pixel mean is then <= 65535 and peak16 is carried in 32 bits; a word that breaks this (c = 1 with
+ * S >= 2^31, say) is not detected and its peak16 is truncated to 32 bits.  The other columns do not depend on it.
+ * Integer sums, minima and maxima: the table is the same from run to run. */
+int keep_regions_label(keep_handle* h, const unsigned char* mask, int64_t H, int64_t W, int connectivity, int64_t min_area,
+                       int32_t* labels_out, int64_t* n_out, void* stream);
+int keep_regions_table(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, const int64_t* acc, int64_t* table_out,
+                       void* stream);
+
 /* Pre-allocate workspace for calls of up to `tiles` tiles and `prompts` x `seq` tokens. */
 int keep_reserve(keep_handle* h, int64_t tiles, int64_t prompts, int64_t seq);
 int64_t keep_workspace_bytes(keep_handle* h);
@@ -317,7 +344,7 @@ int keep_encode_text(keep_handle* h, const int64_t* input_ids, const int64_t* to
  *   bit 1 (2): an output feature row of keep_encode_image / keep_encode_text was not finite: an activation left the fp16 range
  *              (|x| > 65504 in a qkv / MLP-hidden store -- conversions do not saturate, so the overflow reaches the output as NaN
  *              instead of as plausible garbage; the fp32 reference would not overflow);
- *   bit 2 (4): a component-labelling loop of keep_tissue_mask ran into its iteration cap (cannot happen unless the labels were
+ *   bit 2 (4): a component-labelling loop of keep_tissue_mask / keep_regions_label ran into its iteration cap (cannot happen unless the labels were
  *              corrupted: a chain of strictly decreasing pixel indices is shorter than the image); the mask is not valid.
  * Encode calls only ever SET bits; they are cleared here, once the host has seen them, so an error can not be lost between calls.
  * Synchronises `stream`. */

@@ -204,6 +204,23 @@ struct SgemmParams {
 };
 int launch_sgemm_f32(const SgemmParams& p, hipStream_t s);
 
+// 256 threads: exclusive prefix of v over the block; *total = the block's sum.  s: 256 ints of LDS, reusable on return.
+__device__ __forceinline__ int block_exclusive_scan256(int v, int* s, int* total) {
+    const int t = threadIdx.x;
+    s[t] = v;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const int a = t >= o ? s[t - o] : 0;
+        __syncthreads();
+        s[t] += a;
+        __syncthreads();
+    }
+    const int incl = s[t];
+    *total = s[255];
+    __syncthreads();
+    return incl - v;
+}
+
 // Slide-region front end (region.hip): patch grid + tissue rule + stable compaction, patch gather.
 // keep: ncells bytes, counts / offsets: ceil(ncells / 2048) ints each; tmp (patch != 224): B * patch * 224 * 3 bytes
 void launch_region_grid(const unsigned char* region, int64_t row_stride, int ps, int gx, int64_t ncells, int patch, int step, int sat_min,
@@ -229,6 +246,20 @@ void launch_tissue_mask(const unsigned char* med, int h, int w, int thr, int clo
                         int* info, int* err, unsigned char* mask, hipStream_t s);
 void launch_tissue_grid_cells(const unsigned char* mask, int64_t mh, int64_t mw, int64_t ds, int gx, int64_t ncells, int patch, int step,
                               int64_t ox, int64_t oy, int mode, unsigned char* keep, hipStream_t s);
+
+// the labelling alone: foreground components of img, 8- or 4-connected -> labels[p] = the component's smallest pixel index (-1 on the
+// background), info[root] = area | CC_BORDER (labelling.h)
+void launch_cc_label(const unsigned char* img, int h, int w, int conn8, int* labels, int* info, int* err, hipStream_t s);
+
+// Region table (components.hip)
+constexpr int REGIONS_COLS = 14;
+constexpr int REGIONS_SCAN_CHUNK = 2048;               // pixels per block of the rank scan
+// mask -> dense labels 1..n in the order of the components' first pixels, components of < min_area pixels dropped; *n_out = n.
+// roots, info: h w int32 each; counts / offsets: ceil(h w / REGIONS_SCAN_CHUNK) ints each
+void launch_regions_label(const unsigned char* mask, int h, int w, int conn8, int min_area, int* roots, int* info, int* counts, int* offsets,
+                          int* err, int* labels_out, int64_t* n_out, hipStream_t s);
+// labels (values outside 1..n count as background) + acc (nullable) -> table [n][REGIONS_COLS]
+void launch_regions_table(const int* labels, int h, int w, int64_t n, const int64_t* acc, int64_t* table, hipStream_t s);
 
 // Tile scores rasterised onto the thumbnail (heatmap.hip).  acc: one 64-bit word per raster pixel, bits 0..39 the sum
 // of the 16-bit fixed-point values of the covering tiles, bits 40..63 their number

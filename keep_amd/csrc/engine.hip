@@ -1847,6 +1847,43 @@ int keep_heat_render(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, c
     return check_launch(h, "heat_render");
 }
 
+static bool regions_shape_ok(int64_t H, int64_t W) {
+    return H >= 1 && W >= 1 && H <= TISSUE_MAX_PIXELS && W <= TISSUE_MAX_PIXELS && H * W <= TISSUE_MAX_PIXELS;
+}
+
+int keep_regions_label(keep_handle* h, const unsigned char* mask, int64_t H, int64_t W, int connectivity, int64_t min_area, int32_t* labels_out,
+                       int64_t* n_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!mask || !labels_out || !n_out) return h->fail(KEEP_EINVAL, "regions_label: null pointer");
+    if (!regions_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "regions_label: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (connectivity != 4 && connectivity != 8) return h->fail(KEEP_EINVAL, "regions_label: connectivity %d (4 or 8)", connectivity);
+    if (min_area < 1) return h->fail(KEEP_EINVAL, "regions_label: min_area %lld < 1", (long long)min_area);
+    if (((uintptr_t)labels_out & 3) || ((uintptr_t)n_out & 7)) return h->fail(KEEP_EINVAL, "regions_label: labels_out / n_out not aligned");
+    KEEP_ON_DEVICE(h);
+    const size_t n = (size_t)(H * W);
+    const size_t b_lab = align_up(n * 4), b_counts = align_up(((n + REGIONS_SCAN_CHUNK - 1) / REGIONS_SCAN_CHUNK) * sizeof(int));
+    int rc = ensure_arena(h, 2 * b_lab + 2 * b_counts);
+    if (rc) return rc;
+    // an area never exceeds H W <= 2^30: a larger bound decides the same (every component is dropped)
+    launch_regions_label(mask, (int)H, (int)W, connectivity == 8, (int)std::min<int64_t>(min_area, TISSUE_MAX_PIXELS + 1), (int*)h->arena,
+                         (int*)(h->arena + b_lab), (int*)(h->arena + 2 * b_lab), (int*)(h->arena + 2 * b_lab + b_counts), h->err_flag,
+                         labels_out, n_out, (hipStream_t)stream);
+    return check_launch(h, "regions_label");
+}
+
+int keep_regions_table(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, const int64_t* acc, int64_t* table_out,
+                       void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "regions_table: labels is null or not 4-byte aligned");
+    if (!regions_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "regions_table: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (n < 0 || n > H * W) return h->fail(KEEP_EINVAL, "regions_table: n = %lld outside [0, H W]", (long long)n);
+    if ((uintptr_t)acc & 7) return h->fail(KEEP_EINVAL, "regions_table: acc is not 8-byte aligned");
+    if (n > 0 && (!table_out || ((uintptr_t)table_out & 7))) return h->fail(KEEP_EINVAL, "regions_table: table_out is null or not 8-byte aligned");
+    KEEP_ON_DEVICE(h);
+    launch_regions_table(labels, (int)H, (int)W, n, acc, table_out, (hipStream_t)stream);
+    return check_launch(h, "regions_table");
+}
+
 int keep_token_error(keep_handle* h, void* stream) {
     if (!h) return KEEP_EINVAL;
     KEEP_ON_DEVICE(h);

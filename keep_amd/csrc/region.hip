@@ -26,23 +26,6 @@ __device__ __forceinline__ bool region_is_tissue(unsigned r, unsigned g, unsigne
     return mx > 0 && 255u * (mx - mn) >= sat_min * mx;
 }
 
-// 256 threads: exclusive prefix of v over the block; *total = the block's sum.  s: 256 ints of LDS, reusable on return.
-__device__ __forceinline__ int block_exclusive_scan256(int v, int* s, int* total) {
-    const int t = threadIdx.x;
-    s[t] = v;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const int a = t >= o ? s[t - o] : 0;
-        __syncthreads();
-        s[t] += a;
-        __syncthreads();
-    }
-    const int incl = s[t];
-    *total = s[255];
-    __syncthreads();
-    return incl - v;
-}
-
 // 4 waves per cell: wave w takes rows w, w + 4, ...; its lanes consecutive pixels of a row
 __global__ __launch_bounds__(256)
 void region_tissue_count_kernel(const unsigned char* __restrict__ region, int64_t row_stride, int ps, int gx, int64_t ncells,

@@ -23,12 +23,10 @@
 // Pixel indices are int32 (H W <= 2^30, checked by the caller); every kernel walks 64 x 4 pixel tiles, one wave per row, in a
 // grid-stride loop, so a wave always holds 64 consecutive pixels of one row.
 #include "common.h"
+#include "labelling.h"
 #include "../../include/keep_hip.h"
 
 namespace keepk {
-
-constexpr int TISSUE_ERR_BIT = 4;                     // keep_handle::err_flag, bit 2: a labelling loop ran into its iteration cap
-constexpr int CC_BORDER = (int)0x80000000;            // info[root]: bit 31 = the component touches the image border, bits 0..30 = area
 
 __device__ __forceinline__ unsigned tissue_saturation(unsigned r, unsigned g, unsigned b) {
     const unsigned mx = max(r, max(g, b)), mn = min(r, min(g, b));
@@ -135,17 +133,6 @@ __device__ __forceinline__ void cc_union(int* L, int a, int b, int n, int* err) 
     }
     atomicOr(err, TISSUE_ERR_BIT);
 }
-
-// tile t of the 64 x 4 walk -> this thread's pixel (x, y); false when the WAVE's row is outside (wave-uniform), x may still be >= w
-struct CcWalk {
-    int tx; int64_t ntiles;
-    __device__ CcWalk(int h, int w) : tx((w + 63) / 64), ntiles((int64_t)((w + 63) / 64) * ((h + 3) / 4)) {}
-    __device__ bool at(int64_t t, int h, int* x, int* y) const {
-        *x = (int)(t % tx) * 64 + (threadIdx.x & 63);
-        *y = (int)(t / tx) * 4 + (threadIdx.x >> 6);
-        return *y < h;
-    }
-};
 
 template <bool FG>
 __global__ __launch_bounds__(256)
@@ -301,6 +288,11 @@ static void cc_label(const unsigned char* img, int h, int w, int* L, int* info, 
     hipLaunchKernelGGL((cc_merge_kernel<FG, CONN8>), gt, b, 0, s, img, h, w, L, err);
     hipLaunchKernelGGL(cc_compress_kernel, gp, b, 0, s, h, w, L, err);
     hipLaunchKernelGGL(cc_count_kernel, gt, b, 0, s, h, w, L, info);
+}
+
+void launch_cc_label(const unsigned char* img, int h, int w, int conn8, int* labels, int* info, int* err, hipStream_t s) {
+    if (conn8) cc_label<true, true>(img, h, w, labels, info, err, s);
+    else cc_label<true, false>(img, h, w, labels, info, err, s);
 }
 
 void launch_tissue_mask(const unsigned char* med, int h, int w, int thr, int close, int min_hole, int min_area, unsigned char* tmp, int* labels,

@@ -1139,6 +1139,43 @@ class KEEPModel:
                    "heat_render")
         return out
 
+    # ------------------------------------------------------------------ region table
+    @torch.no_grad()
+    def mask_regions(self, mask, connectivity: int = 8, min_area: int = 1, raster=None, labels: bool = True, max_regions: int = 1 << 20):
+        """The connected regions of a mask, numbered, with geometry and scores, on the device ->
+        ``keep_amd.components.RegionTable``.
+
+        ``mask``: uint8 / bool [h,w], numpy or torch, host or device, non-zero = foreground, ``h w <= 2^30``; or a ``TissueMask``, which
+        brings its ``downsample``.  Components are 4- or 8-connected; one is KEPT iff it holds ``>= min_area`` pixels (``min_area >= 1``;
+        note that ``TissueSegmentation.min_area`` DROPS a fragment iff it holds ``<= min_area``).  The kept ones are numbered 1..n in the
+        row-major order of their first pixels, which is ``scipy.ndimage.label``'s numbering with the dropped ones removed.
+        ``raster``: a ``TileRaster`` of the mask's shape (and downsample, where both have one) whose sums fill the score columns;
+        without one they are 0.  ``labels=False`` leaves the int32 [h,w] label image out of the result.  n is read back once to size
+        the table (the one host synchronisation); more than ``max_regions`` regions is a ValueError raised before the table is
+        allocated.  Everything is integer arithmetic, equal to ``keep_amd.components.regions_numpy`` bit for bit and the same from
+        run to run."""
+        from .components import NCOLS, RegionTable, check_raster, check_region_count, check_regions_args, mask_tensor
+        connectivity, min_area, max_regions = check_regions_args(connectivity, min_area, max_regions)
+        m, d = mask_tensor(mask)
+        h, w = int(m.shape[0]), int(m.shape[1])
+        d = check_raster(raster, (h, w), d)
+        self._ready_device()
+        if raster is not None and raster.acc.device != self._device:
+            raise ValueError(f"the raster lives on {raster.acc.device}, this engine on {self._device}")
+        m = m.to(self._device).contiguous()
+        m = m.view(torch.uint8) if m.dtype == torch.bool else m
+        lib, st = _lib.load(), _stream(self._device)
+        lab = torch.empty((h, w), dtype=torch.int32, device=self._device)
+        n_dev = torch.empty((1,), dtype=torch.int64, device=self._device)
+        _lib.check(self._handle, lib.keep_regions_label(self._handle, _ptr(m), h, w, connectivity, min_area, _ptr(lab), _ptr(n_dev), st),
+                   "regions_label")
+        self._queue_flag_check(st)
+        n = check_region_count(int(n_dev.item()), max_regions)
+        table = torch.empty((n, NCOLS), dtype=torch.int64, device=self._device)
+        _lib.check(self._handle, lib.keep_regions_table(self._handle, _ptr(lab), h, w, n, _ptr(None if raster is None else raster.acc),
+                                                        _ptr(table), st), "regions_table")
+        return RegionTable(table, lab if labels else None, d, (0, 0) if raster is None else raster.origin)
+
     @staticmethod
     def _cells_to_coords(cells: torch.Tensor, origin, coord_scale: int) -> torch.Tensor:
         o = torch.tensor(origin, dtype=torch.int64, device=cells.device)
@@ -1298,7 +1335,7 @@ class KEEPModel:
         if bits & 1:
             raise IndexError(f"index out of range in self (input_ids / token_type_ids{when} were outside the embedding tables)")
         if bits & 4:
-            raise _lib.KeepHipError(f"tissue_mask{when}: a component-labelling loop ran into its iteration cap (the mask is not valid)")
+            raise _lib.KeepHipError(f"tissue_mask / mask_regions{when}: a component-labelling loop ran into its iteration cap (the mask is not valid)")
         if bits & 2:
             raise FloatingPointError(f"non-finite output features{when}: an activation exceeded the fp16 range (65504) of the engine's qkv / "
                                      "MLP-hidden stores; these weights need the fp32 reference path")

@@ -347,6 +347,31 @@ def segment_heatmap(classifier, tile_features, tile_coords, downsample, shape, p
     return m.tile_raster(coords, mean[:, int(cls)].contiguous(), patch_size, downsample, shape, origin)
 
 
+def segment_regions(raster, thd=0.5, tissue=None, connectivity=8, min_area=1, model=None):
+    """The lesion table of a segmentation raster: the connected regions of the pixels whose mean is above
+    ``thd``, with area, box, centroid sums and mean / peak score -> ``keep_amd.components.RegionTable``.  ``raster``: the
+    ``TileRaster`` of :func:`segment_heatmap`.  A pixel is set iff a tile covers it, ``sum > quantize(thd) * count`` (int64: the mean
+    in 16-bit fixed point is above the threshold in the same fixed point) and ``tissue`` (a ``TissueMask`` of the raster's shape and
+    downsample, optional) is set there."""
+    from .heatmap import COUNT_SHIFT, MAX_TILES, SUM_MASK, TileRaster, quantize
+    from .region import TissueMask
+    if not isinstance(raster, TileRaster):
+        raise ValueError(f"raster must be a TileRaster, got {type(raster).__name__}")
+    if tissue is not None:
+        if not isinstance(tissue, TissueMask):
+            raise ValueError(f"tissue must be a TissueMask, got {type(tissue).__name__}")
+        if tissue.downsample != raster.downsample or tuple(tissue.mask.shape) != raster.shape:
+            raise ValueError(f"tissue mask has downsample {tissue.downsample} and shape {tuple(tissue.mask.shape)}, the raster "
+                             f"{raster.downsample} and {raster.shape}")
+    t16 = quantize(thd)
+    S, c = raster.acc & SUM_MASK, (raster.acc >> COUNT_SHIFT) & MAX_TILES
+    mask = (c > 0) & (S > t16 * c)
+    if tissue is not None:
+        mask &= tissue.mask.to(mask.device) != 0
+    m = _engine(model, raster.acc)
+    return m.mask_regions(mask, connectivity, min_area, raster=raster)
+
+
 def segment_pred_mask(probs, thd, downsample, shape, patch_size=224, origin=(0, 0), model=None) -> torch.Tensor:
     """The ``pred_mask`` that ``eval_seg_coarse`` paints (segment_utils.py:134-140), at any integer ``downsample`` (the reference's
     level 16 is ``downsample=16``): uint8 {0,255} [h,w] on the device, 255 where any covering tile has ``p > thd``, overlapping tiles
