@@ -265,7 +265,8 @@ int keep_heat_accumulate(keep_handle* h, const int64_t* coords, const float* val
  * all. */
 int keep_heat_mean(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, float uncovered, float* mean_out, int32_t* count_out,
                    unsigned char* pred_out, void* stream);
-/* Replaces: the heatmap blended over the thumbnail that closes CLAM's step of README.md:74 (no blur, no percentile ranks).
+/* Replaces: the heatmap blended over the thumbnail that closes CLAM's step of README.md:74.  CLAM's percentile ranks and blur are
+ * calls of their own, made before this one: keep_sort_f32 / keep_rank_f32 on the tile values, keep_heat_smooth on the accumulator.
  * thumb: uint8 [H,W,C] RGB / RGBA with the layout contract of keep_region_grid, or null for the constant background_rgb
  * (R | G << 8 | B << 16).  mask: uint8 [H,W] contiguous (non-zero = show), or null.  lut: uint8 [256,3].  With S = sum, c = count a
  * pixel is shown iff c > 0, the mask is set and S >= min16 c; its colour index is clamp((2 255 (S - lo16 c) + (hi16 - lo16) c) /
@@ -274,6 +275,34 @@ int keep_heat_mean(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, flo
 int keep_heat_render(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, const unsigned char* thumb, int64_t row_stride_bytes,
                      int pix_stride, int background_rgb, const unsigned char* mask, const unsigned char* lut, int alpha, int lo16, int hi16,
                      int min16, unsigned char* out, void* stream);
+
+/* ---- heatmap percentiles and smoothing ---------------------------------------
+ * Replaces: the Gaussian blur of the overlay in the heatmap that closes CLAM's step of README.md:74, restated as a normalised
+ * convolution in integers (no parity with an image library's border handling is claimed).  acc as above; mask: uint8 [H,W]
+ * contiguous (non-zero = inside), or null; taps: int32 [2 radius + 1] ON THE DEVICE, every tap >= 0, the centre tap >= 1, their sum
+ * <= 32768 (the caller's precondition: a table that breaks it gives meaningless values, nothing worse); 1 <= radius <= 127.
+ * With S, c the fields of a pixel: s = c > 0 and the mask is set; m = s ? (2 S + c) / (2 c) : 0 (the mean in 16-bit fixed point,
+ * rounded half up: peak16's rule).  A = sum_k taps[k] m(y, x + k), B = sum_k taps[k] s(y, x + k) along the row, Nn = sum_k taps[k]
+ * A(y + k, x), D = sum_k taps[k] B(y + k, x) along the column, pixels outside the raster without support;
+ * acc_out = s ? (1 << 40) | (2 Nn + D) / (2 D) : 0, an accumulator of count 1 that every call above reads unchanged.  Pixels
+ * without support neither give nor receive; a constant region stays constant.  PRECONDITION on acc: S <= 65535 c (see
+ * keep_regions_table).  acc_out: int64 [H,W], 8-byte aligned, not acc.  Workspace (6 bytes per pixel) comes from the handle's arena. */
+int keep_heat_smooth(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, const unsigned char* mask, const int32_t* taps, int radius,
+                     int64_t* acc_out, void* stream);
+/* Replaces: the sorted score population behind CLAM's percentile heatmaps (scipy.stats.rankdata over the slide's own tiles,
+ * percentileofscore against a reference population; the step of README.md:74).  values: fp32 [M], 1 <= M <= 2^24 - 1.  NaNs of any
+ * payload or sign are not part of the population and -0.0 counts as +0.0: sorted_out[0:n] holds the n other values in ascending
+ * order (-0 stored as +0), sorted_out[n:M] the NaN 0x7FC00000, *n_out = n (one int64 ON THE DEVICE).  sorted_out may be values.
+ * No host synchronisation; workspace (4 bytes per value + the digit tables, none up to 4096 values) comes from the handle's arena. */
+int keep_sort_f32(keep_handle* h, const float* values, int64_t M, float* sorted_out, int64_t* n_out, void* stream);
+/* Replaces: scipy.stats.rankdata(v, 'average') (self = 1: the queries ARE the population, r2 = 2 less + eq + 1 = twice the average
+ * rank) and scipy.stats.percentileofscore(ref, q, kind='mean') (self = 0: r2 = 2 less + eq) of CLAM's heatmap step.  sorted, M: the
+ * output of keep_sort_f32; n_dev: its n_out, read on the device.  queries: fp32 [N], 0 <= N <= 2^24 - 1.  For a query q that is
+ * not NaN: less = #{sorted[0:n] < q}, eq = #{sorted[0:n] == q} by float comparison, pct = float(double(r2) / double(2 n)), NaN
+ * when n = 0.  A NaN query gives pct = NaN and less = eq = -1.  pct_out fp32 [N], less_out / eq_out int32 [N]: any may be null,
+ * not all. */
+int keep_rank_f32(keep_handle* h, const float* sorted, int64_t M, const int64_t* n_dev, const float* queries, int64_t N, int self,
+                  float* pct_out, int32_t* less_out, int32_t* eq_out, void* stream);
 
 /* Region table: the connected regions of a mask, numbered, with geometry and scores.
  * Replaces: the list of tissue contours with areas and boxes that CLAM's segmentTissue hands back (the step of README.md:74), and

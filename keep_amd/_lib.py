@@ -55,6 +55,9 @@ SIGNATURES = {
     "keep_heat_accumulate": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp]),
     "keep_heat_mean": (_i32, [_vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "keep_heat_render": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "keep_heat_smooth": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp]),
+    "keep_sort_f32": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "keep_rank_f32": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "keep_regions_label": (_i32, [_vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp]),
     "keep_regions_table": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "keep_token_error": (_i32, [_vp, _vp]),

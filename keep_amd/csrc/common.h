@@ -275,6 +275,22 @@ void launch_heat_mean(const int64_t* acc, int h, int w, float uncovered, float* 
 void launch_heat_render(const int64_t* acc, int h, int w, const unsigned char* thumb, int64_t row_stride, int ps, unsigned bg,
                         const unsigned char* mask, const unsigned char* lut, int alpha, int lo16, int hi16, int min16, unsigned char* out,
                         hipStream_t s);
+// Gaussian smoothing under the support.  taps: int32 [2 radius + 1] on the device; rowa (h w uint32) and rowb
+// (h w uint16) hold the row pass; out must not be acc
+constexpr int HEAT_SMOOTH_MAX_RADIUS = 127;
+void launch_heat_smooth(const int64_t* acc, int h, int w, const unsigned char* mask, const int* taps, int radius, unsigned* rowa,
+                        unsigned short* rowb, int64_t* out, hipStream_t s);
+
+// Sorted score population and rank percentiles (rank.hip)
+constexpr int SORT_TILE = 4096;                         // keys per block; up to this many are sorted by one block in LDS
+constexpr int SORT_SCAN_CHUNK = 2048;                   // entries of the digit table per block of the scan
+constexpr int64_t SORT_MAX = ((int64_t)1 << 24) - 1;
+// bytes of workspace for M values (0 up to SORT_TILE) and where the digit table and the chunk totals start in it
+size_t sort_workspace_bytes(int64_t M, size_t* table_off, size_t* totals_off);
+void launch_sort_f32(const float* values, int64_t M, unsigned char* ws, float* sorted_out, int64_t* n_out, hipStream_t s);
+// any of pct / less / eq may be null
+void launch_rank_f32(const float* sorted, int64_t M, const int64_t* n_dev, const float* queries, int64_t N, int self, float* pct,
+                     int* less, int* eq, hipStream_t s);
 
 // Row-wise helpers (rowops.hip)
 // pixels [B,3,16 gh,16 gw] (or uint8 [B,16 gh,16 gw,3]) -> patches [B * gh * gw][768], row-major (y, x) patch order; CLS rows of resid

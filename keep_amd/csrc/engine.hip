@@ -1847,6 +1847,52 @@ int keep_heat_render(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, c
     return check_launch(h, "heat_render");
 }
 
+int keep_heat_smooth(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, const unsigned char* mask, const int32_t* taps, int radius,
+                     int64_t* acc_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "heat_smooth: acc is null or not 8-byte aligned");
+    if (!acc_out || ((uintptr_t)acc_out & 7)) return h->fail(KEEP_EINVAL, "heat_smooth: acc_out is null or not 8-byte aligned");
+    if (acc_out == acc) return h->fail(KEEP_EINVAL, "heat_smooth: acc_out aliases acc");
+    if (heat_shape_error(H, W)) return h->fail(KEEP_EINVAL, "heat_smooth: %lldx%lld: %s", (long long)H, (long long)W, heat_shape_error(H, W));
+    if (!taps || ((uintptr_t)taps & 3)) return h->fail(KEEP_EINVAL, "heat_smooth: taps is null or not 4-byte aligned");
+    if (radius < 1 || radius > HEAT_SMOOTH_MAX_RADIUS) return h->fail(KEEP_EINVAL, "heat_smooth: radius %d outside [1, %d]", radius, HEAT_SMOOTH_MAX_RADIUS);
+    KEEP_ON_DEVICE(h);
+    const size_t n = (size_t)(H * W), b_a = align_up(n * 4);
+    int rc = ensure_arena(h, b_a + align_up(n * 2));
+    if (rc) return rc;
+    launch_heat_smooth(acc, (int)H, (int)W, mask, taps, radius, (unsigned*)h->arena, (unsigned short*)(h->arena + b_a), acc_out, (hipStream_t)stream);
+    return check_launch(h, "heat_smooth");
+}
+
+int keep_sort_f32(keep_handle* h, const float* values, int64_t M, float* sorted_out, int64_t* n_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (M < 1 || M > SORT_MAX) return h->fail(KEEP_EINVAL, "sort_f32: %lld values (1 .. 2^24 - 1)", (long long)M);
+    if (!values || !sorted_out || !n_out) return h->fail(KEEP_EINVAL, "sort_f32: null pointer");
+    if (((uintptr_t)values & 3) || ((uintptr_t)sorted_out & 3) || ((uintptr_t)n_out & 7)) return h->fail(KEEP_EINVAL, "sort_f32: values / sorted_out / n_out not aligned");
+    KEEP_ON_DEVICE(h);
+    size_t table_off, totals_off;
+    int rc = ensure_arena(h, sort_workspace_bytes(M, &table_off, &totals_off));
+    if (rc) return rc;
+    launch_sort_f32(values, M, (unsigned char*)h->arena, sorted_out, n_out, (hipStream_t)stream);
+    return check_launch(h, "sort_f32");
+}
+
+int keep_rank_f32(keep_handle* h, const float* sorted, int64_t M, const int64_t* n_dev, const float* queries, int64_t N, int self,
+                  float* pct_out, int32_t* less_out, int32_t* eq_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (M < 1 || M > SORT_MAX) return h->fail(KEEP_EINVAL, "rank_f32: a population of %lld values (1 .. 2^24 - 1)", (long long)M);
+    if (N < 0 || N > SORT_MAX) return h->fail(KEEP_EINVAL, "rank_f32: %lld queries (0 .. 2^24 - 1)", (long long)N);
+    if (!sorted || !n_dev || (N > 0 && !queries)) return h->fail(KEEP_EINVAL, "rank_f32: null sorted, n or queries");
+    if (self != 0 && self != 1) return h->fail(KEEP_EINVAL, "rank_f32: self %d (0 or 1)", self);
+    if (!pct_out && !less_out && !eq_out) return h->fail(KEEP_EINVAL, "rank_f32: no output");
+    if (((uintptr_t)sorted & 3) || ((uintptr_t)n_dev & 7) || ((uintptr_t)queries & 3) || ((uintptr_t)pct_out & 3) || ((uintptr_t)less_out & 3) ||
+        ((uintptr_t)eq_out & 3))
+        return h->fail(KEEP_EINVAL, "rank_f32: a pointer is not aligned");
+    KEEP_ON_DEVICE(h);
+    launch_rank_f32(sorted, M, n_dev, queries, N, self, pct_out, less_out, eq_out, (hipStream_t)stream);
+    return check_launch(h, "rank_f32");
+}
+
 static bool regions_shape_ok(int64_t H, int64_t W) {
     return H >= 1 && W >= 1 && H <= TISSUE_MAX_PIXELS && W <= TISSUE_MAX_PIXELS && H * W <= TISSUE_MAX_PIXELS;
 }

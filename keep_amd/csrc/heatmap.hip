@@ -8,7 +8,10 @@
 //                     value in 16-bit fixed point: bits 0..39 of a pixel sum q, bits 40..63 count the tiles.  Integer sums do not
 //                     depend on the order of arrival, so the raster is the same however the tiles are split over calls.
 //   heat_mean         one pass: accumulator -> fp32 mean (sum / (65535 count), divided in double), int32 count, {0,255} sum > 0
-//   heat_render       one pass: accumulator (+ thumbnail, + mask) -> colour index by an integer rule -> LUT (in LDS) -> blend
+//   heat_render       one pass: accumulator (+ thumbnail, + mask) -> colour index by an integer rule -> LUT (in LDS) -> blend.  CLAM's
+//                     rank percentiles and blur come before it as calls of their own: keep_sort_f32 / keep_rank_f32 (rank.hip) on
+//                     the tile values, keep_heat_smooth (below) on the accumulator
+//   heat_smooth_row / _col   the Gaussian under the support, two passes (described where they stand)
 //
 // Pixel indices are int32 (h w <= 2^30, checked by the caller); offsets into the accumulator (8 bytes per pixel) are int64.
 #include "common.h"
@@ -175,8 +178,186 @@ void heat_render_kernel(const heat_acc_t* __restrict__ acc, int h, int w, const 
     }
 }
 
+// ---- Gaussian smoothing under the support ----------------------------------------------------------------
+// A normalised convolution in integers.  Per pixel s = covered (and inside the mask), m = s ? (2 S + c) / (2 c) : 0.  The row pass
+// writes A = sum taps m (< 2^31, bit 31 carries the pixel's own s) and B = sum taps s (<= 2^15); the column pass sums both over
+// the rows into Nn (< 2^46, 64 bits) and D (< 2^30) and writes (1 << 40) | (2 Nn + D) / (2 D) on the support, 0 elsewhere.  Both
+// passes stage their input span plus halo in LDS, and a thread makes eight consecutive outputs: a window value is read from LDS
+// once per thread and the fifteen taps a chunk of eight window values meets are read once per chunk (the same address in every
+// lane).  The taps sit in LDS shifted by 7 with zeros on both sides, so tap (offset - output) needs no bounds test.
+
+constexpr int SMOOTH_PER = 8;                           // outputs per thread, both passes
+constexpr int SMOOTH_ROW_THREADS = 128, SMOOTH_ROW_SEG = SMOOTH_ROW_THREADS * SMOOTH_PER;
+constexpr int SMOOTH_MAX_CHUNKS = (2 * HEAT_SMOOTH_MAX_RADIUS + 2 * SMOOTH_PER - 1) / SMOOTH_PER;       // 33
+constexpr int SMOOTH_TAPS_LDS = SMOOTH_PER * SMOOTH_MAX_CHUNKS + 2 * SMOOTH_PER;                        // 280 >= 8 chunks + 15
+constexpr int SMOOTH_COL_LDS_LIMIT = 65536;
+
+__device__ __forceinline__ int smooth_chunks(int radius) { return (2 * radius + 2 * SMOOTH_PER - 1) / SMOOTH_PER; }
+
+// floor(a / b) for a < 2^53, 1 <= b < 2^53: both are exact doubles and the quotient is within one of the rounded division
+__device__ __forceinline__ uint64_t heat_floor_quot(uint64_t a, uint64_t b) {
+    uint64_t q = (uint64_t)((double)a / (double)b);
+    if (q * b > a) --q;
+    else if ((q + 1) * b <= a) ++q;
+    return q;
+}
+
+__device__ __forceinline__ void smooth_stage_taps(const int* __restrict__ taps, int radius, int* tp, int nthreads) {
+    for (int i = threadIdx.x; i < SMOOTH_TAPS_LDS; i += nthreads) {
+        const int k = i - (SMOOTH_PER - 1);
+        tp[i] = (k >= 0 && k <= 2 * radius) ? taps[k] : 0;
+    }
+}
+
+// one block: SMOOTH_ROW_SEG outputs of one row.  win[i] is pixel (y, x0 - radius + i): m | s << 16
+__global__ __launch_bounds__(SMOOTH_ROW_THREADS)
+void heat_smooth_row_kernel(const heat_acc_t* __restrict__ acc, int h, int w, const unsigned char* __restrict__ mask,
+                            const int* __restrict__ taps, int radius, int nseg, int64_t nblocks, unsigned* __restrict__ rowa,
+                            unsigned short* __restrict__ rowb) {
+    __shared__ __attribute__((aligned(16))) unsigned win[SMOOTH_ROW_SEG + SMOOTH_PER * SMOOTH_MAX_CHUNKS];
+    __shared__ int tp[SMOOTH_TAPS_LDS];
+    const int nch = smooth_chunks(radius);
+    smooth_stage_taps(taps, radius, tp, SMOOTH_ROW_THREADS);
+    for (int64_t bid = blockIdx.x; bid < nblocks; bid += gridDim.x) {
+    const int y = (int)(bid / nseg), x0 = (int)(bid - (int64_t)y * nseg) * SMOOTH_ROW_SEG;
+    const int64_t row = (int64_t)y * w;
+    for (int i = threadIdx.x; i < SMOOTH_ROW_SEG + SMOOTH_PER * nch; i += SMOOTH_ROW_THREADS) {
+        const int x = x0 - radius + i;
+        unsigned p = 0;
+        if (i < SMOOTH_ROW_SEG + 2 * radius && x >= 0 && x < w) {
+            const heat_acc_t a = acc[row + x];
+            const heat_acc_t S = a & HEAT_SUM_MASK, c = a >> HEAT_COUNT_SHIFT;
+            if (c != 0 && (mask == nullptr || mask[row + x] != 0)) p = ((unsigned)heat_floor_quot(2 * S + c, 2 * c) & 0xFFFFu) | 0x10000u;
+        }
+        win[i] = p;
+    }
+    __syncthreads();
+    const int first = threadIdx.x * SMOOTH_PER;
+    if (x0 + first < w) {
+    unsigned A[SMOOTH_PER], B[SMOOTH_PER];
+#pragma unroll
+    for (int j = 0; j < SMOOTH_PER; ++j) A[j] = B[j] = 0;
+    for (int c = 0; c < nch; ++c) {
+        const uint4 lo = *reinterpret_cast<const uint4*>(&win[first + SMOOTH_PER * c]), hi = *reinterpret_cast<const uint4*>(&win[first + SMOOTH_PER * c + 4]);
+        const unsigned v[SMOOTH_PER] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        unsigned T[2 * SMOOTH_PER - 1];
+#pragma unroll
+        for (int i = 0; i < 2 * SMOOTH_PER - 1; ++i) T[i] = (unsigned)tp[SMOOTH_PER * c + i];
+#pragma unroll
+        for (int e = 0; e < SMOOTH_PER; ++e) {
+            const unsigned m = v[e] & 0xFFFFu, s = v[e] >> 16;
+#pragma unroll
+            for (int j = 0; j < SMOOTH_PER; ++j) {
+                const unsigned t = T[e - j + SMOOTH_PER - 1];          // tap (8 c + e) - j, zero outside 0 .. 2 radius
+                A[j] += t * m;
+                B[j] += t * s;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < SMOOTH_PER; ++j) {
+        const int x = x0 + first + j;
+        if (x < w) {
+            rowa[row + x] = A[j] | ((win[first + j + radius] >> 16) << 31);
+            rowb[row + x] = (unsigned short)B[j];
+        }
+    }
+    }
+    __syncthreads();                                  // win is staged again for the block's next segment
+    }
+}
+
+// one block: cx = 1 << cshift columns by (256 / cx) * 8 rows of outputs.  LDS row i is raster row y0 - radius + i.
+__global__ __launch_bounds__(256)
+void heat_smooth_col_kernel(const unsigned* __restrict__ rowa, const unsigned short* __restrict__ rowb, int h, int w,
+                            const int* __restrict__ taps, int radius, int cshift, int nxb, int64_t nblocks, heat_acc_t* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smooth_lds[];
+    const int cx = 1 << cshift, ry = (256 >> cshift) * SMOOTH_PER, nch = smooth_chunks(radius);
+    const int rows = ry - SMOOTH_PER + SMOOTH_PER * nch;             // the last group's window ends here
+    int* tp = reinterpret_cast<int*>(smooth_lds);
+    unsigned* a_s = reinterpret_cast<unsigned*>(smooth_lds + SMOOTH_TAPS_LDS * sizeof(int));
+    unsigned short* b_s = reinterpret_cast<unsigned short*>(a_s + rows * cx);
+    smooth_stage_taps(taps, radius, tp, 256);
+    for (int64_t bid = blockIdx.x; bid < nblocks; bid += gridDim.x) {
+    const int by = (int)(bid / nxb), x0 = (int)(bid - (int64_t)by * nxb) * cx, y0 = by * ry;
+    for (int i = threadIdx.x; i < rows * cx; i += 256) {
+        const int r = i >> cshift, x = x0 + (i & (cx - 1)), y = y0 - radius + r;
+        unsigned a = 0;
+        unsigned short b = 0;
+        if (r < ry + 2 * radius && y >= 0 && y < h && x < w) {
+            const int64_t at = (int64_t)y * w + x;
+            a = rowa[at];
+            b = rowb[at];
+        }
+        a_s[i] = a;
+        b_s[i] = b;
+    }
+    __syncthreads();
+    const int col = threadIdx.x & (cx - 1), first = (threadIdx.x >> cshift) * SMOOTH_PER;
+    const int x = x0 + col;
+    if (x < w && y0 + first < h) {
+    uint64_t Nn[SMOOTH_PER];
+    unsigned D[SMOOTH_PER];
+#pragma unroll
+    for (int j = 0; j < SMOOTH_PER; ++j) {
+        Nn[j] = 0;
+        D[j] = 0;
+    }
+    for (int c = 0; c < nch; ++c) {
+        unsigned T[2 * SMOOTH_PER - 1];
+#pragma unroll
+        for (int i = 0; i < 2 * SMOOTH_PER - 1; ++i) T[i] = (unsigned)tp[SMOOTH_PER * c + i];
+#pragma unroll
+        for (int e = 0; e < SMOOTH_PER; ++e) {
+            const int at = ((first + SMOOTH_PER * c + e) << cshift) + col;
+            const unsigned a = a_s[at] & 0x7FFFFFFFu, b = b_s[at];
+#pragma unroll
+            for (int j = 0; j < SMOOTH_PER; ++j) {
+                const unsigned t = T[e - j + SMOOTH_PER - 1];
+                Nn[j] += (uint64_t)t * a;
+                D[j] += t * b;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < SMOOTH_PER; ++j) {
+        const int y = y0 + first + j;
+        if (y < h) {
+            const bool s = (a_s[((first + j + radius) << cshift) + col] >> 31) != 0 && D[j] != 0;        // D >= centre^2 >= 1 on the support
+            out[(int64_t)y * w + x] = s ? ((heat_acc_t)1 << HEAT_COUNT_SHIFT) | heat_floor_quot(2 * Nn[j] + D[j], 2 * (uint64_t)D[j]) : 0;
+        }
+    }
+    }
+    __syncthreads();                                  // the planes are staged again for the block's next tile
+    }
+}
+
 }  // namespace keepk
 using namespace keepk;
+
+// the column pass's LDS for cx = 1 << cshift columns: taps + (A uint32 + B uint16) per staged pixel
+static size_t smooth_col_lds(int radius, int cshift) {
+    const int nch = (2 * radius + 2 * SMOOTH_PER - 1) / SMOOTH_PER, rows = (256 >> cshift) * SMOOTH_PER - SMOOTH_PER + SMOOTH_PER * nch;
+    return SMOOTH_TAPS_LDS * sizeof(int) + (size_t)rows * (1 << cshift) * 6;
+}
+
+// a block per tile up to 2^22 blocks; beyond that (rasters one pixel wide) the blocks stride over the tiles
+static unsigned smooth_grid_for(int64_t blocks) { return (unsigned)(blocks > ((int64_t)1 << 22) ? (int64_t)1 << 22 : blocks); }
+
+void launch_heat_smooth(const int64_t* acc, int h, int w, const unsigned char* mask, const int* taps, int radius, unsigned* rowa,
+                        unsigned short* rowb, int64_t* out, hipStream_t s) {
+    const int nseg = (w + SMOOTH_ROW_SEG - 1) / SMOOTH_ROW_SEG;
+    const int64_t row_blocks = (int64_t)h * nseg;
+    hipLaunchKernelGGL(heat_smooth_row_kernel, dim3(smooth_grid_for(row_blocks)), dim3(SMOOTH_ROW_THREADS), 0, s, (const heat_acc_t*)acc, h, w,
+                       mask, taps, radius, nseg, row_blocks, rowa, rowb);
+    // 64 columns by 32 rows per block while the staged rows fit 64 KiB of LDS (radius <= 64), else 32 columns by 64 rows
+    const int cshift = smooth_col_lds(radius, 6) <= SMOOTH_COL_LDS_LIMIT ? 6 : 5;
+    const int cx = 1 << cshift, ry = (256 >> cshift) * SMOOTH_PER;
+    const int nxb = (w + cx - 1) / cx, nyb = (h + ry - 1) / ry;
+    const int64_t col_blocks = (int64_t)nxb * nyb;
+    hipLaunchKernelGGL(heat_smooth_col_kernel, dim3(smooth_grid_for(col_blocks)), dim3(256), smooth_col_lds(radius, cshift), s, rowa, rowb, h, w,
+                       taps, radius, cshift, nxb, col_blocks, (heat_acc_t*)out);
+}
 
 static unsigned heat_grid_for(int64_t items, int per_block) {
     const int64_t b = (items + per_block - 1) / per_block;

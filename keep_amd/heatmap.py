@@ -12,7 +12,12 @@ The device kernels (``csrc/heatmap.hip``) equal the numpy restatements below exa
 a raster is the same however its tiles are split over calls.
 
 This module holds the host side: argument checks (ValueError before any device call), :class:`TileRaster`, the colour tables and
-the restatements ``raster_numpy`` / ``mean_numpy`` / ``pred_numpy`` / ``render_numpy``."""
+the restatements ``raster_numpy`` / ``mean_numpy`` / ``pred_numpy`` / ``render_numpy``.
+
+The two display steps of CLAM's heatmaps follow below: rank percentiles of the tile values
+(``KEEPModel.score_reference`` / ``percentiles``, :class:`ScoreReference`; ``sort_numpy`` / ``rank_numpy`` / ``percentiles_numpy``) and a
+Gaussian smoothing of the raster under its support (``KEEPModel.smooth_raster``; ``gaussian_taps`` / ``clam_blur`` / ``smooth_numpy``),
+integer-exact like the rest."""
 from typing import Optional, Tuple
 
 import numpy as np
@@ -262,3 +267,180 @@ def render_numpy(acc: np.ndarray, thumbnail: Optional[np.ndarray] = None, alpha:
     idx = np.clip((2 * 255 * (S - lo16 * c) + span * c) // (2 * span * cs), 0, 255)
     blend = (a * lut[idx] + (256 - a) * under + 128) >> 8
     return np.where(shown[..., None], blend, under).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------ percentiles
+CANONICAL_NAN = 0x7FC00000
+MAX_VALUES = MAX_TILES                         # a population or a set of queries: at most the raster's tile cap
+MAX_RADIUS = 127
+TAP_SUM = 32768
+
+
+def check_values(values, name: str = "values", least: int = 1) -> int:
+    """A population or a set of queries: [N] of a floating type, ``least <= N <= 2^24 - 1`` -> N."""
+    vs, vd = tuple(values.shape), values.dtype
+    if not (vd.is_floating_point if isinstance(vd, torch.dtype) else vd.kind == "f"):
+        raise ValueError(f"{name} must be floating point, got {vd}")
+    if len(vs) != 1 or not least <= vs[0] <= MAX_VALUES:
+        raise ValueError(f"{name} must be [N] with {least} <= N <= 2^24 - 1, got {vs}")
+    return int(vs[0])
+
+
+def _float32(values, name: str = "values", least: int = 1) -> np.ndarray:
+    v = values.detach().cpu().numpy() if isinstance(values, torch.Tensor) else np.asarray(values)
+    check_values(v, name, least)
+    return v.astype(np.float32)
+
+
+def sort_numpy(values) -> Tuple[np.ndarray, int]:
+    """keep_sort_f32 restated -> (sorted fp32 [M], n): the n values that are not NaN in ascending order with -0 stored as +0, then
+    M - n NaNs with the bits 0x7FC00000."""
+    v = _float32(values)
+    kept = v[~np.isnan(v)]
+    kept = np.sort(np.where(kept == 0, np.float32(0), kept))
+    out = np.full(v.shape, CANONICAL_NAN, np.uint32).view(np.float32)
+    out[:kept.size] = kept
+    return out, int(kept.size)
+
+
+def rank_numpy(sorted_values: np.ndarray, n: int, queries, self_rank: bool) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """keep_rank_f32 restated -> (pct fp32 [N], less int32 [N], eq int32 [N]).  ``sorted_values`` / ``n``: what :func:`sort_numpy`
+    returns.  ``less`` / ``eq``: how many of the n values are smaller than / equal to the query; ``r2 = 2 less + eq + self_rank`` and
+    ``pct = float32(float64(r2) / float64(2 n))``; a NaN query gives NaN, -1, -1 and n = 0 gives NaN for every query."""
+    q = _float32(queries, "queries", 0)
+    pop = np.asarray(sorted_values, np.float32)[:n]
+    nan = np.isnan(q)
+    qc = np.where(nan | (q == 0), np.float32(0), q)
+    less = np.searchsorted(pop, qc, "left").astype(np.int64)
+    eq = np.searchsorted(pop, qc, "right").astype(np.int64) - less
+    pct = np.full(q.shape, CANONICAL_NAN, np.uint32).view(np.float32)
+    if n > 0:
+        pct[~nan] = ((2 * less + eq + int(bool(self_rank)))[~nan].astype(np.float64) / np.float64(2 * n)).astype(np.float32)
+    return pct, np.where(nan, -1, less).astype(np.int32), np.where(nan, -1, eq).astype(np.int32)
+
+
+def percentiles_numpy(values, reference=None) -> np.ndarray:
+    """``KEEPModel.percentiles`` restated -> fp32 [N]: the values ranked among themselves (twice the average rank over 2 n, the
+    rule of ``scipy.stats.rankdata(v, 'average') / n``), or against the population ``reference``
+    (``scipy.stats.percentileofscore(reference, v, kind='mean') / 100``)."""
+    s, n = sort_numpy(values if reference is None else reference)
+    return rank_numpy(s, n, values, reference is None)[0]
+
+
+class ScoreReference:
+    """A sorted score population on the device: ``sorted`` fp32 [M] (the n values that are not NaN in ascending order, then NaNs),
+    ``n`` int64 [1] on the device, and ``M``.  ``KEEPModel.score_reference`` makes one; it is what a slide's scores are ranked
+    against when an ROI is shown beside the population it came from."""
+
+    def __init__(self, sorted_values: torch.Tensor, n: torch.Tensor, model=None):
+        if not isinstance(sorted_values, torch.Tensor) or sorted_values.dtype != torch.float32 or sorted_values.dim() != 1 or not sorted_values.is_contiguous():
+            raise ValueError("sorted must be a contiguous fp32 [M] tensor")
+        if not isinstance(n, torch.Tensor) or n.dtype != torch.int64 or n.numel() != 1 or n.device != sorted_values.device:
+            raise ValueError("n must be one int64 on sorted's device")
+        self.sorted, self.n, self.M = sorted_values, n, check_values(sorted_values, "sorted")
+        self._model = model
+
+    def __repr__(self):
+        return f"ScoreReference(M={self.M} on {self.sorted.device})"
+
+    def _engine(self):
+        from .model import engine_for
+        if self.sorted.device.type != "cuda":
+            raise ValueError("this population lives on the host: use the numpy restatements (rank_numpy, percentiles_numpy)")
+        return engine_for(device=self.sorted.device, model=self._model)
+
+    def rank(self, values) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (less int32 [N], eq int32 [N]): how many of the population are smaller than / equal to each value; -1 for a NaN."""
+        return self._engine()._rank(self, values, False, False, True)[1:]
+
+    def percentiles(self, values) -> torch.Tensor:
+        """-> fp32 [N]: ``(2 less + eq) / (2 n)``, the values as outsiders to the population."""
+        return self._engine()._rank(self, values, False, True, False)[0]
+
+
+# ------------------------------------------------------------------------------------------------ smoothing (DESIGN.md section 14)
+def gaussian_taps(sigma, radius=None) -> np.ndarray:
+    """Integer Gaussian taps, int32 [2 r + 1]: ``w_k = exp(-k^2 / (2 sigma^2))`` in float64, ``t_k = floor(32768 w_k / sum w)``;
+    r defaults to ``ceil(3 sigma)``.  The floor keeps the table symmetric, non-increasing from the centre and its sum <= 32768."""
+    sigma = float(sigma)
+    if not (sigma > 0.0 and np.isfinite(sigma)):
+        raise ValueError(f"sigma must be a positive number, got {sigma!r}")
+    r = int(np.ceil(3.0 * sigma)) if radius is None else _integer(radius, "radius")
+    if r < 1 or r > MAX_RADIUS:
+        raise ValueError(f"radius must lie in [1, {MAX_RADIUS}], got {r}")
+    k = np.arange(-r, r + 1, dtype=np.float64)
+    w = np.exp(-(k * k) / (2.0 * sigma * sigma))
+    return check_taps(np.floor(TAP_SUM * w / w.sum()).astype(np.int32))
+
+
+def clam_blur(patch, downsample, factor=2) -> Tuple[float, int]:
+    """The size of CLAM's overlay blur -> (sigma, radius): ``ksize = (factor patch // downsample) | 1`` and the sigma an image
+    library derives from a kernel size, ``0.3 ((ksize - 1) / 2 - 1) + 0.8``.  A convenience: feed it to :func:`gaussian_taps`;
+    no parity with such a library's blur is claimed."""
+    patch, d, factor = _integer(patch, "patch"), _integer(downsample, "downsample"), _integer(factor, "factor")
+    if patch < 1 or d < 1 or factor < 1:
+        raise ValueError(f"patch, downsample and factor must be >= 1, got {patch}, {d}, {factor}")
+    ksize = (factor * patch // d) | 1
+    r = (ksize - 1) // 2
+    if r < 1 or r > MAX_RADIUS:
+        raise ValueError(f"kernel size {ksize} gives radius {r} outside [1, {MAX_RADIUS}]")
+    return 0.3 * ((ksize - 1) / 2 - 1) + 0.8, r
+
+
+def check_taps(taps) -> np.ndarray:
+    """A table of taps -> int32 [2 r + 1], 1 <= r <= 127: every tap >= 0, the centre tap >= 1, the sum <= 32768."""
+    t = taps.detach().cpu().numpy() if isinstance(taps, torch.Tensor) else np.asarray(taps)
+    if t.dtype.kind not in "iu" or t.ndim != 1 or t.size % 2 == 0:
+        raise ValueError(f"taps must be an odd number of integers, got {t.dtype} {t.shape}")
+    r = t.size // 2
+    if r < 1 or r > MAX_RADIUS:
+        raise ValueError(f"radius must lie in [1, {MAX_RADIUS}], got {r}")
+    t = t.astype(np.int64)
+    if t.min() < 0 or t[r] < 1 or t.sum() > TAP_SUM:
+        raise ValueError(f"taps must be >= 0 with a centre tap >= 1 and a sum <= {TAP_SUM}: min {t.min()}, centre {t[r]}, sum {t.sum()}")
+    return t.astype(np.int32)
+
+
+def smooth_taps(sigma=None, radius=None, taps=None) -> np.ndarray:
+    """The taps of a smoothing call: ``taps`` as given (checked; ``radius`` must agree with it), or :func:`gaussian_taps`."""
+    if taps is None:
+        if sigma is None:
+            raise ValueError("give sigma (with radius, optionally) or taps")
+        return gaussian_taps(sigma, radius)
+    if sigma is not None:
+        raise ValueError("give sigma or taps, not both")
+    t = check_taps(taps)
+    if radius is not None and _integer(radius, "radius") != t.size // 2:
+        raise ValueError(f"radius {radius} does not match {t.size} taps")
+    return t
+
+
+def smooth_numpy(acc: np.ndarray, taps, mask: Optional[np.ndarray] = None) -> np.ndarray:
+    """keep_heat_smooth restated on the host -> the smoothed accumulator, int64 [h,w] (count 1 on the support, 0 elsewhere)."""
+    t = check_taps(taps).astype(np.int64)
+    r = t.size // 2
+    acc = np.asarray(acc)
+    if acc.dtype != np.int64 or acc.ndim != 2:
+        raise ValueError(f"acc must be int64 [h,w], got {acc.dtype} {acc.shape}")
+    S, c = unpack_numpy(acc)
+    c = c.astype(np.int64)
+    h, w = S.shape
+    s = c > 0
+    if mask is not None:
+        if np.asarray(mask).shape != (h, w):
+            raise ValueError(f"mask must be {(h, w)}, got {np.asarray(mask).shape}")
+        s &= np.asarray(mask) != 0
+    m = np.where(s, (2 * S + c) // (2 * np.maximum(c, 1)), 0)
+
+    def conv(plane, axis):
+        pad = [(0, 0), (0, 0)]
+        pad[axis] = (r, r)
+        p = np.pad(plane, pad)
+        out = np.zeros_like(plane)
+        for k in range(2 * r + 1):
+            if t[k]:
+                out += t[k] * (p[:, k:k + w] if axis == 1 else p[k:k + h])
+        return out
+
+    Nn, D = conv(conv(m, 1), 0), conv(conv(s.astype(np.int64), 1), 0)
+    return np.where(s, (1 << COUNT_SHIFT) | ((2 * Nn + D) // (2 * np.maximum(D, 1))), 0).astype(np.int64)

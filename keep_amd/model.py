@@ -1098,8 +1098,8 @@ class KEEPModel:
         and shape; pixels outside it are not painted.  ``colormap``: "jet", "gray" or a uint8 [256,3] table
         (``keep_amd.heatmap.colormap``).  ``window``: the values mapped to the ends of the table; ``min_value``: pixels whose mean
         is below it are not painted; ``alpha``: the weight of the colour, used as ``round(256 alpha)``.  All in integers on the
-        16-bit fixed-point sums, equal to ``keep_amd.heatmap.render_numpy`` bit for bit.  No blur and no percentile ranks (CLAM has
-        both)."""
+        16-bit fixed-point sums, equal to ``keep_amd.heatmap.render_numpy`` bit for bit.  CLAM's percentile ranks and blur are
+        steps made before this one: :meth:`percentiles` on the tile values, :meth:`smooth_raster` on the raster."""
         from .heatmap import TileRaster, colormap as table, render_args
         from .region import TissueMask, region_layout
         if not isinstance(raster, TileRaster):
@@ -1138,6 +1138,91 @@ class KEEPModel:
                                                               _ptr(md), _ptr(lut), a, lo16, hi16, min16, _ptr(out), _stream(self._device)),
                    "heat_render")
         return out
+
+    # ------------------------------------------------------------------ heatmap percentiles and smoothing
+    def _values_f32(self, values, name: str, least: int) -> torch.Tensor:
+        """A population or queries (host or device, numpy or torch, any floating dtype) checked on the host -> fp32 [N] on the device."""
+        from .heatmap import check_values
+        v = values if isinstance(values, torch.Tensor) else torch.as_tensor(values)
+        check_values(v, name, least)
+        self._ready_device()
+        return v.to(self._device, torch.float32).contiguous()
+
+    @torch.no_grad()
+    def score_reference(self, values):
+        """A score population sorted on the device -> ``keep_amd.heatmap.ScoreReference``.  ``values``: floating
+        point [M], ``1 <= M <= 2^24 - 1``, host or device, numpy or torch, rounded to float32 first.  NaNs are not part of the
+        population and -0 counts as +0; equal to ``keep_amd.heatmap.sort_numpy`` bit for bit.  No host synchronisation."""
+        from .heatmap import ScoreReference
+        v = self._values_f32(values, "values", 1)
+        M = int(v.shape[0])
+        out = torch.empty((M,), dtype=torch.float32, device=self._device)
+        n = torch.empty((1,), dtype=torch.int64, device=self._device)
+        _lib.check(self._handle, _lib.load().keep_sort_f32(self._handle, _ptr(v), M, _ptr(out), _ptr(n), _stream(self._device)), "sort_f32")
+        return ScoreReference(out, n, self)
+
+    def _rank(self, reference, values, self_rank: bool, pct: bool, counts: bool):
+        """keep_rank_f32 -> (pct fp32 | None, less int32 | None, eq int32 | None), each [N] on the device."""
+        from .heatmap import ScoreReference
+        if not isinstance(reference, ScoreReference):
+            raise ValueError(f"reference must be a ScoreReference, got {type(reference).__name__}")
+        q = self._values_f32(values, "values", 0)
+        if reference.sorted.device != self._device:
+            raise ValueError(f"the reference lives on {reference.sorted.device}, this engine on {self._device}")
+        N = int(q.shape[0])
+        outs = [torch.empty((N,), dtype=dt, device=self._device) if on else None
+                for on, dt in ((pct, torch.float32), (counts, torch.int32), (counts, torch.int32))]
+        if N == 0:
+            return tuple(outs)                                          # empty tensors have no address to pass
+        _lib.check(self._handle, _lib.load().keep_rank_f32(self._handle, _ptr(reference.sorted), reference.M, _ptr(reference.n), _ptr(q), N,
+                                                           int(self_rank), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _stream(self._device)),
+                   "rank_f32")
+        return tuple(outs)
+
+    @torch.no_grad()
+    def percentiles(self, values, reference=None) -> torch.Tensor:
+        """Rank percentiles on the device -> fp32 [N] in (0, 1].  ``reference=None`` ranks the values among
+        themselves: ``(2 less + eq + 1) / (2 n)``, which is ``scipy.stats.rankdata(v, 'average') / n`` over the n values that are not
+        NaN.  With a ``ScoreReference`` (:meth:`score_reference`) they are outsiders to that population: ``(2 less + eq) / (2 n)``,
+        ``scipy.stats.percentileofscore(ref, v, kind='mean') / 100``.  A NaN stays NaN.  Equal to
+        ``keep_amd.heatmap.percentiles_numpy`` bit for bit; no host synchronisation."""
+        if reference is None:
+            q = self._values_f32(values, "values", 1)
+            return self._rank(self.score_reference(q), q, True, True, False)[0]
+        return self._rank(reference, values, False, True, False)[0]
+
+    @torch.no_grad()
+    def smooth_raster(self, raster, sigma=None, radius=None, taps=None, tissue=None):
+        """A raster's mean smoothed by a Gaussian under its support -> a new ``TileRaster`` of the same
+        geometry and ``tiles``, whose pixels hold the smoothed mean in 16-bit fixed point with a count of one where the input was
+        covered (and inside ``tissue``), nothing elsewhere.  ``sigma`` (and ``radius``, default ``ceil(3 sigma)``) make the taps
+        with ``keep_amd.heatmap.gaussian_taps``; or pass ``taps``, an odd number of non-negative integers with a centre >= 1 and a sum
+        <= 32768.  ``tissue``: a ``TissueMask`` of the raster's downsample and shape.  A normalised convolution: uncovered and
+        masked-out pixels neither give nor receive, a constant region stays constant.  Integer arithmetic, equal to
+        ``keep_amd.heatmap.smooth_numpy`` bit for bit.  The input must be a raster as ``tile_raster`` makes it (sum <= 65535 count)."""
+        from .heatmap import TileRaster, smooth_taps
+        from .region import TissueMask
+        if not isinstance(raster, TileRaster):
+            raise ValueError(f"raster must be a TileRaster, got {type(raster).__name__}")
+        t = smooth_taps(sigma, radius, taps)
+        h, w = raster.shape
+        if tissue is not None:
+            if not isinstance(tissue, TissueMask):
+                raise ValueError(f"tissue must be a TissueMask, got {type(tissue).__name__}")
+            if tissue.downsample != raster.downsample or tuple(tissue.mask.shape) != (h, w):
+                raise ValueError(f"tissue mask has downsample {tissue.downsample} and shape {tuple(tissue.mask.shape)}, the raster "
+                                 f"{raster.downsample} and {(h, w)}")
+        self._ready_device()
+        if raster.acc.device != self._device:
+            raise ValueError(f"the raster lives on {raster.acc.device}, this engine on {self._device}")
+        td = torch.from_numpy(t).to(self._device)
+        md = None if tissue is None else tissue.mask.to(self._device).contiguous()
+        if md is not None and md.dtype == torch.bool:
+            md = md.view(torch.uint8)
+        out = torch.empty((h, w), dtype=torch.int64, device=self._device)
+        _lib.check(self._handle, _lib.load().keep_heat_smooth(self._handle, _ptr(raster.acc), h, w, _ptr(md), _ptr(td), t.size // 2, _ptr(out),
+                                                              _stream(self._device)), "heat_smooth")
+        return TileRaster(out, raster.downsample, raster.patch, raster.origin, raster.tiles, self)
 
     # ------------------------------------------------------------------ region table (DESIGN.md section 13)
     @torch.no_grad()

@@ -331,20 +331,43 @@ def zero_shot_segment(classifier, tile_features, tile_coords, mask_path, patch_s
 
 
 # ------------------------------------------------------------------------------------------------ heatmap
-def segment_heatmap(classifier, tile_features, tile_coords, downsample, shape, patch_size=224, overlap=True, cls=1, origin=(0, 0), model=None):
+def segment_heatmap(classifier, tile_features, tile_coords, downsample, shape, patch_size=224, overlap=True, cls=1, origin=(0, 0), model=None,
+                    percentile=False, reference=None, blur_sigma=None, blur_radius=None, tissue=None):
     """The segmentation flow ending in slide geometry instead of a dict: ``_probs`` -> :func:`refine` -> ``KEEPModel.tile_raster`` on
     device tensors -> ``keep_amd.heatmap.TileRaster`` of class ``cls``'s refined probability (``.mean()`` is the probability map,
     ``KEEPModel.render_heatmap`` the picture).  No dict is built and the host is visited only where :func:`refine` already does.
-    ``downsample`` / ``shape`` / ``origin``: the raster's geometry, that of the thumbnail and of ``KEEPModel.tissue_mask``."""
-    from .heatmap import check_raster_args
-    check_raster_args(patch_size, downsample, shape, origin)
+    ``downsample`` / ``shape`` / ``origin``: the raster's geometry, that of the thumbnail and of ``KEEPModel.tissue_mask``.
+
+    The display steps of CLAM's heatmaps, all off by default: ``percentile=True`` replaces the refined
+    probabilities by their rank percentiles before rasterising, among the slide's own refined tiles or, with ``reference`` (a
+    ``keep_amd.heatmap.ScoreReference``), against that population; ``blur_sigma`` (with ``blur_radius``, default ``ceil(3 sigma)``)
+    smooths the raster with ``KEEPModel.smooth_raster``, under ``tissue`` (a ``TissueMask`` of the raster's geometry) if given."""
+    from .heatmap import ScoreReference, check_raster_args, gaussian_taps
+    from .region import TissueMask
+    _, d, shape, _ = check_raster_args(patch_size, downsample, shape, origin)
+    if reference is not None and not percentile:
+        raise ValueError("reference= is what percentile=True ranks against: pass both")
+    if reference is not None and not isinstance(reference, ScoreReference):
+        raise ValueError(f"reference must be a ScoreReference, got {type(reference).__name__}")
+    if blur_sigma is None and (blur_radius is not None or tissue is not None):
+        raise ValueError("blur_radius= and tissue= belong to blur_sigma=: pass it too")
+    taps = None if blur_sigma is None else gaussian_taps(blur_sigma, blur_radius)
+    if tissue is not None:
+        if not isinstance(tissue, TissueMask):
+            raise ValueError(f"tissue must be a TissueMask, got {type(tissue).__name__}")
+        if tissue.downsample != d or tuple(tissue.mask.shape) != shape:
+            raise ValueError(f"tissue mask has downsample {tissue.downsample} and shape {tuple(tissue.mask.shape)}, the raster {d} and {shape}")
     m = _engine(model, tile_features, classifier)
     if isinstance(tile_coords, torch.Tensor):
         tile_coords = tile_coords.cpu()                             # refine checks the coordinate range on the host
     coords, mean, _ = refine(_probs(m, classifier, tile_features), tile_coords, patch_size, overlap, model=m)
     if not -mean.shape[1] <= int(cls) < mean.shape[1]:
         raise ValueError(f"cls {cls!r} outside the classifier's {mean.shape[1]} classes")
-    return m.tile_raster(coords, mean[:, int(cls)].contiguous(), patch_size, downsample, shape, origin)
+    values = mean[:, int(cls)].contiguous()
+    if percentile:
+        values = m.percentiles(values, reference)
+    raster = m.tile_raster(coords, values, patch_size, downsample, shape, origin)
+    return raster if taps is None else m.smooth_raster(raster, taps=taps, tissue=tissue)
 
 
 def segment_regions(raster, thd=0.5, tissue=None, connectivity=8, min_area=1, model=None):
