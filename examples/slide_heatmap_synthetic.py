@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
-"""Slide pixels in, heatmap and lesion table out, on one GPU (DESIGN.md sections 10-13): a synthetic slide and its thumbnail ->
-tissue_mask -> encode_region with half-overlapping tiles -> wsi.segment_heatmap -> render_heatmap -> a PNG; wsi.segment_regions -> the
-regions above the median score, largest first.
+"""Slide pixels in, heatmap, lesion table and lesion polygons out, on one GPU (DESIGN.md sections 10-15): a synthetic slide and its
+thumbnail -> tissue_mask -> encode_region with half-overlapping tiles -> wsi.segment_heatmap -> render_heatmap; wsi.segment_regions ->
+the regions above the median score, largest first; region_outlines -> their boundary rings with holes, written as GeoJSON in level-0
+pixels (what QuPath or ASAP open as annotations); draw_outlines -> the lesions outlined in black and the tissue in blue on the PNG.
 
-    python examples/slide_heatmap_synthetic.py [--rows 8] [--cols 10] [--depth 2] [--out slide_heatmap.png]
+    python examples/slide_heatmap_synthetic.py [--rows 8] [--cols 10] [--depth 2] [--out slide_heatmap.png] [--geojson lesions.geojson]
 
 No dataset, weights or tokenizer exist offline, so the slide (stained tiles inside an ellipse, grey glass around it), the weights
 and the two prompts are seeded synthetic data: the picture shows the flow, not a tumour.
 """
 import argparse
+import json
 import os
 import sys
 import tempfile
@@ -42,6 +44,7 @@ def main():
     ap.add_argument("--cols", type=int, default=10)
     ap.add_argument("--depth", type=int, default=2, help="ViT/BERT depth (24 = the real model's shape; small for a quick look)")
     ap.add_argument("--out", default=os.path.join(tempfile.gettempdir(), "slide_heatmap.png"))
+    ap.add_argument("--geojson", default=os.path.join(tempfile.gettempdir(), "slide_lesions.geojson"))
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     shape = KEEPShape() if a.depth >= 24 else small_shape(a.depth, max(1, a.depth // 2))
@@ -68,7 +71,7 @@ def main():
           f"heatmap {tuple(picture.shape)} in {dt * 1e3:.1f} ms")
     thd = float(raster.mean()[raster.count > 0].median())
     lesions = wsi.segment_regions(raster, thd, tissue=tissue, min_area=4, model=model)
-    tissue_regions = model.mask_regions(tissue, labels=False)
+    tissue_regions = model.mask_regions(tissue)
     print(f"{tissue_regions.n} tissue region(s); {lesions.n} region(s) of >= 4 pixels with mean score > {thd:.4f}:")
     print("   id  area px  area mm2 @0.25um  box level-0 (x0, y0, x1, y1)    centroid level-0      mean    peak  border")
     top = lesions.sort("area")
@@ -77,6 +80,14 @@ def main():
         box, (cx, cy) = [int(v) for v in l0["box"][i]], l0["centroid"][i]
         print(f"  {int(top.ids[i]):3d}  {int(top.area[i]):7d}  {top.area_mm2(0.25)[i]:16.4f}  {str(tuple(box)):30s}  ({cx:8.1f}, {cy:8.1f})  "
               f"{top.mean_score()[i]:.4f}  {top.peak_score()[i]:.4f}  {int(top.border[i])}")
+    outlines = model.region_outlines(lesions)
+    holes = outlines.n_holes()
+    print(f"{outlines.n_rings} ring(s), {int(outlines.vertices.shape[0])} vertices; {int(holes.sum())} hole(s); the largest region's outer ring has "
+          f"{len(outlines.polygons(int(top.ids[0]))[0]) if top.n else 0} vertices and a perimeter of {int(outlines.perimeter().max()) if top.n else 0} pixel sides")
+    with open(a.geojson, "w") as f:
+        json.dump(outlines.to_geojson(table=lesions, max_n_holes=8, min_hole_area=2), f)
+    print(f"wrote {a.geojson}")
+    picture = model.draw_outlines(model.draw_outlines(picture, tissue_regions, (0, 0, 255), 1), lesions, (0, 0, 0), 1)
     from PIL import Image
     Image.fromarray(picture.cpu().numpy()).save(a.out)
     print(f"wrote {a.out}")

@@ -331,6 +331,41 @@ int keep_regions_label(keep_handle* h, const unsigned char* mask, int64_t H, int
 int keep_regions_table(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, const int64_t* acc, int64_t* table_out,
                        void* stream);
 
+/* Region outlines: the boundary rings of a label image, with holes, and an outline drawn into an image.
+ * Replaces: the contour polygons with a hole list per contour that CLAM's segmentTissue hands back (cv2.findContours with
+ * RETR_CCOMP; the step of README.md:74) and the polygon annotation a viewer takes a lesion of WSI_evaluation/segment_utils.py's
+ * pred_mask as; restated on the pixel mask as rings of pixel-crack edges on the corner lattice, integer arithmetic, exact and unique.
+ * labels: int32 [H,W] as keep_regions_label writes it, values 0..n (a value outside 1..n counts as background), n >= 0,
+ * 1 <= H W <= 2^28 (an edge slot 4 p + side fits an int32), connectivity 4 or 8.
+ * Edges: pixel p = y W + x with label l > 0 has a directed edge on side s iff the pixel across that side lies outside the image or
+ * carries a label != l: side 0 top, direction +x, start vertex (x, y); 1 right, +y, (x + 1, y); 2 bottom, -x, (x + 1, y + 1); 3 left,
+ * -y, (x, y + 1) (x to the right, y down: the region is on the walker's right).  Slot = 4 p + s.
+ * Successor at the end vertex of side s of p, with AR = p moved one step along the direction, AL = AR moved one step across side s,
+ * "in" = inside the image with label l:  AR in, AL in: side (s + 3) % 4 of AL;  AR in, AL out: side s of AR;  AR out, AL out: side
+ * (s + 1) % 4 of p;  AR out, AL in: side (s + 1) % 4 of p with connectivity 4, side (s + 3) % 4 of AL with connectivity 8 (the
+ * ring passes through the diagonal contact and touches itself there).  The cycles of this permutation are the rings.
+ * An edge is a corner iff its predecessor lies on another side.  A ring's leader is its corner edge with the smallest slot; its
+ * vertices are the start vertices of its corner edges in walking order from the leader; rings are numbered in ascending leader slot.
+ * With labels of keep_regions_label and the same connectivity a region's first ring is its one outer ring, every other a hole.
+ * keep_outline_count: counts_out int64 [2] ON THE DEVICE: E (edges) and V (corner edges).  Workspace: 8 ceil(H W / 2048) bytes.
+ * keep_outline_trace: E, V as read back from keep_outline_count (V = 0 needs no call; 4 <= V <= E, n >= 1).  vertices_out: int32
+ * [V,2] (x, y) on 0..W / 0..H, ring after ring, all V rows; rings_out: int64 [ring_cap,8], the first min(R, ring_cap) rows (may be NULL
+ * when ring_cap = 0); r_out: R, one int64 ON THE DEVICE.  Ring columns:
+ *   0 label    1 start (row of the first vertex)    2 nvert    3 nedge (crack edges: the perimeter in pixel sides)
+ *   4 area2    sum of x_i y_{i+1} - x_{i+1} y_i: twice the enclosed area, > 0 for an outer ring, < 0 for a hole
+ *   5 lead_x, 6 lead_y  the first vertex                       7 hole   1 iff area2 < 0
+ * Workspace: 60 E + 4 H W + 16 ceil(max(H W, E) / 2048) bytes (each part rounded up to 256) + 512.  No host synchronisation; the
+ * number of jumping rounds that do work follows the longest ring (2 ceil(log2(its edges))), the others return at once.
+ * keep_outline_draw: rgb_in / rgb_out uint8 [H,W,3]; out[p] = color (R | G << 8 | B << 16) iff labels[p] = l > 0 and some q with
+ * max(|dx|, |dy|) <= width lies outside the image or has a label != l, else rgb_in[p].  1 <= width <= 16; rgb_out may be rgb_in.
+ * Workspace: H W bytes. */
+int keep_outline_count(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, int connectivity, int64_t* counts_out,
+                       void* stream);
+int keep_outline_trace(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, int connectivity, int64_t E, int64_t V,
+                       int32_t* vertices_out, int64_t* rings_out, int64_t ring_cap, int64_t* r_out, void* stream);
+int keep_outline_draw(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, const unsigned char* rgb_in, unsigned char* rgb_out,
+                      int color, int width, void* stream);
+
 /* Pre-allocate workspace for calls of up to `tiles` tiles and `prompts` x `seq` tokens. */
 int keep_reserve(keep_handle* h, int64_t tiles, int64_t prompts, int64_t seq);
 int64_t keep_workspace_bytes(keep_handle* h);

@@ -60,6 +60,9 @@ SIGNATURES = {
     "keep_rank_f32": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "keep_regions_label": (_i32, [_vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp]),
     "keep_regions_table": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "keep_outline_count": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp]),
+    "keep_outline_trace": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "keep_outline_draw": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _vp]),
     "keep_token_error": (_i32, [_vp, _vp]),
     "keep_token_error_async": (_i32, [_vp, _vp, _vp]),
     "keep_similarity": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _vp, _vp]),

@@ -87,14 +87,16 @@ class RegionTable:
     for label i; ``labels``: int32 ``[h,w]``, 0 = background or dropped (None if not asked for); ``downsample``: level-0 pixels per
     mask pixel (None if neither the mask nor the raster said); ``origin``: the level-0 position of pixel (0, 0); ``ids``: the label of
     every row (1..n until :meth:`sort` permutes a copy).  Every column is an attribute (``.area``, ``.x0`` ...: int64 ``[n]`` views of
-    the table).  The methods below convert on the host in float64 and are not part of the integer contract."""
+    the table); ``connectivity``: the connectivity ``mask_regions`` labelled with (None if unknown), which ``region_outlines`` takes as
+    its default.  The methods below convert on the host in float64 and are not part of the integer contract."""
 
     def __init__(self, table: torch.Tensor, labels: Optional[torch.Tensor] = None, downsample: Optional[int] = None, origin=(0, 0),
-                 ids: Optional[torch.Tensor] = None):
+                 ids: Optional[torch.Tensor] = None, connectivity: Optional[int] = None):
         if not isinstance(table, torch.Tensor) or table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != NCOLS:
             raise ValueError(f"table must be an int64 [n,{NCOLS}] tensor")
         self.table, self.labels, self.downsample = table, labels, downsample
         self.origin = (int(origin[0]), int(origin[1]))
+        self.connectivity = connectivity
         self.ids = torch.arange(1, table.shape[0] + 1, dtype=torch.int64, device=table.device) if ids is None else ids
         self._host = None
 
@@ -161,7 +163,7 @@ class RegionTable:
         else:
             raise ValueError(f"by must be one of {COLUMNS + ('mean_score', 'peak_score')}, got {by!r}")
         order = torch.from_numpy(np.argsort(-key if descending else key, kind="stable")).to(self.table.device)
-        return RegionTable(self.table[order], self.labels, self.downsample, self.origin, self.ids[order])
+        return RegionTable(self.table[order], self.labels, self.downsample, self.origin, self.ids[order], self.connectivity)
 
 
 # ------------------------------------------------------------------------------------------------ the restatement

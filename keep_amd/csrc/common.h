@@ -261,6 +261,23 @@ void launch_regions_label(const unsigned char* mask, int h, int w, int conn8, in
 // labels (values outside 1..n count as background) + acc (nullable) -> table [n][REGIONS_COLS]
 void launch_regions_table(const int* labels, int h, int w, int64_t n, const int64_t* acc, int64_t* table, hipStream_t s);
 
+// Region outlines (outline.hip)
+constexpr int64_t OUTLINE_MAX_PIXELS = (int64_t)1 << 28;  // an edge slot 4 p + side fits an int32 with a bit to spare
+constexpr int OUTLINE_COLS = 8;
+constexpr int OUTLINE_CHUNK = 2048;                     // pixels / edges per block of the scans
+constexpr int OUTLINE_FLAG_WORDS = 96;                  // the per-round flags of both jumping passes and their picks
+constexpr int OUTLINE_MAX_WIDTH = 16;
+size_t outline_count_workspace_bytes(int64_t npix);
+// counts_out[0] = E (edges), counts_out[1] = V (corner edges)
+void launch_outline_count(const int* labels, int H, int W, int n, unsigned char* ws, int64_t* counts_out, hipStream_t s);
+size_t outline_trace_workspace_bytes(int64_t npix, int64_t E);
+// E, V as read back from launch_outline_count (E >= 1); all V vertices, the first min(R, ring_cap) ring rows, *r_out = R
+void launch_outline_trace(const int* labels, int H, int W, int n, int conn8, int E, int64_t V, unsigned char* ws, int* vertices, int64_t* rings,
+                          int64_t ring_cap, int64_t* r_out, hipStream_t s);
+// rowok: H W bytes; rgb_out may be rgb_in
+void launch_outline_draw(const int* labels, int H, int W, const unsigned char* rgb_in, unsigned char* rgb_out, unsigned color, int width,
+                         unsigned char* rowok, hipStream_t s);
+
 // Tile scores rasterised onto the thumbnail (heatmap.hip).  acc: one 64-bit word per raster pixel, bits 0..39 the sum
 // of the 16-bit fixed-point values of the covering tiles, bits 40..63 their number
 constexpr int64_t HEAT_MAX_PIXELS = (int64_t)1 << 30;     // int32 pixel indices

@@ -1930,6 +1930,62 @@ int keep_regions_table(keep_handle* h, const int32_t* labels, int64_t H, int64_t
     return check_launch(h, "regions_table");
 }
 
+static bool outline_shape_ok(int64_t H, int64_t W) {
+    return H >= 1 && W >= 1 && H <= OUTLINE_MAX_PIXELS && W <= OUTLINE_MAX_PIXELS && H * W <= OUTLINE_MAX_PIXELS;
+}
+
+int keep_outline_count(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, int connectivity, int64_t* counts_out,
+                       void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "outline_count: labels is null or not 4-byte aligned");
+    if (!outline_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "outline_count: %lldx%lld pixels (1 <= H W <= 2^28)", (long long)H, (long long)W);
+    if (n < 0 || n > H * W) return h->fail(KEEP_EINVAL, "outline_count: n = %lld outside [0, H W]", (long long)n);
+    if (connectivity != 4 && connectivity != 8) return h->fail(KEEP_EINVAL, "outline_count: connectivity %d (4 or 8)", connectivity);
+    if (!counts_out || ((uintptr_t)counts_out & 7)) return h->fail(KEEP_EINVAL, "outline_count: counts_out is null or not 8-byte aligned");
+    KEEP_ON_DEVICE(h);
+    int rc = ensure_arena(h, outline_count_workspace_bytes(H * W));
+    if (rc) return rc;
+    launch_outline_count(labels, (int)H, (int)W, (int)n, (unsigned char*)h->arena, counts_out, (hipStream_t)stream);
+    return check_launch(h, "outline_count");
+}
+
+int keep_outline_trace(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, int connectivity, int64_t E, int64_t V,
+                       int32_t* vertices_out, int64_t* rings_out, int64_t ring_cap, int64_t* r_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "outline_trace: labels is null or not 4-byte aligned");
+    if (!outline_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "outline_trace: %lldx%lld pixels (1 <= H W <= 2^28)", (long long)H, (long long)W);
+    if (n < 1 || n > H * W) return h->fail(KEEP_EINVAL, "outline_trace: n = %lld outside [1, H W] (without a region there is nothing to trace)", (long long)n);
+    if (connectivity != 4 && connectivity != 8) return h->fail(KEEP_EINVAL, "outline_trace: connectivity %d (4 or 8)", connectivity);
+    if (E < 4 || E > 4 * H * W || V < 4 || V > E)
+        return h->fail(KEEP_EINVAL, "outline_trace: E = %lld, V = %lld (4 <= V <= E <= 4 H W: the values keep_outline_count wrote)", (long long)E,
+                       (long long)V);
+    if (!vertices_out || ((uintptr_t)vertices_out & 3)) return h->fail(KEEP_EINVAL, "outline_trace: vertices_out is null or not 4-byte aligned");
+    if (ring_cap < 0) return h->fail(KEEP_EINVAL, "outline_trace: ring_cap %lld < 0", (long long)ring_cap);
+    if (ring_cap > 0 && (!rings_out || ((uintptr_t)rings_out & 7))) return h->fail(KEEP_EINVAL, "outline_trace: rings_out is null or not 8-byte aligned");
+    if (!r_out || ((uintptr_t)r_out & 7)) return h->fail(KEEP_EINVAL, "outline_trace: r_out is null or not 8-byte aligned");
+    KEEP_ON_DEVICE(h);
+    int rc = ensure_arena(h, outline_trace_workspace_bytes(H * W, E));
+    if (rc) return rc;
+    launch_outline_trace(labels, (int)H, (int)W, (int)n, connectivity == 8, (int)E, V, (unsigned char*)h->arena, vertices_out, rings_out, ring_cap,
+                         r_out, (hipStream_t)stream);
+    return check_launch(h, "outline_trace");
+}
+
+int keep_outline_draw(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, const unsigned char* rgb_in, unsigned char* rgb_out, int color,
+                      int width, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "outline_draw: labels is null or not 4-byte aligned");
+    if (!rgb_in || !rgb_out) return h->fail(KEEP_EINVAL, "outline_draw: null image");
+    if (!outline_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "outline_draw: %lldx%lld pixels (1 <= H W <= 2^28)", (long long)H, (long long)W);
+    if (color < 0 || color > 0xFFFFFF) return h->fail(KEEP_EINVAL, "outline_draw: color 0x%x outside [0, 0xFFFFFF]", color);
+    if (width < 1 || width > OUTLINE_MAX_WIDTH) return h->fail(KEEP_EINVAL, "outline_draw: width %d outside [1, %d]", width, OUTLINE_MAX_WIDTH);
+    KEEP_ON_DEVICE(h);
+    int rc = ensure_arena(h, align_up((size_t)(H * W)));
+    if (rc) return rc;
+    launch_outline_draw(labels, (int)H, (int)W, rgb_in, rgb_out, (unsigned)color, width, (unsigned char*)h->arena, (hipStream_t)stream);
+    return check_launch(h, "outline_draw");
+}
+
 int keep_token_error(keep_handle* h, void* stream) {
     if (!h) return KEEP_EINVAL;
     KEEP_ON_DEVICE(h);

@@ -1259,7 +1259,63 @@ class KEEPModel:
         table = torch.empty((n, NCOLS), dtype=torch.int64, device=self._device)
         _lib.check(self._handle, lib.keep_regions_table(self._handle, _ptr(lab), h, w, n, _ptr(None if raster is None else raster.acc),
                                                         _ptr(table), st), "regions_table")
-        return RegionTable(table, lab if labels else None, d, (0, 0) if raster is None else raster.origin)
+        return RegionTable(table, lab if labels else None, d, (0, 0) if raster is None else raster.origin, connectivity=connectivity)
+
+    # ------------------------------------------------------------------ region outlines
+    @torch.no_grad()
+    def region_outlines(self, regions, connectivity: Optional[int] = None, max_rings: int = 1 << 20, n: Optional[int] = None):
+        """The boundary rings of the regions, with holes, traced on the device ->
+        ``keep_amd.outline.RegionOutlines``: polygons on the corner lattice that ``to_geojson`` hands to a viewer.
+
+        ``regions``: a ``RegionTable`` that kept its labels (``mask_regions`` / ``wsi.segment_regions``), or an int32 [h,w] label image
+        (numpy or torch, host or device, ``h w <= 2^28``) with ``n=``: values outside 1..n count as background.  ``connectivity``
+        defaults to the one the table was labelled with (8 for a label image); with the labelling's own connectivity every region has
+        exactly one outer ring, its first, and every other ring of it is a hole.  Two values are read back: the numbers of edges and
+        of vertices, which size the workspace and the result, and the number of rings; more than ``max_rings`` rings is a ValueError
+        after that.  No thread walks a ring (pointer jumping: the cost follows the logarithm of the longest ring).  Integer
+        arithmetic, equal to ``keep_amd.outline.outlines_numpy`` exactly and the same from run to run."""
+        from .outline import NCOLS, RegionOutlines, check_outline_args, check_ring_count, regions_labels
+        lab, n, conn, d, origin = regions_labels(regions, n, connectivity)
+        if n is None:
+            raise ValueError("a label image needs n=, the number of regions (labels outside 1..n count as background)")
+        connectivity, max_rings = check_outline_args(connectivity if connectivity is not None else (8 if conn is None else conn), max_rings)
+        h, w = int(lab.shape[0]), int(lab.shape[1])
+        self._ready_device()
+        lab = lab.to(self._device).contiguous()
+        lib, st = _lib.load(), _stream(self._device)
+        counts = torch.zeros((2,), dtype=torch.int64, device=self._device)
+        if n > 0:
+            _lib.check(self._handle, lib.keep_outline_count(self._handle, _ptr(lab), h, w, n, connectivity, _ptr(counts), st), "outline_count")
+        E, V = (int(v) for v in counts.tolist()) if n > 0 else (0, 0)
+        vertices = torch.empty((V, 2), dtype=torch.int32, device=self._device)
+        if V == 0:
+            return RegionOutlines(torch.empty((0, NCOLS), dtype=torch.int64, device=self._device), vertices, d, origin, n)
+        cap = min(V // 4, max_rings)
+        rings = torch.empty((cap, NCOLS), dtype=torch.int64, device=self._device)
+        r_dev = torch.empty((1,), dtype=torch.int64, device=self._device)
+        _lib.check(self._handle, lib.keep_outline_trace(self._handle, _ptr(lab), h, w, n, connectivity, E, V, _ptr(vertices),
+                                                        _ptr(rings if cap else None), cap, _ptr(r_dev), st), "outline_trace")
+        R = check_ring_count(int(r_dev.item()), max_rings)
+        return RegionOutlines(rings[:R], vertices, d, origin, n)
+
+    @torch.no_grad()
+    def draw_outlines(self, rgb, regions, color=(0, 0, 0), width: int = 1) -> torch.Tensor:
+        """The regions' outlines drawn into an image on the device -> a new uint8 [h,w,3] on the device.  ``rgb``: uint8 [h,w,3]
+        (``render_heatmap``'s output, a thumbnail), numpy or torch, host or device; ``regions``: a ``RegionTable`` with labels or an
+        int32 [h,w] label image.  A pixel takes ``color`` iff it belongs to a region and its ``(2 width + 1)^2`` window leaves the
+        image or meets another label: a band of ``width`` pixels on the inside of every region, holes included
+        (``1 <= width <= 16``).  Equal to ``keep_amd.outline.draw_numpy`` exactly."""
+        from .outline import check_draw_args, regions_labels, rgb_tensor
+        packed, width = check_draw_args(color, width)
+        lab = regions_labels(regions)[0]
+        h, w = int(lab.shape[0]), int(lab.shape[1])
+        x = rgb_tensor(rgb, (h, w))
+        self._ready_device()
+        lab, x = lab.to(self._device).contiguous(), x.to(self._device).contiguous()
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=self._device)
+        _lib.check(self._handle, _lib.load().keep_outline_draw(self._handle, _ptr(lab), h, w, _ptr(x), _ptr(out), packed, width,
+                                                               _stream(self._device)), "outline_draw")
+        return out
 
     @staticmethod
     def _cells_to_coords(cells: torch.Tensor, origin, coord_scale: int) -> torch.Tensor:
