@@ -366,6 +366,43 @@ int keep_outline_trace(keep_handle* h, const int32_t* labels, int64_t H, int64_t
 int keep_outline_draw(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, const unsigned char* rgb_in, unsigned char* rgb_out,
                       int color, int width, void* stream);
 
+/* Polygon annotations to masks: the inverse of the outlines above.
+ * Replaces: the raster a viewer makes of a pathologist's polygons (ASAP's conversion of CAMELYON16's annotation XML into the
+ * test_040_mask.tif that WSI_evaluation/segment_utils.py reads; a QuPath export painted with an image library), restated as a
+ * scan-line fill at pixel centres in integers, exact; and the per-tile label rule of WSI_evaluation/segment_utils.py:99-103.
+ * keep_poly_fill: vertices int64 [V,2] level-0 (x, y), ring after ring, rings open (the first point not repeated), x to the right,
+ * y down; ring_start int64 [R+1] ascending from 0 to V, ring r owns rows ring_start[r] : ring_start[r+1], at least 3 of them; weight
+ * int32 [R] in {-1, 0, +1}; all three ON THE DEVICE, 8 / 8 / 4-byte aligned.  Mask pixel (i, j) covers level-0 [ox + j d, ox + (j+1) d)
+ * x [oy + i d, oy + (i+1) d); its centre in doubled units is Cx_j = 2 ox + (2 j + 1) d, Cy_i = 2 oy + (2 i + 1) d.
+ * For the edge (xa, ya) -> (xb, yb) of ring r (the last vertex joins the first; skipped if ya == yb): s = +1 if yb < ya else -1,
+ * (xl, yl) the endpoint with the smaller y, (xh, yh) the other.  It crosses row i iff 2 yl <= Cy_i < 2 yh: the rows
+ * [ceil((2 yl - 2 oy - d) / (2 d)), ceil((2 yh - 2 oy - d) / (2 d))) clipped to [0, H).  In row i, with
+ * num = (Cy_i - 2 yl) (xh - xl) + (2 xl - 2 ox - d) (yh - yl) and j0 = clamp(ceil(num / (2 d (yh - yl))), 0, W):
+ * delta[i][j0] += s weight[r] (W is a dump column).  wind[i][j] = the sum of delta[i][0..j]; a pixel is inside iff wind > 0
+ * (KEEP_FILL_UNION) or wind odd (KEEP_FILL_EVENODD); out[i][j] = value (0..255) if inside, else into[i][j], or 0 when into is NULL.
+ * out: uint8 [H,W]; into: uint8 [H,W] or NULL; out may be into.
+ * Limits (KEEP_EINVAL before any device work): 1 <= downsample <= 4096; H, W >= 1 and H (W + 1) <= 2^28; |origin| <= 2^26;
+ * V <= 2^24; R <= 2^20; V >= 3 R; value in 0..255.  PRECONDITION on the arrays, which are not read on the host: every coordinate
+ * within +-2^26 (all products then fit an int64), ring_start and weight as above.  An edge that breaks it (a coordinate beyond the
+ * limit, a ring_start that does not enclose the vertex, a ring of < 3 vertices, a weight outside {-1, 0, 1}) adds nothing; no index
+ * derived from the arrays leaves the workspace.  R = 0 (then V = 0) writes into, or zeros.
+ * C, the number of crossings of edges with rows, is read back once to size the grid: ONE host synchronisation per call (none when
+ * R = 0).  C >= 2^31 is KEEP_EINVAL after that read.  crossings_out (a HOST int64, may be NULL) receives C.
+ * Workspace from the handle's arena: 4 H (W + 1) bytes of delta, zeroed at the head of the call, + 24 V + 16 ceil(V / 2048) + 8 (each
+ * part rounded up to 256).  Integer adds commute: the mask is the same from run to run.
+ * keep_mask_tile_counts: mask uint8 [H,W] (non-zero = set), 1 <= H W <= 2^30, pixel geometry as above with 1 <= downsample <= 2^30 and
+ * |origin| <= 2^40; coords int64 [N,2] level-0 top-left (x, y) ON THE DEVICE, within +-2^60 (not read on the host), N <= 2^24 - 1;
+ * 1 <= patch <= 2^30.  counts_out int32 [N,2]: column 0 the pixels whose centre lies in [x, x + patch) x [y, y + patch) and inside the
+ * mask: columns [ceil((2 (x - ox) - d) / (2 d)), ceil((2 (x + patch - ox) - d) / (2 d))) clipped to [0, W], rows likewise; column 1
+ * those of them that are non-zero.  At downsample 1 and origin 0, 2 counts[n][1] > patch^2 is the label rule of segment_utils.py:99-103.
+ * No workspace, no host synchronisation. */
+enum { KEEP_FILL_UNION = 0, KEEP_FILL_EVENODD = 1 };
+int keep_poly_fill(keep_handle* h, const int64_t* vertices, int64_t V, const int64_t* ring_start, int64_t R, const int32_t* weight,
+                   int64_t downsample, int64_t H, int64_t W, int64_t origin_x, int64_t origin_y, int rule, int value,
+                   const unsigned char* into, unsigned char* out, int64_t* crossings_out, void* stream);
+int keep_mask_tile_counts(keep_handle* h, const unsigned char* mask, int64_t H, int64_t W, int64_t downsample, int64_t origin_x,
+                          int64_t origin_y, const int64_t* coords, int64_t N, int64_t patch, int32_t* counts_out, void* stream);
+
 /* Pre-allocate workspace for calls of up to `tiles` tiles and `prompts` x `seq` tokens. */
 int keep_reserve(keep_handle* h, int64_t tiles, int64_t prompts, int64_t seq);
 int64_t keep_workspace_bytes(keep_handle* h);

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("KEEP_HIP_LIB") or os.path.join(_HERE, "libkeep_hip.so
 KEEP_OK, KEEP_EINVAL, KEEP_ESTATE, KEEP_EKEY, KEEP_EHIP, KEEP_EUNSUPPORTED, KEEP_ENOMEM = 0, -1, -2, -3, -4, -5, -6
 PIX_F32, PIX_F16, PIX_BF16, PIX_U8_HWC = 0, 1, 2, 3
 MASK_FOUR_PT, MASK_FOUR_PT_HARD, MASK_CENTER = 0, 1, 2
+FILL_UNION, FILL_EVENODD = 0, 1
 SIM_RAW, SIM_ARGMAX, SIM_SOFTMAX, SIM_SOFTMAX_F16, SIM_TOP2SCORE = 0, 1, 2, 3, 4
 PREC_FP16, PREC_STRICT, PREC_COMP = 0, 1, 2
 ATTN_PLAIN, ATTN_SPLIT, ATTN_SPLIT_COMPQKV, ATTN_COMPQKV, ATTN_PROJ_CLS, ATTN_COMPQKV_PROJ_CLS = 0, 1, 2, 3, 4, 5        # keep_set_block_precision: attention side of a ViT block
@@ -63,6 +64,8 @@ SIGNATURES = {
     "keep_outline_count": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp]),
     "keep_outline_trace": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "keep_outline_draw": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _vp]),
+    "keep_poly_fill": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, C.POINTER(_i64), _vp]),
+    "keep_mask_tile_counts": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
     "keep_token_error": (_i32, [_vp, _vp]),
     "keep_token_error_async": (_i32, [_vp, _vp, _vp]),
     "keep_similarity": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _vp, _vp]),

@@ -278,6 +278,26 @@ void launch_outline_trace(const int* labels, int H, int W, int n, int conn8, int
 void launch_outline_draw(const int* labels, int H, int W, const unsigned char* rgb_in, unsigned char* rgb_out, unsigned color, int width,
                          unsigned char* rowok, hipStream_t s);
 
+// Polygon annotations to masks (annotation.hip)
+constexpr int64_t POLY_MAX_COORD = (int64_t)1 << 26;      // every coordinate and origin component: the products of the fill fit an int64
+constexpr int64_t POLY_MAX_CELLS = (int64_t)1 << 28;      // h (w + 1): int32 indices into delta
+constexpr int64_t POLY_MAX_VERTICES = (int64_t)1 << 24;
+constexpr int64_t POLY_MAX_RINGS = (int64_t)1 << 20;
+constexpr int64_t POLY_MAX_DOWNSAMPLE = 4096;
+constexpr int64_t POLY_MAX_CROSSINGS = (int64_t)1 << 31;  // exclusive
+constexpr int POLY_CHUNK = 2048;                        // vertices per block of the edge pass
+size_t poly_fill_workspace_bytes(int64_t h, int64_t w, int64_t V);
+// zeroes delta, counts and scans the crossings of every edge (V >= 3, R >= 1) -> the device address of their total C inside ws
+const int64_t* launch_poly_count(const int64_t* vertices, int64_t V, const int64_t* ring_start, int64_t R, const int* weight, int64_t d, int h,
+                                 int w, int64_t ox, int64_t oy, unsigned char* ws, hipStream_t s);
+// C as read back from launch_poly_count, 1 <= C < 2^31: every crossing added into delta
+void launch_poly_crossings(const int64_t* vertices, int64_t V, int64_t d, int h, int w, int64_t ox, int64_t oy, int64_t C, unsigned char* ws,
+                           hipStream_t s);
+// the rows of delta (the head of ws) scanned, the inside test, out; out may be into
+void launch_poly_rows(int h, int w, int evenodd, int value, const unsigned char* into, unsigned char* out, unsigned char* ws, hipStream_t s);
+void launch_mask_tile_counts(const unsigned char* mask, int h, int w, int64_t d, int64_t ox, int64_t oy, const int64_t* coords, int64_t N,
+                             int64_t patch, int32_t* counts, hipStream_t s);
+
 // Tile scores rasterised onto the thumbnail (heatmap.hip).  acc: one 64-bit word per raster pixel, bits 0..39 the sum
 // of the 16-bit fixed-point values of the covering tiles, bits 40..63 their number
 constexpr int64_t HEAT_MAX_PIXELS = (int64_t)1 << 30;     // int32 pixel indices

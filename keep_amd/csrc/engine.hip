@@ -1986,6 +1986,66 @@ int keep_outline_draw(keep_handle* h, const int32_t* labels, int64_t H, int64_t 
     return check_launch(h, "outline_draw");
 }
 
+int keep_poly_fill(keep_handle* h, const int64_t* vertices, int64_t V, const int64_t* ring_start, int64_t R, const int32_t* weight,
+                   int64_t downsample, int64_t H, int64_t W, int64_t origin_x, int64_t origin_y, int rule, int value, const unsigned char* into,
+                   unsigned char* out, int64_t* crossings_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (crossings_out) *crossings_out = 0;
+    if (H < 1 || W < 1 || H > POLY_MAX_CELLS || W > POLY_MAX_CELLS || H * (W + 1) > POLY_MAX_CELLS)
+        return h->fail(KEEP_EINVAL, "poly_fill: %lldx%lld pixels (h, w >= 1, h (w + 1) <= 2^28)", (long long)H, (long long)W);
+    if (downsample < 1 || downsample > POLY_MAX_DOWNSAMPLE) return h->fail(KEEP_EINVAL, "poly_fill: downsample %lld outside [1, 4096]", (long long)downsample);
+    if (origin_x < -POLY_MAX_COORD || origin_x > POLY_MAX_COORD || origin_y < -POLY_MAX_COORD || origin_y > POLY_MAX_COORD)
+        return h->fail(KEEP_EINVAL, "poly_fill: origin (%lld, %lld) outside +-2^26", (long long)origin_x, (long long)origin_y);
+    if (rule != KEEP_FILL_UNION && rule != KEEP_FILL_EVENODD) return h->fail(KEEP_EINVAL, "poly_fill: rule %d (0 union, 1 evenodd)", rule);
+    if (value < 0 || value > 255) return h->fail(KEEP_EINVAL, "poly_fill: value %d outside [0, 255]", value);
+    if (V < 0 || V > POLY_MAX_VERTICES || R < 0 || R > POLY_MAX_RINGS || V < 3 * R || (V > 0 && R == 0))
+        return h->fail(KEEP_EINVAL, "poly_fill: V = %lld, R = %lld (V <= 2^24, R <= 2^20, every ring has >= 3 vertices)", (long long)V, (long long)R);
+    if (R > 0 && (!vertices || !ring_start || !weight)) return h->fail(KEEP_EINVAL, "poly_fill: null vertices, ring_start or weight");
+    if (((uintptr_t)vertices & 7) || ((uintptr_t)ring_start & 7) || ((uintptr_t)weight & 3))
+        return h->fail(KEEP_EINVAL, "poly_fill: vertices / ring_start / weight not aligned");
+    if (!out) return h->fail(KEEP_EINVAL, "poly_fill: out is null");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = ensure_arena(h, poly_fill_workspace_bytes(H, W, V));
+    if (rc) return rc;
+    unsigned char* ws = (unsigned char*)h->arena;
+    if (R == 0) {
+        HIPCHK(h, hipMemsetAsync(ws, 0, (size_t)H * (size_t)(W + 1) * 4, s));
+    } else {
+        const int64_t* c_dev = launch_poly_count(vertices, V, ring_start, R, weight, downsample, (int)H, (int)W, origin_x, origin_y, ws, s);
+        rc = check_launch(h, "poly_fill (edges)");
+        if (rc) return rc;
+        int64_t C = 0;
+        HIPCHK(h, hipMemcpyAsync(&C, c_dev, sizeof C, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));                  // the one host synchronisation: C sizes the grid
+        if (crossings_out) *crossings_out = C;
+        if (C < 0 || C >= POLY_MAX_CROSSINGS)
+            return h->fail(KEEP_EINVAL, "poly_fill: %lld crossings of edges with rows (< 2^31): fill at a larger downsample", (long long)C);
+        if (C > 0) launch_poly_crossings(vertices, V, downsample, (int)H, (int)W, origin_x, origin_y, C, ws, s);
+    }
+    launch_poly_rows((int)H, (int)W, rule == KEEP_FILL_EVENODD, value, into, out, ws, s);
+    return check_launch(h, "poly_fill");
+}
+
+int keep_mask_tile_counts(keep_handle* h, const unsigned char* mask, int64_t H, int64_t W, int64_t downsample, int64_t origin_x, int64_t origin_y,
+                          const int64_t* coords, int64_t N, int64_t patch, int32_t* counts_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!mask) return h->fail(KEEP_EINVAL, "mask_tile_counts: mask is null");
+    if (!regions_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "mask_tile_counts: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (downsample < 1 || downsample > HEAT_MAX_PATCH) return h->fail(KEEP_EINVAL, "mask_tile_counts: downsample %lld outside [1, 2^30]", (long long)downsample);
+    if (patch < 1 || patch > HEAT_MAX_PATCH) return h->fail(KEEP_EINVAL, "mask_tile_counts: patch %lld outside [1, 2^30]", (long long)patch);
+    constexpr int64_t omax = (int64_t)1 << 40;
+    if (origin_x < -omax || origin_x > omax || origin_y < -omax || origin_y > omax)
+        return h->fail(KEEP_EINVAL, "mask_tile_counts: origin (%lld, %lld) outside +-2^40", (long long)origin_x, (long long)origin_y);
+    if (N < 0 || N > HEAT_MAX_TILES) return h->fail(KEEP_EINVAL, "mask_tile_counts: %lld tiles (0 .. 2^24 - 1)", (long long)N);
+    if (N > 0 && (!coords || ((uintptr_t)coords & 7))) return h->fail(KEEP_EINVAL, "mask_tile_counts: coords is null or not 8-byte aligned");
+    if (N > 0 && (!counts_out || ((uintptr_t)counts_out & 7))) return h->fail(KEEP_EINVAL, "mask_tile_counts: counts_out is null or not 8-byte aligned");
+    if (N == 0) return KEEP_OK;
+    KEEP_ON_DEVICE(h);
+    launch_mask_tile_counts(mask, (int)H, (int)W, downsample, origin_x, origin_y, coords, N, patch, counts_out, (hipStream_t)stream);
+    return check_launch(h, "mask_tile_counts");
+}
+
 int keep_token_error(keep_handle* h, void* stream) {
     if (!h) return KEEP_EINVAL;
     KEEP_ON_DEVICE(h);

@@ -19,6 +19,7 @@ import os
 import weakref
 from typing import Dict, List, Mapping, Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1315,6 +1316,88 @@ class KEEPModel:
         out = torch.empty((h, w, 3), dtype=torch.uint8, device=self._device)
         _lib.check(self._handle, _lib.load().keep_outline_draw(self._handle, _ptr(lab), h, w, _ptr(x), _ptr(out), packed, width,
                                                                _stream(self._device)), "outline_draw")
+        return out
+
+    # ------------------------------------------------------------------ polygon annotations
+    @torch.no_grad()
+    def fill_polygons(self, polys, downsample: int, shape, origin=(0, 0), rule: str = "union", value: int = 1, into=None) -> torch.Tensor:
+        """Polygons on level-0 coordinates filled into a mask in thumbnail geometry on the device -> uint8
+        ``[h,w]`` on the device: the inverse of :meth:`region_outlines`.
+
+        ``polys``: a ``keep_amd.annotation.PolygonSet`` (``from_geojson`` / ``from_asap_xml`` / ``from_outlines``; its ring weights follow
+        ``rule``), or a tuple ``(vertices int [V,2], ring_start int [R+1], weight int [R] in {-1, 0, 1})`` of numpy / torch arrays, host
+        or device (arrays on the device are read back once for the argument checks).  One mask pixel covers ``downsample`` x
+        ``downsample`` level-0 pixels (``1..4096``), pixel (0, 0) starts at ``origin``; ``shape = (h, w)`` with ``h (w + 1) <= 2^28``; every
+        coordinate within +-2^26.  A pixel is inside iff its CENTRE is: the winding number there is ``> 0`` (``"union"``: overlapping
+        features unite, a feature's hole does not punch through another feature, the drawing direction does not matter) or odd
+        (``"evenodd"``); a centre exactly on an edge belongs to the polygon on whose left or upper side it lies, so polygons that
+        share an edge partition the pixels.  ``out = value`` (0..255) inside, ``into`` (uint8 ``[h,w]``, host or device) or 0 elsewhere:
+        ``into`` gives a painter's order across calls and ``value=0`` cuts.  The number of edge / row crossings is read back once (the
+        one host synchronisation; it is left in ``last_fill_crossings``); ``>= 2^31`` of them is a ValueError.  Integer arithmetic,
+        equal to ``keep_amd.annotation.fill_numpy`` exactly and the same from run to run."""
+        from .annotation import check_fill_args, check_into, polygon_arrays
+        d, (h, w), (ox, oy), rule_id, value = check_fill_args(downsample, shape, origin, rule, value)
+        vertices, ring_start, weight = polygon_arrays(polys, rule)
+        into = check_into(into, (h, w))
+        self._ready_device()
+        V, R = int(vertices.shape[0]), int(ring_start.shape[0]) - 1
+        vd, rd, wd = (torch.from_numpy(a).to(self._device) for a in (vertices, ring_start, weight))
+        if into is not None:
+            into = (torch.from_numpy(np.ascontiguousarray(into)) if isinstance(into, np.ndarray) else into).to(self._device).contiguous()
+        out = torch.empty((h, w), dtype=torch.uint8, device=self._device)
+        crossings = C.c_int64(0)
+        _lib.check(self._handle, _lib.load().keep_poly_fill(self._handle, _ptr(vd), V, _ptr(rd), R, _ptr(wd), d, h, w, ox, oy, rule_id, value,
+                                                            _ptr(into), _ptr(out), C.byref(crossings), _stream(self._device)), "poly_fill")
+        self.last_fill_crossings = int(crossings.value)
+        return out
+
+    @torch.no_grad()
+    def annotation_mask(self, polys, downsample: int, shape, order=None, rule: str = "union", mode: str = "four_pt"):
+        """A ``PolygonSet`` -> a ``keep_amd.region.TissueMask`` on the device, which ``region_grid`` / ``encode_region`` /
+        ``extract_slide_features`` take as ``tissue=``, ``mask_regions`` as its mask and ``render_heatmap`` as ``tissue=``.
+
+        Without ``order`` everything is filled with 1 in one call of :meth:`fill_polygons`.  ``order``: a sequence of
+        ``(groups, value)`` (``keep_amd.annotation.CAMELYON16_ORDER``: the tumour groups painted 1, then the exclusions painted 0): one
+        fill per entry over the features of those groups, each painted into the result of the one before.  The origin is (0, 0), as a
+        ``TissueMask`` has none; ``mode`` is how a grid cell is tested against the mask."""
+        from .annotation import PolygonSet
+        from .region import TissueMask
+        from .annotation import check_fill_args
+        from .region import MASK_MODES
+        if not isinstance(polys, PolygonSet):
+            raise ValueError(f"polys must be a PolygonSet, got {type(polys).__name__}")
+        if mode not in MASK_MODES:
+            raise ValueError(f"mode must be one of {MASK_MODES}, got {mode!r}")
+        check_fill_args(downsample, shape, (0, 0), rule, 1)
+        if order is None:
+            mask = self.fill_polygons(polys, downsample, shape, (0, 0), rule, 1)
+        else:
+            steps = [(tuple([g] if isinstance(g, str) else g), check_fill_args(downsample, shape, (0, 0), rule, v)[4]) for g, v in order]
+            if not steps:
+                raise ValueError("order is empty")
+            mask = None
+            for groups, v in steps:
+                mask = self.fill_polygons(polys.select(groups=groups), downsample, shape, (0, 0), rule, v, mask)
+        return TissueMask(mask, downsample, mode)
+
+    @torch.no_grad()
+    def mask_tile_counts(self, mask, coords, patch_size: int, downsample: Optional[int] = None, origin=(0, 0)) -> torch.Tensor:
+        """How much of a mask lies under every tile, on the device -> int32 ``[N,2]`` on the device: column 0 the mask pixels whose
+        centre lies in the tile ``[x, x + patch_size) x [y, y + patch_size)`` (clipped to the mask), column 1 those of them that are
+        non-zero.  ``mask``: uint8 / bool ``[h,w]``, numpy or torch, host or device, with ``downsample=``, or a ``TissueMask``, which brings
+        its own; ``coords``: integers ``[N,2]``, level-0 top-left ``(x, y)``, within +-2^60; ``origin``: the level-0 position of mask pixel
+        (0, 0).  At ``downsample=1`` and origin 0, ``2 * counts[:, 1] > patch_size ** 2`` is the tile label rule of the reference's
+        ``segment_utils.py``.  No host synchronisation; equal to ``keep_amd.annotation.tile_counts_numpy`` exactly."""
+        from .annotation import check_tile_args
+        m, c, patch, d, (ox, oy) = check_tile_args(mask, coords, patch_size, downsample, origin)
+        self._ready_device()
+        m = (torch.from_numpy(np.ascontiguousarray(m)) if isinstance(m, np.ndarray) else m).to(self._device).contiguous()
+        m = m.view(torch.uint8) if m.dtype == torch.bool else m
+        c = (torch.from_numpy(np.ascontiguousarray(c)) if isinstance(c, np.ndarray) else c).to(self._device, torch.int64).contiguous()
+        N = int(c.shape[0])
+        out = torch.empty((N, 2), dtype=torch.int32, device=self._device)
+        _lib.check(self._handle, _lib.load().keep_mask_tile_counts(self._handle, _ptr(m), int(m.shape[0]), int(m.shape[1]), d, ox, oy, _ptr(c), N,
+                                                                   patch, _ptr(out), _stream(self._device)), "mask_tile_counts")
         return out
 
     @staticmethod
