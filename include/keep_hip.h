@@ -531,6 +531,15 @@ int keep_profile_reset(keep_handle* h);
 int keep_op_linear(keep_handle* h, const float* a, const float* w, const float* bias, const float* ls,
                    const float* resid, int64_t M, int64_t N, int64_t K, int epi, int split, float* out,
                    void* stream);
+/* keep_op_linear for the residual epilogues (epi 2 or 4 only) with the LayerNorm that follows offered to the GEMM, as the towers do (the small-M and the
+ *   K-sliced split-K paths take it in their reduce kernel; when the GEMM does not, the stand-alone LayerNorm kernel runs on the same parameters).
+ *   epi 2 (ViT): out = resid + ls*(acc+bias), ln_out = LayerNorm(out).   epi 4 (BERT, the normalised row replaces the sum): out = ln_out in fp32.
+ *   ln_out fp32 [M,N]: the fp16 operand planes the kernel wrote in blk layout, read back (hi + lo when split == 1, hi alone when 0); ln_hi fp32 [M,N] or
+ *   NULL: the hi plane alone (a sum cannot tell a swapped pair of planes from a right one).  *did_ln (host): 1 when the GEMM's reduce did the LayerNorm.
+ *   N in {768, 1024}; split 0 / 1. */
+int keep_op_linear_ln(keep_handle* h, const float* a, const float* w, const float* bias, const float* ls,
+                      const float* resid, const float* ln_gamma, const float* ln_beta, float ln_eps, int64_t M, int64_t N,
+                      int64_t K, int epi, int split, float* out, float* ln_out, float* ln_hi, int* did_ln, void* stream);
 /* One MLP half of a ViT block through the tower's own kernels (timm Block: x + ls2 * fc2(gelu(fc1(norm2(x))))):
  *   LayerNorm (writes the fp16 operand and, per mode, its lo plane / MX-fp4 side planes) -> fc1 + GELU -> fc2 + LayerScale + residual.
  *   mode = KEEP_MLP_* 0..3: 0 plain fp16 | 1 split | 2 compensated | 3 compensated, W_lo term only.  x, out fp32 [M, D]; D in {768, 1024}; F % 256 == 0. */
@@ -540,6 +549,11 @@ int keep_op_mlp(keep_handle* h, const float* x, const float* ln_w, const float* 
 /* qkv fp32 [B*T, 3*heads*64] (q|k|v), mask int64 [B,T] or NULL -> out fp32 [B*T, heads*64] */
 int keep_op_attention(keep_handle* h, const float* qkv, const int64_t* mask, int64_t B, int64_t T, int heads,
                       int split, float* out, void* stream);
+/* keep_op_attention without a mask, with the CLS features of the image tower: q_rows > 0 computes only the first q_rows queries of every sequence
+ * (the CLS-only last block; other rows 0); cls_out fp32 [B, heads*64] or NULL: query row 0 of every sequence once more from the fp32 accumulators as
+ * hi + lo (the compact operand of KEEP_ATTN_PROJ_CLS), single pass only -- with split != 0 the launcher refuses it: KEEP_EUNSUPPORTED. */
+int keep_op_attention_cls(keep_handle* h, const float* qkv, int64_t B, int64_t T, int heads, int split, int q_rows,
+                          float* out, float* cls_out, void* stream);
 /* The image tower's attention beyond 512 tokens (timm Attention.forward, scaled_dot_product_attention without a mask, at the
  * sequence lengths of quick_start/keep_inference.py:32-40 with dynamic_img_size): key-blocked online softmax, any T >= 1.
  * qkv fp32 [B*T, 3*heads*64] -> out fp32 [B*T, heads*64]; q_rows > 0: only the first q_rows queries of every sequence (other rows 0) */

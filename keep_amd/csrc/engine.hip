@@ -2364,6 +2364,49 @@ int keep_op_linear(keep_handle* h, const float* a, const float* w, const float* 
     return check_launch(h, "op_linear");
 }
 
+int keep_op_linear_ln(keep_handle* h, const float* a, const float* w, const float* bias, const float* ls, const float* resid,
+                      const float* ln_gamma, const float* ln_beta, float ln_eps, int64_t M, int64_t N, int64_t K, int epi, int split,
+                      float* out, float* ln_out, float* ln_hi, int* did_ln, void* stream) {
+    if (!h || !a || !w || !bias || !resid || !ln_gamma || !ln_beta || !out || !ln_out || !did_ln) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
+    if (M < 1 || (split != 0 && split != 1)) return h->fail(KEEP_EINVAL, "linear_ln needs M >= 1 and split 0 / 1");
+    if (epi != EPI_RESID_LS && epi != EPI_RESID_F32) return h->fail(KEEP_EINVAL, "epilogue %d (linear_ln takes the residual epilogues 2 and 4)", epi);
+    if (epi == EPI_RESID_LS && !ls) return h->fail(KEEP_EINVAL, "missing ls");
+    if ((N != 768 && N != 1024) || K < 64 || K % 32) return h->fail(KEEP_EUNSUPPORTED, "linear_ln needs N in {768, 1024} and K%%32==0");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    Tmp t;
+    const size_t ae = blk_elems(M, K), we = blk_elems(N, K), oe = blk_elems(M, N);
+    f16* a_hi = t.get<f16>(ae); f16* a_lo = t.get<f16>(ae);
+    f16* w_hi = t.get<f16>(we); f16* w_lo = t.get<f16>(we);
+    f16* n_hi = t.get<f16>(oe); f16* n_lo = t.get<f16>(oe);
+    float* ws = t.get<float>(SKINNY_WS_BYTES / 4);
+    if (!a_hi || !a_lo || !w_hi || !w_lo || !n_hi || !n_lo || !ws) return h->fail(KEEP_ENOMEM, "temp alloc");
+    launch_split_blockify(a, a_hi, a_lo, (int)M, (int)K, s); launch_split_blockify(w, w_hi, w_lo, (int)N, (int)K, s);
+    // as in the towers: the residual stream is updated in place (ViT: resid += ...; BERT: out_f32 == resid), the LayerNorm that follows reads it there
+    HIPCHK(h, hipMemcpyAsync(out, resid, M * N * sizeof(float), hipMemcpyDeviceToDevice, s));
+    LnParams ln{};
+    ln.tune = &h->tune;
+    ln.x = out; ln.x_stride = N; ln.rows = (int)M; ln.D = (int)N; ln.eps = ln_eps; ln.gamma = ln_gamma; ln.beta = ln_beta;
+    ln.out_hi = n_hi; ln.out_lo = split ? n_lo : nullptr; ln.out_kt = (int)(N / 32);
+    if (epi == EPI_RESID_F32) { ln.out_f32 = out; ln.out_f32_stride = N; }      // BERT: the normalised row replaces the sum
+    GemmParams p{};
+    p.tune = &h->tune;
+    p.a_hi = a_hi; p.a_lo = a_lo; p.w_hi = w_hi; p.w_lo = w_lo; p.M = (int)M; p.N = (int)N; p.K = (int)K;
+    p.nseg = split ? 3 : 1; p.bias = bias; p.ls = ls; p.patches_per_img = 196;
+    p.splitk_ws = ws; p.splitk_bytes = SKINNY_WS_BYTES;
+    p.resid = out;
+    if (epi == EPI_RESID_F32) p.out_f32 = out;
+    offer_ln(p, ln);
+    const int rc = launch_gemm_f16(p, epi, s);
+    if (rc < 0) return h->fail(KEEP_EUNSUPPORTED, "op_linear_ln: no kernel for this shape / mode");
+    if (!(rc & GEMM_DID_LN) && launch_layernorm(ln, s)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %lld", (long long)N);
+    launch_unblockify_f32(n_hi, ln.out_lo, ln_out, (int)M, (int)N, s);
+    if (ln_hi) launch_unblockify_f32(n_hi, nullptr, ln_hi, (int)M, (int)N, s);      // the hi plane on its own: hi + lo does not tell the two planes apart
+    HIPCHK(h, hipStreamSynchronize(s));
+    *did_ln = (rc & GEMM_DID_LN) ? 1 : 0;
+    return check_launch(h, "op_linear_ln");
+}
+
 int keep_op_mlp(keep_handle* h, const float* x, const float* ln_w, const float* ln_b, const float* fc1_w, const float* fc1_b,
                 const float* fc2_w, const float* fc2_b, const float* ls, int64_t M, int64_t D, int64_t F, int mode, float* out, void* stream) {
     if (!h || !x || !ln_w || !ln_b || !fc1_w || !fc1_b || !fc2_w || !fc2_b || !ls || !out) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
@@ -2431,6 +2474,40 @@ int keep_op_attention(keep_handle* h, const float* qkv, const int64_t* mask, int
     launch_unblockify_f32(o_hi, split ? o_lo : nullptr, out, (int)M, (int)D, s);
     HIPCHK(h, hipStreamSynchronize(s));
     return check_launch(h, "op_attention");
+}
+
+int keep_op_attention_cls(keep_handle* h, const float* qkv, int64_t B, int64_t T, int heads, int split, int q_rows, float* out, float* cls_out,
+                          void* stream) {
+    if (!h || !qkv || !out || B < 1 || T < 1 || heads < 1 || q_rows < 0) return h ? h->fail(KEEP_EINVAL, "bad attention arguments") : KEEP_EINVAL;
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t M = B * T, D = (int64_t)heads * 64;
+    Tmp t;
+    f16* q_hi = t.get<f16>(M * 3 * D); f16* q_lo = t.get<f16>(M * 3 * D);
+    const size_t oe = blk_elems(M, D), ce = blk_elems(B, D);
+    f16* o_hi = t.get<f16>(oe); f16* o_lo = t.get<f16>(oe);
+    f16* c_hi = t.get<f16>(ce); f16* c_lo = t.get<f16>(ce);      // the compact [B, D] operand of KEEP_ATTN_PROJ_CLS
+    if (!q_hi || !q_lo || !o_hi || !o_lo || !c_hi || !c_lo) return h->fail(KEEP_ENOMEM, "temp alloc");
+    HIPCHK(h, hipMemsetAsync(o_hi, 0, oe * sizeof(f16), s));      // rows past q_rows read back as 0
+    HIPCHK(h, hipMemsetAsync(o_lo, 0, oe * sizeof(f16), s));
+    HIPCHK(h, hipMemsetAsync(c_hi, 0, ce * sizeof(f16), s));
+    HIPCHK(h, hipMemsetAsync(c_lo, 0, ce * sizeof(f16), s));
+    launch_split_f16(qkv, q_hi, q_lo, M * 3 * D, s);
+    AttnParams a{};
+    a.tune = &h->tune;
+    if (split && T > 256) {
+        a.part_bytes = (size_t)B * heads * T * ATT_PART_FLOATS * sizeof(float);
+        a.part_ws = t.get<float>(a.part_bytes / sizeof(float));
+        if (!a.part_ws) return h->fail(KEEP_ENOMEM, "temp alloc");
+    }
+    a.qkv_hi = q_hi; a.qkv_lo = q_lo; a.out_hi = o_hi; a.out_lo = split ? o_lo : nullptr; a.mask = nullptr;
+    a.batch = (int)B; a.ntok = (int)T; a.heads = heads; a.split = split; a.scale = 0.125f; a.out_kt = (int)(D / 32); a.q_rows = q_rows;
+    if (cls_out) { a.cls_hi = c_hi; a.cls_lo = c_lo; }           // (split: launch_attention refuses the planes -- reported, not worked round)
+    if (launch_attention(a, s)) return h->fail(KEEP_EUNSUPPORTED, "attention: T %lld%s unsupported", (long long)T, (cls_out && split) ? " with cls_out in split mode" : "");
+    launch_unblockify_f32(o_hi, split ? o_lo : nullptr, out, (int)M, (int)D, s);
+    if (cls_out) launch_unblockify_f32(c_hi, c_lo, cls_out, (int)B, (int)D, s);
+    HIPCHK(h, hipStreamSynchronize(s));
+    return check_launch(h, "op_attention_cls");
 }
 
 int keep_op_attention_long(keep_handle* h, const float* qkv, int64_t B, int64_t T, int heads, int split, int q_rows, float* out, void* stream) {

@@ -60,6 +60,23 @@ class Ops:
         _lib.check(self._h, rc, "op_linear")
         return out
 
+    def linear_ln(self, a, w, bias, ln_gamma, ln_beta, ln_eps, epi=EPI_RESID_LS, split=False, ls=None, resid=None, hi=False):
+        """A residual linear (epi 2 / 4) with the LayerNorm that follows offered to the GEMM, as the towers do -> (out, ln_out, did_ln).
+        ln_out is read back from the fp16 operand planes (hi + lo when split, else hi); did_ln is 1 when the GEMM's reduce did the LayerNorm.
+        hi=True: -> (out, ln_out, did_ln, ln_hi) with the hi plane on its own."""
+        a, w, bias, ls, resid, ln_gamma, ln_beta = map(self._f, (a, w, bias, ls, resid, ln_gamma, ln_beta))
+        M, K = a.shape
+        N = w.shape[0]
+        out = torch.empty((M, N), dtype=torch.float32, device=self.device)
+        ln_out = torch.empty((M, N), dtype=torch.float32, device=self.device)
+        ln_hi = torch.empty((M, N), dtype=torch.float32, device=self.device) if hi else None
+        did = C.c_int(-1)
+        rc = _lib.load().keep_op_linear_ln(self._h, _ptr(a), _ptr(w), _ptr(bias), _ptr(ls), _ptr(resid), _ptr(ln_gamma), _ptr(ln_beta),
+                                           float(ln_eps), M, N, K, int(epi), int(split), _ptr(out), _ptr(ln_out), _ptr(ln_hi), C.byref(did),
+                                           _stream(self.device))
+        _lib.check(self._h, rc, "op_linear_ln")
+        return (out, ln_out, did.value, ln_hi) if hi else (out, ln_out, did.value)
+
     def mlp(self, x, ln_w, ln_b, fc1_w, fc1_b, fc2_w, fc2_b, ls, mode=0):
         """x + ls * fc2(gelu(fc1(layernorm(x)))) through the tower's kernels; mode 0 fp16, 1 split, 2 compensated."""
         x, ln_w, ln_b, fc1_w, fc1_b, fc2_w, fc2_b, ls = map(self._f, (x, ln_w, ln_b, fc1_w, fc1_b, fc2_w, fc2_b, ls))
@@ -79,6 +96,17 @@ class Ops:
                                            _stream(self.device))
         _lib.check(self._h, rc, "op_attention")
         return out
+
+    def attention_cls(self, qkv, B, T, heads, split=False, q_rows=0, cls=False):
+        """Unmasked attention with the image tower's CLS features: q_rows > 0 computes only the first q_rows queries of every sequence
+        (other rows 0); cls=True also returns the [B, heads*64] CLS rows as hi + lo of the fp32 accumulators -> out, or (out, cls_out)."""
+        qkv = self._f(qkv)
+        out = torch.empty((B * T, heads * 64), dtype=torch.float32, device=self.device)
+        cls_out = torch.empty((B, heads * 64), dtype=torch.float32, device=self.device) if cls else None
+        rc = _lib.load().keep_op_attention_cls(self._h, _ptr(qkv), B, T, heads, int(split), int(q_rows), _ptr(out), _ptr(cls_out),
+                                               _stream(self.device))
+        _lib.check(self._h, rc, "op_attention_cls")
+        return (out, cls_out) if cls else out
 
     def attention_long(self, qkv, B, T, heads, split=False, q_rows=0):
         """The key-blocked attention kernel the image tower runs beyond 512 tokens (any T; no key mask)."""
