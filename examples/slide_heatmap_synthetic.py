@@ -3,6 +3,8 @@
 thumbnail -> tissue_mask -> encode_region with half-overlapping tiles -> wsi.segment_heatmap -> render_heatmap; wsi.segment_regions ->
 the regions above the median score, largest first; region_outlines -> their boundary rings with holes, written as GeoJSON in level-0
 pixels (what QuPath or ASAP open as annotations); draw_outlines -> the lesions outlined in black and the tissue in blue on the PNG.
+Last the GeoJSON is read back as the ground truth and the heatmap is evaluated against it, as the reference's
+eval_seg_auc / eval_seg_coarse do against a mask: tile AUROC, the threshold of the best tpr - fpr, Dice at level 16, the threshold sweep.
 
     python examples/slide_heatmap_synthetic.py [--rows 8] [--cols 10] [--depth 2] [--out slide_heatmap.png] [--geojson lesions.geojson]
 
@@ -91,6 +93,17 @@ def main():
     from PIL import Image
     Image.fromarray(picture.cpu().numpy()).save(a.out)
     print(f"wrote {a.out}")
+    from keep_amd.annotation import PolygonSet
+    truth = PolygonSet.from_geojson(a.geojson)                            # the polygons just written: what a pathologist would have drawn
+    try:
+        roc, overlap, sweep = wsi.segment_evaluate(classifier, feats, coords, truth, patch_size=PATCH, overlap=True,
+                                                   shape=tuple(thumb.shape[:2]), sweep=True, model=model)
+    except ValueError as e:                                               # every tile on one side of the outlines: no ROC to speak of
+        print(f"not evaluated: {e}")
+        return
+    print(f"against its own outlines: tile AUROC {roc.auc:.4f} over {roc.n_pos} + {roc.n_neg} tiles, best threshold {roc.best_threshold:.4f} "
+          f"({len(roc.thresholds)} points, {int(roc.kept.sum())} kept); Dice at level 16 {overlap.dice:.4f}, IoU {overlap.iou:.4f}; "
+          f"pixel sweep: best Dice {sweep.best_dice:.4f} at {sweep.best_threshold:.4f}, pixel AUROC {sweep.auc:.4f}")
 
 
 if __name__ == "__main__":

@@ -403,6 +403,43 @@ int keep_poly_fill(keep_handle* h, const int64_t* vertices, int64_t V, const int
 int keep_mask_tile_counts(keep_handle* h, const unsigned char* mask, int64_t H, int64_t W, int64_t downsample, int64_t origin_x,
                           int64_t origin_y, const int64_t* coords, int64_t N, int64_t patch, int32_t* counts_out, void* stream);
 
+/* Segmentation evaluation: tile ROC, mask overlap, threshold sweep.
+ * keep_eval_roc replaces: the arithmetic of eval_seg_auc (WSI_evaluation/segment_utils.py:105-119): roc_auc_score, roc_curve and
+ * thresholds[np.argmax(tpr - fpr)] of scikit-learn over the tiles of a slide.  scores fp32 [N], labels uint8 [N] (non-zero =
+ * positive), both ON THE DEVICE, 0 <= N <= 2^24 - 1.  A NaN score removes its tile and -0.0 counts as +0.0, as in keep_sort_f32.
+ * scalars_out: int64 [8] ON THE DEVICE:
+ *   0 n   the scored tiles      1 P   the positives among them      2 Nn  the negatives
+ *   3 U2  the sum over the positives of 2 less + eq, less / eq the negatives below / equal to the positive's score (<= 2^49);
+ *         AUC = double(U2) / (2.0 P Nn): the exact area under the ROC curve, ties as the trapezoid takes them, rounded once
+ *   4 K   the distinct scores = the points of the curve
+ *   5 best_k   the row of the best threshold, or -1 for the point (0, 0) with threshold +inf that roc_curve prepends
+ *   6 the best threshold's fp32 bits, zero-extended (0x7F800000 = +inf)      7 the number of kept points
+ * The curve, rows 0..K-1 for the distinct scores in DESCENDING order: thresholds_out fp32, fps_out / tps_out int32 (the negatives /
+ * positives with score >= threshold), kept_out uint8: 1 for what roc_curve(drop_intermediate=True) keeps: the first and the last
+ * point and every point between where the second difference of fps or of tps is not zero.  Each has room for N entries (K <= n <=
+ * N; the rows from K on are not written); all four may be NULL together, and the scalars are the same.
+ * Best threshold: over the kept points J = double(tps) / double(P) - double(fps) / double(Nn) in IEEE fp64, the first maximum in
+ * row order; when no kept point has J > 0 (constant scores, scores worse than chance) the answer is +inf, as np.argmax picks the
+ * prepended point.  P = 0 or Nn = 0 (N = 0 included) is reported in the scalars, with best_k = -1, and is no error here.
+ * No host synchronisation.  Workspace from the handle's arena: 12 N bytes + the sort's (4 N + its digit tables, none up to 4096
+ * values) + 4 ceil(N / 2048) + 16 KiB, and 13 N more when the curve outputs are NULL (each part rounded up to 256).  Integer
+ * arithmetic, integer atomics and one order-independent (max J, min row) reduction: the same from run to run.
+ * keep_eval_mask_counts replaces: the counting of eval_seg_coarse (segment_utils.py:130-151).  a, b: uint8 [H,W], within: uint8
+ * [H,W] or NULL, contiguous, non-zero = set, 1 <= H W <= 2^30.  counts_out: int64 [4] ON THE DEVICE, over the pixels where within
+ * is set (all when NULL): set in a, set in b, set in both, considered.  The reference's uint8 product mask_img * pred_mask is
+ * non-zero exactly where both are (255 v = -v mod 256), so "set in both" is its count.  No workspace, no host synchronisation.
+ * keep_eval_raster_hist: a threshold sweep at pixel level, which the reference does not have (it takes Dice at one threshold).
+ * acc: the int64 [H,W] accumulator of keep_heat_accumulate, 8-byte aligned, under the PRECONDITION S <= 65535 c stated at
+ * keep_regions_table (a word that breaks it counts in bin 65535); truth: uint8 [H,W]; within: uint8 [H,W] or NULL.  hist_out:
+ * int64 [2,65537] ON THE DEVICE, row = truth set: bin m <= 65535 counts the covered pixels (c > 0) whose mean in 16-bit fixed point
+ * (2 S + c) / (2 c) is m, bin 65536 the uncovered ones; pixels outside within count nowhere.  No workspace, no host synchronisation. */
+int keep_eval_roc(keep_handle* h, const float* scores, const unsigned char* labels, int64_t N, int64_t* scalars_out, float* thresholds_out,
+                  int32_t* fps_out, int32_t* tps_out, unsigned char* kept_out, void* stream);
+int keep_eval_mask_counts(keep_handle* h, const unsigned char* a, const unsigned char* b, const unsigned char* within, int64_t H, int64_t W,
+                          int64_t* counts_out, void* stream);
+int keep_eval_raster_hist(keep_handle* h, const int64_t* acc, const unsigned char* truth, const unsigned char* within, int64_t H, int64_t W,
+                          int64_t* hist_out, void* stream);
+
 /* Pre-allocate workspace for calls of up to `tiles` tiles and `prompts` x `seq` tokens. */
 int keep_reserve(keep_handle* h, int64_t tiles, int64_t prompts, int64_t seq);
 int64_t keep_workspace_bytes(keep_handle* h);

@@ -66,6 +66,9 @@ SIGNATURES = {
     "keep_outline_draw": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _vp]),
     "keep_poly_fill": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, C.POINTER(_i64), _vp]),
     "keep_mask_tile_counts": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "keep_eval_roc": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "keep_eval_mask_counts": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "keep_eval_raster_hist": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "keep_token_error": (_i32, [_vp, _vp]),
     "keep_token_error_async": (_i32, [_vp, _vp, _vp]),
     "keep_similarity": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _vp, _vp]),

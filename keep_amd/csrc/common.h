@@ -329,6 +329,20 @@ void launch_sort_f32(const float* values, int64_t M, unsigned char* ws, float* s
 void launch_rank_f32(const float* sorted, int64_t M, const int64_t* n_dev, const float* queries, int64_t N, int self, float* pct,
                      int* less, int* eq, hipStream_t s);
 
+// Segmentation evaluation (eval.hip)
+constexpr int EVAL_SCAN_CHUNK = 2048;                   // entries per block of the scan over the distinct-score flags
+constexpr int EVAL_BEST_BLOCKS = 1024;                  // blocks (and candidates) of the best-threshold reduction
+constexpr int EVAL_HIST_BINS = 65537;                   // per truth value: the means 0..65535, then the uncovered pixels
+constexpr int EVAL_ROC_SCALARS = 8;
+size_t eval_roc_workspace_bytes(int64_t N, bool own_curve);
+// scalars: int64 [EVAL_ROC_SCALARS]; thr / fps / tps / kept: N entries each, or all null (the curve then lives in ws)
+void launch_eval_roc(const float* scores, const unsigned char* labels, int64_t N, unsigned char* ws, int64_t* scalars, float* thr, int* fps,
+                     int* tps, unsigned char* kept, hipStream_t s);
+// out: int64 [4], zeroed here; within may be null
+void launch_eval_mask_counts(const unsigned char* a, const unsigned char* b, const unsigned char* within, int64_t n, int64_t* out, hipStream_t s);
+// hist: int64 [2][EVAL_HIST_BINS], zeroed here; within may be null
+void launch_eval_raster_hist(const int64_t* acc, const unsigned char* truth, const unsigned char* within, int64_t n, int64_t* hist, hipStream_t s);
+
 // Row-wise helpers (rowops.hip)
 // pixels [B,3,16 gh,16 gw] (or uint8 [B,16 gh,16 gw,3]) -> patches [B * gh * gw][768], row-major (y, x) patch order; CLS rows of resid
 void launch_im2col(const void* pixels, int dtype, int B, int gh, int gw, f16* out_hi, f16* out_lo,      // out in blk layout (KT = 24)

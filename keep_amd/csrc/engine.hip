@@ -2046,6 +2046,46 @@ int keep_mask_tile_counts(keep_handle* h, const unsigned char* mask, int64_t H, 
     return check_launch(h, "mask_tile_counts");
 }
 
+int keep_eval_roc(keep_handle* h, const float* scores, const unsigned char* labels, int64_t N, int64_t* scalars_out, float* thresholds_out,
+                  int32_t* fps_out, int32_t* tps_out, unsigned char* kept_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (N < 0 || N > SORT_MAX) return h->fail(KEEP_EINVAL, "eval_roc: %lld tiles (0 .. 2^24 - 1)", (long long)N);
+    if (N > 0 && (!scores || !labels)) return h->fail(KEEP_EINVAL, "eval_roc: null scores or labels");
+    if (!scalars_out || ((uintptr_t)scalars_out & 7)) return h->fail(KEEP_EINVAL, "eval_roc: scalars_out is null or not 8-byte aligned");
+    const int given = (thresholds_out != nullptr) + (fps_out != nullptr) + (tps_out != nullptr) + (kept_out != nullptr);
+    if (given != 0 && given != 4) return h->fail(KEEP_EINVAL, "eval_roc: the four curve outputs go together: all or none");
+    if (((uintptr_t)scores & 3) || ((uintptr_t)thresholds_out & 3) || ((uintptr_t)fps_out & 3) || ((uintptr_t)tps_out & 3))
+        return h->fail(KEEP_EINVAL, "eval_roc: scores / thresholds_out / fps_out / tps_out not 4-byte aligned");
+    KEEP_ON_DEVICE(h);
+    int rc = ensure_arena(h, eval_roc_workspace_bytes(N, given == 0));
+    if (rc) return rc;
+    launch_eval_roc(scores, labels, N, (unsigned char*)h->arena, scalars_out, thresholds_out, fps_out, tps_out, kept_out, (hipStream_t)stream);
+    return check_launch(h, "eval_roc");
+}
+
+int keep_eval_mask_counts(keep_handle* h, const unsigned char* a, const unsigned char* b, const unsigned char* within, int64_t H, int64_t W,
+                          int64_t* counts_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!a || !b) return h->fail(KEEP_EINVAL, "eval_mask_counts: a mask is null");
+    if (!regions_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "eval_mask_counts: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (!counts_out || ((uintptr_t)counts_out & 7)) return h->fail(KEEP_EINVAL, "eval_mask_counts: counts_out is null or not 8-byte aligned");
+    KEEP_ON_DEVICE(h);
+    launch_eval_mask_counts(a, b, within, H * W, counts_out, (hipStream_t)stream);
+    return check_launch(h, "eval_mask_counts");
+}
+
+int keep_eval_raster_hist(keep_handle* h, const int64_t* acc, const unsigned char* truth, const unsigned char* within, int64_t H, int64_t W,
+                          int64_t* hist_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "eval_raster_hist: acc is null or not 8-byte aligned");
+    if (!truth) return h->fail(KEEP_EINVAL, "eval_raster_hist: truth is null");
+    if (!regions_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "eval_raster_hist: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (!hist_out || ((uintptr_t)hist_out & 7)) return h->fail(KEEP_EINVAL, "eval_raster_hist: hist_out is null or not 8-byte aligned");
+    KEEP_ON_DEVICE(h);
+    launch_eval_raster_hist(acc, truth, within, H * W, hist_out, (hipStream_t)stream);
+    return check_launch(h, "eval_raster_hist");
+}
+
 int keep_token_error(keep_handle* h, void* stream) {
     if (!h) return KEEP_EINVAL;
     KEEP_ON_DEVICE(h);

@@ -1400,6 +1400,136 @@ class KEEPModel:
                                                                    patch, _ptr(out), _stream(self._device)), "mask_tile_counts")
         return out
 
+    # ------------------------------------------------------------------ segmentation evaluation
+    def _mask_u8(self, m) -> torch.Tensor:
+        """A checked mask (numpy or torch, bool or uint8, host or device) -> contiguous uint8 on the device."""
+        m = (torch.from_numpy(np.ascontiguousarray(m)) if isinstance(m, np.ndarray) else m).to(self._device).contiguous()
+        return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+    @torch.no_grad()
+    def tile_roc(self, scores, labels, curve: bool = True):
+        """The tile-level ROC of ``eval_seg_auc`` (``segment_utils.py:105-119``) on the device ->
+        ``keep_amd.evaluation.RocResult``: ``auc`` (what ``roc_auc_score`` computes, exact and rounded once), ``best_threshold`` (the
+        reference's ``thresholds[np.argmax(tpr - fpr)]``, ``inf`` when no threshold beats chance) and, with ``curve=True``, the whole
+        curve as device tensors.  ``scores``: floating point [N], rounded to float32; ``labels``: bool / integers [N], non-zero =
+        positive; host or device, numpy or torch; ``1 <= N <= 2^24 - 1``.  A NaN score removes its tile.  One class only (or no tile
+        left) is the ``ValueError`` scikit-learn raises.  One read of eight scalars (the one host synchronisation; with ``curve=True``
+        it also sizes the curve); equal to ``keep_amd.evaluation.roc_numpy`` exactly."""
+        import struct
+        from .evaluation import RocResult, check_roc_args
+        s = scores if isinstance(scores, torch.Tensor) else torch.as_tensor(np.asarray(scores))
+        l = labels if isinstance(labels, torch.Tensor) else torch.as_tensor(np.asarray(labels))
+        N = check_roc_args(s, l)
+        self._ready_device()
+        s = s.to(self._device, torch.float32).contiguous()
+        l = (l.to(self._device) != 0).to(torch.uint8).contiguous()
+        scalars = torch.empty((8,), dtype=torch.int64, device=self._device)
+        outs = [torch.empty((N,), dtype=dt, device=self._device) if curve else None for dt in (torch.float32, torch.int32, torch.int32, torch.uint8)]
+        _lib.check(self._handle, _lib.load().keep_eval_roc(self._handle, _ptr(s), _ptr(l), N, _ptr(scalars), _ptr(outs[0]), _ptr(outs[1]),
+                                                           _ptr(outs[2]), _ptr(outs[3]), _stream(self._device)), "eval_roc")
+        n, P, Nn, u2, K, _, bits, _ = scalars.tolist()
+        best = struct.unpack("<f", struct.pack("<I", bits & 0xFFFFFFFF))[0]
+        if not curve:
+            return RocResult(n, P, Nn, u2, best)
+        return RocResult(n, P, Nn, u2, best, outs[0][:K], outs[1][:K], outs[2][:K], outs[3][:K].to(torch.bool))
+
+    @torch.no_grad()
+    def mask_overlap(self, a, b, within=None):
+        """The overlap counts of two masks on the device, the counting of ``eval_seg_coarse`` (``segment_utils.py:130-151``) ->
+        ``keep_amd.evaluation.MaskOverlap`` (``.dice``, ``.iou``, ``.confusion`` follow in Python integers).  ``a``, ``b`` and the
+        optional ``within``: bool / uint8 ``[h,w]`` of one shape, numpy or torch, host or device, or ``TissueMask``s; non-zero = set;
+        only the pixels where ``within`` is set are considered.  One read of four integers; equal to
+        ``keep_amd.evaluation.mask_counts_numpy`` exactly."""
+        from .evaluation import MaskOverlap, check_mask
+        a = check_mask(a, "a")
+        shape = (int(a.shape[0]), int(a.shape[1]))
+        b = check_mask(b, "b", shape)
+        within = None if within is None else check_mask(within, "within", shape)
+        self._ready_device()
+        a, b, within = self._mask_u8(a), self._mask_u8(b), (None if within is None else self._mask_u8(within))
+        out = torch.empty((4,), dtype=torch.int64, device=self._device)
+        _lib.check(self._handle, _lib.load().keep_eval_mask_counts(self._handle, _ptr(a), _ptr(b), _ptr(within), shape[0], shape[1], _ptr(out),
+                                                                   _stream(self._device)), "eval_mask_counts")
+        return MaskOverlap(*out.tolist())
+
+    @torch.no_grad()
+    def raster_hist(self, raster, truth, within=None) -> torch.Tensor:
+        """int64 ``[2, 65537]`` on the device: the raster's pixels (inside ``within``) by truth and by their mean in 16-bit fixed
+        point, the uncovered ones in bin 65536.  Arguments as :meth:`raster_sweep`.  No host synchronisation; equal to
+        ``keep_amd.evaluation.raster_hist_numpy`` exactly."""
+        from .evaluation import HIST_BINS, check_mask, check_same_geometry
+        from .heatmap import TileRaster
+        if not isinstance(raster, TileRaster):
+            raise ValueError(f"raster must be a TileRaster, got {type(raster).__name__}")
+        check_same_geometry(raster, truth, "truth")
+        check_same_geometry(raster, within, "within")
+        truth = check_mask(truth, "truth", raster.shape)
+        within = None if within is None else check_mask(within, "within", raster.shape)
+        self._ready_device()
+        if raster.acc.device != self._device:
+            raise ValueError(f"the raster lives on {raster.acc.device}, this engine on {self._device}")
+        truth, within = self._mask_u8(truth), (None if within is None else self._mask_u8(within))
+        hist = torch.empty((2, HIST_BINS), dtype=torch.int64, device=self._device)
+        h, w = raster.shape
+        _lib.check(self._handle, _lib.load().keep_eval_raster_hist(self._handle, _ptr(raster.acc), _ptr(truth), _ptr(within), h, w, _ptr(hist),
+                                                                   _stream(self._device)), "eval_raster_hist")
+        return hist
+
+    @torch.no_grad()
+    def raster_sweep(self, raster, truth, within=None):
+        """Every threshold of a heatmap against a truth mask at once -> ``keep_amd.evaluation.RasterSweep``:
+        TP / FP / FN and Dice of "mean > t" for the 65536 thresholds of the raster's fixed point, the threshold of the best Dice and
+        the pixel-level AUROC.  ``raster``: a ``TileRaster`` (``tile_raster`` / ``wsi.segment_heatmap``); ``truth`` / ``within``: bool /
+        uint8 ``[h,w]`` of the raster's shape or ``TissueMask``s of its geometry (``fill_polygons`` / ``annotation_mask`` at the raster's
+        downsample make one).  One histogram kernel, then cumulative sums with torch on the device."""
+        from .evaluation import sweep_from_hist
+        return sweep_from_hist(self.raster_hist(raster, truth, within))
+
+    @torch.no_grad()
+    def annotation_tile_labels(self, polys_or_mask, coords, patch_size: int, order=None, rule: str = "union",
+                               max_band_bytes: int = 1 << 28) -> torch.Tensor:
+        """A label per tile from the ground truth, by the reference's rule (``segment_utils.py:99-103``): 1 iff more than half of the
+        tile's level-0 pixels are set -> uint8 ``[N]`` on the device.  ``coords``: integers ``[N,2]``, level-0 top-left ``(x, y)``.
+
+        A ``PolygonSet`` is filled at downsample 1 -- a level-0 mask of a whole slide would not fit, so in horizontal bands of whole
+        tile rows over the tiles' x extent, at most ``max_band_bytes`` of mask each (``keep_amd.evaluation.plan_label_bands``), with
+        :meth:`mask_tile_counts` per band; no tile is clipped by a band, so the labels do not depend on the banding.  ``order``
+        (``keep_amd.annotation.CAMELYON16_ORDER``) paints group after group as :meth:`annotation_mask` does.  A ``TissueMask`` of
+        downsample d (origin 0) gives ``2 c1 d^2 > patch_size^2`` with c1 the set mask pixels whose centre lies in the tile: the
+        reference's rule at d = 1; a bare bool / uint8 ``[h,w]`` array is a level-0 mask (d = 1).  Pixels outside a mask are not set."""
+        from .annotation import PolygonSet, check_fill_args, check_tile_args
+        from .evaluation import plan_label_bands
+        from .region import TissueMask
+        if not isinstance(polys_or_mask, PolygonSet):
+            mask = polys_or_mask if isinstance(polys_or_mask, TissueMask) else TissueMask(polys_or_mask, 1)
+            if order is not None:
+                raise ValueError("order= paints the groups of a PolygonSet: a mask has none")
+            counts = self.mask_tile_counts(mask, coords, patch_size)
+            return (2 * counts[:, 1].to(torch.int64) * mask.downsample ** 2 > int(patch_size) ** 2).to(torch.uint8)
+        polys = polys_or_mask
+        _, c, patch, _, _ = check_tile_args(np.zeros((1, 1), np.uint8), coords, patch_size, 1)
+        steps = [(None, 1)] if order is None else [(tuple([g] if isinstance(g, str) else g), int(v)) for g, v in order]
+        if not steps:
+            raise ValueError("order is empty")
+        self._ready_device()
+        c = (torch.from_numpy(np.ascontiguousarray(c)) if isinstance(c, np.ndarray) else c).to(self._device, torch.int64).contiguous()
+        labels = torch.zeros((int(c.shape[0]),), dtype=torch.uint8, device=self._device)
+        if c.shape[0] == 0:
+            return labels
+        x0, y_all = int(c[:, 0].min()), c[:, 1]
+        x1 = int(c[:, 0].max()) + patch
+        sets = [(polys if g is None else polys.select(groups=g), v) for g, v in steps]
+        for y_first, y_last in plan_label_bands(y_all.cpu().numpy(), x0, x1, patch, max_band_bytes):
+            shape, origin = (y_last + patch - y_first, x1 - x0), (x0, y_first)
+            check_fill_args(1, shape, origin, rule, 1)
+            mask = None
+            for sel, v in sets:
+                mask = self.fill_polygons(sel, 1, shape, origin, rule, v, mask)
+            rows = torch.nonzero((y_all >= y_first) & (y_all <= y_last)).squeeze(1)
+            counts = self.mask_tile_counts(mask, c[rows], patch, 1, origin)
+            labels[rows] = (2 * counts[:, 1].to(torch.int64) > patch * patch).to(torch.uint8)
+        return labels
+
     @staticmethod
     def _cells_to_coords(cells: torch.Tensor, origin, coord_scale: int) -> torch.Tensor:
         o = torch.tensor(origin, dtype=torch.int64, device=cells.device)

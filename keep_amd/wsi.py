@@ -320,14 +320,113 @@ def zero_shot_segment_probs(classifier, tile_features, tile_coords, patch_size=2
 
 
 def zero_shot_segment(classifier, tile_features, tile_coords, mask_path, patch_size=224, overlap=True, model=None):
-    """segment_utils.py:44-60.  The probability map is computed here; the AUC / Dice evaluation against an openslide mask that
-    follows in the reference (``eval_seg_auc`` / ``eval_seg_coarse``, :91-152) is out of scope (needs
-    openslide and real WSI masks) -- pass ``mask_path=None`` to get the map, which is what those two functions consume."""
+    """segment_utils.py:44-60.  ``mask_path=None`` returns the probability map.  With an annotation -- a ``PolygonSet``, a pair
+    ``(PolygonSet, order)``, a ``TissueMask``, or a path ending in ``.xml`` (ASAP) / ``.geojson`` / ``.json`` -- it goes on as the
+    reference does: ``(auc, dice)`` from :func:`eval_seg_auc` and :func:`eval_seg_coarse` at the best threshold of the ROC
+    (DESIGN.md section 17).  Any other path (a slide file: the mask pyramid of the reference needs openslide) is not read."""
+    from .evaluation import resolve_annotation
     probs_all_refined = zero_shot_segment_probs(classifier, tile_features, tile_coords, patch_size, overlap, model=model)
     if mask_path is None:
         return probs_all_refined
-    raise NotImplementedError("AUC / Dice against an openslide mask (segment_utils.py:91-152) is outside the hot path; "
-                              "call with mask_path=None and feed the returned map to the reference's eval_seg_auc / eval_seg_coarse")
+    truth = resolve_annotation(mask_path)
+    if truth is None:
+        raise NotImplementedError("AUC / Dice against an openslide mask (segment_utils.py:91-152) is outside the hot path; "
+                                  "call with mask_path=None and feed the returned map to the reference's eval_seg_auc / eval_seg_coarse")
+    m = _engine(model, tile_features, classifier)
+    auc, best_thd = eval_seg_auc(probs_all_refined, truth, patch_size=patch_size, model=m)
+    dice = eval_seg_coarse(probs_all_refined, truth, patch_size=patch_size, thd=best_thd, model=m)
+    return auc, dice
+
+
+# ------------------------------------------------------------------------------------------------ evaluation (DESIGN.md section 17)
+def _tile_probs(probs) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``{"x_y": p}`` or a ``(coords, p)`` pair, host or device -> (coords int64 [N,2], p [N]) as torch tensors where they were."""
+    if isinstance(probs, Mapping):
+        return (torch.tensor([str2cood(k) for k in probs], dtype=torch.int64).reshape(-1, 2),
+                torch.tensor(list(probs.values()), dtype=torch.float64))
+    coords, p = probs
+    coords = torch.as_tensor(np.asarray(coords)) if not isinstance(coords, torch.Tensor) else coords
+    p = torch.as_tensor(np.asarray(p)) if not isinstance(p, torch.Tensor) else p
+    return coords.reshape(-1, 2), p.reshape(-1)
+
+
+def _annotation(mask_path):
+    """-> (PolygonSet | TissueMask, order), already resolved pairs pass through."""
+    from .annotation import PolygonSet
+    from .evaluation import resolve_annotation
+    from .region import TissueMask
+    if isinstance(mask_path, tuple) and len(mask_path) == 2 and isinstance(mask_path[0], (PolygonSet, TissueMask)) and \
+            not isinstance(mask_path[1], (PolygonSet, TissueMask)):
+        return mask_path
+    truth = resolve_annotation(mask_path)
+    if truth is None:
+        raise NotImplementedError(f"mask_path {mask_path!r}: a PolygonSet, (PolygonSet, order), a TissueMask, or a path ending in .xml / "
+                                  ".geojson / .json (a mask pyramid needs openslide, which this package does not read)")
+    return truth
+
+
+def eval_seg_auc(probs_all_refined, mask_path, patch_size=224, save_path='./', model=None, rule="union", max_band_bytes=1 << 28):
+    """segment_utils.py:91-119 on the device -> ``(auc, best_threshold)`` as Python floats: a label per tile from the ground truth
+    (``KEEPModel.annotation_tile_labels``: more than half of the tile's level-0 pixels set), the tile-level AUROC and
+    ``thresholds[np.argmax(tpr - fpr)]`` (``KEEPModel.tile_roc``).  ``probs_all_refined``: the dict of
+    ``zero_shot_segment(mask_path=None)`` or a ``(coords, p)`` pair, host or device (the scores are taken as float32, which the
+    dict's values are).  ``mask_path``: see :func:`zero_shot_segment`.  ``save_path`` is unused, as in the reference."""
+    truth, order = _annotation(mask_path)
+    coords, p = _tile_probs(probs_all_refined)
+    m = _engine(model, p, coords)
+    labels = m.annotation_tile_labels(truth, coords, patch_size, order=order, rule=rule, max_band_bytes=max_band_bytes)
+    roc = m.tile_roc(p.to(torch.float32), labels, curve=False)
+    return roc.auc, roc.best_threshold
+
+
+def _truth_mask16(m: KEEPModel, truth, order, shape, rule: str, d: int = 16) -> torch.Tensor:
+    from .region import TissueMask
+    if isinstance(truth, TissueMask):
+        if truth.downsample != d or tuple(truth.mask.shape) != tuple(shape):
+            raise ValueError(f"the truth mask has downsample {truth.downsample} and shape {tuple(truth.mask.shape)}, the evaluation runs at "
+                             f"{d} and {tuple(shape)}")
+        return truth.mask
+    return m.annotation_mask(truth, d, shape, order=order, rule=rule).mask
+
+
+def eval_seg_coarse(probs_all_refined, mask_path, patch_size=224, thd=0.5, model=None, shape=None, rule="union"):
+    """segment_utils.py:122-152 on the device -> Dice (``2 both / (truth + pred)`` in Python integers; 1 when both masks are empty).
+    At downsample 16, the reference's level: the prediction is :func:`segment_pred_mask` (255 where a tile with ``p > thd`` covers the
+    pixel), the truth is the annotation filled at pixel centres (``KEEPModel.annotation_mask``; no parity with a pyramid file's own
+    down-sampling is claimed) or a ``TissueMask`` of downsample 16.  ``shape``: the masks' ``(h, w)``; by default the smallest that
+    covers every tile and every vertex, or the ``TissueMask``'s own."""
+    from .evaluation import default_eval_shape
+    from .region import TissueMask
+    truth, order = _annotation(mask_path)
+    coords, p = _tile_probs(probs_all_refined)
+    m = _engine(model, p, coords)
+    if shape is None:
+        shape = tuple(truth.mask.shape) if isinstance(truth, TissueMask) else default_eval_shape(coords, truth, patch_size, 16)
+    pred = segment_pred_mask((coords, p), thd, 16, shape, patch_size, model=m)
+    return m.mask_overlap(_truth_mask16(m, truth, order, shape, rule), pred).dice
+
+
+def segment_evaluate(classifier, tile_features, tile_coords, annotation, patch_size=224, overlap=True, shape=None, sweep=False, rule="union",
+                     model=None):
+    """:func:`zero_shot_segment` with an annotation, without the dict and with the whole results: ``(RocResult, MaskOverlap)`` of the
+    tile ROC and of the level-16 masks at its best threshold, and with ``sweep=True`` a third, the ``RasterSweep`` of the
+    refined probabilities' raster (what :func:`segment_heatmap` makes at downsample 16) against the same truth mask."""
+    from .evaluation import default_eval_shape
+    from .region import TissueMask
+    truth, order = _annotation(annotation)
+    m = _engine(model, tile_features, classifier)
+    if isinstance(tile_coords, torch.Tensor):
+        tile_coords = tile_coords.cpu()                             # refine checks the coordinate range on the host
+    coords, mean, _ = refine(_probs(m, classifier, tile_features), tile_coords, patch_size, overlap, model=m)
+    p = mean[:, 1].contiguous()
+    roc = m.tile_roc(p, m.annotation_tile_labels(truth, coords, patch_size, order=order, rule=rule))
+    if shape is None:
+        shape = tuple(truth.mask.shape) if isinstance(truth, TissueMask) else default_eval_shape(coords, truth, patch_size, 16)
+    mask16 = _truth_mask16(m, truth, order, shape, rule)
+    ov = m.mask_overlap(mask16, segment_pred_mask((coords, p), roc.best_threshold, 16, shape, patch_size, model=m))
+    if not sweep:
+        return roc, ov
+    return roc, ov, m.raster_sweep(m.tile_raster(coords, p, patch_size, 16, shape), mask16)
 
 
 # ------------------------------------------------------------------------------------------------ heatmap (DESIGN.md section 12)
