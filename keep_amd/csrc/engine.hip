@@ -1,27 +1,16 @@
-// Host side of libkeep_hip: handle, weight store (release state_dict key layout), workspace arena,
-// tower orchestration and the extern "C" boundary declared in include/keep_hip.h.
+// Host side of libkeep_hip: weight store (release state_dict key layout), workspace arena, tower orchestration and the encoder's
+// part of the extern "C" boundary declared in include/keep_hip.h.  The handle itself is handle.h; the slide-geometry entry
+// points (patch grid, tissue mask, heatmap, sort / rank, regions, outlines, polygon fill, evaluation) are slide_api.hip.
 //
 // Orchestration mirrors the reference's call order, not its code:
 //   encode_image  quick_start/keep_inference.py:54-58  -> timm VisionTransformer.forward
 //   encode_text   quick_start/keep_inference.py:60-62  -> HF BertModel.forward           
-#include "common.h"
+#include "handle.h"
 #include "quant4.h"
-#include "../../include/keep_hip.h"
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <map>
-#include <string>
-#include <vector>
-
-#define HIPCHK(h, expr)                                                                      \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess) return (h)->fail(KEEP_EHIP, "%s: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
 
 namespace {
 
@@ -29,255 +18,10 @@ namespace {
 // and replayed as one graph launch: ~90 dependent kernels of 10-25 us whose host-side issue (1.4 ms) otherwise runs next to them
 constexpr int64_t TXT_GRAPH_ROWS = 4096;
 
-// Every entry point runs on the handle's device and puts the caller's current device back (torch keeps its own notion of
-// the current device per thread; changing it behind its back redirects the caller's next allocation).
-struct DevGuard {
-    int prev = -1; bool ok = true;
-    explicit DevGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess; else prev = -1;
-    }
-    ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-#define KEEP_ON_DEVICE(h) DevGuard _guard((h)->device); if (!_guard.ok) return (h)->fail(KEEP_EHIP, "hipSetDevice(%d) failed", (h)->device)
-
-struct WTensor {
-    std::vector<int64_t> shape;
-    int64_t numel = 0;
-    float* f32 = nullptr;     // kept for vectors / embeddings / head / pooler
-    f16* hi = nullptr;        // GEMM weights: fp16 planes
-    f16* lo = nullptr;
-    unsigned char* q = nullptr;   // MX-fp4 side planes of (hi, lo) and their scales (quant4.h); K % 128 == 0 weights only
-    unsigned char* sc = nullptr;
-    float prescale = 1.f;     // the planes hold prescale * W (a power of two; proj / fc2 of the image tower only): folded back through LayerScale and bias at finalize
-};
-
-enum Tag {
-    T_VIT_IM2COL, T_VIT_PATCH, T_VIT_LN, T_VIT_QKV, T_VIT_ATTN, T_VIT_PROJ, T_VIT_FC1, T_VIT_FC2, T_VIT_HEAD,
-    T_TXT_EMBED, T_TXT_LN, T_TXT_QKV, T_TXT_ATTN, T_TXT_OUT, T_TXT_FFN1, T_TXT_FFN2, T_TXT_POOL, T_SIM,
-    // image-tower launches that are NOT the plain single-pass kernel of their operator: split products / compensated (MX-fp4) products of the
-    // blocks the precision setting names ("x" = extra passes), and the CLS-rows-only operators of the last block ("tail": small-M kernels).
-    // The plain tags above then time one kernel instantiation each (bench.py's roofline block needs a per-kernel figure).
-    T_VIT_QKV_X, T_VIT_ATTN_X, T_VIT_PROJ_X, T_VIT_FC1_X, T_VIT_FC2_X, T_VIT_TAIL, T_COUNT
-};
 const char* kTagNames[T_COUNT] = {
     "vit.im2col", "vit.patch", "vit.ln", "vit.qkv", "vit.attn", "vit.proj", "vit.fc1", "vit.fc2", "vit.head",
     "text.embed", "text.ln", "text.qkv", "text.attn", "text.out", "text.ffn1", "text.ffn2", "text.pool", "sim",
     "vit.qkv.x", "vit.attn.x", "vit.proj.x", "vit.fc1.x", "vit.fc2.x", "vit.tail"};
-
-struct VitBlock {
-    const float *n1w, *n1b, *n2w, *n2b, *qkv_b, *proj_b, *fc1_b, *fc2_b, *ls1, *ls2;
-    const WTensor *qkv, *proj, *fc1, *fc2;
-};
-struct BertLayer {
-    WTensor qkv;                 // fused [3H, H]
-    float* qkv_b = nullptr;      // fused [3H]
-    const float *o_b, *ln1w, *ln1b, *i_b, *d_b, *ln2w, *ln2b;
-    const WTensor *o, *i, *d;
-};
-
-}  // namespace
-
-struct keep_handle {
-    int device = 0;
-    std::string err;
-    std::string load_warnings;   // '\n'-separated notes of keep_load_tensor calls (a weight the fp16 planes resolve poorly); read and cleared by keep_load_warnings
-    std::map<std::string, WTensor> w;
-    bool finalized = false;
-
-    // dims (filled at finalize)
-    int vit_depth = 0, vit_D = 0, vit_heads = 0, vit_F = 0, proj_dim = 0;
-    int bert_layers = 0, bert_H = 0, bert_heads = 0, bert_F = 0, bert_vocab = 0, bert_maxpos = 0, bert_types = 0;
-    std::vector<VitBlock> vblocks;
-    std::vector<BertLayer> blayers;
-    std::vector<float*> owned_vecs;   // LayerScale / bias vectors re-derived for pre-scaled weights (finalize_vit)
-
-    // options
-    KeepTune tune;               // kernel selection (travels in the launch parameter blocks; nothing is process-wide)
-    int precision = KEEP_PREC_COMP;
-    int strict_blocks = 0;       // first n blocks / layers as full hi/lo split products (any mode)
-    // The prefix shorthands (state of the last keep_set_option; they only take effect once one of them is set -- see plan_default below)
-    int comp_full_blocks = 1;    // KEEP_PREC_COMP: first n ViT blocks run qkv / attention / proj as split products as well
-    int comp_mlp_blocks = 8;     // KEEP_PREC_COMP: first n ViT blocks run fc1 / fc2 as compensated (fp16 + MX-fp4) products
-    int fused_screening = 1;     // keep_prompt_scores: 1 fused compensated GEMM (default) | 2 fused 3-pass split GEMM | 0 logits through HBM (any C)
-    int comp_min_tiles = 32;     // lanes with fewer tiles take the split product where a compensated one is asked for (small-M kernels)
-    int comp_qkv = 0;            // 1: KEEP_PREC_COMP, blocks < comp_full_blocks: the qkv GEMM as a compensated product (x1.5) instead of a split one (x3);
-                                 // q / k / v still stored as hi + lo planes, attention still a split product.  Measured (round 3): +0.9 % at equal settings,
-                                 // but block 0's qkv is where the error budget is tightest (the 3 % of the rounding variance the fp4 terms leave is
-                                 // amplified by all 24 blocks): calibrate() then needs 10 compensated MLP blocks instead of 6 -- a net loss.  Off.
-    int comp_qkv_from = 1 << 20; // the same for the split-attention blocks with index >= this only (block 0 keeps its three-pass qkv)
-    // The per-block plan of KEEP_PREC_COMP (keep_set_block_precision; the four options above are prefix shorthands that rewrite it):
-    //   attn_mode[i]  attention side of block i: KEEP_ATTN_PLAIN | KEEP_ATTN_SPLIT (qkv, q/k/v storage, attention, proj as split products) |
-    //                 KEEP_ATTN_SPLIT_COMPQKV (the same with the qkv GEMM as a compensated product) | KEEP_ATTN_COMPQKV (compensated qkv only) |
-    //                 KEEP_ATTN_PROJ_CLS (plain for every row + the CLS rows' proj again as a split product on their fp32-grade attention output) |
-    //                 KEEP_ATTN_COMPQKV_PROJ_CLS (both of the last two)
-    //   mlp_mode[i]   fc1 / fc2 of block i: KEEP_MLP_PLAIN | KEEP_MLP_SPLIT | KEEP_MLP_COMP (both MX-fp4 correction terms) | KEEP_MLP_COMP_W (the W_lo term only) |
-    //                 KEEP_MLP_CLS (plain for every row + the CLS rows again as split products)
-    // Which block gets what is a measured, per-checkpoint decision (tools/precision_budget.py, KEEPModel.calibrate).
-    static constexpr int MAX_BLOCKS = 64;
-    unsigned char attn_mode[MAX_BLOCKS] = {}, mlp_mode[MAX_BLOCKS] = {};
-    bool plan_custom = false;    // keep_set_block_precision was called since the last prefix option
-    void plan_from_prefix() {
-        for (int i = 0; i < MAX_BLOCKS; ++i) {
-            attn_mode[i] = i < comp_full_blocks ? ((comp_qkv || i >= comp_qkv_from) ? KEEP_ATTN_SPLIT_COMPQKV : KEEP_ATTN_SPLIT) : KEEP_ATTN_PLAIN;
-            mlp_mode[i] = i < comp_mlp_blocks ? KEEP_MLP_COMP : KEEP_MLP_PLAIN;
-        }
-        plan_custom = false;
-    }
-    // The plan a handle starts with (no calibration has seen the weights yet): block 0's attention side as split products with a compensated qkv
-    // and its MLP compensated -- the first block's rounding errors, in EVERY row, are amplified by all the attention layers that follow: 45-48 % of the
-    // all-fp16 error variance on the synthetic checkpoints --, every other block plain with the CLS rows' MLP redone as split products (the pooled
-    // feature is a CLS row).  profiles/r05_precision_budget.md: cosine rms 8.5e-6 on the bench weights, a quarter of what the 1e-4 tolerance allows a
-    // 100 000-tile slide, 3 % slower than what KEEPModel.calibrate picks for them.
-    void plan_default() {
-        for (int i = 0; i < MAX_BLOCKS; ++i) { attn_mode[i] = KEEP_ATTN_PLAIN; mlp_mode[i] = KEEP_MLP_CLS; }
-        attn_mode[0] = KEEP_ATTN_SPLIT_COMPQKV; mlp_mode[0] = KEEP_MLP_COMP;
-        plan_custom = false;
-    }
-    keep_handle() { plan_default(); }
-    // keep_classify: tiles whose top-2 cosine margin is below this are re-encoded in KEEP_PREC_STRICT before their label is taken.
-    // Default = 2 x the north-star tolerance (both cosines of a pair can move by 1e-4 in opposite directions) + 25 %.
-    float label_margin = 2.5e-4f;
-    char* cls_buf = nullptr; size_t cls_bytes = 0;     // keep_classify scratch (features, similarity, flags, staged tiles): outside the arena, which the encodes carve
-    int max_tiles = 256;
-    int max_prompts = 64;
-    int cls_tail = 1;            // last ViT block: proj / MLP on the CLS rows only (exact; 0 = evaluate every token)
-    // Mean-input compensation of the weight-rounding error (keep_calibrate_bias).  A plain fp16 GEMM computes A_hi W_hi^T: the W_lo A_hi term it drops has
-    // a part that is the SAME for every row -- W_lo a_mean, a_mean = the mean input row of that GEMM (GELU outputs are positive, LayerNorm outputs carry their
-    // bias, attention outputs are averages) -- which no amount of averaging over tiles removes.  It is a constant vector per GEMM: folded into the bias the plain
-    // launches use.  cal[i].sum[site]: column sums of the site's input over the calibration tiles; cal[i].bias[site]: bias + W_lo a_mean.
-    struct SiteCal { float* sum[4] = {nullptr, nullptr, nullptr, nullptr}; float* bias[4] = {nullptr, nullptr, nullptr, nullptr}; double rows[4] = {0, 0, 0, 0}; };
-    std::vector<SiteCal> cal;    // per ViT block; sites: 0 qkv, 1 proj, 2 fc1, 3 fc2
-    bool capture = false;        // the running encode accumulates cal[i].sum
-    bool bias_ready = false;     // cal[i].bias hold corrected biases for the loaded weights
-    int cal_cls_tail = 1;        // cls_tail at the time of the calibration (switching it afterwards invalidates the last block's averages)
-    int bias_correction = 1;     // plain launches use them (0: the checkpoint's own biases)
-    void free_cal() {
-        for (auto& c : cal) for (int k = 0; k < 4; ++k) { if (c.sum[k]) (void)hipFree(c.sum[k]); if (c.bias[k]) (void)hipFree(c.bias[k]); }
-        cal.clear(); bias_ready = false;
-    }
-    // Patch grids other than 14 x 14 (keep_encode_image_hw): the position table resampled to each grid (timm resample_abs_pos_embed), fp32
-    // [gh gw + 1][D] on the device, built outside any graph capture on first use; at most POS_CACHE grids, the oldest dropped first (with
-    // the captured graphs, which bake its address in); dropped whenever the image tower's weights are (re)finalised or pos_embed is reloaded.
-    struct PosSlot { int gh, gw; float* buf; };
-    static constexpr int POS_CACHE = 8;
-    std::vector<PosSlot> pos_cache;
-    void drop_pos_cache() {
-        if (pos_cache.empty()) return;
-        (void)hipDeviceSynchronize();
-        for (auto& e : pos_cache) (void)hipFree(e.buf);
-        pos_cache.clear();
-        ++opt_epoch;
-    }
-    // KEEP_PREC_COMP at grids other than 14 x 14: the per-block plan is calibrated on 197-token tiles.  Measured against strict on the bench weights
-    // (tools/grid_precision.py, 2 000 tiles per family) it stays at the 224 figure from 257 to 1025 tokens (worst 6.7e-5) and gets
-    // worse below 197 (7.1e-5 at 101 tokens, 8.1e-5 at 50).  1 (default): the plan for 197 <= tokens <= 1025, KEEP_PREC_STRICT outside that band;
-    // 0: every grid but 14 x 14 strict; 2: the plan at every grid (measurements only).
-    int grid_plan = 1;
-    bool grid_keeps_plan(int ntok) const { return grid_plan == 2 || (grid_plan == 1 && ntok >= 197 && ntok <= 1025); }
-    int patch_split = 1;         // 0: the patch-embedding GEMM as one fp16 pass (experiments; measured in profiles/r05_patch_embed_plain.txt)
-    // 2128 (default): the plain proj GEMMs of the image tower on the 256x128 / 4-wave / two-workgroups-per-CU kernel (GemmParams.impl_hint) -- proj is the one GEMM whose
-    // tile is 40 % fp32 residual read-modify-write epilogue, and with two workgroups on a CU one's epilogue runs under the other's K loop: -8.5 % on the proj launches,
-    // +0.57 % end to end in a six-round rotated A/B on the round-5 plan (profiles/r05_ab_two_workgroups_per_cu.txt; qkv / fc1 / fc2 on the same kernel lose 1.6-4.3 %:
-    // 1.5 x the operand bytes per FLOP).  0: the persistent 256x256 kernel.  Bit-identical results either way (same K order per output).
-    int proj_impl = 2128;
-    // hipGraph replay of launch-bound calls (one prompt / one tile: ~100 dependent kernels of a few us each)
-    struct GraphSlot { hipGraphExec_t exec; unsigned long long epoch; char* arena; };
-    std::map<std::string, GraphSlot> graphs;
-    int use_graphs = 1;
-    unsigned long long opt_epoch = 0;   // bumped by keep_set_option / keep_finalize_weights: graphs captured under an older epoch are dropped
-    hipStream_t cap_stream = nullptr;
-    int lane_min_tiles = 16;     // a lane is only opened for at least this many tiles (32 tiles: 7.09 -> 6.50 ms as 2 x 16; 16 tiles as 2 x 8 loses)
-    int n_streams = 2;           // concurrent sub-batches inside keep_encode_image (1 = everything on the caller's stream)
-    hipStream_t aux[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
-
-    // workspace arena
-    char* arena = nullptr;
-    size_t arena_bytes = 0;
-    int* err_flag = nullptr;     // device int, sticky: bit 0 out-of-range token ids, bit 1 non-finite output features (fp16 range exceeded), bit 2 (value 4) a tissue-labelling loop hit its cap
-
-    // profiling
-    int prof_mode = 0;           // 0 off, 1 the tags of prof_mask, 2 all
-    unsigned long long prof_mask = 0;
-    struct Rec { hipEvent_t a, b; int tag; };
-    std::vector<Rec> recs;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-    double prof_ms[T_COUNT] = {0};
-    int64_t prof_n[T_COUNT] = {0};
-    double prof_flops[T_COUNT] = {0};      // executed FLOPs (2*M*N*K) of the profiled GEMM launches
-
-    int fail(int code, const char* fmt, ...) {
-        char buf[1024];
-        va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-        err = buf;
-        return code;
-    }
-    // Where the 11 bits of an fp16 operand are not enough (tools/precision_study.py: block 0 alone is 41 % of the cosine error
-    // variance, blocks 0-1 52 %, and outside them the MLP GEMMs carry > 80 %):
-    //   attention side (qkv, q/k/v storage, softmax probabilities, proj) of block i: split product or plain
-    //   MLP (fc1, fc2) of block i: 0 plain | 1 split (three fp16 passes) | 2 compensated (fp16 pass + two MX-fp4 correction terms)
-    int plan_attn(int i) const { return (precision == KEEP_PREC_COMP && i >= 0 && i < MAX_BLOCKS) ? attn_mode[i] : KEEP_ATTN_PLAIN; }
-    // lanes too small for the 256x256 kernel take split products wherever a compensated one is asked for (they run on the small-M / K-sliced kernels)
-    bool vit_attn_split(int i, int lane_tiles = 1 << 20) const {
-        if (precision == KEEP_PREC_STRICT || i < strict_blocks) return true;
-        const int a = plan_attn(i);
-        return a == KEEP_ATTN_SPLIT || a == KEEP_ATTN_SPLIT_COMPQKV || ((a == KEEP_ATTN_COMPQKV || a == KEEP_ATTN_COMPQKV_PROJ_CLS) && !(lane_tiles >= comp_min_tiles && vit_has_q));
-    }
-    bool vit_qkv_comp(int i, int lane_tiles) const {
-        if (precision != KEEP_PREC_COMP || i < strict_blocks || !(lane_tiles >= comp_min_tiles && vit_has_q)) return false;
-        const int a = plan_attn(i);
-        return a == KEEP_ATTN_SPLIT_COMPQKV || a == KEEP_ATTN_COMPQKV || a == KEEP_ATTN_COMPQKV_PROJ_CLS;
-    }
-    // fc1 / fc2 of block i: 0 plain | 1 split (three fp16 passes) | 2 compensated (both MX-fp4 terms) | 3 compensated, W_lo term only | 4 plain + CLS rows split
-    // (lane_tiles == 0: the last block's CLS-rows-only tail, which is the "CLS rows as split products" half on its own)
-    int vit_mlp_mode(int i, int lane_tiles) const {
-        if (precision == KEEP_PREC_STRICT || i < strict_blocks) return KEEP_MLP_SPLIT;
-        if (precision != KEEP_PREC_COMP || i < 0 || i >= MAX_BLOCKS) return KEEP_MLP_PLAIN;
-        const int m = mlp_mode[i];
-        if (m == KEEP_MLP_COMP || m == KEEP_MLP_COMP_W) return (lane_tiles >= comp_min_tiles && vit_has_q) ? m : KEEP_MLP_SPLIT;
-        if (m == KEEP_MLP_CLS) return lane_tiles == 0 ? KEEP_MLP_SPLIT : KEEP_MLP_CLS;
-        return m;
-    }
-    // the text tower is 1 % of a slide's work: in the compensated mode it simply runs split products throughout, at every length BertModel accepts
-    // (T <= 512 = max_position_embeddings; above 256 keys the split attention runs as two key windows of <= 256, merged like an online softmax)
-    bool txt_split(int l, int T) const { (void)T; return precision == KEEP_PREC_STRICT || l < strict_blocks || precision == KEEP_PREC_COMP; }
-    bool any_split() const { return precision != KEEP_PREC_FP16 || strict_blocks > 0; }
-    bool vit_has_q = false;      // every fc1 / fc2 weight has its fp4 side planes (dims % 128 == 0)
-    bool any_comp() const {
-        if (precision != KEEP_PREC_COMP || !vit_has_q) return false;
-        for (int i = 0; i < MAX_BLOCKS && i < (vit_depth ? vit_depth : MAX_BLOCKS); ++i)
-            if (mlp_mode[i] == KEEP_MLP_COMP || mlp_mode[i] == KEEP_MLP_COMP_W || attn_mode[i] == KEEP_ATTN_SPLIT_COMPQKV || attn_mode[i] == KEEP_ATTN_COMPQKV || attn_mode[i] == KEEP_ATTN_COMPQKV_PROJ_CLS) return true;
-        return false;
-    }
-
-    bool prof_on(int tag) const { return prof_mode == 2 || (prof_mode == 1 && ((prof_mask >> tag) & 1ull)); }
-    void prof_add_flops(int tag, double f) { if (prof_on(tag)) prof_flops[tag] += f; }
-    void prof_begin(int tag, hipStream_t s) {
-        if (!prof_on(tag)) return;
-        Rec r; r.tag = tag;
-        if (!pool.empty()) { r.a = pool.back().first; r.b = pool.back().second; pool.pop_back(); }
-        else { hipEventCreate(&r.a); hipEventCreate(&r.b); }
-        hipEventRecord(r.a, s);
-        recs.push_back(r);
-    }
-    void prof_end(int tag, hipStream_t s) {
-        if (!prof_on(tag)) return;
-        hipEventRecord(recs.back().b, s);
-    }
-    void prof_collect() {
-        for (auto& r : recs) {
-            hipEventSynchronize(r.b);
-            float ms = 0.f;
-            hipEventElapsedTime(&ms, r.a, r.b);
-            prof_ms[r.tag] += ms; prof_n[r.tag] += 1;
-            pool.push_back({r.a, r.b});
-        }
-        recs.clear();
-    }
-};
-
-namespace {
 
 struct Scope {     // RAII profile bracket
     keep_handle* h; int tag; hipStream_t s;
@@ -388,6 +132,7 @@ TxtWs carve_txt(const keep_handle* h, char* arena, int64_t Pc, int64_t T, bool s
     }
     return w;
 }
+}  // namespace
 
 int ensure_arena(keep_handle* h, size_t bytes) {
     if (bytes <= h->arena_bytes) return KEEP_OK;
@@ -405,6 +150,7 @@ int check_launch(keep_handle* h, const char* what) {
     return KEEP_OK;
 }
 
+namespace {
 
 void drop_graphs(keep_handle* h) {
     for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second.exec);
@@ -1633,457 +1379,6 @@ int keep_resize_crop_u8(keep_handle* h, const unsigned char* src, int64_t B, int
     launch_resize_crop_u8(src, (int)B, (int)H, (int)W, xbounds, xweights, xksize, (int)crop_left, (int)size, ybounds, yweights, yksize,
                           (int)crop_top, (int)size, (unsigned char*)h->arena, out, (hipStream_t)stream);
     return check_launch(h, "resize_crop_u8");
-}
-
-static int region_view_check(keep_handle* h, const unsigned char* region, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
-                             int64_t patch) {
-    if (!region || H < 1 || W < 1) return h->fail(KEEP_EINVAL, "region: null pointer or empty shape %lldx%lld", (long long)H, (long long)W);
-    if (pix_stride != 3 && pix_stride != 4) return h->fail(KEEP_EINVAL, "region: pixel stride %d (3 = RGB, 4 = RGBA)", pix_stride);
-    if (W > INT32_MAX || H > INT32_MAX || row_stride_bytes < W * pix_stride)
-        return h->fail(KEEP_EINVAL, "region: row stride %lld bytes < width %lld x pixel stride %d (or a side >= 2^31)", (long long)row_stride_bytes,
-                       (long long)W, pix_stride);
-    if (patch < 16 || patch > REGION_MAX_PATCH) return h->fail(KEEP_EINVAL, "region: patch %lld outside [16, %d]", (long long)patch, REGION_MAX_PATCH);
-    return KEEP_OK;
-}
-
-int keep_region_grid(keep_handle* h, const unsigned char* region, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride, int64_t patch,
-                     int64_t step, int sat_min, int64_t min_pixels, int32_t* cell_xy_out, int64_t* n_out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    int rc = region_view_check(h, region, H, W, row_stride_bytes, pix_stride, patch);
-    if (rc) return rc;
-    if (step < 1) return h->fail(KEEP_EINVAL, "region_grid: step %lld < 1", (long long)step);
-    if (sat_min < 0 || sat_min > 255) return h->fail(KEEP_EINVAL, "region_grid: sat_min %d outside [0, 255]", sat_min);
-    if (min_pixels < 0 || min_pixels > patch * patch)
-        return h->fail(KEEP_EINVAL, "region_grid: min_pixels %lld outside [0, patch^2 = %lld]", (long long)min_pixels, (long long)(patch * patch));
-    if (!cell_xy_out || !n_out) return h->fail(KEEP_EINVAL, "region_grid: null output");
-    const int64_t gx = W >= patch ? (W - patch) / step + 1 : 0, gy = H >= patch ? (H - patch) / step + 1 : 0;
-    const int64_t ncells = gx * gy;
-    if (ncells > INT32_MAX) return h->fail(KEEP_EINVAL, "region_grid: %lld cells (limit 2^31 - 1)", (long long)ncells);
-    KEEP_ON_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    if (ncells == 0) {
-        HIPCHK(h, hipMemsetAsync(n_out, 0, sizeof(int64_t), s));
-        return KEEP_OK;
-    }
-    const int64_t nb = (ncells + REGION_GRID_CHUNK - 1) / REGION_GRID_CHUNK;
-    const size_t b_keep = align_up((size_t)ncells), b_counts = align_up((size_t)nb * 4);
-    rc = ensure_arena(h, b_keep + 2 * b_counts);
-    if (rc) return rc;
-    launch_region_grid(region, row_stride_bytes, pix_stride, (int)gx, ncells, (int)patch, (int)step, sat_min, (int)min_pixels,
-                       (unsigned char*)h->arena, (int*)(h->arena + b_keep), (int*)(h->arena + b_keep + b_counts), cell_xy_out, n_out, s);
-    return check_launch(h, "region_grid");
-}
-
-int keep_region_patches_u8(keep_handle* h, const unsigned char* region, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
-                           const int32_t* cell_xy, int64_t B, int64_t patch, const int32_t* xbounds, const int32_t* xweights, int xksize,
-                           const int32_t* ybounds, const int32_t* yweights, int yksize, unsigned char* out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    int rc = region_view_check(h, region, H, W, row_stride_bytes, pix_stride, patch);
-    if (rc) return rc;
-    if (B < 0 || B > INT32_MAX / 224 || (B > 0 && (!cell_xy || !out))) return h->fail(KEEP_EINVAL, "region_patches: bad B %lld or null pointer", (long long)B);
-    if (patch != 224 && (!xbounds || !xweights || !ybounds || !yweights || xksize < 1 || yksize < 1))
-        return h->fail(KEEP_EINVAL, "region_patches: patch %lld needs the Resize(224) tables", (long long)patch);
-    if (patch > H || patch > W) return h->fail(KEEP_EINVAL, "region_patches: patch %lld larger than the region %lldx%lld", (long long)patch,
-                                               (long long)W, (long long)H);
-    if (B == 0) return KEEP_OK;
-    KEEP_ON_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    // [flag][horizontally resized rows]: the flag is read back before any pixel is touched (the one synchronisation of this call),
-    // so a cell outside the region is an error, not an out-of-bounds read
-    const size_t b_flag = align_up(sizeof(int)), b_tmp = patch == 224 ? 0 : align_up((size_t)B * patch * 224 * 3);
-    rc = ensure_arena(h, b_flag + b_tmp);
-    if (rc) return rc;
-    int* bad = (int*)h->arena;
-    HIPCHK(h, hipMemsetAsync(bad, 0, sizeof(int), s));
-    launch_region_check_cells(cell_xy, (int)B, H, W, (int)patch, bad, s);
-    rc = check_launch(h, "region_check_cells");
-    if (rc) return rc;
-    int bad_h = 0;
-    HIPCHK(h, hipMemcpyAsync(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    if (bad_h) return h->fail(KEEP_EINVAL, "region_patches: a cell (x, y) has x < 0, y < 0, x + %lld > %lld or y + %lld > %lld", (long long)patch,
-                              (long long)W, (long long)patch, (long long)H);
-    launch_region_patches_u8(region, row_stride_bytes, pix_stride, cell_xy, (int)B, (int)patch, xbounds, xweights, xksize, ybounds, yweights,
-                             yksize, (unsigned char*)h->arena + b_flag, out, s);
-    return check_launch(h, "region_patches_u8");
-}
-
-int keep_tissue_median_hist(keep_handle* h, const unsigned char* thumb, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
-                            int ksize, unsigned char* median_out, int32_t* hist_out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (!thumb || H < 1 || W < 1) return h->fail(KEEP_EINVAL, "tissue_median_hist: null pointer or empty shape %lldx%lld", (long long)H, (long long)W);
-    if (pix_stride != 3 && pix_stride != 4) return h->fail(KEEP_EINVAL, "tissue_median_hist: pixel stride %d (3 = RGB, 4 = RGBA)", pix_stride);
-    if (H > TISSUE_MAX_PIXELS || W > TISSUE_MAX_PIXELS || H * W > TISSUE_MAX_PIXELS)
-        return h->fail(KEEP_EINVAL, "tissue_median_hist: %lldx%lld pixels (limit H W <= 2^30)", (long long)H, (long long)W);
-    if (row_stride_bytes < W * pix_stride)
-        return h->fail(KEEP_EINVAL, "tissue_median_hist: row stride %lld bytes < width %lld x pixel stride %d", (long long)row_stride_bytes,
-                       (long long)W, pix_stride);
-    if (ksize < 1 || ksize > 15 || ksize % 2 == 0) return h->fail(KEEP_EINVAL, "tissue_median_hist: ksize %d (odd, 1..15)", ksize);
-    if (!median_out || !hist_out) return h->fail(KEEP_EINVAL, "tissue_median_hist: null output");
-    KEEP_ON_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(h, hipMemsetAsync(hist_out, 0, 256 * sizeof(int32_t), s));
-    if (launch_tissue_median_hist(thumb, row_stride_bytes, pix_stride, (int)H, (int)W, ksize, median_out, hist_out, s))
-        return h->fail(KEEP_EUNSUPPORTED, "tissue_median_hist: no kernel for ksize %d", ksize);
-    return check_launch(h, "tissue_median_hist");
-}
-
-int keep_tissue_mask(keep_handle* h, const unsigned char* median, int64_t H, int64_t W, int threshold, int close, int64_t min_hole,
-                     int64_t min_area, unsigned char* mask_out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (!median || !mask_out || median == mask_out) return h->fail(KEEP_EINVAL, "tissue_mask: null pointer, or mask_out aliases median");
-    if (H < 1 || W < 1 || H > TISSUE_MAX_PIXELS || W > TISSUE_MAX_PIXELS || H * W > TISSUE_MAX_PIXELS)
-        return h->fail(KEEP_EINVAL, "tissue_mask: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
-    if (threshold < 0 || threshold > 255) return h->fail(KEEP_EINVAL, "tissue_mask: threshold %d outside [0, 255]", threshold);
-    if (close < 0 || close > 31) return h->fail(KEEP_EINVAL, "tissue_mask: close %d outside [0, 31]", close);
-    if (min_hole < 0 || min_area < 0) return h->fail(KEEP_EINVAL, "tissue_mask: min_hole %lld / min_area %lld < 0", (long long)min_hole, (long long)min_area);
-    KEEP_ON_DEVICE(h);
-    const size_t n = (size_t)(H * W);
-    const bool label = min_hole > 0 || min_area > 0;
-    const size_t b_tmp = close > 0 ? align_up(n) : 0, b_lab = label ? align_up(n * 4) : 0;
-    int rc = ensure_arena(h, b_tmp + 2 * b_lab);
-    if (rc) return rc;
-    // an area never exceeds H W <= 2^30: larger bounds decide the same
-    launch_tissue_mask(median, (int)H, (int)W, threshold, close, (int)std::min<int64_t>(min_hole, TISSUE_MAX_PIXELS),
-                       (int)std::min<int64_t>(min_area, TISSUE_MAX_PIXELS), (unsigned char*)h->arena, (int*)(h->arena + b_tmp),
-                       (int*)(h->arena + b_tmp + b_lab), h->err_flag, mask_out, (hipStream_t)stream);
-    return check_launch(h, "tissue_mask");
-}
-
-int keep_region_grid_mask(keep_handle* h, const unsigned char* mask, int64_t mh, int64_t mw, int64_t downsample, int64_t H, int64_t W,
-                          int64_t patch, int64_t step, int64_t origin_x, int64_t origin_y, int mode, int32_t* cell_xy_out, int64_t* n_out,
-                          void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (!mask || mh < 1 || mw < 1 || mh > INT32_MAX || mw > INT32_MAX)
-        return h->fail(KEEP_EINVAL, "region_grid_mask: null mask or bad mask shape %lldx%lld", (long long)mh, (long long)mw);
-    if (downsample < 1 || downsample > INT32_MAX) return h->fail(KEEP_EINVAL, "region_grid_mask: downsample %lld < 1", (long long)downsample);
-    if (H < 1 || W < 1 || H > INT32_MAX || W > INT32_MAX) return h->fail(KEEP_EINVAL, "region_grid_mask: region shape %lldx%lld", (long long)H, (long long)W);
-    if (patch < 16 || patch > REGION_MAX_PATCH) return h->fail(KEEP_EINVAL, "region_grid_mask: patch %lld outside [16, %d]", (long long)patch, REGION_MAX_PATCH);
-    if (step < 1) return h->fail(KEEP_EINVAL, "region_grid_mask: step %lld < 1", (long long)step);
-    constexpr int64_t omax = (int64_t)1 << 40;
-    if (origin_x < -omax || origin_x > omax || origin_y < -omax || origin_y > omax)
-        return h->fail(KEEP_EINVAL, "region_grid_mask: origin (%lld, %lld) outside +-2^40", (long long)origin_x, (long long)origin_y);
-    if (mode < KEEP_MASK_FOUR_PT || mode > KEEP_MASK_CENTER) return h->fail(KEEP_EINVAL, "region_grid_mask: mode %d (0 four_pt, 1 four_pt_hard, 2 center)", mode);
-    if (!cell_xy_out || !n_out) return h->fail(KEEP_EINVAL, "region_grid_mask: null output");
-    const int64_t gx = W >= patch ? (W - patch) / step + 1 : 0, gy = H >= patch ? (H - patch) / step + 1 : 0;
-    const int64_t ncells = gx * gy;
-    if (ncells > INT32_MAX) return h->fail(KEEP_EINVAL, "region_grid_mask: %lld cells (limit 2^31 - 1)", (long long)ncells);
-    KEEP_ON_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    if (ncells == 0) {
-        HIPCHK(h, hipMemsetAsync(n_out, 0, sizeof(int64_t), s));
-        return KEEP_OK;
-    }
-    const int64_t nb = (ncells + REGION_GRID_CHUNK - 1) / REGION_GRID_CHUNK;
-    const size_t b_keep = align_up((size_t)ncells), b_counts = align_up((size_t)nb * 4);
-    int rc = ensure_arena(h, b_keep + 2 * b_counts);
-    if (rc) return rc;
-    unsigned char* keep = (unsigned char*)h->arena;
-    launch_tissue_grid_cells(mask, mh, mw, downsample, (int)gx, ncells, (int)patch, (int)step, origin_x, origin_y, mode, keep, s);
-    launch_region_compact(keep, (int)gx, ncells, (int)step, (int*)(h->arena + b_keep), (int*)(h->arena + b_keep + b_counts), cell_xy_out, n_out, s);
-    return check_launch(h, "region_grid_mask");
-}
-
-static const char* heat_shape_error(int64_t H, int64_t W) {
-    return (H < 1 || W < 1 || H > HEAT_MAX_PIXELS || W > HEAT_MAX_PIXELS || H * W > HEAT_MAX_PIXELS) ? "raster shape (1 <= H W <= 2^30)" : nullptr;
-}
-
-int keep_heat_accumulate(keep_handle* h, const int64_t* coords, const float* values, int64_t N, int64_t patch, int64_t downsample,
-                         int64_t H, int64_t W, int64_t origin_x, int64_t origin_y, int zero_first, int64_t* acc, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "heat_accumulate: acc is null or not 8-byte aligned");
-    if (N < 0 || N > HEAT_MAX_TILES) return h->fail(KEEP_EINVAL, "heat_accumulate: %lld tiles (0 .. 2^24 - 1)", (long long)N);
-    if (N > 0 && (!coords || !values)) return h->fail(KEEP_EINVAL, "heat_accumulate: null coords or values");
-    if (heat_shape_error(H, W)) return h->fail(KEEP_EINVAL, "heat_accumulate: %lldx%lld: %s", (long long)H, (long long)W, heat_shape_error(H, W));
-    if (patch < 1 || patch > HEAT_MAX_PATCH) return h->fail(KEEP_EINVAL, "heat_accumulate: patch %lld outside [1, 2^30]", (long long)patch);
-    if (downsample < 1 || downsample > patch)
-        return h->fail(KEEP_EINVAL, "heat_accumulate: downsample %lld outside [1, patch = %lld]", (long long)downsample, (long long)patch);
-    constexpr int64_t omax = (int64_t)1 << 40;
-    if (origin_x < -omax || origin_x > omax || origin_y < -omax || origin_y > omax)
-        return h->fail(KEEP_EINVAL, "heat_accumulate: origin (%lld, %lld) outside +-2^40", (long long)origin_x, (long long)origin_y);
-    if (origin_x % downsample || origin_y % downsample)
-        return h->fail(KEEP_EINVAL, "heat_accumulate: origin (%lld, %lld) is not a multiple of downsample %lld", (long long)origin_x,
-                       (long long)origin_y, (long long)downsample);
-    KEEP_ON_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    if (zero_first) HIPCHK(h, hipMemsetAsync(acc, 0, (size_t)(H * W) * sizeof(int64_t), s));
-    launch_heat_accumulate(coords, values, N, patch, downsample, (int)H, (int)W, origin_x, origin_y, acc, s);
-    return check_launch(h, "heat_accumulate");
-}
-
-int keep_heat_mean(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, float uncovered, float* mean_out, int32_t* count_out,
-                   unsigned char* pred_out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "heat_mean: acc is null or not 8-byte aligned");
-    if (heat_shape_error(H, W)) return h->fail(KEEP_EINVAL, "heat_mean: %lldx%lld: %s", (long long)H, (long long)W, heat_shape_error(H, W));
-    if (!mean_out && !count_out && !pred_out) return h->fail(KEEP_EINVAL, "heat_mean: no output");
-    if (((uintptr_t)mean_out & 3) || ((uintptr_t)count_out & 3)) return h->fail(KEEP_EINVAL, "heat_mean: mean_out / count_out not 4-byte aligned");
-    KEEP_ON_DEVICE(h);
-    launch_heat_mean(acc, (int)H, (int)W, uncovered, mean_out, count_out, pred_out, (hipStream_t)stream);
-    return check_launch(h, "heat_mean");
-}
-
-int keep_heat_render(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, const unsigned char* thumb, int64_t row_stride_bytes,
-                     int pix_stride, int background_rgb, const unsigned char* mask, const unsigned char* lut, int alpha, int lo16, int hi16,
-                     int min16, unsigned char* out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "heat_render: acc is null or not 8-byte aligned");
-    if (!lut || !out) return h->fail(KEEP_EINVAL, "heat_render: null lut or output");
-    if (heat_shape_error(H, W)) return h->fail(KEEP_EINVAL, "heat_render: %lldx%lld: %s", (long long)H, (long long)W, heat_shape_error(H, W));
-    if (thumb) {
-        if (pix_stride != 3 && pix_stride != 4) return h->fail(KEEP_EINVAL, "heat_render: pixel stride %d (3 = RGB, 4 = RGBA)", pix_stride);
-        if (row_stride_bytes < W * pix_stride)
-            return h->fail(KEEP_EINVAL, "heat_render: row stride %lld bytes < width %lld x pixel stride %d", (long long)row_stride_bytes,
-                           (long long)W, pix_stride);
-    } else if (background_rgb < 0 || background_rgb > 0xFFFFFF) {
-        return h->fail(KEEP_EINVAL, "heat_render: background 0x%x outside [0, 0xFFFFFF]", background_rgb);
-    }
-    if (alpha < 0 || alpha > 256) return h->fail(KEEP_EINVAL, "heat_render: alpha %d outside [0, 256]", alpha);
-    if (lo16 < 0 || hi16 > 65535 || lo16 >= hi16) return h->fail(KEEP_EINVAL, "heat_render: window [%d, %d] (0 <= lo16 < hi16 <= 65535)", lo16, hi16);
-    if (min16 < 0 || min16 > 65535) return h->fail(KEEP_EINVAL, "heat_render: min16 %d outside [0, 65535]", min16);
-    KEEP_ON_DEVICE(h);
-    launch_heat_render(acc, (int)H, (int)W, thumb, row_stride_bytes, pix_stride, (unsigned)background_rgb, mask, lut, alpha, lo16, hi16, min16,
-                       out, (hipStream_t)stream);
-    return check_launch(h, "heat_render");
-}
-
-int keep_heat_smooth(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, const unsigned char* mask, const int32_t* taps, int radius,
-                     int64_t* acc_out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "heat_smooth: acc is null or not 8-byte aligned");
-    if (!acc_out || ((uintptr_t)acc_out & 7)) return h->fail(KEEP_EINVAL, "heat_smooth: acc_out is null or not 8-byte aligned");
-    if (acc_out == acc) return h->fail(KEEP_EINVAL, "heat_smooth: acc_out aliases acc");
-    if (heat_shape_error(H, W)) return h->fail(KEEP_EINVAL, "heat_smooth: %lldx%lld: %s", (long long)H, (long long)W, heat_shape_error(H, W));
-    if (!taps || ((uintptr_t)taps & 3)) return h->fail(KEEP_EINVAL, "heat_smooth: taps is null or not 4-byte aligned");
-    if (radius < 1 || radius > HEAT_SMOOTH_MAX_RADIUS) return h->fail(KEEP_EINVAL, "heat_smooth: radius %d outside [1, %d]", radius, HEAT_SMOOTH_MAX_RADIUS);
-    KEEP_ON_DEVICE(h);
-    const size_t n = (size_t)(H * W), b_a = align_up(n * 4);
-    int rc = ensure_arena(h, b_a + align_up(n * 2));
-    if (rc) return rc;
-    launch_heat_smooth(acc, (int)H, (int)W, mask, taps, radius, (unsigned*)h->arena, (unsigned short*)(h->arena + b_a), acc_out, (hipStream_t)stream);
-    return check_launch(h, "heat_smooth");
-}
-
-int keep_sort_f32(keep_handle* h, const float* values, int64_t M, float* sorted_out, int64_t* n_out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (M < 1 || M > SORT_MAX) return h->fail(KEEP_EINVAL, "sort_f32: %lld values (1 .. 2^24 - 1)", (long long)M);
-    if (!values || !sorted_out || !n_out) return h->fail(KEEP_EINVAL, "sort_f32: null pointer");
-    if (((uintptr_t)values & 3) || ((uintptr_t)sorted_out & 3) || ((uintptr_t)n_out & 7)) return h->fail(KEEP_EINVAL, "sort_f32: values / sorted_out / n_out not aligned");
-    KEEP_ON_DEVICE(h);
-    size_t table_off, totals_off;
-    int rc = ensure_arena(h, sort_workspace_bytes(M, &table_off, &totals_off));
-    if (rc) return rc;
-    launch_sort_f32(values, M, (unsigned char*)h->arena, sorted_out, n_out, (hipStream_t)stream);
-    return check_launch(h, "sort_f32");
-}
-
-int keep_rank_f32(keep_handle* h, const float* sorted, int64_t M, const int64_t* n_dev, const float* queries, int64_t N, int self,
-                  float* pct_out, int32_t* less_out, int32_t* eq_out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (M < 1 || M > SORT_MAX) return h->fail(KEEP_EINVAL, "rank_f32: a population of %lld values (1 .. 2^24 - 1)", (long long)M);
-    if (N < 0 || N > SORT_MAX) return h->fail(KEEP_EINVAL, "rank_f32: %lld queries (0 .. 2^24 - 1)", (long long)N);
-    if (!sorted || !n_dev || (N > 0 && !queries)) return h->fail(KEEP_EINVAL, "rank_f32: null sorted, n or queries");
-    if (self != 0 && self != 1) return h->fail(KEEP_EINVAL, "rank_f32: self %d (0 or 1)", self);
-    if (!pct_out && !less_out && !eq_out) return h->fail(KEEP_EINVAL, "rank_f32: no output");
-    if (((uintptr_t)sorted & 3) || ((uintptr_t)n_dev & 7) || ((uintptr_t)queries & 3) || ((uintptr_t)pct_out & 3) || ((uintptr_t)less_out & 3) ||
-        ((uintptr_t)eq_out & 3))
-        return h->fail(KEEP_EINVAL, "rank_f32: a pointer is not aligned");
-    KEEP_ON_DEVICE(h);
-    launch_rank_f32(sorted, M, n_dev, queries, N, self, pct_out, less_out, eq_out, (hipStream_t)stream);
-    return check_launch(h, "rank_f32");
-}
-
-static bool regions_shape_ok(int64_t H, int64_t W) {
-    return H >= 1 && W >= 1 && H <= TISSUE_MAX_PIXELS && W <= TISSUE_MAX_PIXELS && H * W <= TISSUE_MAX_PIXELS;
-}
-
-int keep_regions_label(keep_handle* h, const unsigned char* mask, int64_t H, int64_t W, int connectivity, int64_t min_area, int32_t* labels_out,
-                       int64_t* n_out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (!mask || !labels_out || !n_out) return h->fail(KEEP_EINVAL, "regions_label: null pointer");
-    if (!regions_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "regions_label: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
-    if (connectivity != 4 && connectivity != 8) return h->fail(KEEP_EINVAL, "regions_label: connectivity %d (4 or 8)", connectivity);
-    if (min_area < 1) return h->fail(KEEP_EINVAL, "regions_label: min_area %lld < 1", (long long)min_area);
-    if (((uintptr_t)labels_out & 3) || ((uintptr_t)n_out & 7)) return h->fail(KEEP_EINVAL, "regions_label: labels_out / n_out not aligned");
-    KEEP_ON_DEVICE(h);
-    const size_t n = (size_t)(H * W);
-    const size_t b_lab = align_up(n * 4), b_counts = align_up(((n + REGIONS_SCAN_CHUNK - 1) / REGIONS_SCAN_CHUNK) * sizeof(int));
-    int rc = ensure_arena(h, 2 * b_lab + 2 * b_counts);
-    if (rc) return rc;
-    // an area never exceeds H W <= 2^30: a larger bound decides the same (every component is dropped)
-    launch_regions_label(mask, (int)H, (int)W, connectivity == 8, (int)std::min<int64_t>(min_area, TISSUE_MAX_PIXELS + 1), (int*)h->arena,
-                         (int*)(h->arena + b_lab), (int*)(h->arena + 2 * b_lab), (int*)(h->arena + 2 * b_lab + b_counts), h->err_flag,
-                         labels_out, n_out, (hipStream_t)stream);
-    return check_launch(h, "regions_label");
-}
-
-int keep_regions_table(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, const int64_t* acc, int64_t* table_out,
-                       void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "regions_table: labels is null or not 4-byte aligned");
-    if (!regions_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "regions_table: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
-    if (n < 0 || n > H * W) return h->fail(KEEP_EINVAL, "regions_table: n = %lld outside [0, H W]", (long long)n);
-    if ((uintptr_t)acc & 7) return h->fail(KEEP_EINVAL, "regions_table: acc is not 8-byte aligned");
-    if (n > 0 && (!table_out || ((uintptr_t)table_out & 7))) return h->fail(KEEP_EINVAL, "regions_table: table_out is null or not 8-byte aligned");
-    KEEP_ON_DEVICE(h);
-    launch_regions_table(labels, (int)H, (int)W, n, acc, table_out, (hipStream_t)stream);
-    return check_launch(h, "regions_table");
-}
-
-static bool outline_shape_ok(int64_t H, int64_t W) {
-    return H >= 1 && W >= 1 && H <= OUTLINE_MAX_PIXELS && W <= OUTLINE_MAX_PIXELS && H * W <= OUTLINE_MAX_PIXELS;
-}
-
-int keep_outline_count(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, int connectivity, int64_t* counts_out,
-                       void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "outline_count: labels is null or not 4-byte aligned");
-    if (!outline_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "outline_count: %lldx%lld pixels (1 <= H W <= 2^28)", (long long)H, (long long)W);
-    if (n < 0 || n > H * W) return h->fail(KEEP_EINVAL, "outline_count: n = %lld outside [0, H W]", (long long)n);
-    if (connectivity != 4 && connectivity != 8) return h->fail(KEEP_EINVAL, "outline_count: connectivity %d (4 or 8)", connectivity);
-    if (!counts_out || ((uintptr_t)counts_out & 7)) return h->fail(KEEP_EINVAL, "outline_count: counts_out is null or not 8-byte aligned");
-    KEEP_ON_DEVICE(h);
-    int rc = ensure_arena(h, outline_count_workspace_bytes(H * W));
-    if (rc) return rc;
-    launch_outline_count(labels, (int)H, (int)W, (int)n, (unsigned char*)h->arena, counts_out, (hipStream_t)stream);
-    return check_launch(h, "outline_count");
-}
-
-int keep_outline_trace(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, int connectivity, int64_t E, int64_t V,
-                       int32_t* vertices_out, int64_t* rings_out, int64_t ring_cap, int64_t* r_out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "outline_trace: labels is null or not 4-byte aligned");
-    if (!outline_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "outline_trace: %lldx%lld pixels (1 <= H W <= 2^28)", (long long)H, (long long)W);
-    if (n < 1 || n > H * W) return h->fail(KEEP_EINVAL, "outline_trace: n = %lld outside [1, H W] (without a region there is nothing to trace)", (long long)n);
-    if (connectivity != 4 && connectivity != 8) return h->fail(KEEP_EINVAL, "outline_trace: connectivity %d (4 or 8)", connectivity);
-    if (E < 4 || E > 4 * H * W || V < 4 || V > E)
-        return h->fail(KEEP_EINVAL, "outline_trace: E = %lld, V = %lld (4 <= V <= E <= 4 H W: the values keep_outline_count wrote)", (long long)E,
-                       (long long)V);
-    if (!vertices_out || ((uintptr_t)vertices_out & 3)) return h->fail(KEEP_EINVAL, "outline_trace: vertices_out is null or not 4-byte aligned");
-    if (ring_cap < 0) return h->fail(KEEP_EINVAL, "outline_trace: ring_cap %lld < 0", (long long)ring_cap);
-    if (ring_cap > 0 && (!rings_out || ((uintptr_t)rings_out & 7))) return h->fail(KEEP_EINVAL, "outline_trace: rings_out is null or not 8-byte aligned");
-    if (!r_out || ((uintptr_t)r_out & 7)) return h->fail(KEEP_EINVAL, "outline_trace: r_out is null or not 8-byte aligned");
-    KEEP_ON_DEVICE(h);
-    int rc = ensure_arena(h, outline_trace_workspace_bytes(H * W, E));
-    if (rc) return rc;
-    launch_outline_trace(labels, (int)H, (int)W, (int)n, connectivity == 8, (int)E, V, (unsigned char*)h->arena, vertices_out, rings_out, ring_cap,
-                         r_out, (hipStream_t)stream);
-    return check_launch(h, "outline_trace");
-}
-
-int keep_outline_draw(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, const unsigned char* rgb_in, unsigned char* rgb_out, int color,
-                      int width, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "outline_draw: labels is null or not 4-byte aligned");
-    if (!rgb_in || !rgb_out) return h->fail(KEEP_EINVAL, "outline_draw: null image");
-    if (!outline_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "outline_draw: %lldx%lld pixels (1 <= H W <= 2^28)", (long long)H, (long long)W);
-    if (color < 0 || color > 0xFFFFFF) return h->fail(KEEP_EINVAL, "outline_draw: color 0x%x outside [0, 0xFFFFFF]", color);
-    if (width < 1 || width > OUTLINE_MAX_WIDTH) return h->fail(KEEP_EINVAL, "outline_draw: width %d outside [1, %d]", width, OUTLINE_MAX_WIDTH);
-    KEEP_ON_DEVICE(h);
-    int rc = ensure_arena(h, align_up((size_t)(H * W)));
-    if (rc) return rc;
-    launch_outline_draw(labels, (int)H, (int)W, rgb_in, rgb_out, (unsigned)color, width, (unsigned char*)h->arena, (hipStream_t)stream);
-    return check_launch(h, "outline_draw");
-}
-
-int keep_poly_fill(keep_handle* h, const int64_t* vertices, int64_t V, const int64_t* ring_start, int64_t R, const int32_t* weight,
-                   int64_t downsample, int64_t H, int64_t W, int64_t origin_x, int64_t origin_y, int rule, int value, const unsigned char* into,
-                   unsigned char* out, int64_t* crossings_out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (crossings_out) *crossings_out = 0;
-    if (H < 1 || W < 1 || H > POLY_MAX_CELLS || W > POLY_MAX_CELLS || H * (W + 1) > POLY_MAX_CELLS)
-        return h->fail(KEEP_EINVAL, "poly_fill: %lldx%lld pixels (h, w >= 1, h (w + 1) <= 2^28)", (long long)H, (long long)W);
-    if (downsample < 1 || downsample > POLY_MAX_DOWNSAMPLE) return h->fail(KEEP_EINVAL, "poly_fill: downsample %lld outside [1, 4096]", (long long)downsample);
-    if (origin_x < -POLY_MAX_COORD || origin_x > POLY_MAX_COORD || origin_y < -POLY_MAX_COORD || origin_y > POLY_MAX_COORD)
-        return h->fail(KEEP_EINVAL, "poly_fill: origin (%lld, %lld) outside +-2^26", (long long)origin_x, (long long)origin_y);
-    if (rule != KEEP_FILL_UNION && rule != KEEP_FILL_EVENODD) return h->fail(KEEP_EINVAL, "poly_fill: rule %d (0 union, 1 evenodd)", rule);
-    if (value < 0 || value > 255) return h->fail(KEEP_EINVAL, "poly_fill: value %d outside [0, 255]", value);
-    if (V < 0 || V > POLY_MAX_VERTICES || R < 0 || R > POLY_MAX_RINGS || V < 3 * R || (V > 0 && R == 0))
-        return h->fail(KEEP_EINVAL, "poly_fill: V = %lld, R = %lld (V <= 2^24, R <= 2^20, every ring has >= 3 vertices)", (long long)V, (long long)R);
-    if (R > 0 && (!vertices || !ring_start || !weight)) return h->fail(KEEP_EINVAL, "poly_fill: null vertices, ring_start or weight");
-    if (((uintptr_t)vertices & 7) || ((uintptr_t)ring_start & 7) || ((uintptr_t)weight & 3))
-        return h->fail(KEEP_EINVAL, "poly_fill: vertices / ring_start / weight not aligned");
-    if (!out) return h->fail(KEEP_EINVAL, "poly_fill: out is null");
-    KEEP_ON_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    int rc = ensure_arena(h, poly_fill_workspace_bytes(H, W, V));
-    if (rc) return rc;
-    unsigned char* ws = (unsigned char*)h->arena;
-    if (R == 0) {
-        HIPCHK(h, hipMemsetAsync(ws, 0, (size_t)H * (size_t)(W + 1) * 4, s));
-    } else {
-        const int64_t* c_dev = launch_poly_count(vertices, V, ring_start, R, weight, downsample, (int)H, (int)W, origin_x, origin_y, ws, s);
-        rc = check_launch(h, "poly_fill (edges)");
-        if (rc) return rc;
-        int64_t C = 0;
-        HIPCHK(h, hipMemcpyAsync(&C, c_dev, sizeof C, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));                  // the one host synchronisation: C sizes the grid
-        if (crossings_out) *crossings_out = C;
-        if (C < 0 || C >= POLY_MAX_CROSSINGS)
-            return h->fail(KEEP_EINVAL, "poly_fill: %lld crossings of edges with rows (< 2^31): fill at a larger downsample", (long long)C);
-        if (C > 0) launch_poly_crossings(vertices, V, downsample, (int)H, (int)W, origin_x, origin_y, C, ws, s);
-    }
-    launch_poly_rows((int)H, (int)W, rule == KEEP_FILL_EVENODD, value, into, out, ws, s);
-    return check_launch(h, "poly_fill");
-}
-
-int keep_mask_tile_counts(keep_handle* h, const unsigned char* mask, int64_t H, int64_t W, int64_t downsample, int64_t origin_x, int64_t origin_y,
-                          const int64_t* coords, int64_t N, int64_t patch, int32_t* counts_out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (!mask) return h->fail(KEEP_EINVAL, "mask_tile_counts: mask is null");
-    if (!regions_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "mask_tile_counts: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
-    if (downsample < 1 || downsample > HEAT_MAX_PATCH) return h->fail(KEEP_EINVAL, "mask_tile_counts: downsample %lld outside [1, 2^30]", (long long)downsample);
-    if (patch < 1 || patch > HEAT_MAX_PATCH) return h->fail(KEEP_EINVAL, "mask_tile_counts: patch %lld outside [1, 2^30]", (long long)patch);
-    constexpr int64_t omax = (int64_t)1 << 40;
-    if (origin_x < -omax || origin_x > omax || origin_y < -omax || origin_y > omax)
-        return h->fail(KEEP_EINVAL, "mask_tile_counts: origin (%lld, %lld) outside +-2^40", (long long)origin_x, (long long)origin_y);
-    if (N < 0 || N > HEAT_MAX_TILES) return h->fail(KEEP_EINVAL, "mask_tile_counts: %lld tiles (0 .. 2^24 - 1)", (long long)N);
-    if (N > 0 && (!coords || ((uintptr_t)coords & 7))) return h->fail(KEEP_EINVAL, "mask_tile_counts: coords is null or not 8-byte aligned");
-    if (N > 0 && (!counts_out || ((uintptr_t)counts_out & 7))) return h->fail(KEEP_EINVAL, "mask_tile_counts: counts_out is null or not 8-byte aligned");
-    if (N == 0) return KEEP_OK;
-    KEEP_ON_DEVICE(h);
-    launch_mask_tile_counts(mask, (int)H, (int)W, downsample, origin_x, origin_y, coords, N, patch, counts_out, (hipStream_t)stream);
-    return check_launch(h, "mask_tile_counts");
-}
-
-int keep_eval_roc(keep_handle* h, const float* scores, const unsigned char* labels, int64_t N, int64_t* scalars_out, float* thresholds_out,
-                  int32_t* fps_out, int32_t* tps_out, unsigned char* kept_out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (N < 0 || N > SORT_MAX) return h->fail(KEEP_EINVAL, "eval_roc: %lld tiles (0 .. 2^24 - 1)", (long long)N);
-    if (N > 0 && (!scores || !labels)) return h->fail(KEEP_EINVAL, "eval_roc: null scores or labels");
-    if (!scalars_out || ((uintptr_t)scalars_out & 7)) return h->fail(KEEP_EINVAL, "eval_roc: scalars_out is null or not 8-byte aligned");
-    const int given = (thresholds_out != nullptr) + (fps_out != nullptr) + (tps_out != nullptr) + (kept_out != nullptr);
-    if (given != 0 && given != 4) return h->fail(KEEP_EINVAL, "eval_roc: the four curve outputs go together: all or none");
-    if (((uintptr_t)scores & 3) || ((uintptr_t)thresholds_out & 3) || ((uintptr_t)fps_out & 3) || ((uintptr_t)tps_out & 3))
-        return h->fail(KEEP_EINVAL, "eval_roc: scores / thresholds_out / fps_out / tps_out not 4-byte aligned");
-    KEEP_ON_DEVICE(h);
-    int rc = ensure_arena(h, eval_roc_workspace_bytes(N, given == 0));
-    if (rc) return rc;
-    launch_eval_roc(scores, labels, N, (unsigned char*)h->arena, scalars_out, thresholds_out, fps_out, tps_out, kept_out, (hipStream_t)stream);
-    return check_launch(h, "eval_roc");
-}
-
-int keep_eval_mask_counts(keep_handle* h, const unsigned char* a, const unsigned char* b, const unsigned char* within, int64_t H, int64_t W,
-                          int64_t* counts_out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (!a || !b) return h->fail(KEEP_EINVAL, "eval_mask_counts: a mask is null");
-    if (!regions_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "eval_mask_counts: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
-    if (!counts_out || ((uintptr_t)counts_out & 7)) return h->fail(KEEP_EINVAL, "eval_mask_counts: counts_out is null or not 8-byte aligned");
-    KEEP_ON_DEVICE(h);
-    launch_eval_mask_counts(a, b, within, H * W, counts_out, (hipStream_t)stream);
-    return check_launch(h, "eval_mask_counts");
-}
-
-int keep_eval_raster_hist(keep_handle* h, const int64_t* acc, const unsigned char* truth, const unsigned char* within, int64_t H, int64_t W,
-                          int64_t* hist_out, void* stream) {
-    if (!h) return KEEP_EINVAL;
-    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "eval_raster_hist: acc is null or not 8-byte aligned");
-    if (!truth) return h->fail(KEEP_EINVAL, "eval_raster_hist: truth is null");
-    if (!regions_shape_ok(H, W)) return h->fail(KEEP_EINVAL, "eval_raster_hist: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
-    if (!hist_out || ((uintptr_t)hist_out & 7)) return h->fail(KEEP_EINVAL, "eval_raster_hist: hist_out is null or not 8-byte aligned");
-    KEEP_ON_DEVICE(h);
-    launch_eval_raster_hist(acc, truth, within, H * W, hist_out, (hipStream_t)stream);
-    return check_launch(h, "eval_raster_hist");
 }
 
 int keep_token_error(keep_handle* h, void* stream) {

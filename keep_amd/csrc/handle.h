@@ -1,0 +1,264 @@
+// The engine handle: what keep_create returns and every extern "C" entry point receives.  engine.hip owns it (weights, arena,
+// towers, graphs, profile); slide_api.hip uses its device, error text, arena and error flag.
+#pragma once
+#include "common.h"
+#include "../../include/keep_hip.h"
+
+#include <cstdarg>
+#include <cstdio>
+#include <map>
+#include <string>
+#include <utility>
+#include <vector>
+
+#define HIPCHK(h, expr)                                                                      \
+    do {                                                                                     \
+        hipError_t _e = (expr);                                                              \
+        if (_e != hipSuccess) return (h)->fail(KEEP_EHIP, "%s: %s", #expr, hipGetErrorString(_e)); \
+    } while (0)
+
+// Every entry point runs on the handle's device and puts the caller's current device back (torch keeps its own notion of
+// the current device per thread; changing it behind its back redirects the caller's next allocation).
+struct DevGuard {
+    int prev = -1; bool ok = true;
+    explicit DevGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess; else prev = -1;
+    }
+    ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+#define KEEP_ON_DEVICE(h) DevGuard _guard((h)->device); if (!_guard.ok) return (h)->fail(KEEP_EHIP, "hipSetDevice(%d) failed", (h)->device)
+
+struct WTensor {
+    std::vector<int64_t> shape;
+    int64_t numel = 0;
+    float* f32 = nullptr;     // kept for vectors / embeddings / head / pooler
+    f16* hi = nullptr;        // GEMM weights: fp16 planes
+    f16* lo = nullptr;
+    unsigned char* q = nullptr;   // MX-fp4 side planes of (hi, lo) and their scales (quant4.h); K % 128 == 0 weights only
+    unsigned char* sc = nullptr;
+    float prescale = 1.f;     // the planes hold prescale * W (a power of two; proj / fc2 of the image tower only): folded back through LayerScale and bias at finalize
+};
+
+enum Tag {
+    T_VIT_IM2COL, T_VIT_PATCH, T_VIT_LN, T_VIT_QKV, T_VIT_ATTN, T_VIT_PROJ, T_VIT_FC1, T_VIT_FC2, T_VIT_HEAD,
+    T_TXT_EMBED, T_TXT_LN, T_TXT_QKV, T_TXT_ATTN, T_TXT_OUT, T_TXT_FFN1, T_TXT_FFN2, T_TXT_POOL, T_SIM,
+    // image-tower launches that are NOT the plain single-pass kernel of their operator: split products / compensated (MX-fp4) products of the
+    // blocks the precision setting names ("x" = extra passes), and the CLS-rows-only operators of the last block ("tail": small-M kernels).
+    // The plain tags above then time one kernel instantiation each (bench.py's roofline block needs a per-kernel figure).
+    T_VIT_QKV_X, T_VIT_ATTN_X, T_VIT_PROJ_X, T_VIT_FC1_X, T_VIT_FC2_X, T_VIT_TAIL, T_COUNT
+};
+
+struct VitBlock {
+    const float *n1w, *n1b, *n2w, *n2b, *qkv_b, *proj_b, *fc1_b, *fc2_b, *ls1, *ls2;
+    const WTensor *qkv, *proj, *fc1, *fc2;
+};
+struct BertLayer {
+    WTensor qkv;                 // fused [3H, H]
+    float* qkv_b = nullptr;      // fused [3H]
+    const float *o_b, *ln1w, *ln1b, *i_b, *d_b, *ln2w, *ln2b;
+    const WTensor *o, *i, *d;
+};
+
+struct keep_handle {
+    int device = 0;
+    std::string err;
+    std::string load_warnings;   // '\n'-separated notes of keep_load_tensor calls (a weight the fp16 planes resolve poorly); read and cleared by keep_load_warnings
+    std::map<std::string, WTensor> w;
+    bool finalized = false;
+
+    // dims (filled at finalize)
+    int vit_depth = 0, vit_D = 0, vit_heads = 0, vit_F = 0, proj_dim = 0;
+    int bert_layers = 0, bert_H = 0, bert_heads = 0, bert_F = 0, bert_vocab = 0, bert_maxpos = 0, bert_types = 0;
+    std::vector<VitBlock> vblocks;
+    std::vector<BertLayer> blayers;
+    std::vector<float*> owned_vecs;   // LayerScale / bias vectors re-derived for pre-scaled weights (finalize_vit)
+
+    // options
+    KeepTune tune;               // kernel selection (travels in the launch parameter blocks; nothing is process-wide)
+    int precision = KEEP_PREC_COMP;
+    int strict_blocks = 0;       // first n blocks / layers as full hi/lo split products (any mode)
+    // The prefix shorthands (state of the last keep_set_option; they only take effect once one of them is set -- see plan_default below)
+    int comp_full_blocks = 1;    // KEEP_PREC_COMP: first n ViT blocks run qkv / attention / proj as split products as well
+    int comp_mlp_blocks = 8;     // KEEP_PREC_COMP: first n ViT blocks run fc1 / fc2 as compensated (fp16 + MX-fp4) products
+    int fused_screening = 1;     // keep_prompt_scores: 1 fused compensated GEMM (default) | 2 fused 3-pass split GEMM | 0 logits through HBM (any C)
+    int comp_min_tiles = 32;     // lanes with fewer tiles take the split product where a compensated one is asked for (small-M kernels)
+    int comp_qkv = 0;            // 1: KEEP_PREC_COMP, blocks < comp_full_blocks: the qkv GEMM as a compensated product (x1.5) instead of a split one (x3);
+                                 // q / k / v still stored as hi + lo planes, attention still a split product.  Measured (round 3): +0.9 % at equal settings,
+                                 // but block 0's qkv is where the error budget is tightest (the 3 % of the rounding variance the fp4 terms leave is
+                                 // amplified by all 24 blocks): calibrate() then needs 10 compensated MLP blocks instead of 6 -- a net loss.  Off.
+    int comp_qkv_from = 1 << 20; // the same for the split-attention blocks with index >= this only (block 0 keeps its three-pass qkv)
+    // The per-block plan of KEEP_PREC_COMP (keep_set_block_precision; the four options above are prefix shorthands that rewrite it):
+    //   attn_mode[i]  attention side of block i: KEEP_ATTN_PLAIN | KEEP_ATTN_SPLIT (qkv, q/k/v storage, attention, proj as split products) |
+    //                 KEEP_ATTN_SPLIT_COMPQKV (the same with the qkv GEMM as a compensated product) | KEEP_ATTN_COMPQKV (compensated qkv only) |
+    //                 KEEP_ATTN_PROJ_CLS (plain for every row + the CLS rows' proj again as a split product on their fp32-grade attention output) |
+    //                 KEEP_ATTN_COMPQKV_PROJ_CLS (both of the last two)
+    //   mlp_mode[i]   fc1 / fc2 of block i: KEEP_MLP_PLAIN | KEEP_MLP_SPLIT | KEEP_MLP_COMP (both MX-fp4 correction terms) | KEEP_MLP_COMP_W (the W_lo term only) |
+    //                 KEEP_MLP_CLS (plain for every row + the CLS rows again as split products)
+    // Which block gets what is a measured, per-checkpoint decision (tools/precision_budget.py, KEEPModel.calibrate).
+    static constexpr int MAX_BLOCKS = 64;
+    unsigned char attn_mode[MAX_BLOCKS] = {}, mlp_mode[MAX_BLOCKS] = {};
+    bool plan_custom = false;    // keep_set_block_precision was called since the last prefix option
+    void plan_from_prefix() {
+        for (int i = 0; i < MAX_BLOCKS; ++i) {
+            attn_mode[i] = i < comp_full_blocks ? ((comp_qkv || i >= comp_qkv_from) ? KEEP_ATTN_SPLIT_COMPQKV : KEEP_ATTN_SPLIT) : KEEP_ATTN_PLAIN;
+            mlp_mode[i] = i < comp_mlp_blocks ? KEEP_MLP_COMP : KEEP_MLP_PLAIN;
+        }
+        plan_custom = false;
+    }
+    // The plan a handle starts with (no calibration has seen the weights yet): block 0's attention side as split products with a compensated qkv
+    // and its MLP compensated -- the first block's rounding errors, in EVERY row, are amplified by all the attention layers that follow: 45-48 % of the
+    // all-fp16 error variance on the synthetic checkpoints --, every other block plain with the CLS rows' MLP redone as split products (the pooled
+    // feature is a CLS row).  profiles/r05_precision_budget.md: cosine rms 8.5e-6 on the bench weights, a quarter of what the 1e-4 tolerance allows a
+    // 100 000-tile slide, 3 % slower than what KEEPModel.calibrate picks for them.
+    void plan_default() {
+        for (int i = 0; i < MAX_BLOCKS; ++i) { attn_mode[i] = KEEP_ATTN_PLAIN; mlp_mode[i] = KEEP_MLP_CLS; }
+        attn_mode[0] = KEEP_ATTN_SPLIT_COMPQKV; mlp_mode[0] = KEEP_MLP_COMP;
+        plan_custom = false;
+    }
+    keep_handle() { plan_default(); }
+    // keep_classify: tiles whose top-2 cosine margin is below this are re-encoded in KEEP_PREC_STRICT before their label is taken.
+    // Default = 2 x the north-star tolerance (both cosines of a pair can move by 1e-4 in opposite directions) + 25 %.
+    float label_margin = 2.5e-4f;
+    char* cls_buf = nullptr; size_t cls_bytes = 0;     // keep_classify scratch (features, similarity, flags, staged tiles): outside the arena, which the encodes carve
+    int max_tiles = 256;
+    int max_prompts = 64;
+    int cls_tail = 1;            // last ViT block: proj / MLP on the CLS rows only (exact; 0 = evaluate every token)
+    // Mean-input compensation of the weight-rounding error (keep_calibrate_bias).  A plain fp16 GEMM computes A_hi W_hi^T: the W_lo A_hi term it drops has
+    // a part that is the SAME for every row -- W_lo a_mean, a_mean = the mean input row of that GEMM (GELU outputs are positive, LayerNorm outputs carry their
+    // bias, attention outputs are averages) -- which no amount of averaging over tiles removes.  It is a constant vector per GEMM: folded into the bias the plain
+    // launches use.  cal[i].sum[site]: column sums of the site's input over the calibration tiles; cal[i].bias[site]: bias + W_lo a_mean.
+    struct SiteCal { float* sum[4] = {nullptr, nullptr, nullptr, nullptr}; float* bias[4] = {nullptr, nullptr, nullptr, nullptr}; double rows[4] = {0, 0, 0, 0}; };
+    std::vector<SiteCal> cal;    // per ViT block; sites: 0 qkv, 1 proj, 2 fc1, 3 fc2
+    bool capture = false;        // the running encode accumulates cal[i].sum
+    bool bias_ready = false;     // cal[i].bias hold corrected biases for the loaded weights
+    int cal_cls_tail = 1;        // cls_tail at the time of the calibration (switching it afterwards invalidates the last block's averages)
+    int bias_correction = 1;     // plain launches use them (0: the checkpoint's own biases)
+    void free_cal() {
+        for (auto& c : cal) for (int k = 0; k < 4; ++k) { if (c.sum[k]) (void)hipFree(c.sum[k]); if (c.bias[k]) (void)hipFree(c.bias[k]); }
+        cal.clear(); bias_ready = false;
+    }
+    // Patch grids other than 14 x 14 (keep_encode_image_hw): the position table resampled to each grid (timm resample_abs_pos_embed), fp32
+    // [gh gw + 1][D] on the device, built outside any graph capture on first use; at most POS_CACHE grids, the oldest dropped first (with
+    // the captured graphs, which bake its address in); dropped whenever the image tower's weights are (re)finalised or pos_embed is reloaded.
+    struct PosSlot { int gh, gw; float* buf; };
+    static constexpr int POS_CACHE = 8;
+    std::vector<PosSlot> pos_cache;
+    void drop_pos_cache() {
+        if (pos_cache.empty()) return;
+        (void)hipDeviceSynchronize();
+        for (auto& e : pos_cache) (void)hipFree(e.buf);
+        pos_cache.clear();
+        ++opt_epoch;
+    }
+    // KEEP_PREC_COMP at grids other than 14 x 14: the per-block plan is calibrated on 197-token tiles.  Measured against strict on the bench weights
+    // (tools/grid_precision.py, 2 000 tiles per family) it stays at the 224 figure from 257 to 1025 tokens (worst 6.7e-5) and gets
+    // worse below 197 (7.1e-5 at 101 tokens, 8.1e-5 at 50).  1 (default): the plan for 197 <= tokens <= 1025, KEEP_PREC_STRICT outside that band;
+    // 0: every grid but 14 x 14 strict; 2: the plan at every grid (measurements only).
+    int grid_plan = 1;
+    bool grid_keeps_plan(int ntok) const { return grid_plan == 2 || (grid_plan == 1 && ntok >= 197 && ntok <= 1025); }
+    int patch_split = 1;         // 0: the patch-embedding GEMM as one fp16 pass (experiments; measured in profiles/r05_patch_embed_plain.txt)
+    // 2128 (default): the plain proj GEMMs of the image tower on the 256x128 / 4-wave / two-workgroups-per-CU kernel (GemmParams.impl_hint) -- proj is the one GEMM whose
+    // tile is 40 % fp32 residual read-modify-write epilogue, and with two workgroups on a CU one's epilogue runs under the other's K loop: -8.5 % on the proj launches,
+    // +0.57 % end to end in a six-round rotated A/B on the round-5 plan (profiles/r05_ab_two_workgroups_per_cu.txt; qkv / fc1 / fc2 on the same kernel lose 1.6-4.3 %:
+    // 1.5 x the operand bytes per FLOP).  0: the persistent 256x256 kernel.  Bit-identical results either way (same K order per output).
+    int proj_impl = 2128;
+    // hipGraph replay of launch-bound calls (one prompt / one tile: ~100 dependent kernels of a few us each)
+    struct GraphSlot { hipGraphExec_t exec; unsigned long long epoch; char* arena; };
+    std::map<std::string, GraphSlot> graphs;
+    int use_graphs = 1;
+    unsigned long long opt_epoch = 0;   // bumped by keep_set_option / keep_finalize_weights: graphs captured under an older epoch are dropped
+    hipStream_t cap_stream = nullptr;
+    int lane_min_tiles = 16;     // a lane is only opened for at least this many tiles (32 tiles: 7.09 -> 6.50 ms as 2 x 16; 16 tiles as 2 x 8 loses)
+    int n_streams = 2;           // concurrent sub-batches inside keep_encode_image (1 = everything on the caller's stream)
+    hipStream_t aux[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev_fork = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
+
+    // workspace arena
+    char* arena = nullptr;
+    size_t arena_bytes = 0;
+    int* err_flag = nullptr;     // device int, sticky: bit 0 out-of-range token ids, bit 1 non-finite output features (fp16 range exceeded), bit 2 (value 4) a tissue-labelling loop hit its cap
+
+    // profiling
+    int prof_mode = 0;           // 0 off, 1 the tags of prof_mask, 2 all
+    unsigned long long prof_mask = 0;
+    struct Rec { hipEvent_t a, b; int tag; };
+    std::vector<Rec> recs;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
+    double prof_ms[T_COUNT] = {0};
+    int64_t prof_n[T_COUNT] = {0};
+    double prof_flops[T_COUNT] = {0};      // executed FLOPs (2*M*N*K) of the profiled GEMM launches
+
+    int fail(int code, const char* fmt, ...) {
+        char buf[1024];
+        va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+        err = buf;
+        return code;
+    }
+    // Where the 11 bits of an fp16 operand are not enough (tools/precision_study.py: block 0 alone is 41 % of the cosine error
+    // variance, blocks 0-1 52 %, and outside them the MLP GEMMs carry > 80 %):
+    //   attention side (qkv, q/k/v storage, softmax probabilities, proj) of block i: split product or plain
+    //   MLP (fc1, fc2) of block i: 0 plain | 1 split (three fp16 passes) | 2 compensated (fp16 pass + two MX-fp4 correction terms)
+    int plan_attn(int i) const { return (precision == KEEP_PREC_COMP && i >= 0 && i < MAX_BLOCKS) ? attn_mode[i] : KEEP_ATTN_PLAIN; }
+    // lanes too small for the 256x256 kernel take split products wherever a compensated one is asked for (they run on the small-M / K-sliced kernels)
+    bool vit_attn_split(int i, int lane_tiles = 1 << 20) const {
+        if (precision == KEEP_PREC_STRICT || i < strict_blocks) return true;
+        const int a = plan_attn(i);
+        return a == KEEP_ATTN_SPLIT || a == KEEP_ATTN_SPLIT_COMPQKV || ((a == KEEP_ATTN_COMPQKV || a == KEEP_ATTN_COMPQKV_PROJ_CLS) && !(lane_tiles >= comp_min_tiles && vit_has_q));
+    }
+    bool vit_qkv_comp(int i, int lane_tiles) const {
+        if (precision != KEEP_PREC_COMP || i < strict_blocks || !(lane_tiles >= comp_min_tiles && vit_has_q)) return false;
+        const int a = plan_attn(i);
+        return a == KEEP_ATTN_SPLIT_COMPQKV || a == KEEP_ATTN_COMPQKV || a == KEEP_ATTN_COMPQKV_PROJ_CLS;
+    }
+    // fc1 / fc2 of block i: 0 plain | 1 split (three fp16 passes) | 2 compensated (both MX-fp4 terms) | 3 compensated, W_lo term only | 4 plain + CLS rows split
+    // (lane_tiles == 0: the last block's CLS-rows-only tail, which is the "CLS rows as split products" half on its own)
+    int vit_mlp_mode(int i, int lane_tiles) const {
+        if (precision == KEEP_PREC_STRICT || i < strict_blocks) return KEEP_MLP_SPLIT;
+        if (precision != KEEP_PREC_COMP || i < 0 || i >= MAX_BLOCKS) return KEEP_MLP_PLAIN;
+        const int m = mlp_mode[i];
+        if (m == KEEP_MLP_COMP || m == KEEP_MLP_COMP_W) return (lane_tiles >= comp_min_tiles && vit_has_q) ? m : KEEP_MLP_SPLIT;
+        if (m == KEEP_MLP_CLS) return lane_tiles == 0 ? KEEP_MLP_SPLIT : KEEP_MLP_CLS;
+        return m;
+    }
+    // the text tower is 1 % of a slide's work: in the compensated mode it simply runs split products throughout, at every length BertModel accepts
+    // (T <= 512 = max_position_embeddings; above 256 keys the split attention runs as two key windows of <= 256, merged like an online softmax)
+    bool txt_split(int l, int T) const { (void)T; return precision == KEEP_PREC_STRICT || l < strict_blocks || precision == KEEP_PREC_COMP; }
+    bool any_split() const { return precision != KEEP_PREC_FP16 || strict_blocks > 0; }
+    bool vit_has_q = false;      // every fc1 / fc2 weight has its fp4 side planes (dims % 128 == 0)
+    bool any_comp() const {
+        if (precision != KEEP_PREC_COMP || !vit_has_q) return false;
+        for (int i = 0; i < MAX_BLOCKS && i < (vit_depth ? vit_depth : MAX_BLOCKS); ++i)
+            if (mlp_mode[i] == KEEP_MLP_COMP || mlp_mode[i] == KEEP_MLP_COMP_W || attn_mode[i] == KEEP_ATTN_SPLIT_COMPQKV || attn_mode[i] == KEEP_ATTN_COMPQKV || attn_mode[i] == KEEP_ATTN_COMPQKV_PROJ_CLS) return true;
+        return false;
+    }
+
+    bool prof_on(int tag) const { return prof_mode == 2 || (prof_mode == 1 && ((prof_mask >> tag) & 1ull)); }
+    void prof_add_flops(int tag, double f) { if (prof_on(tag)) prof_flops[tag] += f; }
+    void prof_begin(int tag, hipStream_t s) {
+        if (!prof_on(tag)) return;
+        Rec r; r.tag = tag;
+        if (!pool.empty()) { r.a = pool.back().first; r.b = pool.back().second; pool.pop_back(); }
+        else { hipEventCreate(&r.a); hipEventCreate(&r.b); }
+        hipEventRecord(r.a, s);
+        recs.push_back(r);
+    }
+    void prof_end(int tag, hipStream_t s) {
+        if (!prof_on(tag)) return;
+        hipEventRecord(recs.back().b, s);
+    }
+    void prof_collect() {
+        for (auto& r : recs) {
+            hipEventSynchronize(r.b);
+            float ms = 0.f;
+            hipEventElapsedTime(&ms, r.a, r.b);
+            prof_ms[r.tag] += ms; prof_n[r.tag] += 1;
+            pool.push_back({r.a, r.b});
+        }
+        recs.clear();
+    }
+};
+
+// defined in engine.hip
+int ensure_arena(keep_handle* h, size_t bytes);            // grows the workspace arena to at least `bytes` (synchronises the device when it has to)
+int check_launch(keep_handle* h, const char* what);        // hipGetLastError after a launch, as a KEEP_E* code with the handle's error text set

@@ -1,0 +1,463 @@
+// The slide-geometry entry points of include/keep_hip.h: patch grid, tissue mask, heatmap, sort / rank, region table, outlines, polygon
+// fill and segmentation evaluation.  Host code only: each function validates its arguments, carves its workspace from the handle's
+// arena, calls the launch_* of its kernel file (region / tissue / heatmap / rank / components / outline / annotation / eval .hip) and
+// reports the launch.  Of the handle (handle.h) they use the device, the error text, the arena and the sticky error flag.
+#include "handle.h"
+
+#include <algorithm>
+
+static size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+// Checks that several entry points share; `who` is the entry point's name as its error messages spell it.
+// 1 <= H, W and H W <= limit (the kernels index pixels with an int32)
+static bool pixels_ok(int64_t H, int64_t W, int64_t limit) { return H >= 1 && W >= 1 && H <= limit && W <= limit && H * W <= limit; }
+
+// level-0 origin of a raster or mask: within +-2^40, so that origin + coordinate stays far inside an int64
+static int origin_check(keep_handle* h, const char* who, int64_t origin_x, int64_t origin_y) {
+    constexpr int64_t omax = (int64_t)1 << 40;
+    if (origin_x < -omax || origin_x > omax || origin_y < -omax || origin_y > omax)
+        return h->fail(KEEP_EINVAL, "%s: origin (%lld, %lld) outside +-2^40", who, (long long)origin_x, (long long)origin_y);
+    return KEEP_OK;
+}
+
+// a strided uint8 view of RGB or RGBA pixels, rows at least a row's bytes apart; two checks because tissue_median_hist has its pixel cap between them
+static int pix_stride_check(keep_handle* h, const char* who, int pix_stride) {
+    if (pix_stride != 3 && pix_stride != 4) return h->fail(KEEP_EINVAL, "%s: pixel stride %d (3 = RGB, 4 = RGBA)", who, pix_stride);
+    return KEEP_OK;
+}
+static int row_stride_check(keep_handle* h, const char* who, int64_t W, int64_t row_stride_bytes, int pix_stride) {
+    if (row_stride_bytes < W * pix_stride)
+        return h->fail(KEEP_EINVAL, "%s: row stride %lld bytes < width %lld x pixel stride %d", who, (long long)row_stride_bytes, (long long)W, pix_stride);
+    return KEEP_OK;
+}
+
+extern "C" {
+
+static int region_view_check(keep_handle* h, const unsigned char* region, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
+                             int64_t patch) {
+    if (!region || H < 1 || W < 1) return h->fail(KEEP_EINVAL, "region: null pointer or empty shape %lldx%lld", (long long)H, (long long)W);
+    if (int rc = pix_stride_check(h, "region", pix_stride)) return rc;
+    if (W > INT32_MAX || H > INT32_MAX || row_stride_bytes < W * pix_stride)
+        return h->fail(KEEP_EINVAL, "region: row stride %lld bytes < width %lld x pixel stride %d (or a side >= 2^31)", (long long)row_stride_bytes,
+                       (long long)W, pix_stride);
+    if (patch < 16 || patch > REGION_MAX_PATCH) return h->fail(KEEP_EINVAL, "region: patch %lld outside [16, %d]", (long long)patch, REGION_MAX_PATCH);
+    return KEEP_OK;
+}
+
+int keep_region_grid(keep_handle* h, const unsigned char* region, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride, int64_t patch,
+                     int64_t step, int sat_min, int64_t min_pixels, int32_t* cell_xy_out, int64_t* n_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    int rc = region_view_check(h, region, H, W, row_stride_bytes, pix_stride, patch);
+    if (rc) return rc;
+    if (step < 1) return h->fail(KEEP_EINVAL, "region_grid: step %lld < 1", (long long)step);
+    if (sat_min < 0 || sat_min > 255) return h->fail(KEEP_EINVAL, "region_grid: sat_min %d outside [0, 255]", sat_min);
+    if (min_pixels < 0 || min_pixels > patch * patch)
+        return h->fail(KEEP_EINVAL, "region_grid: min_pixels %lld outside [0, patch^2 = %lld]", (long long)min_pixels, (long long)(patch * patch));
+    if (!cell_xy_out || !n_out) return h->fail(KEEP_EINVAL, "region_grid: null output");
+    const int64_t gx = W >= patch ? (W - patch) / step + 1 : 0, gy = H >= patch ? (H - patch) / step + 1 : 0;
+    const int64_t ncells = gx * gy;
+    if (ncells > INT32_MAX) return h->fail(KEEP_EINVAL, "region_grid: %lld cells (limit 2^31 - 1)", (long long)ncells);
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (ncells == 0) {
+        HIPCHK(h, hipMemsetAsync(n_out, 0, sizeof(int64_t), s));
+        return KEEP_OK;
+    }
+    const int64_t nb = (ncells + REGION_GRID_CHUNK - 1) / REGION_GRID_CHUNK;
+    const size_t b_keep = align_up((size_t)ncells), b_counts = align_up((size_t)nb * 4);
+    rc = ensure_arena(h, b_keep + 2 * b_counts);
+    if (rc) return rc;
+    launch_region_grid(region, row_stride_bytes, pix_stride, (int)gx, ncells, (int)patch, (int)step, sat_min, (int)min_pixels,
+                       (unsigned char*)h->arena, (int*)(h->arena + b_keep), (int*)(h->arena + b_keep + b_counts), cell_xy_out, n_out, s);
+    return check_launch(h, "region_grid");
+}
+
+int keep_region_patches_u8(keep_handle* h, const unsigned char* region, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
+                           const int32_t* cell_xy, int64_t B, int64_t patch, const int32_t* xbounds, const int32_t* xweights, int xksize,
+                           const int32_t* ybounds, const int32_t* yweights, int yksize, unsigned char* out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    int rc = region_view_check(h, region, H, W, row_stride_bytes, pix_stride, patch);
+    if (rc) return rc;
+    if (B < 0 || B > INT32_MAX / 224 || (B > 0 && (!cell_xy || !out))) return h->fail(KEEP_EINVAL, "region_patches: bad B %lld or null pointer", (long long)B);
+    if (patch != 224 && (!xbounds || !xweights || !ybounds || !yweights || xksize < 1 || yksize < 1))
+        return h->fail(KEEP_EINVAL, "region_patches: patch %lld needs the Resize(224) tables", (long long)patch);
+    if (patch > H || patch > W) return h->fail(KEEP_EINVAL, "region_patches: patch %lld larger than the region %lldx%lld", (long long)patch,
+                                               (long long)W, (long long)H);
+    if (B == 0) return KEEP_OK;
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    // [flag][horizontally resized rows]: the flag is read back before any pixel is touched (the one synchronisation of this call),
+    // so a cell outside the region is an error, not an out-of-bounds read
+    const size_t b_flag = align_up(sizeof(int)), b_tmp = patch == 224 ? 0 : align_up((size_t)B * patch * 224 * 3);
+    rc = ensure_arena(h, b_flag + b_tmp);
+    if (rc) return rc;
+    int* bad = (int*)h->arena;
+    HIPCHK(h, hipMemsetAsync(bad, 0, sizeof(int), s));
+    launch_region_check_cells(cell_xy, (int)B, H, W, (int)patch, bad, s);
+    rc = check_launch(h, "region_check_cells");
+    if (rc) return rc;
+    int bad_h = 0;
+    HIPCHK(h, hipMemcpyAsync(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (bad_h) return h->fail(KEEP_EINVAL, "region_patches: a cell (x, y) has x < 0, y < 0, x + %lld > %lld or y + %lld > %lld", (long long)patch,
+                              (long long)W, (long long)patch, (long long)H);
+    launch_region_patches_u8(region, row_stride_bytes, pix_stride, cell_xy, (int)B, (int)patch, xbounds, xweights, xksize, ybounds, yweights,
+                             yksize, (unsigned char*)h->arena + b_flag, out, s);
+    return check_launch(h, "region_patches_u8");
+}
+
+int keep_tissue_median_hist(keep_handle* h, const unsigned char* thumb, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
+                            int ksize, unsigned char* median_out, int32_t* hist_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!thumb || H < 1 || W < 1) return h->fail(KEEP_EINVAL, "tissue_median_hist: null pointer or empty shape %lldx%lld", (long long)H, (long long)W);
+    if (int rc = pix_stride_check(h, "tissue_median_hist", pix_stride)) return rc;
+    if (!pixels_ok(H, W, TISSUE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "tissue_median_hist: %lldx%lld pixels (limit H W <= 2^30)", (long long)H, (long long)W);
+    if (int rc = row_stride_check(h, "tissue_median_hist", W, row_stride_bytes, pix_stride)) return rc;
+    if (ksize < 1 || ksize > 15 || ksize % 2 == 0) return h->fail(KEEP_EINVAL, "tissue_median_hist: ksize %d (odd, 1..15)", ksize);
+    if (!median_out || !hist_out) return h->fail(KEEP_EINVAL, "tissue_median_hist: null output");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(h, hipMemsetAsync(hist_out, 0, 256 * sizeof(int32_t), s));
+    if (launch_tissue_median_hist(thumb, row_stride_bytes, pix_stride, (int)H, (int)W, ksize, median_out, hist_out, s))
+        return h->fail(KEEP_EUNSUPPORTED, "tissue_median_hist: no kernel for ksize %d", ksize);
+    return check_launch(h, "tissue_median_hist");
+}
+
+int keep_tissue_mask(keep_handle* h, const unsigned char* median, int64_t H, int64_t W, int threshold, int close, int64_t min_hole,
+                     int64_t min_area, unsigned char* mask_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!median || !mask_out || median == mask_out) return h->fail(KEEP_EINVAL, "tissue_mask: null pointer, or mask_out aliases median");
+    if (!pixels_ok(H, W, TISSUE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "tissue_mask: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (threshold < 0 || threshold > 255) return h->fail(KEEP_EINVAL, "tissue_mask: threshold %d outside [0, 255]", threshold);
+    if (close < 0 || close > 31) return h->fail(KEEP_EINVAL, "tissue_mask: close %d outside [0, 31]", close);
+    if (min_hole < 0 || min_area < 0) return h->fail(KEEP_EINVAL, "tissue_mask: min_hole %lld / min_area %lld < 0", (long long)min_hole, (long long)min_area);
+    KEEP_ON_DEVICE(h);
+    const size_t n = (size_t)(H * W);
+    const bool label = min_hole > 0 || min_area > 0;
+    const size_t b_tmp = close > 0 ? align_up(n) : 0, b_lab = label ? align_up(n * 4) : 0;
+    int rc = ensure_arena(h, b_tmp + 2 * b_lab);
+    if (rc) return rc;
+    // an area never exceeds H W <= 2^30: larger bounds decide the same
+    launch_tissue_mask(median, (int)H, (int)W, threshold, close, (int)std::min<int64_t>(min_hole, TISSUE_MAX_PIXELS),
+                       (int)std::min<int64_t>(min_area, TISSUE_MAX_PIXELS), (unsigned char*)h->arena, (int*)(h->arena + b_tmp),
+                       (int*)(h->arena + b_tmp + b_lab), h->err_flag, mask_out, (hipStream_t)stream);
+    return check_launch(h, "tissue_mask");
+}
+
+int keep_region_grid_mask(keep_handle* h, const unsigned char* mask, int64_t mh, int64_t mw, int64_t downsample, int64_t H, int64_t W,
+                          int64_t patch, int64_t step, int64_t origin_x, int64_t origin_y, int mode, int32_t* cell_xy_out, int64_t* n_out,
+                          void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!mask || mh < 1 || mw < 1 || mh > INT32_MAX || mw > INT32_MAX)
+        return h->fail(KEEP_EINVAL, "region_grid_mask: null mask or bad mask shape %lldx%lld", (long long)mh, (long long)mw);
+    if (downsample < 1 || downsample > INT32_MAX) return h->fail(KEEP_EINVAL, "region_grid_mask: downsample %lld < 1", (long long)downsample);
+    if (H < 1 || W < 1 || H > INT32_MAX || W > INT32_MAX) return h->fail(KEEP_EINVAL, "region_grid_mask: region shape %lldx%lld", (long long)H, (long long)W);
+    if (patch < 16 || patch > REGION_MAX_PATCH) return h->fail(KEEP_EINVAL, "region_grid_mask: patch %lld outside [16, %d]", (long long)patch, REGION_MAX_PATCH);
+    if (step < 1) return h->fail(KEEP_EINVAL, "region_grid_mask: step %lld < 1", (long long)step);
+    if (int rc = origin_check(h, "region_grid_mask", origin_x, origin_y)) return rc;
+    if (mode < KEEP_MASK_FOUR_PT || mode > KEEP_MASK_CENTER) return h->fail(KEEP_EINVAL, "region_grid_mask: mode %d (0 four_pt, 1 four_pt_hard, 2 center)", mode);
+    if (!cell_xy_out || !n_out) return h->fail(KEEP_EINVAL, "region_grid_mask: null output");
+    const int64_t gx = W >= patch ? (W - patch) / step + 1 : 0, gy = H >= patch ? (H - patch) / step + 1 : 0;
+    const int64_t ncells = gx * gy;
+    if (ncells > INT32_MAX) return h->fail(KEEP_EINVAL, "region_grid_mask: %lld cells (limit 2^31 - 1)", (long long)ncells);
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (ncells == 0) {
+        HIPCHK(h, hipMemsetAsync(n_out, 0, sizeof(int64_t), s));
+        return KEEP_OK;
+    }
+    const int64_t nb = (ncells + REGION_GRID_CHUNK - 1) / REGION_GRID_CHUNK;
+    const size_t b_keep = align_up((size_t)ncells), b_counts = align_up((size_t)nb * 4);
+    int rc = ensure_arena(h, b_keep + 2 * b_counts);
+    if (rc) return rc;
+    unsigned char* keep = (unsigned char*)h->arena;
+    launch_tissue_grid_cells(mask, mh, mw, downsample, (int)gx, ncells, (int)patch, (int)step, origin_x, origin_y, mode, keep, s);
+    launch_region_compact(keep, (int)gx, ncells, (int)step, (int*)(h->arena + b_keep), (int*)(h->arena + b_keep + b_counts), cell_xy_out, n_out, s);
+    return check_launch(h, "region_grid_mask");
+}
+
+int keep_heat_accumulate(keep_handle* h, const int64_t* coords, const float* values, int64_t N, int64_t patch, int64_t downsample,
+                         int64_t H, int64_t W, int64_t origin_x, int64_t origin_y, int zero_first, int64_t* acc, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "heat_accumulate: acc is null or not 8-byte aligned");
+    if (N < 0 || N > HEAT_MAX_TILES) return h->fail(KEEP_EINVAL, "heat_accumulate: %lld tiles (0 .. 2^24 - 1)", (long long)N);
+    if (N > 0 && (!coords || !values)) return h->fail(KEEP_EINVAL, "heat_accumulate: null coords or values");
+    if (!pixels_ok(H, W, HEAT_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "heat_accumulate: %lldx%lld: raster shape (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (patch < 1 || patch > HEAT_MAX_PATCH) return h->fail(KEEP_EINVAL, "heat_accumulate: patch %lld outside [1, 2^30]", (long long)patch);
+    if (downsample < 1 || downsample > patch)
+        return h->fail(KEEP_EINVAL, "heat_accumulate: downsample %lld outside [1, patch = %lld]", (long long)downsample, (long long)patch);
+    if (int rc = origin_check(h, "heat_accumulate", origin_x, origin_y)) return rc;
+    if (origin_x % downsample || origin_y % downsample)
+        return h->fail(KEEP_EINVAL, "heat_accumulate: origin (%lld, %lld) is not a multiple of downsample %lld", (long long)origin_x,
+                       (long long)origin_y, (long long)downsample);
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (zero_first) HIPCHK(h, hipMemsetAsync(acc, 0, (size_t)(H * W) * sizeof(int64_t), s));
+    launch_heat_accumulate(coords, values, N, patch, downsample, (int)H, (int)W, origin_x, origin_y, acc, s);
+    return check_launch(h, "heat_accumulate");
+}
+
+int keep_heat_mean(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, float uncovered, float* mean_out, int32_t* count_out,
+                   unsigned char* pred_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "heat_mean: acc is null or not 8-byte aligned");
+    if (!pixels_ok(H, W, HEAT_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "heat_mean: %lldx%lld: raster shape (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (!mean_out && !count_out && !pred_out) return h->fail(KEEP_EINVAL, "heat_mean: no output");
+    if (((uintptr_t)mean_out & 3) || ((uintptr_t)count_out & 3)) return h->fail(KEEP_EINVAL, "heat_mean: mean_out / count_out not 4-byte aligned");
+    KEEP_ON_DEVICE(h);
+    launch_heat_mean(acc, (int)H, (int)W, uncovered, mean_out, count_out, pred_out, (hipStream_t)stream);
+    return check_launch(h, "heat_mean");
+}
+
+int keep_heat_render(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, const unsigned char* thumb, int64_t row_stride_bytes,
+                     int pix_stride, int background_rgb, const unsigned char* mask, const unsigned char* lut, int alpha, int lo16, int hi16,
+                     int min16, unsigned char* out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "heat_render: acc is null or not 8-byte aligned");
+    if (!lut || !out) return h->fail(KEEP_EINVAL, "heat_render: null lut or output");
+    if (!pixels_ok(H, W, HEAT_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "heat_render: %lldx%lld: raster shape (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (thumb) {
+        if (int rc = pix_stride_check(h, "heat_render", pix_stride)) return rc;
+        if (int rc = row_stride_check(h, "heat_render", W, row_stride_bytes, pix_stride)) return rc;
+    } else if (background_rgb < 0 || background_rgb > 0xFFFFFF) {
+        return h->fail(KEEP_EINVAL, "heat_render: background 0x%x outside [0, 0xFFFFFF]", background_rgb);
+    }
+    if (alpha < 0 || alpha > 256) return h->fail(KEEP_EINVAL, "heat_render: alpha %d outside [0, 256]", alpha);
+    if (lo16 < 0 || hi16 > 65535 || lo16 >= hi16) return h->fail(KEEP_EINVAL, "heat_render: window [%d, %d] (0 <= lo16 < hi16 <= 65535)", lo16, hi16);
+    if (min16 < 0 || min16 > 65535) return h->fail(KEEP_EINVAL, "heat_render: min16 %d outside [0, 65535]", min16);
+    KEEP_ON_DEVICE(h);
+    launch_heat_render(acc, (int)H, (int)W, thumb, row_stride_bytes, pix_stride, (unsigned)background_rgb, mask, lut, alpha, lo16, hi16, min16,
+                       out, (hipStream_t)stream);
+    return check_launch(h, "heat_render");
+}
+
+int keep_heat_smooth(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, const unsigned char* mask, const int32_t* taps, int radius,
+                     int64_t* acc_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "heat_smooth: acc is null or not 8-byte aligned");
+    if (!acc_out || ((uintptr_t)acc_out & 7)) return h->fail(KEEP_EINVAL, "heat_smooth: acc_out is null or not 8-byte aligned");
+    if (acc_out == acc) return h->fail(KEEP_EINVAL, "heat_smooth: acc_out aliases acc");
+    if (!pixels_ok(H, W, HEAT_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "heat_smooth: %lldx%lld: raster shape (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (!taps || ((uintptr_t)taps & 3)) return h->fail(KEEP_EINVAL, "heat_smooth: taps is null or not 4-byte aligned");
+    if (radius < 1 || radius > HEAT_SMOOTH_MAX_RADIUS) return h->fail(KEEP_EINVAL, "heat_smooth: radius %d outside [1, %d]", radius, HEAT_SMOOTH_MAX_RADIUS);
+    KEEP_ON_DEVICE(h);
+    const size_t n = (size_t)(H * W), b_a = align_up(n * 4);
+    int rc = ensure_arena(h, b_a + align_up(n * 2));
+    if (rc) return rc;
+    launch_heat_smooth(acc, (int)H, (int)W, mask, taps, radius, (unsigned*)h->arena, (unsigned short*)(h->arena + b_a), acc_out, (hipStream_t)stream);
+    return check_launch(h, "heat_smooth");
+}
+
+int keep_sort_f32(keep_handle* h, const float* values, int64_t M, float* sorted_out, int64_t* n_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (M < 1 || M > SORT_MAX) return h->fail(KEEP_EINVAL, "sort_f32: %lld values (1 .. 2^24 - 1)", (long long)M);
+    if (!values || !sorted_out || !n_out) return h->fail(KEEP_EINVAL, "sort_f32: null pointer");
+    if (((uintptr_t)values & 3) || ((uintptr_t)sorted_out & 3) || ((uintptr_t)n_out & 7)) return h->fail(KEEP_EINVAL, "sort_f32: values / sorted_out / n_out not aligned");
+    KEEP_ON_DEVICE(h);
+    size_t table_off, totals_off;
+    int rc = ensure_arena(h, sort_workspace_bytes(M, &table_off, &totals_off));
+    if (rc) return rc;
+    launch_sort_f32(values, M, (unsigned char*)h->arena, sorted_out, n_out, (hipStream_t)stream);
+    return check_launch(h, "sort_f32");
+}
+
+int keep_rank_f32(keep_handle* h, const float* sorted, int64_t M, const int64_t* n_dev, const float* queries, int64_t N, int self,
+                  float* pct_out, int32_t* less_out, int32_t* eq_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (M < 1 || M > SORT_MAX) return h->fail(KEEP_EINVAL, "rank_f32: a population of %lld values (1 .. 2^24 - 1)", (long long)M);
+    if (N < 0 || N > SORT_MAX) return h->fail(KEEP_EINVAL, "rank_f32: %lld queries (0 .. 2^24 - 1)", (long long)N);
+    if (!sorted || !n_dev || (N > 0 && !queries)) return h->fail(KEEP_EINVAL, "rank_f32: null sorted, n or queries");
+    if (self != 0 && self != 1) return h->fail(KEEP_EINVAL, "rank_f32: self %d (0 or 1)", self);
+    if (!pct_out && !less_out && !eq_out) return h->fail(KEEP_EINVAL, "rank_f32: no output");
+    if (((uintptr_t)sorted & 3) || ((uintptr_t)n_dev & 7) || ((uintptr_t)queries & 3) || ((uintptr_t)pct_out & 3) || ((uintptr_t)less_out & 3) ||
+        ((uintptr_t)eq_out & 3))
+        return h->fail(KEEP_EINVAL, "rank_f32: a pointer is not aligned");
+    KEEP_ON_DEVICE(h);
+    launch_rank_f32(sorted, M, n_dev, queries, N, self, pct_out, less_out, eq_out, (hipStream_t)stream);
+    return check_launch(h, "rank_f32");
+}
+
+int keep_regions_label(keep_handle* h, const unsigned char* mask, int64_t H, int64_t W, int connectivity, int64_t min_area, int32_t* labels_out,
+                       int64_t* n_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!mask || !labels_out || !n_out) return h->fail(KEEP_EINVAL, "regions_label: null pointer");
+    if (!pixels_ok(H, W, TISSUE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "regions_label: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (connectivity != 4 && connectivity != 8) return h->fail(KEEP_EINVAL, "regions_label: connectivity %d (4 or 8)", connectivity);
+    if (min_area < 1) return h->fail(KEEP_EINVAL, "regions_label: min_area %lld < 1", (long long)min_area);
+    if (((uintptr_t)labels_out & 3) || ((uintptr_t)n_out & 7)) return h->fail(KEEP_EINVAL, "regions_label: labels_out / n_out not aligned");
+    KEEP_ON_DEVICE(h);
+    const size_t n = (size_t)(H * W);
+    const size_t b_lab = align_up(n * 4), b_counts = align_up(((n + REGIONS_SCAN_CHUNK - 1) / REGIONS_SCAN_CHUNK) * sizeof(int));
+    int rc = ensure_arena(h, 2 * b_lab + 2 * b_counts);
+    if (rc) return rc;
+    // an area never exceeds H W <= 2^30: a larger bound decides the same (every component is dropped)
+    launch_regions_label(mask, (int)H, (int)W, connectivity == 8, (int)std::min<int64_t>(min_area, TISSUE_MAX_PIXELS + 1), (int*)h->arena,
+                         (int*)(h->arena + b_lab), (int*)(h->arena + 2 * b_lab), (int*)(h->arena + 2 * b_lab + b_counts), h->err_flag,
+                         labels_out, n_out, (hipStream_t)stream);
+    return check_launch(h, "regions_label");
+}
+
+int keep_regions_table(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, const int64_t* acc, int64_t* table_out,
+                       void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "regions_table: labels is null or not 4-byte aligned");
+    if (!pixels_ok(H, W, TISSUE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "regions_table: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (n < 0 || n > H * W) return h->fail(KEEP_EINVAL, "regions_table: n = %lld outside [0, H W]", (long long)n);
+    if ((uintptr_t)acc & 7) return h->fail(KEEP_EINVAL, "regions_table: acc is not 8-byte aligned");
+    if (n > 0 && (!table_out || ((uintptr_t)table_out & 7))) return h->fail(KEEP_EINVAL, "regions_table: table_out is null or not 8-byte aligned");
+    KEEP_ON_DEVICE(h);
+    launch_regions_table(labels, (int)H, (int)W, n, acc, table_out, (hipStream_t)stream);
+    return check_launch(h, "regions_table");
+}
+
+int keep_outline_count(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, int connectivity, int64_t* counts_out,
+                       void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "outline_count: labels is null or not 4-byte aligned");
+    if (!pixels_ok(H, W, OUTLINE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "outline_count: %lldx%lld pixels (1 <= H W <= 2^28)", (long long)H, (long long)W);
+    if (n < 0 || n > H * W) return h->fail(KEEP_EINVAL, "outline_count: n = %lld outside [0, H W]", (long long)n);
+    if (connectivity != 4 && connectivity != 8) return h->fail(KEEP_EINVAL, "outline_count: connectivity %d (4 or 8)", connectivity);
+    if (!counts_out || ((uintptr_t)counts_out & 7)) return h->fail(KEEP_EINVAL, "outline_count: counts_out is null or not 8-byte aligned");
+    KEEP_ON_DEVICE(h);
+    int rc = ensure_arena(h, outline_count_workspace_bytes(H * W));
+    if (rc) return rc;
+    launch_outline_count(labels, (int)H, (int)W, (int)n, (unsigned char*)h->arena, counts_out, (hipStream_t)stream);
+    return check_launch(h, "outline_count");
+}
+
+int keep_outline_trace(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, int connectivity, int64_t E, int64_t V,
+                       int32_t* vertices_out, int64_t* rings_out, int64_t ring_cap, int64_t* r_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "outline_trace: labels is null or not 4-byte aligned");
+    if (!pixels_ok(H, W, OUTLINE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "outline_trace: %lldx%lld pixels (1 <= H W <= 2^28)", (long long)H, (long long)W);
+    if (n < 1 || n > H * W) return h->fail(KEEP_EINVAL, "outline_trace: n = %lld outside [1, H W] (without a region there is nothing to trace)", (long long)n);
+    if (connectivity != 4 && connectivity != 8) return h->fail(KEEP_EINVAL, "outline_trace: connectivity %d (4 or 8)", connectivity);
+    if (E < 4 || E > 4 * H * W || V < 4 || V > E)
+        return h->fail(KEEP_EINVAL, "outline_trace: E = %lld, V = %lld (4 <= V <= E <= 4 H W: the values keep_outline_count wrote)", (long long)E,
+                       (long long)V);
+    if (!vertices_out || ((uintptr_t)vertices_out & 3)) return h->fail(KEEP_EINVAL, "outline_trace: vertices_out is null or not 4-byte aligned");
+    if (ring_cap < 0) return h->fail(KEEP_EINVAL, "outline_trace: ring_cap %lld < 0", (long long)ring_cap);
+    if (ring_cap > 0 && (!rings_out || ((uintptr_t)rings_out & 7))) return h->fail(KEEP_EINVAL, "outline_trace: rings_out is null or not 8-byte aligned");
+    if (!r_out || ((uintptr_t)r_out & 7)) return h->fail(KEEP_EINVAL, "outline_trace: r_out is null or not 8-byte aligned");
+    KEEP_ON_DEVICE(h);
+    int rc = ensure_arena(h, outline_trace_workspace_bytes(H * W, E));
+    if (rc) return rc;
+    launch_outline_trace(labels, (int)H, (int)W, (int)n, connectivity == 8, (int)E, V, (unsigned char*)h->arena, vertices_out, rings_out, ring_cap,
+                         r_out, (hipStream_t)stream);
+    return check_launch(h, "outline_trace");
+}
+
+int keep_outline_draw(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, const unsigned char* rgb_in, unsigned char* rgb_out, int color,
+                      int width, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "outline_draw: labels is null or not 4-byte aligned");
+    if (!rgb_in || !rgb_out) return h->fail(KEEP_EINVAL, "outline_draw: null image");
+    if (!pixels_ok(H, W, OUTLINE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "outline_draw: %lldx%lld pixels (1 <= H W <= 2^28)", (long long)H, (long long)W);
+    if (color < 0 || color > 0xFFFFFF) return h->fail(KEEP_EINVAL, "outline_draw: color 0x%x outside [0, 0xFFFFFF]", color);
+    if (width < 1 || width > OUTLINE_MAX_WIDTH) return h->fail(KEEP_EINVAL, "outline_draw: width %d outside [1, %d]", width, OUTLINE_MAX_WIDTH);
+    KEEP_ON_DEVICE(h);
+    int rc = ensure_arena(h, align_up((size_t)(H * W)));
+    if (rc) return rc;
+    launch_outline_draw(labels, (int)H, (int)W, rgb_in, rgb_out, (unsigned)color, width, (unsigned char*)h->arena, (hipStream_t)stream);
+    return check_launch(h, "outline_draw");
+}
+
+int keep_poly_fill(keep_handle* h, const int64_t* vertices, int64_t V, const int64_t* ring_start, int64_t R, const int32_t* weight,
+                   int64_t downsample, int64_t H, int64_t W, int64_t origin_x, int64_t origin_y, int rule, int value, const unsigned char* into,
+                   unsigned char* out, int64_t* crossings_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (crossings_out) *crossings_out = 0;
+    if (H < 1 || W < 1 || H > POLY_MAX_CELLS || W > POLY_MAX_CELLS || H * (W + 1) > POLY_MAX_CELLS)
+        return h->fail(KEEP_EINVAL, "poly_fill: %lldx%lld pixels (h, w >= 1, h (w + 1) <= 2^28)", (long long)H, (long long)W);
+    if (downsample < 1 || downsample > POLY_MAX_DOWNSAMPLE) return h->fail(KEEP_EINVAL, "poly_fill: downsample %lld outside [1, 4096]", (long long)downsample);
+    if (origin_x < -POLY_MAX_COORD || origin_x > POLY_MAX_COORD || origin_y < -POLY_MAX_COORD || origin_y > POLY_MAX_COORD)
+        return h->fail(KEEP_EINVAL, "poly_fill: origin (%lld, %lld) outside +-2^26", (long long)origin_x, (long long)origin_y);
+    if (rule != KEEP_FILL_UNION && rule != KEEP_FILL_EVENODD) return h->fail(KEEP_EINVAL, "poly_fill: rule %d (0 union, 1 evenodd)", rule);
+    if (value < 0 || value > 255) return h->fail(KEEP_EINVAL, "poly_fill: value %d outside [0, 255]", value);
+    if (V < 0 || V > POLY_MAX_VERTICES || R < 0 || R > POLY_MAX_RINGS || V < 3 * R || (V > 0 && R == 0))
+        return h->fail(KEEP_EINVAL, "poly_fill: V = %lld, R = %lld (V <= 2^24, R <= 2^20, every ring has >= 3 vertices)", (long long)V, (long long)R);
+    if (R > 0 && (!vertices || !ring_start || !weight)) return h->fail(KEEP_EINVAL, "poly_fill: null vertices, ring_start or weight");
+    if (((uintptr_t)vertices & 7) || ((uintptr_t)ring_start & 7) || ((uintptr_t)weight & 3))
+        return h->fail(KEEP_EINVAL, "poly_fill: vertices / ring_start / weight not aligned");
+    if (!out) return h->fail(KEEP_EINVAL, "poly_fill: out is null");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = ensure_arena(h, poly_fill_workspace_bytes(H, W, V));
+    if (rc) return rc;
+    unsigned char* ws = (unsigned char*)h->arena;
+    if (R == 0) {
+        HIPCHK(h, hipMemsetAsync(ws, 0, (size_t)H * (size_t)(W + 1) * 4, s));
+    } else {
+        const int64_t* c_dev = launch_poly_count(vertices, V, ring_start, R, weight, downsample, (int)H, (int)W, origin_x, origin_y, ws, s);
+        rc = check_launch(h, "poly_fill (edges)");
+        if (rc) return rc;
+        int64_t C = 0;
+        HIPCHK(h, hipMemcpyAsync(&C, c_dev, sizeof C, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));                  // the one host synchronisation: C sizes the grid
+        if (crossings_out) *crossings_out = C;
+        if (C < 0 || C >= POLY_MAX_CROSSINGS)
+            return h->fail(KEEP_EINVAL, "poly_fill: %lld crossings of edges with rows (< 2^31): fill at a larger downsample", (long long)C);
+        if (C > 0) launch_poly_crossings(vertices, V, downsample, (int)H, (int)W, origin_x, origin_y, C, ws, s);
+    }
+    launch_poly_rows((int)H, (int)W, rule == KEEP_FILL_EVENODD, value, into, out, ws, s);
+    return check_launch(h, "poly_fill");
+}
+
+int keep_mask_tile_counts(keep_handle* h, const unsigned char* mask, int64_t H, int64_t W, int64_t downsample, int64_t origin_x, int64_t origin_y,
+                          const int64_t* coords, int64_t N, int64_t patch, int32_t* counts_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!mask) return h->fail(KEEP_EINVAL, "mask_tile_counts: mask is null");
+    if (!pixels_ok(H, W, TISSUE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "mask_tile_counts: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (downsample < 1 || downsample > HEAT_MAX_PATCH) return h->fail(KEEP_EINVAL, "mask_tile_counts: downsample %lld outside [1, 2^30]", (long long)downsample);
+    if (patch < 1 || patch > HEAT_MAX_PATCH) return h->fail(KEEP_EINVAL, "mask_tile_counts: patch %lld outside [1, 2^30]", (long long)patch);
+    if (int rc = origin_check(h, "mask_tile_counts", origin_x, origin_y)) return rc;
+    if (N < 0 || N > HEAT_MAX_TILES) return h->fail(KEEP_EINVAL, "mask_tile_counts: %lld tiles (0 .. 2^24 - 1)", (long long)N);
+    if (N > 0 && (!coords || ((uintptr_t)coords & 7))) return h->fail(KEEP_EINVAL, "mask_tile_counts: coords is null or not 8-byte aligned");
+    if (N > 0 && (!counts_out || ((uintptr_t)counts_out & 7))) return h->fail(KEEP_EINVAL, "mask_tile_counts: counts_out is null or not 8-byte aligned");
+    if (N == 0) return KEEP_OK;
+    KEEP_ON_DEVICE(h);
+    launch_mask_tile_counts(mask, (int)H, (int)W, downsample, origin_x, origin_y, coords, N, patch, counts_out, (hipStream_t)stream);
+    return check_launch(h, "mask_tile_counts");
+}
+
+int keep_eval_roc(keep_handle* h, const float* scores, const unsigned char* labels, int64_t N, int64_t* scalars_out, float* thresholds_out,
+                  int32_t* fps_out, int32_t* tps_out, unsigned char* kept_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (N < 0 || N > SORT_MAX) return h->fail(KEEP_EINVAL, "eval_roc: %lld tiles (0 .. 2^24 - 1)", (long long)N);
+    if (N > 0 && (!scores || !labels)) return h->fail(KEEP_EINVAL, "eval_roc: null scores or labels");
+    if (!scalars_out || ((uintptr_t)scalars_out & 7)) return h->fail(KEEP_EINVAL, "eval_roc: scalars_out is null or not 8-byte aligned");
+    const int given = (thresholds_out != nullptr) + (fps_out != nullptr) + (tps_out != nullptr) + (kept_out != nullptr);
+    if (given != 0 && given != 4) return h->fail(KEEP_EINVAL, "eval_roc: the four curve outputs go together: all or none");
+    if (((uintptr_t)scores & 3) || ((uintptr_t)thresholds_out & 3) || ((uintptr_t)fps_out & 3) || ((uintptr_t)tps_out & 3))
+        return h->fail(KEEP_EINVAL, "eval_roc: scores / thresholds_out / fps_out / tps_out not 4-byte aligned");
+    KEEP_ON_DEVICE(h);
+    int rc = ensure_arena(h, eval_roc_workspace_bytes(N, given == 0));
+    if (rc) return rc;
+    launch_eval_roc(scores, labels, N, (unsigned char*)h->arena, scalars_out, thresholds_out, fps_out, tps_out, kept_out, (hipStream_t)stream);
+    return check_launch(h, "eval_roc");
+}
+
+int keep_eval_mask_counts(keep_handle* h, const unsigned char* a, const unsigned char* b, const unsigned char* within, int64_t H, int64_t W,
+                          int64_t* counts_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!a || !b) return h->fail(KEEP_EINVAL, "eval_mask_counts: a mask is null");
+    if (!pixels_ok(H, W, TISSUE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "eval_mask_counts: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (!counts_out || ((uintptr_t)counts_out & 7)) return h->fail(KEEP_EINVAL, "eval_mask_counts: counts_out is null or not 8-byte aligned");
+    KEEP_ON_DEVICE(h);
+    launch_eval_mask_counts(a, b, within, H * W, counts_out, (hipStream_t)stream);
+    return check_launch(h, "eval_mask_counts");
+}
+
+int keep_eval_raster_hist(keep_handle* h, const int64_t* acc, const unsigned char* truth, const unsigned char* within, int64_t H, int64_t W,
+                          int64_t* hist_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "eval_raster_hist: acc is null or not 8-byte aligned");
+    if (!truth) return h->fail(KEEP_EINVAL, "eval_raster_hist: truth is null");
+    if (!pixels_ok(H, W, TISSUE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "eval_raster_hist: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (!hist_out || ((uintptr_t)hist_out & 7)) return h->fail(KEEP_EINVAL, "eval_raster_hist: hist_out is null or not 8-byte aligned");
+    KEEP_ON_DEVICE(h);
+    launch_eval_raster_hist(acc, truth, within, H * W, hist_out, (hipStream_t)stream);
+    return check_launch(h, "eval_raster_hist");
+}
+
+}  // extern "C"

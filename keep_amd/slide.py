@@ -1,0 +1,644 @@
+"""The slide-analysis methods of ``KEEPModel``: patch grid and tiles of a region, tissue mask, heatmap raster, percentiles and
+smoothing, region table, outlines, polygon fill and segmentation evaluation (DESIGN.md sections 10-17).  Thin wrappers of the
+entry points in csrc/slide_api.hip; the argument checks and the numpy references live in the feature modules imported below."""
+from __future__ import annotations
+
+import ctypes as C
+import struct
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .annotation import PolygonSet, check_fill_args, check_into, check_tile_args, polygon_arrays
+from .components import NCOLS as REGION_COLS, RegionTable, check_raster, check_region_count, check_regions_args, mask_tensor
+from .evaluation import HIST_BINS, MaskOverlap, RocResult, check_mask, check_roc_args, check_same_geometry, plan_label_bands, sweep_from_hist
+from .heatmap import (MAX_TILES, ScoreReference, TileRaster, check_raster_args, check_tiles, check_values, colormap as colormap_table, render_args,
+                      smooth_taps)
+from .outline import NCOLS as RING_COLS, RegionOutlines, check_draw_args, check_outline_args, check_ring_count, regions_labels, rgb_tensor
+from .region import (MASK_MODES, TILE, TissueMask, TissueSegmentation, check_downsample, check_grid_args, grid_shape, otsu_threshold, region_layout,
+                     resize_tables, thumbnail_layout, tissue_params)
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _stream(device: torch.device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _check_tile_raster(raster) -> None:
+    if not isinstance(raster, TileRaster):
+        raise ValueError(f"raster must be a TileRaster, got {type(raster).__name__}")
+
+
+def _check_tissue(tissue, raster) -> None:
+    """``tissue=`` beside a raster: a ``TissueMask`` of the raster's downsample and shape."""
+    if not isinstance(tissue, TissueMask):
+        raise ValueError(f"tissue must be a TissueMask, got {type(tissue).__name__}")
+    if tissue.downsample != raster.downsample or tuple(tissue.mask.shape) != raster.shape:
+        raise ValueError(f"tissue mask has downsample {tissue.downsample} and shape {tuple(tissue.mask.shape)}, the raster "
+                         f"{raster.downsample} and {raster.shape}")
+
+
+class SlideOps:
+    """Base of ``KEEPModel``, which supplies what these methods use of the engine: ``_handle``, ``_device``, ``_ready()``,
+    ``_ready_device()``, ``_queue_flag_check()``, ``encode_image_uint8()``, ``config`` and ``_heat_luts``."""
+
+    def _call(self, name: str, *args) -> None:
+        """``keep_<name>(handle, *args, current stream)``; a failure raises with the library's message, labelled ``name``."""
+        _lib.check(self._handle, getattr(_lib.load(), "keep_" + name)(self._handle, *args, _stream(self._device)), name)
+
+    def _on_device(self, a, dtype=None) -> torch.Tensor:
+        """numpy or torch, host or device -> contiguous on the engine's device, as ``dtype`` if one is given; a bool mask as uint8."""
+        t = (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a).to(self._device, dtype).contiguous()
+        return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+    def _raster_here(self, raster) -> None:
+        if raster.acc.device != self._device:
+            raise ValueError(f"the raster lives on {raster.acc.device}, this engine on {self._device}")
+
+    # ------------------------------------------------------------------ slide regions
+    @staticmethod
+    def _region_tensor(region) -> torch.Tensor:
+        """uint8 [H,W,3|4] tensor or numpy array, checked on the host (shape / dtype / pixel-stride errors before any device work)."""
+        x = torch.from_numpy(region) if not isinstance(region, torch.Tensor) else region
+        region_layout(x)
+        return x
+
+    def _region_on_device(self, x: torch.Tensor) -> Tuple[torch.Tensor, int, int, int, int]:
+        """-> (device view, H, W, C, row_stride_bytes); a device region of any row stride is used in place."""
+        if x.device != self._device:
+            x = x.to(self._device)                                 # a cropped host view arrives contiguous
+        H, W, C, row = region_layout(x)
+        return x, H, W, C, row
+
+    def _region_cells(self, xd: torch.Tensor, H: int, W: int, C: int, row: int, patch: int, step: int, sat_min: int,
+                      min_pixels: int) -> torch.Tensor:
+        """keep_region_grid -> the kept cells' (x, y) offsets in the region, int32 [N,2] on the device (reads N back: one sync)."""
+        gy, gx = grid_shape(H, W, patch, step)
+        if gy * gx == 0:
+            return torch.empty((0, 2), dtype=torch.int32, device=self._device)
+        cells = torch.empty((gy * gx, 2), dtype=torch.int32, device=self._device)
+        n = torch.empty((1,), dtype=torch.int64, device=self._device)
+        self._call("region_grid", _ptr(xd), H, W, row, C, patch, step, sat_min, min_pixels, _ptr(cells), _ptr(n))
+        return cells[:int(n.item())]
+
+    def _region_tiles(self, xd: torch.Tensor, H: int, W: int, C: int, row: int, cells: torch.Tensor, patch: int) -> torch.Tensor:
+        """keep_region_patches_u8: int32 [B,2] cells -> uint8 [B,224,224,3] tiles on the device."""
+        cells = cells.to(self._device, torch.int32).contiguous()
+        B = int(cells.shape[0])
+        out = torch.empty((B, TILE, TILE, 3), dtype=torch.uint8, device=self._device)
+        if patch == TILE:
+            xb = xk = None
+            xks = 0
+        else:
+            xb, xk, xks = resize_tables(patch, self._device)
+        self._call("region_patches_u8", _ptr(xd), H, W, row, C, _ptr(cells), B, patch, _ptr(xb), _ptr(xk), xks, _ptr(xb), _ptr(xk), xks, _ptr(out))
+        return out
+
+    def _mask_cells(self, mask, H: int, W: int, patch: int, step: int, origin) -> torch.Tensor:
+        """keep_region_grid_mask -> the kept cells' (x, y) offsets in an H x W region at ``origin``, int32 [N,2] on the device (reads N
+        back: one sync).  The region's pixels play no part."""
+        gy, gx = grid_shape(H, W, patch, step)
+        if gy * gx == 0:
+            return torch.empty((0, 2), dtype=torch.int32, device=self._device)
+        md = mask.mask.to(self._device)
+        cells = torch.empty((gy * gx, 2), dtype=torch.int32, device=self._device)
+        n = torch.empty((1,), dtype=torch.int64, device=self._device)
+        self._call("region_grid_mask", _ptr(md), int(md.shape[0]), int(md.shape[1]), mask.downsample, H, W, patch, step, origin[0], origin[1],
+                   MASK_MODES.index(mask.mode), _ptr(cells), _ptr(n))
+        return cells[:int(n.item())]
+
+    @torch.no_grad()
+    def tissue_mask(self, thumbnail, downsample: int, params=None):
+        """Tissue segmentation of a slide thumbnail on the device -> ``keep_amd.region.TissueMask``.
+
+        ``thumbnail``: uint8 [h,w,3] (RGB) or [h,w,4] (RGBA, alpha ignored), host or device, numpy or torch, any row stride,
+        ``h w <= 2^30``; one pixel of it covers ``downsample`` x ``downsample`` pixels of the level that will be tiled.  ``params``: a
+        ``keep_amd.region.TissueSegmentation`` (default: its defaults).  Stages, after CLAM's ``segmentTissue`` but on the pixel mask
+        instead of contour polygons, all in integers and equal to ``keep_amd.region.tissue_mask_numpy`` bit for bit: HSV saturation,
+        k x k median, fixed or Otsu threshold (the histogram is made on the device, the 256-candidate choice on the host; the
+        threshold used is ``.threshold`` of the result), closing, small holes filled, small fragments dropped.  The mask stays on
+        the engine's device; hand the result to ``region_grid`` / ``encode_region`` / ``extract_slide_features`` as ``tissue=``."""
+        params = TissueSegmentation() if params is None else params
+        if not isinstance(params, TissueSegmentation):
+            raise ValueError(f"params must be a TissueSegmentation, got {params!r}")
+        downsample = check_downsample(downsample)
+        x = torch.from_numpy(thumbnail) if not isinstance(thumbnail, torch.Tensor) else thumbnail
+        thumbnail_layout(x)
+        self._ready_device()
+        if x.device != self._device:
+            x = x.to(self._device)
+        h, w, C, row = thumbnail_layout(x)
+        med = torch.empty((h, w), dtype=torch.uint8, device=self._device)
+        hist = torch.empty((256,), dtype=torch.int32, device=self._device)
+        self._call("tissue_median_hist", _ptr(x), h, w, row, C, params.mthresh, _ptr(med), _ptr(hist))
+        t = otsu_threshold(hist.cpu().tolist()) if params.use_otsu else int(params.sthresh)
+        mask = torch.empty((h, w), dtype=torch.uint8, device=self._device)
+        self._call("tissue_mask", _ptr(med), h, w, t, params.close, params.min_hole, params.min_area, _ptr(mask))
+        self._queue_flag_check(_stream(self._device))
+        self.last_tissue_median, self.last_tissue_hist = med, hist                  # the intermediates, for inspection and tests
+        return TissueMask(mask, downsample, params.mode, t)
+
+    # ------------------------------------------------------------------ heatmap
+    @torch.no_grad()
+    def tile_raster(self, coords, values, patch_size: int, downsample: int, shape, origin=(0, 0), into=None):
+        """Per-tile values rasterised in slide geometry on the device -> ``keep_amd.heatmap.TileRaster``.
+
+        ``coords``: integers [N,2], level-0 ``(x, y)`` (the convention of ``wsi.refine`` / ``cood2str`` / ``region_grid``); ``values``:
+        floating point [N]; both host or device, numpy or torch.  ``patch_size``: a tile's footprint in the units of the coords
+        (``patch_size * coord_scale`` of ``encode_region``); one raster pixel covers ``downsample`` x ``downsample`` of them,
+        ``1 <= downsample <= patch_size``; ``shape``: the raster's ``(h, w)``, ``h w <= 2^30``; ``origin``: the level-0 position of raster
+        pixel (0, 0), a multiple of ``downsample``.  Tile n adds ``rint(clip(float32(v), 0, 1) * 65535)`` and a count of one to the
+        columns ``[(x - ox) // d, (x - ox + P) // d)`` and the rows likewise (floor division, clipped to the raster); a NaN value skips
+        its tile; duplicate coords each count (pass the output of ``wsi.refine`` for first-occurrence-wins).  Coordinates must stay
+        within +-2^62 (they are not read on the host).  ``into``: an earlier raster of the same geometry to add to; the result is the
+        same however the tiles are split over calls.  At most 2^24 - 1 tiles go into one raster.  No host synchronisation."""
+        patch, d, (h, w), origin = check_raster_args(patch_size, downsample, shape, origin)
+        c = coords if isinstance(coords, torch.Tensor) else torch.as_tensor(coords)
+        v = values if isinstance(values, torch.Tensor) else torch.as_tensor(values)
+        N = check_tiles(c, v)
+        if into is not None:
+            if not isinstance(into, TileRaster):
+                raise ValueError(f"into must be a TileRaster, got {type(into).__name__}")
+            into.check_geometry(patch, d, (h, w), origin)
+            into.claim(N)                                           # raises beyond the cap, before any device work
+        elif N > MAX_TILES:
+            raise ValueError(f"a raster takes at most 2^24 - 1 = {MAX_TILES} tiles in all, got {N}")
+        self._ready_device()
+        if into is None:
+            into, zero = TileRaster(torch.empty((h, w), dtype=torch.int64, device=self._device), d, patch, origin, N, self), 1
+        elif into.acc.device != self._device:
+            into.tiles -= N
+            raise ValueError(f"into= raster lives on {into.acc.device}, this engine on {self._device}")
+        else:
+            zero = 0
+        c = c.to(self._device, torch.int64).contiguous()
+        v = v.to(self._device, torch.float32).contiguous()
+        self._call("heat_accumulate", _ptr(c), _ptr(v), N, patch, d, h, w, origin[0], origin[1], zero, _ptr(into.acc))
+        return into
+
+    def _heat_read(self, raster, uncovered: float, mean: bool, count: bool, pred: bool):
+        """keep_heat_mean -> (mean fp32 | None, count int32 | None, pred uint8 | None), each [h,w] on the device."""
+        h, w = raster.shape
+        outs = [torch.empty((h, w), dtype=dt, device=self._device) if on else None
+                for on, dt in ((mean, torch.float32), (count, torch.int32), (pred, torch.uint8))]
+        self._call("heat_mean", _ptr(raster.acc), h, w, uncovered, _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]))
+        return tuple(outs)
+
+    @torch.no_grad()
+    def render_heatmap(self, raster, thumbnail=None, alpha: float = 0.4, colormap="jet", tissue=None, window=(0.0, 1.0),
+                       min_value: float = 0.0, background=(255, 255, 255)) -> torch.Tensor:
+        """The raster's mean, coloured and blended over the thumbnail -> uint8 [h,w,3] on the device.
+
+        ``thumbnail``: uint8 [h,w,3|4] of the raster's shape (the layout contract of :meth:`tissue_mask`: any row stride, alpha
+        ignored; host or device), or None for the constant ``background``.  ``tissue``: a ``TissueMask`` of the raster's downsample
+        and shape; pixels outside it are not painted.  ``colormap``: "jet", "gray" or a uint8 [256,3] table
+        (``keep_amd.heatmap.colormap``).  ``window``: the values mapped to the ends of the table; ``min_value``: pixels whose mean
+        is below it are not painted; ``alpha``: the weight of the colour, used as ``round(256 alpha)``.  All in integers on the
+        16-bit fixed-point sums, equal to ``keep_amd.heatmap.render_numpy`` bit for bit.  CLAM's percentile ranks and blur are
+        steps made before this one: :meth:`percentiles` on the tile values, :meth:`smooth_raster` on the raster."""
+        _check_tile_raster(raster)
+        a, lo16, hi16, min16, bg = render_args(alpha, window, min_value, background)
+        h, w = raster.shape
+        key = colormap if isinstance(colormap, str) else None
+        lut_host = colormap_table(colormap)
+        x = None
+        if thumbnail is not None:
+            x = torch.from_numpy(thumbnail) if not isinstance(thumbnail, torch.Tensor) else thumbnail
+            if region_layout(x)[:2] != (h, w):
+                raise ValueError(f"thumbnail is {tuple(x.shape[:2])}, the raster {(h, w)}")
+        if tissue is not None:
+            _check_tissue(tissue, raster)
+        self._ready_device()
+        self._raster_here(raster)
+        lut = self._heat_luts.get(key)
+        if lut is None or lut.device != self._device:
+            lut = torch.from_numpy(lut_host).to(self._device)
+            if key is not None:
+                self._heat_luts[key] = lut                              # the named tables are uploaded once
+        ps, row = 3, 0
+        if x is not None:
+            if x.device != self._device:
+                x = x.to(self._device)
+            _, _, ps, row = region_layout(x)
+        md = None if tissue is None else tissue.mask.to(self._device)
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=self._device)
+        self._call("heat_render", _ptr(raster.acc), h, w, _ptr(x), row, ps, bg[0] | bg[1] << 8 | bg[2] << 16, _ptr(md), _ptr(lut), a, lo16, hi16,
+                   min16, _ptr(out))
+        return out
+
+    # ------------------------------------------------------------------ heatmap percentiles and smoothing
+    def _values_f32(self, values, name: str, least: int) -> torch.Tensor:
+        """A population or queries (host or device, numpy or torch, any floating dtype) checked on the host -> fp32 [N] on the device."""
+        v = values if isinstance(values, torch.Tensor) else torch.as_tensor(values)
+        check_values(v, name, least)
+        self._ready_device()
+        return v.to(self._device, torch.float32).contiguous()
+
+    @torch.no_grad()
+    def score_reference(self, values):
+        """A score population sorted on the device -> ``keep_amd.heatmap.ScoreReference``.  ``values``: floating
+        point [M], ``1 <= M <= 2^24 - 1``, host or device, numpy or torch, rounded to float32 first.  NaNs are not part of the
+        population and -0 counts as +0; equal to ``keep_amd.heatmap.sort_numpy`` bit for bit.  No host synchronisation."""
+        v = self._values_f32(values, "values", 1)
+        M = int(v.shape[0])
+        out = torch.empty((M,), dtype=torch.float32, device=self._device)
+        n = torch.empty((1,), dtype=torch.int64, device=self._device)
+        self._call("sort_f32", _ptr(v), M, _ptr(out), _ptr(n))
+        return ScoreReference(out, n, self)
+
+    def _rank(self, reference, values, self_rank: bool, pct: bool, counts: bool):
+        """keep_rank_f32 -> (pct fp32 | None, less int32 | None, eq int32 | None), each [N] on the device."""
+        if not isinstance(reference, ScoreReference):
+            raise ValueError(f"reference must be a ScoreReference, got {type(reference).__name__}")
+        q = self._values_f32(values, "values", 0)
+        if reference.sorted.device != self._device:
+            raise ValueError(f"the reference lives on {reference.sorted.device}, this engine on {self._device}")
+        N = int(q.shape[0])
+        outs = [torch.empty((N,), dtype=dt, device=self._device) if on else None
+                for on, dt in ((pct, torch.float32), (counts, torch.int32), (counts, torch.int32))]
+        if N == 0:
+            return tuple(outs)                                          # empty tensors have no address to pass
+        self._call("rank_f32", _ptr(reference.sorted), reference.M, _ptr(reference.n), _ptr(q), N, int(self_rank), _ptr(outs[0]), _ptr(outs[1]),
+                   _ptr(outs[2]))
+        return tuple(outs)
+
+    @torch.no_grad()
+    def percentiles(self, values, reference=None) -> torch.Tensor:
+        """Rank percentiles on the device -> fp32 [N] in (0, 1].  ``reference=None`` ranks the values among
+        themselves: ``(2 less + eq + 1) / (2 n)``, which is ``scipy.stats.rankdata(v, 'average') / n`` over the n values that are not
+        NaN.  With a ``ScoreReference`` (:meth:`score_reference`) they are outsiders to that population: ``(2 less + eq) / (2 n)``,
+        ``scipy.stats.percentileofscore(ref, v, kind='mean') / 100``.  A NaN stays NaN.  Equal to
+        ``keep_amd.heatmap.percentiles_numpy`` bit for bit; no host synchronisation."""
+        if reference is None:
+            q = self._values_f32(values, "values", 1)
+            return self._rank(self.score_reference(q), q, True, True, False)[0]
+        return self._rank(reference, values, False, True, False)[0]
+
+    @torch.no_grad()
+    def smooth_raster(self, raster, sigma=None, radius=None, taps=None, tissue=None):
+        """A raster's mean smoothed by a Gaussian under its support -> a new ``TileRaster`` of the same
+        geometry and ``tiles``, whose pixels hold the smoothed mean in 16-bit fixed point with a count of one where the input was
+        covered (and inside ``tissue``), nothing elsewhere.  ``sigma`` (and ``radius``, default ``ceil(3 sigma)``) make the taps
+        with ``keep_amd.heatmap.gaussian_taps``; or pass ``taps``, an odd number of non-negative integers with a centre >= 1 and a sum
+        <= 32768.  ``tissue``: a ``TissueMask`` of the raster's downsample and shape.  A normalised convolution: uncovered and
+        masked-out pixels neither give nor receive, a constant region stays constant.  Integer arithmetic, equal to
+        ``keep_amd.heatmap.smooth_numpy`` bit for bit.  The input must be a raster as ``tile_raster`` makes it (sum <= 65535 count)."""
+        _check_tile_raster(raster)
+        t = smooth_taps(sigma, radius, taps)
+        h, w = raster.shape
+        if tissue is not None:
+            _check_tissue(tissue, raster)
+        self._ready_device()
+        self._raster_here(raster)
+        td = torch.from_numpy(t).to(self._device)
+        md = None if tissue is None else self._on_device(tissue.mask)
+        out = torch.empty((h, w), dtype=torch.int64, device=self._device)
+        self._call("heat_smooth", _ptr(raster.acc), h, w, _ptr(md), _ptr(td), t.size // 2, _ptr(out))
+        return TileRaster(out, raster.downsample, raster.patch, raster.origin, raster.tiles, self)
+
+    # ------------------------------------------------------------------ region table
+    @torch.no_grad()
+    def mask_regions(self, mask, connectivity: int = 8, min_area: int = 1, raster=None, labels: bool = True, max_regions: int = 1 << 20):
+        """The connected regions of a mask, numbered, with geometry and scores, on the device ->
+        ``keep_amd.components.RegionTable``.
+
+        ``mask``: uint8 / bool [h,w], numpy or torch, host or device, non-zero = foreground, ``h w <= 2^30``; or a ``TissueMask``, which
+        brings its ``downsample``.  Components are 4- or 8-connected; one is KEPT iff it holds ``>= min_area`` pixels (``min_area >= 1``;
+        note that ``TissueSegmentation.min_area`` DROPS a fragment iff it holds ``<= min_area``).  The kept ones are numbered 1..n in the
+        row-major order of their first pixels, which is ``scipy.ndimage.label``'s numbering with the dropped ones removed.
+        ``raster``: a ``TileRaster`` of the mask's shape (and downsample, where both have one) whose sums fill the score columns;
+        without one they are 0.  ``labels=False`` leaves the int32 [h,w] label image out of the result.  n is read back once to size
+        the table (the one host synchronisation); more than ``max_regions`` regions is a ValueError raised before the table is
+        allocated.  Everything is integer arithmetic, equal to ``keep_amd.components.regions_numpy`` bit for bit and the same from
+        run to run."""
+        connectivity, min_area, max_regions = check_regions_args(connectivity, min_area, max_regions)
+        m, d = mask_tensor(mask)
+        h, w = int(m.shape[0]), int(m.shape[1])
+        d = check_raster(raster, (h, w), d)
+        self._ready_device()
+        if raster is not None:
+            self._raster_here(raster)
+        m = self._on_device(m)
+        lab = torch.empty((h, w), dtype=torch.int32, device=self._device)
+        n_dev = torch.empty((1,), dtype=torch.int64, device=self._device)
+        self._call("regions_label", _ptr(m), h, w, connectivity, min_area, _ptr(lab), _ptr(n_dev))
+        self._queue_flag_check(_stream(self._device))
+        n = check_region_count(int(n_dev.item()), max_regions)
+        table = torch.empty((n, REGION_COLS), dtype=torch.int64, device=self._device)
+        self._call("regions_table", _ptr(lab), h, w, n, _ptr(None if raster is None else raster.acc), _ptr(table))
+        return RegionTable(table, lab if labels else None, d, (0, 0) if raster is None else raster.origin, connectivity=connectivity)
+
+    # ------------------------------------------------------------------ region outlines
+    @torch.no_grad()
+    def region_outlines(self, regions, connectivity: Optional[int] = None, max_rings: int = 1 << 20, n: Optional[int] = None):
+        """The boundary rings of the regions, with holes, traced on the device ->
+        ``keep_amd.outline.RegionOutlines``: polygons on the corner lattice that ``to_geojson`` hands to a viewer.
+
+        ``regions``: a ``RegionTable`` that kept its labels (``mask_regions`` / ``wsi.segment_regions``), or an int32 [h,w] label image
+        (numpy or torch, host or device, ``h w <= 2^28``) with ``n=``: values outside 1..n count as background.  ``connectivity``
+        defaults to the one the table was labelled with (8 for a label image); with the labelling's own connectivity every region has
+        exactly one outer ring, its first, and every other ring of it is a hole.  Two values are read back: the numbers of edges and
+        of vertices, which size the workspace and the result, and the number of rings; more than ``max_rings`` rings is a ValueError
+        after that.  No thread walks a ring (pointer jumping: the cost follows the logarithm of the longest ring).  Integer
+        arithmetic, equal to ``keep_amd.outline.outlines_numpy`` exactly and the same from run to run."""
+        lab, n, conn, d, origin = regions_labels(regions, n, connectivity)
+        if n is None:
+            raise ValueError("a label image needs n=, the number of regions (labels outside 1..n count as background)")
+        connectivity, max_rings = check_outline_args(connectivity if connectivity is not None else (8 if conn is None else conn), max_rings)
+        h, w = int(lab.shape[0]), int(lab.shape[1])
+        self._ready_device()
+        lab = lab.to(self._device).contiguous()
+        counts = torch.zeros((2,), dtype=torch.int64, device=self._device)
+        if n > 0:
+            self._call("outline_count", _ptr(lab), h, w, n, connectivity, _ptr(counts))
+        E, V = (int(v) for v in counts.tolist()) if n > 0 else (0, 0)
+        vertices = torch.empty((V, 2), dtype=torch.int32, device=self._device)
+        if V == 0:
+            return RegionOutlines(torch.empty((0, RING_COLS), dtype=torch.int64, device=self._device), vertices, d, origin, n)
+        cap = min(V // 4, max_rings)
+        rings = torch.empty((cap, RING_COLS), dtype=torch.int64, device=self._device)
+        r_dev = torch.empty((1,), dtype=torch.int64, device=self._device)
+        self._call("outline_trace", _ptr(lab), h, w, n, connectivity, E, V, _ptr(vertices), _ptr(rings if cap else None), cap, _ptr(r_dev))
+        R = check_ring_count(int(r_dev.item()), max_rings)
+        return RegionOutlines(rings[:R], vertices, d, origin, n)
+
+    @torch.no_grad()
+    def draw_outlines(self, rgb, regions, color=(0, 0, 0), width: int = 1) -> torch.Tensor:
+        """The regions' outlines drawn into an image on the device -> a new uint8 [h,w,3] on the device.  ``rgb``: uint8 [h,w,3]
+        (``render_heatmap``'s output, a thumbnail), numpy or torch, host or device; ``regions``: a ``RegionTable`` with labels or an
+        int32 [h,w] label image.  A pixel takes ``color`` iff it belongs to a region and its ``(2 width + 1)^2`` window leaves the
+        image or meets another label: a band of ``width`` pixels on the inside of every region, holes included
+        (``1 <= width <= 16``).  Equal to ``keep_amd.outline.draw_numpy`` exactly."""
+        packed, width = check_draw_args(color, width)
+        lab = regions_labels(regions)[0]
+        h, w = int(lab.shape[0]), int(lab.shape[1])
+        x = rgb_tensor(rgb, (h, w))
+        self._ready_device()
+        lab, x = lab.to(self._device).contiguous(), x.to(self._device).contiguous()
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=self._device)
+        self._call("outline_draw", _ptr(lab), h, w, _ptr(x), _ptr(out), packed, width)
+        return out
+
+    # ------------------------------------------------------------------ polygon annotations
+    @torch.no_grad()
+    def fill_polygons(self, polys, downsample: int, shape, origin=(0, 0), rule: str = "union", value: int = 1, into=None) -> torch.Tensor:
+        """Polygons on level-0 coordinates filled into a mask in thumbnail geometry on the device -> uint8
+        ``[h,w]`` on the device: the inverse of :meth:`region_outlines`.
+
+        ``polys``: a ``keep_amd.annotation.PolygonSet`` (``from_geojson`` / ``from_asap_xml`` / ``from_outlines``; its ring weights follow
+        ``rule``), or a tuple ``(vertices int [V,2], ring_start int [R+1], weight int [R] in {-1, 0, 1})`` of numpy / torch arrays, host
+        or device (arrays on the device are read back once for the argument checks).  One mask pixel covers ``downsample`` x
+        ``downsample`` level-0 pixels (``1..4096``), pixel (0, 0) starts at ``origin``; ``shape = (h, w)`` with ``h (w + 1) <= 2^28``; every
+        coordinate within +-2^26.  A pixel is inside iff its CENTRE is: the winding number there is ``> 0`` (``"union"``: overlapping
+        features unite, a feature's hole does not punch through another feature, the drawing direction does not matter) or odd
+        (``"evenodd"``); a centre exactly on an edge belongs to the polygon on whose left or upper side it lies, so polygons that
+        share an edge partition the pixels.  ``out = value`` (0..255) inside, ``into`` (uint8 ``[h,w]``, host or device) or 0 elsewhere:
+        ``into`` gives a painter's order across calls and ``value=0`` cuts.  The number of edge / row crossings is read back once (the
+        one host synchronisation; it is left in ``last_fill_crossings``); ``>= 2^31`` of them is a ValueError.  Integer arithmetic,
+        equal to ``keep_amd.annotation.fill_numpy`` exactly and the same from run to run."""
+        d, (h, w), (ox, oy), rule_id, value = check_fill_args(downsample, shape, origin, rule, value)
+        vertices, ring_start, weight = polygon_arrays(polys, rule)
+        into = check_into(into, (h, w))
+        self._ready_device()
+        V, R = int(vertices.shape[0]), int(ring_start.shape[0]) - 1
+        vd, rd, wd = (torch.from_numpy(a).to(self._device) for a in (vertices, ring_start, weight))
+        into = None if into is None else self._on_device(into)
+        out = torch.empty((h, w), dtype=torch.uint8, device=self._device)
+        crossings = C.c_int64(0)
+        self._call("poly_fill", _ptr(vd), V, _ptr(rd), R, _ptr(wd), d, h, w, ox, oy, rule_id, value, _ptr(into), _ptr(out), C.byref(crossings))
+        self.last_fill_crossings = int(crossings.value)
+        return out
+
+    @torch.no_grad()
+    def annotation_mask(self, polys, downsample: int, shape, order=None, rule: str = "union", mode: str = "four_pt"):
+        """A ``PolygonSet`` -> a ``keep_amd.region.TissueMask`` on the device, which ``region_grid`` / ``encode_region`` /
+        ``extract_slide_features`` take as ``tissue=``, ``mask_regions`` as its mask and ``render_heatmap`` as ``tissue=``.
+
+        Without ``order`` everything is filled with 1 in one call of :meth:`fill_polygons`.  ``order``: a sequence of
+        ``(groups, value)`` (``keep_amd.annotation.CAMELYON16_ORDER``: the tumour groups painted 1, then the exclusions painted 0): one
+        fill per entry over the features of those groups, each painted into the result of the one before.  The origin is (0, 0), as a
+        ``TissueMask`` has none; ``mode`` is how a grid cell is tested against the mask."""
+        if not isinstance(polys, PolygonSet):
+            raise ValueError(f"polys must be a PolygonSet, got {type(polys).__name__}")
+        if mode not in MASK_MODES:
+            raise ValueError(f"mode must be one of {MASK_MODES}, got {mode!r}")
+        check_fill_args(downsample, shape, (0, 0), rule, 1)
+        if order is None:
+            mask = self.fill_polygons(polys, downsample, shape, (0, 0), rule, 1)
+        else:
+            steps = [(tuple([g] if isinstance(g, str) else g), check_fill_args(downsample, shape, (0, 0), rule, v)[4]) for g, v in order]
+            if not steps:
+                raise ValueError("order is empty")
+            mask = None
+            for groups, v in steps:
+                mask = self.fill_polygons(polys.select(groups=groups), downsample, shape, (0, 0), rule, v, mask)
+        return TissueMask(mask, downsample, mode)
+
+    @torch.no_grad()
+    def mask_tile_counts(self, mask, coords, patch_size: int, downsample: Optional[int] = None, origin=(0, 0)) -> torch.Tensor:
+        """How much of a mask lies under every tile, on the device -> int32 ``[N,2]`` on the device: column 0 the mask pixels whose
+        centre lies in the tile ``[x, x + patch_size) x [y, y + patch_size)`` (clipped to the mask), column 1 those of them that are
+        non-zero.  ``mask``: uint8 / bool ``[h,w]``, numpy or torch, host or device, with ``downsample=``, or a ``TissueMask``, which brings
+        its own; ``coords``: integers ``[N,2]``, level-0 top-left ``(x, y)``, within +-2^60; ``origin``: the level-0 position of mask pixel
+        (0, 0).  At ``downsample=1`` and origin 0, ``2 * counts[:, 1] > patch_size ** 2`` is the tile label rule of the reference's
+        ``segment_utils.py``.  No host synchronisation; equal to ``keep_amd.annotation.tile_counts_numpy`` exactly."""
+        m, c, patch, d, (ox, oy) = check_tile_args(mask, coords, patch_size, downsample, origin)
+        self._ready_device()
+        m, c = self._on_device(m), self._on_device(c, torch.int64)
+        N = int(c.shape[0])
+        out = torch.empty((N, 2), dtype=torch.int32, device=self._device)
+        self._call("mask_tile_counts", _ptr(m), int(m.shape[0]), int(m.shape[1]), d, ox, oy, _ptr(c), N, patch, _ptr(out))
+        return out
+
+    # ------------------------------------------------------------------ segmentation evaluation
+    @torch.no_grad()
+    def tile_roc(self, scores, labels, curve: bool = True):
+        """The tile-level ROC of ``eval_seg_auc`` (``segment_utils.py:105-119``) on the device ->
+        ``keep_amd.evaluation.RocResult``: ``auc`` (what ``roc_auc_score`` computes, exact and rounded once), ``best_threshold`` (the
+        reference's ``thresholds[np.argmax(tpr - fpr)]``, ``inf`` when no threshold beats chance) and, with ``curve=True``, the whole
+        curve as device tensors.  ``scores``: floating point [N], rounded to float32; ``labels``: bool / integers [N], non-zero =
+        positive; host or device, numpy or torch; ``1 <= N <= 2^24 - 1``.  A NaN score removes its tile.  One class only (or no tile
+        left) is the ``ValueError`` scikit-learn raises.  One read of eight scalars (the one host synchronisation; with ``curve=True``
+        it also sizes the curve); equal to ``keep_amd.evaluation.roc_numpy`` exactly."""
+        s = scores if isinstance(scores, torch.Tensor) else torch.as_tensor(np.asarray(scores))
+        l = labels if isinstance(labels, torch.Tensor) else torch.as_tensor(np.asarray(labels))
+        N = check_roc_args(s, l)
+        self._ready_device()
+        s = s.to(self._device, torch.float32).contiguous()
+        l = (l.to(self._device) != 0).to(torch.uint8).contiguous()
+        scalars = torch.empty((8,), dtype=torch.int64, device=self._device)
+        outs = [torch.empty((N,), dtype=dt, device=self._device) if curve else None for dt in (torch.float32, torch.int32, torch.int32, torch.uint8)]
+        self._call("eval_roc", _ptr(s), _ptr(l), N, _ptr(scalars), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]))
+        n, P, Nn, u2, K, _, bits, _ = scalars.tolist()
+        best = struct.unpack("<f", struct.pack("<I", bits & 0xFFFFFFFF))[0]
+        if not curve:
+            return RocResult(n, P, Nn, u2, best)
+        return RocResult(n, P, Nn, u2, best, outs[0][:K], outs[1][:K], outs[2][:K], outs[3][:K].to(torch.bool))
+
+    @torch.no_grad()
+    def mask_overlap(self, a, b, within=None):
+        """The overlap counts of two masks on the device, the counting of ``eval_seg_coarse`` (``segment_utils.py:130-151``) ->
+        ``keep_amd.evaluation.MaskOverlap`` (``.dice``, ``.iou``, ``.confusion`` follow in Python integers).  ``a``, ``b`` and the
+        optional ``within``: bool / uint8 ``[h,w]`` of one shape, numpy or torch, host or device, or ``TissueMask``s; non-zero = set;
+        only the pixels where ``within`` is set are considered.  One read of four integers; equal to
+        ``keep_amd.evaluation.mask_counts_numpy`` exactly."""
+        a = check_mask(a, "a")
+        shape = (int(a.shape[0]), int(a.shape[1]))
+        b = check_mask(b, "b", shape)
+        within = None if within is None else check_mask(within, "within", shape)
+        self._ready_device()
+        a, b, within = self._on_device(a), self._on_device(b), (None if within is None else self._on_device(within))
+        out = torch.empty((4,), dtype=torch.int64, device=self._device)
+        self._call("eval_mask_counts", _ptr(a), _ptr(b), _ptr(within), shape[0], shape[1], _ptr(out))
+        return MaskOverlap(*out.tolist())
+
+    @torch.no_grad()
+    def raster_hist(self, raster, truth, within=None) -> torch.Tensor:
+        """int64 ``[2, 65537]`` on the device: the raster's pixels (inside ``within``) by truth and by their mean in 16-bit fixed
+        point, the uncovered ones in bin 65536.  Arguments as :meth:`raster_sweep`.  No host synchronisation; equal to
+        ``keep_amd.evaluation.raster_hist_numpy`` exactly."""
+        _check_tile_raster(raster)
+        check_same_geometry(raster, truth, "truth")
+        check_same_geometry(raster, within, "within")
+        truth = check_mask(truth, "truth", raster.shape)
+        within = None if within is None else check_mask(within, "within", raster.shape)
+        self._ready_device()
+        self._raster_here(raster)
+        truth, within = self._on_device(truth), (None if within is None else self._on_device(within))
+        hist = torch.empty((2, HIST_BINS), dtype=torch.int64, device=self._device)
+        h, w = raster.shape
+        self._call("eval_raster_hist", _ptr(raster.acc), _ptr(truth), _ptr(within), h, w, _ptr(hist))
+        return hist
+
+    @torch.no_grad()
+    def raster_sweep(self, raster, truth, within=None):
+        """Every threshold of a heatmap against a truth mask at once -> ``keep_amd.evaluation.RasterSweep``:
+        TP / FP / FN and Dice of "mean > t" for the 65536 thresholds of the raster's fixed point, the threshold of the best Dice and
+        the pixel-level AUROC.  ``raster``: a ``TileRaster`` (``tile_raster`` / ``wsi.segment_heatmap``); ``truth`` / ``within``: bool /
+        uint8 ``[h,w]`` of the raster's shape or ``TissueMask``s of its geometry (``fill_polygons`` / ``annotation_mask`` at the raster's
+        downsample make one).  One histogram kernel, then cumulative sums with torch on the device."""
+        return sweep_from_hist(self.raster_hist(raster, truth, within))
+
+    @torch.no_grad()
+    def annotation_tile_labels(self, polys_or_mask, coords, patch_size: int, order=None, rule: str = "union",
+                               max_band_bytes: int = 1 << 28) -> torch.Tensor:
+        """A label per tile from the ground truth, by the reference's rule (``segment_utils.py:99-103``): 1 iff more than half of the
+        tile's level-0 pixels are set -> uint8 ``[N]`` on the device.  ``coords``: integers ``[N,2]``, level-0 top-left ``(x, y)``.
+
+        A ``PolygonSet`` is filled at downsample 1 -- a level-0 mask of a whole slide would not fit, so in horizontal bands of whole
+        tile rows over the tiles' x extent, at most ``max_band_bytes`` of mask each (``keep_amd.evaluation.plan_label_bands``), with
+        :meth:`mask_tile_counts` per band; no tile is clipped by a band, so the labels do not depend on the banding.  ``order``
+        (``keep_amd.annotation.CAMELYON16_ORDER``) paints group after group as :meth:`annotation_mask` does.  A ``TissueMask`` of
+        downsample d (origin 0) gives ``2 c1 d^2 > patch_size^2`` with c1 the set mask pixels whose centre lies in the tile: the
+        reference's rule at d = 1; a bare bool / uint8 ``[h,w]`` array is a level-0 mask (d = 1).  Pixels outside a mask are not set."""
+        if not isinstance(polys_or_mask, PolygonSet):
+            mask = polys_or_mask if isinstance(polys_or_mask, TissueMask) else TissueMask(polys_or_mask, 1)
+            if order is not None:
+                raise ValueError("order= paints the groups of a PolygonSet: a mask has none")
+            counts = self.mask_tile_counts(mask, coords, patch_size)
+            return (2 * counts[:, 1].to(torch.int64) * mask.downsample ** 2 > int(patch_size) ** 2).to(torch.uint8)
+        polys = polys_or_mask
+        _, c, patch, _, _ = check_tile_args(np.zeros((1, 1), np.uint8), coords, patch_size, 1)
+        steps = [(None, 1)] if order is None else [(tuple([g] if isinstance(g, str) else g), int(v)) for g, v in order]
+        if not steps:
+            raise ValueError("order is empty")
+        self._ready_device()
+        c = self._on_device(c, torch.int64)
+        labels = torch.zeros((int(c.shape[0]),), dtype=torch.uint8, device=self._device)
+        if c.shape[0] == 0:
+            return labels
+        x0, y_all = int(c[:, 0].min()), c[:, 1]
+        x1 = int(c[:, 0].max()) + patch
+        sets = [(polys if g is None else polys.select(groups=g), v) for g, v in steps]
+        for y_first, y_last in plan_label_bands(y_all.cpu().numpy(), x0, x1, patch, max_band_bytes):
+            shape, origin = (y_last + patch - y_first, x1 - x0), (x0, y_first)
+            check_fill_args(1, shape, origin, rule, 1)
+            mask = None
+            for sel, v in sets:
+                mask = self.fill_polygons(sel, 1, shape, origin, rule, v, mask)
+            rows = torch.nonzero((y_all >= y_first) & (y_all <= y_last)).squeeze(1)
+            counts = self.mask_tile_counts(mask, c[rows], patch, 1, origin)
+            labels[rows] = (2 * counts[:, 1].to(torch.int64) > patch * patch).to(torch.uint8)
+        return labels
+
+    @staticmethod
+    def _cells_to_coords(cells: torch.Tensor, origin, coord_scale: int) -> torch.Tensor:
+        o = torch.tensor(origin, dtype=torch.int64, device=cells.device)
+        return (cells.to(torch.int64) + o) * coord_scale
+
+    @torch.no_grad()
+    def region_grid(self, region, patch_size: int = 224, step: Optional[int] = None, tissue=None, origin=(0, 0),
+                    coord_scale: int = 1) -> torch.Tensor:
+        """Patch grid over a uint8 region [H,W,3] (RGB) or [H,W,4] (RGBA, alpha ignored as PIL's ``convert("RGB")`` drops it), host or
+        device, any row stride -> the level-0 coords int64 [N,2] ``(x, y)`` of the kept cells, on the region's device.
+
+        Cells of side ``patch_size`` sit at ``(gx step, gy step)`` (``step`` defaults to ``patch_size``) wherever they lie wholly inside
+        the region, in row-major order; coords are ``(origin + cell offset) * coord_scale`` (the convention of refine_seg / cood2str and
+        the CLAM .h5 files; ``coord_scale`` for a region read at a downsampled level).  ``tissue`` (default off: every cell) is an exact
+        integer rule (keep_amd.region.TissueRule): a pixel is tissue iff ``max(r,g,b) > 0`` and ``255 (max - min) >= sat_min max``, a cell
+        is kept iff it holds ``>= ceil(min_fraction patch^2)`` of them.  That rule is deliberately NOT CLAM's contour segmentation;
+        a ``keep_amd.region.TissueMask`` (from :meth:`tissue_mask`, or a caller's own) is the other choice: a cell is then tested at
+        CLAM's ``four_pt`` / ``four_pt_hard`` / ``center`` points, in level coordinates including ``origin``, against the mask
+        (DESIGN.md section 11), and the region's pixels are not read."""
+        patch, step, origin, coord_scale = check_grid_args(patch_size, step, origin, coord_scale)
+        x = self._region_tensor(region)
+        if isinstance(tissue, TissueMask):                         # decided by the mask: the region gives its shape, no pixel is read
+            self._ready_device()
+            H, W, _, _ = region_layout(x)
+            cells = self._mask_cells(tissue, H, W, patch, step, origin)
+        else:
+            sat_min, min_pixels = tissue_params(tissue, patch)
+            self._ready_device()
+            xd, H, W, C, row = self._region_on_device(x)
+            cells = self._region_cells(xd, H, W, C, row, patch, step, sat_min, min_pixels)
+        coords = self._cells_to_coords(cells, origin, coord_scale)
+        return coords if x.device == self._device else coords.to(x.device)
+
+    @torch.no_grad()
+    def region_patches_uint8(self, region, coords: torch.Tensor, patch_size: int, origin=(0, 0), coord_scale: int = 1) -> torch.Tensor:
+        """The tiles of ``coords`` (as :meth:`region_grid` returns them, same ``origin`` / ``coord_scale``) cut from ``region`` on the
+        device -> uint8 [N,224,224,3]: the patches themselves at ``patch_size == 224``, else the reference transform's
+        ``Resize(224, BICUBIC)`` + ``CenterCrop(224)`` of each patch, bit-identical to PIL.  A coord outside the region is a ValueError."""
+        patch, _, origin, coord_scale = check_grid_args(patch_size, None, origin, coord_scale)
+        coords = torch.as_tensor(coords)
+        if coords.dim() != 2 or coords.shape[1] != 2:
+            raise ValueError(f"coords must be [N,2] (x, y), got {tuple(coords.shape)}")
+        x = self._region_tensor(region)
+        self._ready_device()
+        xd, H, W, C, row = self._region_on_device(x)
+        c = coords.to(self._device, torch.int64)
+        cells = (torch.div(c, coord_scale, rounding_mode="floor") - torch.tensor(origin, dtype=torch.int64, device=self._device))
+        cells = cells.clamp(-(1 << 31), (1 << 31) - 1).to(torch.int32)          # out of int32 range stays outside the region
+        out = self._region_tiles(xd, H, W, C, row, cells, patch)
+        return out if x.device == self._device else out.to(x.device)
+
+    @torch.no_grad()
+    def encode_region(self, region, patch_size: int = 224, step: Optional[int] = None, tissue=None, origin=(0, 0), coord_scale: int = 1,
+                      batch: int = 256) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Slide pixels in, what the WSI functions take out: the grid of :meth:`region_grid`, the tiles of
+        :meth:`region_patches_uint8` and :meth:`encode_image_uint8`, ``batch`` tiles at a time -> (features fp32 [N,768],
+        coords int64 [N,2]) on the region's device; ``[0,768]`` / ``[0,2]`` when no cell is kept.  ``tissue`` as in
+        :meth:`region_grid`: off, the per-pixel rule, or a ``TissueMask``."""
+        patch, step, origin, coord_scale = check_grid_args(patch_size, step, origin, coord_scale)
+        by_mask = isinstance(tissue, TissueMask)
+        sat_min, min_pixels = (0, 0) if by_mask else tissue_params(tissue, patch)
+        if isinstance(batch, bool) or int(batch) != batch or batch < 1:
+            raise ValueError(f"batch must be an integer >= 1, got {batch!r}")
+        x = self._region_tensor(region)
+        self._ready()
+        xd, H, W, C, row = self._region_on_device(x)
+        cells = self._mask_cells(tissue, H, W, patch, step, origin) if by_mask else \
+            self._region_cells(xd, H, W, C, row, patch, step, sat_min, min_pixels)
+        N = int(cells.shape[0])
+        feats = torch.empty((N, self.config.projection_dim), dtype=torch.float32, device=self._device)
+        for i in range(0, N, int(batch)):
+            feats[i:i + batch] = self.encode_image_uint8(self._region_tiles(xd, H, W, C, row, cells[i:i + batch], patch))
+        coords = self._cells_to_coords(cells, origin, coord_scale)
+        if x.device == self._device:
+            return feats, coords
+        return feats.to(x.device), coords.to(x.device)
