@@ -1,6 +1,7 @@
-// Host side of libkeep_hip: weight store (release state_dict key layout), workspace arena, tower orchestration and the encoder's
-// part of the extern "C" boundary declared in include/keep_hip.h.  The handle itself is handle.h; the slide-geometry entry
-// points (patch grid, tissue mask, heatmap, sort / rank, regions, outlines, polygon fill, evaluation) are slide_api.hip.
+// Host side of libkeep_hip: workspace arena, graph replay, tower orchestration, options and the encoder's part of the extern "C"
+// boundary declared in include/keep_hip.h.  The handle itself is handle.h; weight ingestion is weights.hip; the single-operator
+// entry points and probes are op_api.hip; the slide-geometry entry points (patch grid, tissue mask, heatmap, sort / rank, regions,
+// outlines, polygon fill, evaluation) are slide_api.hip.
 //
 // Orchestration mirrors the reference's call order, not its code:
 //   encode_image  quick_start/keep_inference.py:54-58  -> timm VisionTransformer.forward
@@ -29,73 +30,46 @@ struct Scope {     // RAII profile bracket
     ~Scope() { h->prof_end(tag, s); }
 };
 
-bool starts_with(const std::string& s, const char* p) { return s.rfind(p, 0) == 0; }
-bool ends_with(const std::string& s, const char* p) {
-    const size_t n = strlen(p);
-    return s.size() >= n && s.compare(s.size() - n, n, p) == 0;
-}
-
-// GEMM weights are stored as fp16 planes only; everything else keeps fp32.
-bool is_gemm_weight(const std::string& k) {
-    if (k == "visual.patch_embed.proj.weight") return true;
-    if (starts_with(k, "visual.blocks.") && ends_with(k, ".weight") &&
-        (k.find(".attn.qkv.") != std::string::npos || k.find(".attn.proj.") != std::string::npos ||
-         k.find(".mlp.fc1.") != std::string::npos || k.find(".mlp.fc2.") != std::string::npos)) return true;
-    if (starts_with(k, "text.encoder.layer.") && ends_with(k, ".weight") && k.find("LayerNorm") == std::string::npos) return true;
-    return false;
-}
-
-int64_t numel_of(const std::vector<int64_t>& s) { int64_t n = 1; for (auto d : s) n *= d; return n; }
-
-const WTensor* find(keep_handle* h, const std::string& k) {
-    auto it = h->w.find(k);
-    return it == h->w.end() ? nullptr : &it->second;
-}
-
-bool shape_is(const WTensor* t, std::initializer_list<int64_t> s) {
-    if (!t || t->shape.size() != s.size()) return false;
-    size_t i = 0;
-    for (auto d : s) if (t->shape[i++] != d) return false;
-    return true;
-}
-
 size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// Hands out 256-byte-aligned pieces of an arena.  Without a base it only measures: every pointer is null and `off` is what the layout consumes,
+// so a workspace is described once (carve_vit / carve_txt) and its size is whatever that description took.
 struct Carver {
     char* base; size_t off = 0;
     explicit Carver(char* b) : base(b) {}
-    template <typename T> T* take(size_t n) { T* p = reinterpret_cast<T*>(base + off); off += align_up(n * sizeof(T)); return p; }
+    template <typename T> T* take(size_t n) { T* p = base ? reinterpret_cast<T*>(base + off) : nullptr; off += align_up(n * sizeof(T)); return p; }
 };
+// Every tower workspace is this much larger than the buffers carved from it.  Kept from the hand-written size formulas the carve-derived sizes
+// replace (they ended in "+ 4096"); the reason is not recorded.  Arena sizes, and with them the staging offsets behind a workspace, depend on it.
+constexpr size_t WS_TAIL_BYTES = 4096;
 
-struct VitWs { float* splitk; float* resid; f16 *xn_hi, *xn_lo, *qkv_hi, *qkv_lo, *att_hi, *att_lo, *mlp_hi, *mlp_lo, *pat_hi, *pat_lo; float *cls, *h1;
+// What both towers carve, in this order: M token rows of width D and hidden width F (lo planes in split mode only), and -- last in either
+// tower -- the state split attention parks per (item, head, query) between its two key windows of <= 256 keys (launch_attention).
+struct TowerWs { float* splitk; float* resid; f16 *xn_hi, *xn_lo, *qkv_hi, *qkv_lo, *att_hi, *att_lo, *mlp_hi, *mlp_lo;
+                 float* part; size_t part_bytes;
+                 size_t bytes; };                            // the whole layout, WS_TAIL_BYTES included
+struct VitWs : TowerWs { f16 *pat_hi, *pat_lo; float *cls, *h1;
                unsigned char *xn_q, *xn_sc, *mlp_q, *mlp_sc;     // MX-fp4 side planes of the LayerNorm-2 output and of the MLP hidden (compensated mode)
                // compact CLS-row buffers for the last block
-               float* c_resid; f16 *c_att_hi, *c_att_lo, *c_xn_hi, *c_xn_lo, *c_mlp_hi, *c_mlp_lo;
-               float* part; size_t part_bytes; };            // split attention's two-window state (256 < ntok <= 512 only)
-struct TxtWs { float* splitk; float* resid; f16 *xn_hi, *xn_lo, *qkv_hi, *qkv_lo, *att_hi, *att_lo, *mlp_hi, *mlp_lo; float* attn_part; size_t attn_part_bytes; };
+               float* c_resid; f16 *c_att_hi, *c_att_lo, *c_xn_hi, *c_xn_lo, *c_mlp_hi, *c_mlp_lo; };
 
-// split attention over 256 < ntok <= 512 keys parks a partial state per (tile, head, query) between its two key windows (launch_attention)
-size_t vit_part_bytes(const keep_handle* h, int64_t Bc, int ntok, bool split) {
-    return (split && ntok > 256 && ntok <= 512) ? (size_t)Bc * h->vit_heads * ntok * ATT_PART_FLOATS * sizeof(float) : 0;
-}
-size_t vit_ws_bytes(const keep_handle* h, int64_t Bc, bool split, int ntok = 197) {
-    const size_t M = (size_t)Bc * ntok, Mp = (size_t)Bc * (ntok - 1), D = h->vit_D, F = h->vit_F, k = split ? 2 : 1;
-    const size_t part = vit_part_bytes(h, Bc, ntok, split);
-    const size_t comp = h->any_comp() ? align_up(keepk::q4_data_bytes(M, D)) + align_up(keepk::q4_scale_bytes(M, D)) +
-                                        align_up(keepk::q4_data_bytes(M, F)) + align_up(keepk::q4_scale_bytes(M, F)) : 0;
-    return comp + align_up(SKINNY_WS_BYTES) + align_up(M * D * 4) + k * (align_up(blk_elems(M, D) * 2) * 2 + align_up(M * 3 * D * 2) + align_up(blk_elems(M, F) * 2)) + 2 * align_up(blk_elems(Mp, 768) * 2) +
-           align_up((size_t)Bc * D * 4) + align_up((size_t)Bc * h->proj_dim * 4) + 4096 +
-           align_up((size_t)Bc * D * 4) + 2 * (2 * align_up(blk_elems(Bc, D) * 2) + align_up(blk_elems(Bc, F) * 2)) + (part ? align_up(part) : 0);
-}
-VitWs carve_vit(const keep_handle* h, char* arena, int64_t Bc, bool split, int ntok = 197) {
-    const size_t M = (size_t)Bc * ntok, Mp = (size_t)Bc * (ntok - 1), D = h->vit_D, F = h->vit_F;
-    Carver c(arena); VitWs w{};
+void carve_tower(Carver& c, TowerWs& w, size_t M, size_t D, size_t F, bool split) {
     w.splitk = c.take<float>(SKINNY_WS_BYTES / 4);
     w.resid = c.take<float>(M * D);
     w.xn_hi = c.take<f16>(blk_elems(M, D));  w.xn_lo = split ? c.take<f16>(blk_elems(M, D)) : nullptr;
     w.qkv_hi = c.take<f16>(M * 3 * D);       w.qkv_lo = split ? c.take<f16>(M * 3 * D) : nullptr;
     w.att_hi = c.take<f16>(blk_elems(M, D)); w.att_lo = split ? c.take<f16>(blk_elems(M, D)) : nullptr;
     w.mlp_hi = c.take<f16>(blk_elems(M, F)); w.mlp_lo = split ? c.take<f16>(blk_elems(M, F)) : nullptr;
+}
+void carve_part(Carver& c, TowerWs& w, size_t queries, bool windowed) {      // queries = items x heads x tokens
+    w.part_bytes = windowed ? queries * ATT_PART_FLOATS * sizeof(float) : 0;
+    if (w.part_bytes) w.part = c.take<float>(w.part_bytes / sizeof(float));
+    w.bytes = c.off + WS_TAIL_BYTES;
+}
+VitWs carve_vit(const keep_handle* h, char* arena, int64_t Bc, bool split, int ntok = 197) {
+    const size_t M = (size_t)Bc * ntok, Mp = (size_t)Bc * (ntok - 1), D = h->vit_D, F = h->vit_F;
+    Carver c(arena); VitWs w{};
+    carve_tower(c, w, M, D, F, split);
     w.pat_hi = c.take<f16>(blk_elems(Mp, 768)); w.pat_lo = c.take<f16>(blk_elems(Mp, 768));
     w.cls = c.take<float>((size_t)Bc * D);
     w.h1 = c.take<float>((size_t)Bc * h->proj_dim);
@@ -107,30 +81,55 @@ VitWs carve_vit(const keep_handle* h, char* arena, int64_t Bc, bool split, int n
         w.xn_q = c.take<unsigned char>(keepk::q4_data_bytes(M, D));  w.xn_sc = c.take<unsigned char>(keepk::q4_scale_bytes(M, D));
         w.mlp_q = c.take<unsigned char>(keepk::q4_data_bytes(M, F)); w.mlp_sc = c.take<unsigned char>(keepk::q4_scale_bytes(M, F));
     }
-    w.part_bytes = vit_part_bytes(h, Bc, ntok, split);
-    if (w.part_bytes) w.part = c.take<float>(w.part_bytes / sizeof(float));
+    carve_part(c, w, M * h->vit_heads, split && ntok > 256 && ntok <= 512);   // beyond 512 tokens the key-blocked kernel runs, which keeps no state
     return w;
 }
-size_t txt_ws_bytes(const keep_handle* h, int64_t Pc, int64_t T, bool split) {
-    const size_t M = (size_t)Pc * T, H = h->bert_H, F = h->bert_F, k = split ? 2 : 1;
-    // split attention over more than 256 keys parks a partial state per (prompt, head, query) between its two key windows
-    const size_t part = (split && T > 256) ? align_up((size_t)Pc * h->bert_heads * T * ATT_PART_FLOATS * sizeof(float)) : 0;
-    return align_up(SKINNY_WS_BYTES) + align_up(M * H * 4) + k * (align_up(blk_elems(M, H) * 2) * 2 + align_up(M * 3 * H * 2) + align_up(blk_elems(M, F) * 2)) + part + 4096;
+TowerWs carve_txt(const keep_handle* h, char* arena, int64_t Pc, int64_t T, bool split) {
+    Carver c(arena); TowerWs w{};
+    carve_tower(c, w, (size_t)Pc * T, h->bert_H, h->bert_F, split);
+    carve_part(c, w, (size_t)Pc * T * h->bert_heads, split && T > 256);
+    return w;
 }
-TxtWs carve_txt(const keep_handle* h, char* arena, int64_t Pc, int64_t T, bool split) {
-    const size_t M = (size_t)Pc * T, H = h->bert_H, F = h->bert_F;
-    Carver c(arena); TxtWs w{};
-    w.splitk = c.take<float>(SKINNY_WS_BYTES / 4);
-    w.resid = c.take<float>(M * H);
-    w.xn_hi = c.take<f16>(blk_elems(M, H));  w.xn_lo = split ? c.take<f16>(blk_elems(M, H)) : nullptr;
-    w.qkv_hi = c.take<f16>(M * 3 * H);       w.qkv_lo = split ? c.take<f16>(M * 3 * H) : nullptr;
-    w.att_hi = c.take<f16>(blk_elems(M, H)); w.att_lo = split ? c.take<f16>(blk_elems(M, H)) : nullptr;
-    w.mlp_hi = c.take<f16>(blk_elems(M, F)); w.mlp_lo = split ? c.take<f16>(blk_elems(M, F)) : nullptr;
-    if (split && T > 256) {
-        w.attn_part_bytes = (size_t)Pc * h->bert_heads * T * ATT_PART_FLOATS * sizeof(float);
-        w.attn_part = c.take<float>(w.attn_part_bytes / sizeof(float));
+size_t vit_ws_bytes(const keep_handle* h, int64_t Bc, bool split, int ntok = 197) { return carve_vit(h, nullptr, Bc, split, ntok).bytes; }
+size_t txt_ws_bytes(const keep_handle* h, int64_t Pc, int64_t T, bool split) { return carve_txt(h, nullptr, Pc, T, split).bytes; }
+
+// How one keep_encode_image call of B tiles of ntok tokens lays the arena out: `lanes` concurrent sub-batches of at most `per` tiles, each on
+// lane_bytes of workspace.  staged: the call is replayed as a captured graph (or, for keep_reserve, may be), which runs as ONE lane of all B
+// tiles on copies of the pixels and of the output parked behind the workspace (at most SKINNY_MAX_M token rows: never enough for a second lane).
+struct VitPlan { int lanes; int64_t per; bool split; size_t lane_bytes, o_pix, o_out, total; };
+VitPlan vit_plan(const keep_handle* h, int64_t B, int ntok, size_t tile_bytes, bool staged) {
+    VitPlan p{};
+    // lanes: split the batch over n_streams concurrent sub-batches once there is enough work for each (in 197-token tile equivalents)
+    p.lanes = h->n_streams;
+    while (p.lanes > 1 && B * ntok < (int64_t)p.lanes * h->lane_min_tiles * 197) --p.lanes;
+    p.per = (B + p.lanes - 1) / p.lanes;
+    // sub-batches are bounded in tokens: per * ntok <= max_tiles * 197 (a 512 x 512 call needs the arena of a 224 x 224 one)
+    const int64_t per_max = std::max<int64_t>((int64_t)h->max_tiles * 197 / ntok, 1);
+    if (p.per > per_max && !(staged && B <= h->max_tiles)) p.per = per_max;
+    p.split = h->any_split();
+    p.lane_bytes = align_up(vit_ws_bytes(h, p.per, p.split, ntok));
+    p.total = p.lane_bytes * p.lanes;
+    if (staged) {
+        p.o_pix = p.total;
+        p.o_out = p.o_pix + align_up((size_t)B * tile_bytes);
+        p.total = p.o_out + align_up((size_t)B * h->proj_dim * sizeof(float));
     }
-    return w;
+    return p;
+}
+// The same for one keep_encode_text call of P prompts of T tokens: chunks of at most `pc` prompts on one workspace; a graph-replayed call runs
+// on staged ids / types / mask and a staged output behind it.
+struct TxtPlan { int64_t pc; bool split; size_t ws_bytes, o_ids, o_types, o_mask, o_out, total; };
+TxtPlan txt_plan(const keep_handle* h, int64_t P, int64_t T, bool staged) {
+    TxtPlan p{};
+    p.pc = P < h->max_prompts ? P : h->max_prompts;
+    p.split = h->any_split();
+    p.total = p.ws_bytes = align_up(txt_ws_bytes(h, p.pc, T, p.split));
+    if (staged) {
+        const size_t nb = align_up((size_t)P * T * sizeof(int64_t));
+        p.o_ids = p.ws_bytes; p.o_types = p.o_ids + nb; p.o_mask = p.o_types + nb; p.o_out = p.o_mask + nb;
+        p.total = p.o_out + align_up((size_t)P * h->bert_H * sizeof(float));
+    }
+    return p;
 }
 }  // namespace
 
@@ -191,23 +190,6 @@ int run_gemm(keep_handle* h, int tag, GemmParams p, int epi, hipStream_t s, floa
     return launch_gemm_f16(p, epi, s);
 }
 
-// offer the LayerNorm that follows a residual GEMM to the GEMM itself (taken only on the small-M split-K path)
-void offer_ln(GemmParams& p, const LnParams& ln) {
-    p.ln_gamma = ln.gamma; p.ln_beta = ln.beta; p.ln_eps = ln.eps;
-    p.ln_out_hi = ln.out_hi; p.ln_out_lo = ln.out_lo; p.ln_out_f32 = ln.out_f32;
-}
-
-GemmParams gemm_params(const keep_handle* h, const f16* a_hi, const f16* a_lo, const WTensor* w, int M, bool split, const float* bias) {
-    GemmParams p{};
-    p.tune = &h->tune;
-    p.a_hi = a_hi; p.a_lo = a_lo; p.w_hi = w->hi; p.w_lo = w->lo;
-    p.M = M; p.N = (int)w->shape[0]; p.K = (int)(w->numel / w->shape[0]);
-    p.nseg = split ? 3 : 1;
-    p.bias = bias;
-    p.patches_per_img = 196;
-    return p;
-}
-
 // ---------------------------------------------------------------------------------------------
 // One sub-batch of tiles in flight on one stream ("lane").  keep_encode_image runs up to n_streams lanes
 // concurrently and issues their kernels layer-interleaved, so one lane's memory-bound phases (LayerNorm,
@@ -229,12 +211,12 @@ int vit_begin(keep_handle* h, VitLane& L) {
     {
         Scope sc(h, T_VIT_IM2COL, s);
         launch_im2col(pixels, pix_dtype, Bc, L.gh, L.gw, ws.pat_hi, sp0 ? ws.pat_lo : nullptr,
-                      find(h, "visual.cls_token")->f32, L.pos, ws.resid, D, s);
+                      find_weight(h, "visual.cls_token")->f32, L.pos, ws.resid, D, s);
     }
     {
         Scope sc(h, T_VIT_PATCH, s);
-        GemmParams p = gemm_params(h, ws.pat_hi, ws.pat_lo, find(h, "visual.patch_embed.proj.weight"), Bc * (L.ntok - 1), sp0,
-                                   find(h, "visual.patch_embed.proj.bias")->f32);
+        GemmParams p = gemm_params(h, ws.pat_hi, ws.pat_lo, find_weight(h, "visual.patch_embed.proj.weight"), Bc * (L.ntok - 1), sp0,
+                                   find_weight(h, "visual.patch_embed.proj.bias")->f32);
         p.pos = L.pos; p.patches_per_img = L.ntok - 1;
         p.resid = ws.resid;
         if (run_gemm(h, T_VIT_PATCH, p, EPI_PATCH, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "patch-embedding GEMM launch failed");
@@ -270,9 +252,7 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
     // qkv of a split-attention block in the compensated mode: fp16 pass + MX-fp4 correction terms instead of three fp16 passes (lanes
     // large enough for the 256x256 kernel; LayerNorm-1 then writes the fp4 planes of its output instead of the lo plane)
     const bool qkv_q = h->vit_qkv_comp(i, Bc) && b.qkv->q && ws.xn_q && !L.xn_ready;
-    LnParams ln{};
-    ln.tune = &h->tune;
-    ln.x = ws.resid; ln.x_stride = D; ln.rows = M; ln.D = D; ln.eps = 1e-6f;
+    LnParams ln = ln_params(h, ws.resid, D, M, D, 1e-6f);
     ln.out_hi = ws.xn_hi; ln.out_lo = (sp && !qkv_q) ? ws.xn_lo : nullptr; ln.out_kt = D / 32;
     ln.out_q = qkv_q ? ws.xn_q : nullptr; ln.out_sc = qkv_q ? ws.xn_sc : nullptr;
     if (!L.xn_ready) {
@@ -292,10 +272,7 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
     }
     {
         Scope sc(h, sp ? T_VIT_ATTN_X : T_VIT_ATTN, s);
-        AttnParams a{};
-        a.tune = &h->tune;
-        a.qkv_hi = ws.qkv_hi; a.qkv_lo = ws.qkv_lo; a.out_hi = ws.att_hi; a.out_lo = sp ? ws.att_lo : nullptr;
-        a.mask = nullptr; a.batch = Bc; a.ntok = ntok; a.heads = h->vit_heads; a.split = sp; a.scale = 0.125f; a.out_kt = D / 32;
+        AttnParams a = attn_params(h, ws.qkv_hi, ws.qkv_lo, ws.att_hi, sp ? ws.att_lo : nullptr, Bc, ntok, h->vit_heads, sp, D / 32);
         a.q_rows = cls_only ? 1 : 0;
         if (proj_cls) { a.cls_hi = ws.c_att_hi; a.cls_lo = ws.c_att_lo; }
         a.part_ws = ws.part; a.part_bytes = ws.part_bytes;
@@ -341,19 +318,15 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
         launch_gather_rows_f32(ws.resid, (int64_t)ntok * D, ws.c_resid, Bc, D, s);
     }
     bool cls_ln_done = false;   // LayerNorm-2 of the compact CLS rows already written (hi + lo) by the CLS-row proj's epilogue
+    LnParams cl = ln_params(h, ws.c_resid, D, Bc, D, 1e-6f);      // LayerNorm-2 of the compact CLS rows (KEEP_MLP_CLS)
+    cl.gamma = b.n2w; cl.beta = b.n2b; cl.out_hi = ws.c_xn_hi; cl.out_lo = ws.c_xn_lo; cl.out_kt = D / 32;
     if (proj_cls) {
         // [Bc, D] x W_proj^T as a split product on the small-M kernels: the CLS rows' attention output from the fp32 accumulators (hi + lo) against W hi + lo,
         // + LayerScale + the residual.  With KEEP_MLP_CLS in the same block the chain continues on the compact rows (its LayerNorm-2 is fused into this GEMM's reduce)
         Scope sc(h, T_VIT_TAIL, s);
         GemmParams r = gemm_params(h, ws.c_att_hi, ws.c_att_lo, b.proj, Bc, true, b.proj_b);
         r.ls = b.ls1; r.resid = ws.c_resid;
-        LnParams cl{};
-        if (mlp_cls) {
-            cl.tune = &h->tune;
-            cl.x = ws.c_resid; cl.x_stride = D; cl.rows = Bc; cl.D = D; cl.eps = 1e-6f; cl.gamma = b.n2w; cl.beta = b.n2b;
-            cl.out_hi = ws.c_xn_hi; cl.out_lo = ws.c_xn_lo; cl.out_kt = D / 32;
-            offer_ln(r, cl);
-        }
+        if (mlp_cls) offer_ln(r, cl);
         const int rc = run_gemm(h, T_VIT_TAIL, r, EPI_RESID_LS, s, ws.splitk);
         if (rc < 0) return h->fail(KEEP_EUNSUPPORTED, "CLS-row proj GEMM launch failed");
         cls_ln_done = mlp_cls && (rc & GEMM_DID_LN);
@@ -361,10 +334,6 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
     if (mlp_cls) {
         // LayerNorm-2 -> fc1 + GELU -> fc2 + LayerScale + residual as split products on the compact rows.  0.5 % of the rows; the feature is pooled from them.
         Scope sc(h, T_VIT_TAIL, s);
-        LnParams cl{};
-        cl.tune = &h->tune;
-        cl.x = ws.c_resid; cl.x_stride = D; cl.rows = Bc; cl.D = D; cl.eps = 1e-6f; cl.gamma = b.n2w; cl.beta = b.n2b;
-        cl.out_hi = ws.c_xn_hi; cl.out_lo = ws.c_xn_lo; cl.out_kt = D / 32;
         if (!cls_ln_done && launch_layernorm(cl, s)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %d", D);
         GemmParams p = gemm_params(h, ws.c_xn_hi, ws.c_xn_lo, b.fc1, Bc, true, b.fc1_b);
         p.out_hi = ws.c_mlp_hi; p.out_lo = ws.c_mlp_lo; p.out_kt = h->vit_F / 32;
@@ -424,22 +393,19 @@ int vit_end(keep_handle* h, VitLane& L) {
     {
         // final LayerNorm is per-token, global_pool='token' reads row 0 only -> normalise CLS rows only
         Scope sc(h, T_VIT_HEAD, s);
-        LnParams ln{};
-        ln.tune = &h->tune;
-        ln.x = L.cls_compact ? ws.c_resid : ws.resid; ln.x_stride = L.cls_compact ? (int64_t)D : (int64_t)L.ntok * D;
-        ln.rows = Bc; ln.D = D; ln.eps = 1e-6f;
-        ln.gamma = find(h, "visual.norm.weight")->f32; ln.beta = find(h, "visual.norm.bias")->f32;
+        LnParams ln = ln_params(h, L.cls_compact ? ws.c_resid : ws.resid, L.cls_compact ? (int64_t)D : (int64_t)L.ntok * D, Bc, D, 1e-6f);
+        ln.gamma = find_weight(h, "visual.norm.weight")->f32; ln.beta = find_weight(h, "visual.norm.bias")->f32;
         ln.out_f32 = ws.cls; ln.out_f32_stride = D;
         launch_layernorm(ln, s);
-        const WTensor* w0 = find(h, "visual_head.0.weight");
-        const WTensor* w2 = find(h, "visual_head.2.weight");
+        const WTensor* w0 = find_weight(h, "visual_head.0.weight");
+        const WTensor* w2 = find_weight(h, "visual_head.2.weight");
         SgemmParams g{};
         g.tune = &h->tune;
         g.a = ws.cls; g.lda = D; g.b = w0->f32; g.ldb = D; g.out = ws.h1; g.ldo = h->proj_dim;
-        g.bias = find(h, "visual_head.0.bias")->f32; g.M = Bc; g.N = h->proj_dim; g.K = D; g.scale = 1.f; g.act = ACT_GELU;
+        g.bias = find_weight(h, "visual_head.0.bias")->f32; g.M = Bc; g.N = h->proj_dim; g.K = D; g.scale = 1.f; g.act = ACT_GELU;
         if (launch_sgemm_f32(g, s)) return h->fail(KEEP_EUNSUPPORTED, "visual_head.0 shape");
         g.a = ws.h1; g.lda = h->proj_dim; g.b = w2->f32; g.ldb = h->proj_dim; g.out = out; g.ldo = h->proj_dim;
-        g.bias = find(h, "visual_head.2.bias")->f32; g.K = h->proj_dim; g.act = ACT_NONE;
+        g.bias = find_weight(h, "visual_head.2.bias")->f32; g.K = h->proj_dim; g.act = ACT_NONE;
         if (launch_sgemm_f32(g, s)) return h->fail(KEEP_EUNSUPPORTED, "visual_head.2 shape");
         launch_l2norm_rows(out, Bc, h->proj_dim, 1e-12f, s, h->err_flag);
     }
@@ -450,14 +416,14 @@ int txt_chunk(keep_handle* h, const int64_t* ids, const int64_t* types, const in
               float* out, hipStream_t s) {
     const bool any_split = h->any_split();
     const int H = h->bert_H, M = Pc * T;
-    TxtWs ws = carve_txt(h, h->arena, Pc, T, any_split);
+    TowerWs ws = carve_txt(h, h->arena, Pc, T, any_split);
     {
         Scope sc(h, T_TXT_EMBED, s);
-        launch_bert_embed_ln(ids, types, find(h, "text.embeddings.word_embeddings.weight")->f32,
-                             find(h, "text.embeddings.position_embeddings.weight")->f32,
-                             find(h, "text.embeddings.token_type_embeddings.weight")->f32,
-                             find(h, "text.embeddings.LayerNorm.weight")->f32,
-                             find(h, "text.embeddings.LayerNorm.bias")->f32, 1e-12f, Pc, T, H, h->bert_vocab,
+        launch_bert_embed_ln(ids, types, find_weight(h, "text.embeddings.word_embeddings.weight")->f32,
+                             find_weight(h, "text.embeddings.position_embeddings.weight")->f32,
+                             find_weight(h, "text.embeddings.token_type_embeddings.weight")->f32,
+                             find_weight(h, "text.embeddings.LayerNorm.weight")->f32,
+                             find_weight(h, "text.embeddings.LayerNorm.bias")->f32, 1e-12f, Pc, T, H, h->bert_vocab,
                              h->bert_types, ws.resid, ws.xn_hi, any_split ? ws.xn_lo : nullptr, h->err_flag, s);
     }
     for (int l = 0; l < h->bert_layers; ++l) {
@@ -472,16 +438,12 @@ int txt_chunk(keep_handle* h, const int64_t* ids, const int64_t* types, const in
         }
         {
             Scope sc(h, T_TXT_ATTN, s);
-            AttnParams a{};
-            a.tune = &h->tune;
-            a.qkv_hi = ws.qkv_hi; a.qkv_lo = ws.qkv_lo; a.out_hi = ws.att_hi; a.out_lo = sp ? ws.att_lo : nullptr;
-            a.mask = mask; a.batch = Pc; a.ntok = T; a.heads = h->bert_heads; a.split = sp; a.scale = 0.125f; a.out_kt = H / 32;
-            a.part_ws = ws.attn_part; a.part_bytes = ws.attn_part_bytes;
+            AttnParams a = attn_params(h, ws.qkv_hi, ws.qkv_lo, ws.att_hi, sp ? ws.att_lo : nullptr, Pc, T, h->bert_heads, sp, H / 32);
+            a.mask = mask;
+            a.part_ws = ws.part; a.part_bytes = ws.part_bytes;
             if (launch_attention(a, s)) return h->fail(KEEP_EUNSUPPORTED, "sequence length %d unsupported (max 512)", T);
         }
-        LnParams ln{};
-        ln.tune = &h->tune;
-        ln.x = ws.resid; ln.x_stride = H; ln.rows = M; ln.D = H; ln.eps = 1e-12f;
+        LnParams ln = ln_params(h, ws.resid, H, M, H, 1e-12f);
         ln.out_f32 = ws.resid; ln.out_f32_stride = H; ln.out_hi = ws.xn_hi; ln.out_kt = H / 32;
         ln.gamma = b.ln1w; ln.beta = b.ln1b; ln.out_lo = sp ? ws.xn_lo : nullptr;
         int did;
@@ -522,290 +484,20 @@ int txt_chunk(keep_handle* h, const int64_t* ids, const int64_t* types, const in
         SgemmParams g{};
         g.tune = &h->tune;
         g.a = ws.resid; g.lda = (int64_t)T * H;            // row p*T: the [CLS] token of prompt p
-        g.b = find(h, "text.pooler.dense.weight")->f32; g.ldb = H; g.out = out; g.ldo = H;
-        g.bias = find(h, "text.pooler.dense.bias")->f32; g.M = Pc; g.N = H; g.K = H; g.scale = 1.f; g.act = ACT_TANH;
+        g.b = find_weight(h, "text.pooler.dense.weight")->f32; g.ldb = H; g.out = out; g.ldo = H;
+        g.bias = find_weight(h, "text.pooler.dense.bias")->f32; g.M = Pc; g.N = H; g.K = H; g.scale = 1.f; g.act = ACT_TANH;
         if (launch_sgemm_f32(g, s)) return h->fail(KEEP_EUNSUPPORTED, "pooler shape");
         launch_l2norm_rows(out, Pc, H, 1e-12f, s, h->err_flag);
     }
     return check_launch(h, "encode_text");
 }
 
-// store one state_dict entry
-int store_tensor(keep_handle* h, const std::string& key, const float* dev, const std::vector<int64_t>& shape) {
-    WTensor t; t.shape = shape; t.numel = numel_of(shape);
-    if (t.numel <= 0) return h->fail(KEEP_EINVAL, "%s: empty tensor", key.c_str());
-    if (is_gemm_weight(key)) {
-        // fp16 hi/lo planes in blk layout; rows (out features) must fill whole 256-row tiles
-        const int64_t n = t.shape[0], k = t.numel / t.shape[0];
-        if (n % 256 || k % 32) return h->fail(KEEP_EUNSUPPORTED, "%s: [%lld,%lld] is not tileable (rows %% 256, cols %% 32)", key.c_str(), (long long)n, (long long)k);
-        // The GEMM operand planes are fp16: 11 significant bits between 6.1e-5 and 65504, fewer below (subnormals), none above.  A weight whose
-        // entries sit above that window cannot be represented at all: refused.  (Below it: see the warning further down.)
-        {
-            float host[2] = {0.f, 0.f};
-            HIPCHK(h, hipMemsetAsync(h->err_flag + 2, 0, 2 * sizeof(float), nullptr));
-            launch_weight_stats(dev, t.numel, reinterpret_cast<float*>(h->err_flag + 2), nullptr);
-            HIPCHK(h, hipMemcpy(host, h->err_flag + 2, sizeof host, hipMemcpyDeviceToHost));
-            const double rms = sqrt((double)host[1] / (double)t.numel);
-            if (!(host[0] <= 6.0e4f)) return h->fail(KEEP_EUNSUPPORTED, "%s: max |w| = %g does not fit the fp16 operand planes (65504) or is not finite", key.c_str(), (double)host[0]);
-            // A weight far below fp16's normal range (a projection whose magnitude lives in its LayerScale, a pruned or dead layer) still loads, as it
-            // does in the reference.  proj / fc2 of the image tower are pre-scaled by a power of two into the window -- exact: their epilogue is
-            // ls * (acc + bias), and finalize_vit hands it ls / 2^k and bias * 2^k -- any other weight keeps its entries (they fall into fp16
-            // subnormals and lose RELATIVE precision; what such a layer adds to the stream is as small as the layer) and the caller is told.
-            if (rms > 0.0 && rms < 2.5e-4) {
-                const bool foldable = starts_with(key, "visual.blocks.") && (key.find(".attn.proj.weight") != std::string::npos || key.find(".mlp.fc2.weight") != std::string::npos);
-                char buf[512];
-                if (foldable && t.numel < (1ll << 31)) {
-                    float k2 = exp2f(roundf(log2f(0.02f / (float)rms)));
-                    while (host[0] * k2 > 3.0e4f) k2 *= 0.5f;
-                    t.prescale = k2;
-                    snprintf(buf, sizeof buf, "%s: rms %g is below fp16's normal range; stored as 2^%d * W with LayerScale / bias adjusted (exact)", key.c_str(), rms, (int)log2f(k2));
-                } else {
-                    snprintf(buf, sizeof buf, "%s: rms %g is below what the fp16 operand planes resolve with 11 bits (entries fall into fp16 subnormals): "
-                                              "this layer's products carry fewer significant bits than the error budget assumes", key.c_str(), rms);
-                }
-                h->load_warnings += (h->load_warnings.empty() ? "" : "\n") + std::string(buf);
-            }
-        }
-        float* scaled = nullptr;
-        if (t.prescale != 1.f) {
-            HIPCHK(h, hipMalloc(&scaled, t.numel * sizeof(float)));
-            launch_scale_vec(dev, (int)t.numel, t.prescale, scaled, nullptr);
-            dev = scaled;
-        }
-        HIPCHK(h, hipMalloc(&t.hi, t.numel * sizeof(f16)));
-        HIPCHK(h, hipMalloc(&t.lo, t.numel * sizeof(f16)));
-        // the MLP weights of the image tower also get the MX-fp4 side planes of the compensated product (quant4.h)
-        if ((key.find(".mlp.fc") != std::string::npos || key.find(".attn.qkv.") != std::string::npos) && starts_with(key, "visual.") && k % 128 == 0 && k >= 256) {
-            HIPCHK(h, hipMalloc(&t.q, keepk::q4_data_bytes(n, k)));
-            HIPCHK(h, hipMalloc(&t.sc, keepk::q4_scale_bytes(n, k)));
-            launch_quant_blockify(dev, t.hi, t.lo, t.q, t.sc, (int)n, (int)k, nullptr);
-        } else {
-            launch_split_blockify(dev, t.hi, t.lo, (int)n, (int)k, nullptr);
-        }
-        HIPCHK(h, hipStreamSynchronize(nullptr));
-        if (scaled) (void)hipFree(scaled);
-    } else {
-        const size_t bytes = (size_t)(t.numel > 4 ? t.numel : 4) * sizeof(float);
-        HIPCHK(h, hipMalloc(&t.f32, bytes));
-        HIPCHK(h, hipMemcpy(t.f32, dev, t.numel * sizeof(float), hipMemcpyDeviceToDevice));
-    }
-    auto it = h->w.find(key);
-    if (it != h->w.end()) {
-        if (it->second.f32) hipFree(it->second.f32);
-        if (it->second.hi) hipFree(it->second.hi);
-        if (it->second.lo) hipFree(it->second.lo);
-        if (it->second.q) hipFree(it->second.q);
-        if (it->second.sc) hipFree(it->second.sc);
-    }
-    h->w[key] = t;
-    h->finalized = false;
-    return KEEP_OK;
-}
-
-const float* need_vec(keep_handle* h, const std::string& key, int64_t n, std::string& missing) {
-    const WTensor* t = find(h, key);
-    if (!t || !t->f32 || t->numel != n) { missing += (missing.empty() ? "" : ", ") + key; return nullptr; }
-    return t->f32;
-}
-const WTensor* need_mat(keep_handle* h, const std::string& key, int64_t n, int64_t k, std::string& missing) {
-    const WTensor* t = find(h, key);
-    if (!t || !t->hi || t->shape.empty() || t->shape[0] != n || t->numel != n * k) {
-        missing += (missing.empty() ? "" : ", ") + key; return nullptr;
-    }
-    return t;
-}
-
-int finalize_vit(keep_handle* h) {
-    h->vblocks.clear(); h->vit_depth = 0;
-    h->free_cal();               // corrected biases belong to the weights they were calibrated on
-    h->drop_pos_cache();         // so do the resampled position tables
-    for (float* v : h->owned_vecs) (void)hipFree(v);
-    h->owned_vecs.clear();
-    const WTensor* pe = find(h, "visual.patch_embed.proj.weight");
-    if (!pe) {
-        for (auto& kv : h->w) if (starts_with(kv.first, "visual")) return h->fail(KEEP_EKEY, "missing key visual.patch_embed.proj.weight");
-        return KEEP_OK;     // image tower not loaded
-    }
-    if (pe->shape.size() != 4 || pe->shape[1] != 3 || pe->shape[2] != 16 || pe->shape[3] != 16)
-        return h->fail(KEEP_EUNSUPPORTED, "patch_embed.proj.weight must be [D,3,16,16]");
-    const int64_t D = pe->shape[0];
-    if (D % 256 || D > 1024) return h->fail(KEEP_EUNSUPPORTED, "embed dim %lld unsupported", (long long)D);
-    int depth = 0;
-    while (find(h, "visual.blocks." + std::to_string(depth) + ".attn.qkv.weight")) ++depth;
-    if (!depth) return h->fail(KEEP_EKEY, "missing key visual.blocks.0.attn.qkv.weight");
-    const WTensor* fc1 = find(h, "visual.blocks.0.mlp.fc1.weight");
-    if (!fc1) return h->fail(KEEP_EKEY, "missing key visual.blocks.0.mlp.fc1.weight");
-    const int64_t F = fc1->shape[0];
-    const WTensor* h0 = find(h, "visual_head.0.weight");
-    if (!h0 || h0->shape.size() != 2 || h0->shape[1] != D) return h->fail(KEEP_EKEY, "missing or mis-shaped key visual_head.0.weight");
-    const int64_t PJ = h0->shape[0];
-    std::string miss;
-    need_vec(h, "visual.cls_token", D, miss);
-    need_vec(h, "visual.pos_embed", 197 * D, miss);
-    need_vec(h, "visual.patch_embed.proj.bias", D, miss);
-    need_vec(h, "visual.norm.weight", D, miss);
-    need_vec(h, "visual.norm.bias", D, miss);
-    need_vec(h, "visual_head.0.bias", PJ, miss);
-    need_vec(h, "visual_head.2.weight", PJ * PJ, miss);
-    need_vec(h, "visual_head.2.bias", PJ, miss);
-    for (int i = 0; i < depth; ++i) {
-        const std::string p = "visual.blocks." + std::to_string(i) + ".";
-        VitBlock b{};
-        b.n1w = need_vec(h, p + "norm1.weight", D, miss); b.n1b = need_vec(h, p + "norm1.bias", D, miss);
-        b.n2w = need_vec(h, p + "norm2.weight", D, miss); b.n2b = need_vec(h, p + "norm2.bias", D, miss);
-        b.qkv = need_mat(h, p + "attn.qkv.weight", 3 * D, D, miss); b.qkv_b = need_vec(h, p + "attn.qkv.bias", 3 * D, miss);
-        b.proj = need_mat(h, p + "attn.proj.weight", D, D, miss);   b.proj_b = need_vec(h, p + "attn.proj.bias", D, miss);
-        b.fc1 = need_mat(h, p + "mlp.fc1.weight", F, D, miss);      b.fc1_b = need_vec(h, p + "mlp.fc1.bias", F, miss);
-        b.fc2 = need_mat(h, p + "mlp.fc2.weight", D, F, miss);      b.fc2_b = need_vec(h, p + "mlp.fc2.bias", D, miss);
-        b.ls1 = need_vec(h, p + "ls1.gamma", D, miss);              b.ls2 = need_vec(h, p + "ls2.gamma", D, miss);
-        h->vblocks.push_back(b);
-    }
-    if (!miss.empty()) return h->fail(KEEP_EKEY, "missing or mis-shaped key(s): %s", miss.c_str());
-    if (F % 256 || D % 256 || PJ % 16) return h->fail(KEEP_EUNSUPPORTED, "ViT dims not tileable");
-    // pre-scaled proj / fc2 planes (store_tensor): ls * (acc + b) with acc = 2^k * (a . w)  ->  (ls / 2^k) * (acc + 2^k * b), exact in fp32
-    auto rescaled = [&](const float* v, float f) -> const float* {
-        float* o = nullptr;
-        if (hipMalloc(&o, D * sizeof(float)) != hipSuccess) return nullptr;
-        launch_scale_vec(v, (int)D, f, o, nullptr);
-        h->owned_vecs.push_back(o);
-        return o;
-    };
-    for (auto& b : h->vblocks) {
-        if (b.proj->prescale != 1.f) { b.ls1 = rescaled(b.ls1, 1.f / b.proj->prescale); b.proj_b = rescaled(b.proj_b, b.proj->prescale); }
-        if (b.fc2->prescale != 1.f) { b.ls2 = rescaled(b.ls2, 1.f / b.fc2->prescale); b.fc2_b = rescaled(b.fc2_b, b.fc2->prescale); }
-        if (!b.ls1 || !b.proj_b || !b.ls2 || !b.fc2_b) return h->fail(KEEP_EHIP, "hipMalloc failed for a rescaled LayerScale / bias vector");
-    }
-    HIPCHK(h, hipStreamSynchronize(nullptr));
-    h->vit_has_q = true;
-    for (auto& b : h->vblocks) if (!b.fc1->q || !b.fc2->q) h->vit_has_q = false;
-    if (depth > keep_handle::MAX_BLOCKS) return h->fail(KEEP_EUNSUPPORTED, "image tower of %d blocks (the per-block precision plan holds %d)", depth, keep_handle::MAX_BLOCKS);
-    h->vit_depth = depth; h->vit_D = (int)D; h->vit_heads = (int)(D / 64); h->vit_F = (int)F; h->proj_dim = (int)PJ;
-    return KEEP_OK;
-}
-
-int finalize_bert(keep_handle* h) {
-    for (auto& l : h->blayers) { if (l.qkv.hi) hipFree(l.qkv.hi); if (l.qkv.lo) hipFree(l.qkv.lo); if (l.qkv_b) hipFree(l.qkv_b); }
-    h->blayers.clear(); h->bert_layers = 0;
-    const WTensor* we = find(h, "text.embeddings.word_embeddings.weight");
-    if (!we) {
-        for (auto& kv : h->w) if (starts_with(kv.first, "text.")) return h->fail(KEEP_EKEY, "missing key text.embeddings.word_embeddings.weight");
-        return KEEP_OK;
-    }
-    if (we->shape.size() != 2) return h->fail(KEEP_EINVAL, "word_embeddings must be 2-D");
-    const int64_t V = we->shape[0], H = we->shape[1];
-    if (H != 768 && H != 1024) return h->fail(KEEP_EUNSUPPORTED, "hidden size %lld unsupported (768 or 1024)", (long long)H);
-    int L = 0;
-    while (find(h, "text.encoder.layer." + std::to_string(L) + ".attention.self.query.weight")) ++L;
-    if (!L) return h->fail(KEEP_EKEY, "missing key text.encoder.layer.0.attention.self.query.weight");
-    const WTensor* iw = find(h, "text.encoder.layer.0.intermediate.dense.weight");
-    if (!iw) return h->fail(KEEP_EKEY, "missing key text.encoder.layer.0.intermediate.dense.weight");
-    const int64_t F = iw->shape[0];
-    const WTensor* pos = find(h, "text.embeddings.position_embeddings.weight");
-    const WTensor* typ = find(h, "text.embeddings.token_type_embeddings.weight");
-    if (!pos || !typ || pos->shape.size() != 2 || typ->shape.size() != 2 || pos->shape[1] != H || typ->shape[1] != H)
-        return h->fail(KEEP_EKEY, "missing or mis-shaped position/token_type embeddings");
-    std::string miss;
-    need_vec(h, "text.embeddings.LayerNorm.weight", H, miss);
-    need_vec(h, "text.embeddings.LayerNorm.bias", H, miss);
-    need_vec(h, "text.pooler.dense.weight", H * H, miss);
-    need_vec(h, "text.pooler.dense.bias", H, miss);
-    h->blayers.resize(L);
-    for (int l = 0; l < L; ++l) {
-        const std::string p = "text.encoder.layer." + std::to_string(l) + ".";
-        BertLayer& b = h->blayers[l];
-        const WTensor* q = need_mat(h, p + "attention.self.query.weight", H, H, miss);
-        const WTensor* k = need_mat(h, p + "attention.self.key.weight", H, H, miss);
-        const WTensor* v = need_mat(h, p + "attention.self.value.weight", H, H, miss);
-        const float* qb = need_vec(h, p + "attention.self.query.bias", H, miss);
-        const float* kb = need_vec(h, p + "attention.self.key.bias", H, miss);
-        const float* vb = need_vec(h, p + "attention.self.value.bias", H, miss);
-        b.o = need_mat(h, p + "attention.output.dense.weight", H, H, miss);
-        b.o_b = need_vec(h, p + "attention.output.dense.bias", H, miss);
-        b.ln1w = need_vec(h, p + "attention.output.LayerNorm.weight", H, miss);
-        b.ln1b = need_vec(h, p + "attention.output.LayerNorm.bias", H, miss);
-        b.i = need_mat(h, p + "intermediate.dense.weight", F, H, miss);
-        b.i_b = need_vec(h, p + "intermediate.dense.bias", F, miss);
-        b.d = need_mat(h, p + "output.dense.weight", H, F, miss);
-        b.d_b = need_vec(h, p + "output.dense.bias", H, miss);
-        b.ln2w = need_vec(h, p + "output.LayerNorm.weight", H, miss);
-        b.ln2b = need_vec(h, p + "output.LayerNorm.bias", H, miss);
-        if (!miss.empty()) continue;
-        // fuse q|k|v into one [3H,H] weight so the layer needs a single projection GEMM
-        b.qkv.shape = {3 * H, H}; b.qkv.numel = 3 * H * H;
-        HIPCHK(h, hipMalloc(&b.qkv.hi, b.qkv.numel * sizeof(f16)));
-        HIPCHK(h, hipMalloc(&b.qkv.lo, b.qkv.numel * sizeof(f16)));
-        HIPCHK(h, hipMalloc(&b.qkv_b, 3 * H * sizeof(float)));
-        const WTensor* parts[3] = {q, k, v};
-        const float* bparts[3] = {qb, kb, vb};
-        for (int j = 0; j < 3; ++j) {
-            HIPCHK(h, hipMemcpy(b.qkv.hi + (size_t)j * H * H, parts[j]->hi, H * H * sizeof(f16), hipMemcpyDeviceToDevice));
-            HIPCHK(h, hipMemcpy(b.qkv.lo + (size_t)j * H * H, parts[j]->lo, H * H * sizeof(f16), hipMemcpyDeviceToDevice));
-            HIPCHK(h, hipMemcpy(b.qkv_b + (size_t)j * H, bparts[j], H * sizeof(float), hipMemcpyDeviceToDevice));
-        }
-    }
-    if (!miss.empty()) { h->blayers.clear(); return h->fail(KEEP_EKEY, "missing or mis-shaped key(s): %s", miss.c_str()); }
-    if (F % 256 || H % 256) return h->fail(KEEP_EUNSUPPORTED, "BERT dims not tileable");
-    h->bert_layers = L; h->bert_H = (int)H; h->bert_heads = (int)(H / 64); h->bert_F = (int)F;
-    h->bert_vocab = (int)V; h->bert_maxpos = (int)pos->shape[0]; h->bert_types = (int)typ->shape[0];
-    return KEEP_OK;
-}
-
-bool known_key(const std::string& k) {
-    static const char* exact[] = {"logit_scale", "visual.cls_token", "visual.pos_embed", "visual.patch_embed.proj.weight",
-        "visual.patch_embed.proj.bias", "visual.norm.weight", "visual.norm.bias", "visual_head.0.weight", "visual_head.0.bias",
-        "visual_head.2.weight", "visual_head.2.bias", "text.embeddings.word_embeddings.weight",
-        "text.embeddings.position_embeddings.weight", "text.embeddings.token_type_embeddings.weight",
-        "text.embeddings.LayerNorm.weight", "text.embeddings.LayerNorm.bias", "text.pooler.dense.weight", "text.pooler.dense.bias"};
-    for (auto e : exact) if (k == e) return true;
-    static const char* vsuf[] = {"norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias",
-        "ls1.gamma", "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias", "ls2.gamma"};
-    static const char* tsuf[] = {"attention.self.query.weight", "attention.self.query.bias", "attention.self.key.weight",
-        "attention.self.key.bias", "attention.self.value.weight", "attention.self.value.bias", "attention.output.dense.weight",
-        "attention.output.dense.bias", "attention.output.LayerNorm.weight", "attention.output.LayerNorm.bias",
-        "intermediate.dense.weight", "intermediate.dense.bias", "output.dense.weight", "output.dense.bias",
-        "output.LayerNorm.weight", "output.LayerNorm.bias"};
-    auto layered = [&](const char* prefix, const char* const* suf, size_t n) {
-        if (!starts_with(k, prefix)) return false;
-        size_t i = strlen(prefix), j = i;
-        while (j < k.size() && k[j] >= '0' && k[j] <= '9') ++j;
-        if (j == i || j >= k.size() || k[j] != '.') return false;
-        const std::string rest = k.substr(j + 1);
-        for (size_t q = 0; q < n; ++q) if (rest == suf[q]) return true;
-        return false;
-    };
-    return layered("visual.blocks.", vsuf, sizeof vsuf / sizeof *vsuf) || layered("text.encoder.layer.", tsuf, sizeof tsuf / sizeof *tsuf);
-}
 
 int tag_by_name(const char* name) {
     for (int i = 0; i < T_COUNT; ++i) if (!strcmp(name, kTagNames[i])) return i;
     return -1;
 }
 
-// temp device buffers for the op entry points
-struct Tmp {
-    std::vector<void*> ptrs;
-    ~Tmp() { for (auto p : ptrs) hipFree(p); }
-    template <typename T> T* get(size_t n) { void* p = nullptr; if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) return nullptr; ptrs.push_back(p); return (T*)p; }
-};
-
-// one wave: shader-clock cycles (s_memtime) against the constant 100 MHz counter (s_memrealtime) over ~`spin_us` microseconds
-__global__ void clock_probe_kernel(long long* out, int spin_ticks) {
-    if (threadIdx.x != 0) return;
-    const long long r0 = (long long)__builtin_amdgcn_s_memrealtime(), c0 = (long long)__builtin_readcyclecounter();
-    long long r1 = r0;
-    while (r1 - r0 < spin_ticks) { __builtin_amdgcn_s_sleep(32); r1 = (long long)__builtin_amdgcn_s_memrealtime(); }
-    const long long c1 = (long long)__builtin_readcyclecounter();
-    out[0] = c1 - c0; out[1] = r1 - r0;
-}
-
-__global__ void f16_planes_to_f32_kernel(const f16* hi, const f16* lo, float* out, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        out[i] = (float)hi[i] + (lo ? (float)lo[i] : 0.f);
-}
-void planes_to_f32(const f16* hi, const f16* lo, float* out, int64_t n, hipStream_t s) {
-    int blocks = (int)((n + 255) / 256); if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(f16_planes_to_f32_kernel, dim3(blocks), dim3(256), 0, s, hi, lo, out, n);
-}
 
 // ATen's antialiased bicubic resample (F.interpolate(mode="bicubic", antialias=True, align_corners=False), what timm's
 // resample_abs_pos_embed calls) as a weight table, in double: Keys cubic with a = -0.5, support 2 max(in / out, 1), window clipped at the
@@ -839,7 +531,7 @@ void aa_bicubic_table(int in, int out, std::vector<int>& beg, std::vector<double
 // CLS row as it is + the 14 x 14 patch table resampled to gh x gw (cached per grid, POS_CACHE grids).  Allocates and synchronises: never
 // called inside a graph capture (encode_image_run asks for it before graph_run).
 int vit_pos_table(keep_handle* h, int gh, int gw, const float** out) {
-    const float* pos = find(h, "visual.pos_embed")->f32;
+    const float* pos = find_weight(h, "visual.pos_embed")->f32;
     if (gh == 14 && gw == 14) { *out = pos; return KEEP_OK; }
     for (const auto& e : h->pos_cache) if (e.gh == gh && e.gw == gw) { *out = e.buf; return KEEP_OK; }
     if ((int)h->pos_cache.size() >= keep_handle::POS_CACHE) {
@@ -859,7 +551,7 @@ int vit_pos_table(keep_handle* h, int gh, int gw, const float** out) {
     Tmp t;
     int* d_yb = t.get<int>(yb.size()); int* d_xb = t.get<int>(xb.size());
     double* d_wy = t.get<double>(wy.size()); double* d_wx = t.get<double>(wx.size());
-    if (!d_yb || !d_xb || !d_wy || !d_wx) { (void)hipFree(buf); return h->fail(KEEP_ENOMEM, "position table: temp alloc"); }
+    if (!t.ok) { (void)hipFree(buf); return h->fail(KEEP_ENOMEM, "position table: temp alloc"); }
     hipError_t e = hipMemcpy(d_yb, yb.data(), yb.size() * sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_xb, xb.data(), xb.size() * sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_wy, wy.data(), wy.size() * sizeof(double), hipMemcpyHostToDevice);
@@ -884,14 +576,15 @@ int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t 
     if (rc) return rc;
     const size_t px = pix_dtype == KEEP_PIX_F32 ? 4 : (pix_dtype == KEEP_PIX_U8_HWC ? 1 : 2);    // bytes per value; 3 * 16 gh * 16 gw values per tile in every layout
     const size_t tile_vals = (size_t)3 * (gh * 16) * (gw * 16);
-    if (h->use_graphs && !h->prof_mode && B * ntok <= SKINNY_MAX_M && B <= h->max_tiles) {
-        const bool sp = h->any_split();
-        const size_t ws_bytes = align_up(vit_ws_bytes(h, B, sp, ntok)), ib = (size_t)B * tile_vals * px, ob = (size_t)B * h->proj_dim * sizeof(float);
-        rc = ensure_arena(h, ws_bytes + align_up(ib) + align_up(ob));
-        if (rc) return rc;
-        char* st_pix = h->arena + ws_bytes;
-        float* st_out = (float*)(h->arena + ws_bytes + align_up(ib));
-        HIPCHK(h, hipMemcpyAsync(st_pix, pixels, ib, hipMemcpyDeviceToDevice, s));
+    const bool graph = h->use_graphs && !h->prof_mode && B * ntok <= SKINNY_MAX_M && B <= h->max_tiles;
+    const VitPlan plan = vit_plan(h, B, ntok, tile_vals * px, graph);
+    rc = ensure_arena(h, plan.total);
+    if (rc) return rc;
+    if (graph) {
+        const size_t ob = (size_t)B * h->proj_dim * sizeof(float);
+        char* st_pix = h->arena + plan.o_pix;
+        float* st_out = (float*)(h->arena + plan.o_out);
+        HIPCHK(h, hipMemcpyAsync(st_pix, pixels, (size_t)B * tile_vals * px, hipMemcpyDeviceToDevice, s));
         char key[96];
         if (g14) snprintf(key, sizeof key, "img|%lld|%d|%d", (long long)B, pix_dtype, h->precision);     // (keep_classify switches the precision per call, without an option epoch)
         else snprintf(key, sizeof key, "img|%lld|%d|%d|%dx%d", (long long)B, pix_dtype, h->precision, gh, gw);
@@ -899,7 +592,7 @@ int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t 
             VitLane L{};
             L.Bc = (int)B; L.pixels = st_pix; L.pix_dtype = pix_dtype; L.out = st_out; L.s = cs;
             L.gh = gh; L.gw = gw; L.ntok = ntok; L.pos = pos;
-            L.ws = carve_vit(h, h->arena, L.Bc, sp, ntok);
+            L.ws = carve_vit(h, h->arena, L.Bc, plan.split, ntok);
             int r = vit_begin(h, L);
             for (int i = 0; !r && i < h->vit_depth; ++i) r = vit_layer(h, L, i);
             return r ? r : vit_end(h, L);
@@ -908,17 +601,8 @@ int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t 
         HIPCHK(h, hipMemcpyAsync(out, st_out, ob, hipMemcpyDeviceToDevice, s));
         return KEEP_OK;
     }
-    // lanes: split the batch over n_streams concurrent sub-batches once there is enough work for each (in 197-token tile equivalents)
-    int lanes = h->n_streams;
-    while (lanes > 1 && B * ntok < (int64_t)lanes * h->lane_min_tiles * 197) --lanes;
-    int64_t per = (B + lanes - 1) / lanes;
-    // sub-batches are bounded in tokens: per * ntok <= max_tiles * 197 (a 512 x 512 call needs the arena of a 224 x 224 one)
-    const int64_t per_max = std::max<int64_t>((int64_t)h->max_tiles * 197 / ntok, 1);
-    if (per > per_max) per = per_max;
-    const bool split = h->any_split();
-    const size_t lane_bytes = align_up(vit_ws_bytes(h, per, split, ntok));
-    rc = ensure_arena(h, lane_bytes * lanes);
-    if (rc) return rc;
+    const int lanes = plan.lanes;
+    const int64_t per = plan.per;
     if (lanes > 1) {
         if (!h->ev_fork) HIPCHK(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
         for (int l = 0; l < lanes; ++l) {
@@ -941,7 +625,7 @@ int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t 
             x.out = out + lo * h->proj_dim;
             x.s = lanes > 1 ? h->aux[l] : s;
             x.gh = gh; x.gw = gw; x.ntok = ntok; x.pos = pos;
-            x.ws = carve_vit(h, h->arena + (size_t)l * lane_bytes, x.Bc, split, ntok);
+            x.ws = carve_vit(h, h->arena + (size_t)l * plan.lane_bytes, x.Bc, plan.split, ntok);
         }
         for (int l = 0; l < nl; ++l) if ((rc = vit_begin(h, L[l]))) return rc;
         for (int i = 0; i < h->vit_depth; ++i)
@@ -992,6 +676,44 @@ int similarity_run(keep_handle* h, const float* img, const float* txt, int64_t N
 }
 
 
+// The options that are one int of the handle (hm) or of its kernel-selection block (tm): keep_set_option and keep_get_option both walk this
+// table.  A bool is stored as v ? 1 : 0; anything else must lie in [lo, hi] or the call fails with `msg`.  The options whose domain is a set
+// (precision, proj_impl, attn_waves, gemm_impl), the float label_margin, the read-only names and the diagnostics are explicit cases beside it.
+enum : unsigned { OPT_REPLAN = 1,       // a prefix shorthand: the whole per-block plan is rewritten from the four of them (a plan set block by block is replaced)
+                  OPT_WRITEONLY = 2 };  // keep_get_option answers -1.  TODO: fused_screening and lane_min_tiles can be set but not read back; making them readable changes behaviour
+struct Opt { const char* name; int keep_handle::* hm; int KeepTune::* tm; bool is_bool; int lo, hi; const char* msg; unsigned flags; };
+constexpr int NO_MAX = 0x7fffffff;
+static_assert(SKINNY_MAX_M == 1024, "the gemm_skinny_m message below spells the bound out");
+const Opt kOptions[] = {
+    {"graphs", &keep_handle::use_graphs, nullptr, true, 0, 0, nullptr, 0},
+    {"strict_blocks", &keep_handle::strict_blocks, nullptr, false, 0, NO_MAX, "strict_blocks < 0", 0},
+    {"comp_full_blocks", &keep_handle::comp_full_blocks, nullptr, false, 0, NO_MAX, "comp_full_blocks < 0", OPT_REPLAN},
+    {"comp_mlp_blocks", &keep_handle::comp_mlp_blocks, nullptr, false, 0, NO_MAX, "comp_mlp_blocks < 0", OPT_REPLAN},
+    {"comp_qkv", &keep_handle::comp_qkv, nullptr, true, 0, 0, nullptr, OPT_REPLAN},
+    {"comp_qkv_from", &keep_handle::comp_qkv_from, nullptr, false, 0, NO_MAX, "comp_qkv_from < 0", OPT_REPLAN},
+    {"comp_min_tiles", &keep_handle::comp_min_tiles, nullptr, false, 24, NO_MAX, "comp_min_tiles must be >= 24 (the compensated product needs the 256x256 kernel)", 0},
+    {"fused_screening", &keep_handle::fused_screening, nullptr, false, 0, 2, "fused_screening must be 0..2", OPT_WRITEONLY},
+    {"max_tiles", &keep_handle::max_tiles, nullptr, false, 1, NO_MAX, "max_tiles < 1", 0},
+    {"max_prompts", &keep_handle::max_prompts, nullptr, false, 1, NO_MAX, "max_prompts < 1", 0},
+    {"cls_tail", &keep_handle::cls_tail, nullptr, true, 0, 0, nullptr, 0},
+    {"patch_split", &keep_handle::patch_split, nullptr, true, 0, 0, nullptr, 0},
+    {"grid_plan", &keep_handle::grid_plan, nullptr, false, 0, 2, "grid_plan must be 0, 1 or 2", 0},
+    {"bias_correction", &keep_handle::bias_correction, nullptr, true, 0, 0, nullptr, 0},
+    {"streams", &keep_handle::n_streams, nullptr, false, 1, 4, "streams must be 1..4", 0},
+    {"lane_min_tiles", &keep_handle::lane_min_tiles, nullptr, false, 6, NO_MAX, "lane_min_tiles must be >= 6", OPT_WRITEONLY},
+    {"gemm_persistent", nullptr, &KeepTune::gemm_persistent, false, 0, 1024, "gemm_persistent must be 0..1024", 0},
+    {"gemm_splitk_tiles", nullptr, &KeepTune::gemm_splitk_tiles, false, 0, 256, "gemm_splitk_tiles must be 0..256", 0},
+    {"sgemv_m", nullptr, &KeepTune::sgemv_m, false, 0, 16, "sgemv_m must be 0..16", 0},
+    {"skinny_wide", nullptr, &KeepTune::skinny_wide, true, 0, 0, nullptr, 0},
+    {"gemm_skinny_m", nullptr, &KeepTune::gemm_skinny_m, false, 0, SKINNY_MAX_M, "gemm_skinny_m must be 0..1024", 0},
+    {"ln_impl", nullptr, &KeepTune::ln_impl, false, 0, 2, "ln_impl must be 0, 1 or 2", 0},
+};
+const Opt* find_opt(const char* name) {
+    for (const Opt& o : kOptions) if (!strcmp(name, o.name)) return &o;
+    return nullptr;
+}
+int& opt_value(keep_handle* h, const Opt& o) { return o.hm ? h->*o.hm : h->tune.*o.tm; }
+
 }  // namespace
 
 // =============================================================================================
@@ -1040,94 +762,24 @@ int keep_destroy(keep_handle* h) {
 
 const char* keep_last_error(keep_handle* h) { return h ? h->err.c_str() : "null handle"; }
 
-const char* keep_load_warnings(keep_handle* h) {
-    if (!h) return "";
-    static thread_local std::string out;
-    out.swap(h->load_warnings);
-    h->load_warnings.clear();
-    return out.c_str();
-}
-
-int keep_load_tensor(keep_handle* h, const char* key, const float* data, int ndim, const int64_t* shape, int on_device) {
-    if (!h || !key || !data || ndim < 0 || ndim > 8) return KEEP_EINVAL;
-    KEEP_ON_DEVICE(h);
-    const std::string k(key);
-    if (k == "text.embeddings.position_ids" || k == "text.embeddings.token_type_ids") return KEEP_OK;   // buffers of older checkpoints
-    if (!known_key(k)) return h->fail(KEEP_EKEY, "unexpected key %s", key);
-    if (k == "visual.pos_embed") h->drop_pos_cache();
-    std::vector<int64_t> shp(shape, shape + ndim);
-    if (ndim == 0) shp = {1};
-    const int64_t n = numel_of(shp);
-    if (n <= 0) return h->fail(KEEP_EINVAL, "%s: bad shape", key);
-    if (on_device) {
-        // the repack below runs on the null stream; whatever produced `data` (e.g. a dtype conversion on the caller's
-        // stream) must have finished first, and this entry point takes no stream: load time, so simply drain the device
-        HIPCHK(h, hipDeviceSynchronize());
-        return store_tensor(h, k, data, shp);
-    }
-    float* tmp = nullptr;
-    HIPCHK(h, hipMalloc(&tmp, n * sizeof(float)));
-    hipError_t e = hipMemcpy(tmp, data, n * sizeof(float), hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? store_tensor(h, k, tmp, shp) : h->fail(KEEP_EHIP, "H2D copy of %s failed", key);
-    hipFree(tmp);
-    return rc;
-}
-
-int keep_finalize_weights(keep_handle* h) {
-    if (!h) return KEEP_EINVAL;
-    KEEP_ON_DEVICE(h);
-    ++h->opt_epoch;
-    int rc = finalize_vit(h);
-    if (rc) return rc;
-    rc = finalize_bert(h);
-    if (rc) return rc;
-    if (!h->vit_depth && !h->bert_layers) return h->fail(KEEP_EKEY, "no tower loaded");
-    HIPCHK(h, hipDeviceSynchronize());
-    h->finalized = true;
-    return KEEP_OK;
-}
-
-int keep_vit_depth(keep_handle* h) { return h && h->finalized ? h->vit_depth : 0; }
-int keep_bert_layers(keep_handle* h) { return h && h->finalized ? h->bert_layers : 0; }
-
 int keep_set_option(keep_handle* h, const char* name, double value) {
     if (!h || !name) return KEEP_EINVAL;
     const std::string n(name);
     const int v = (int)value;
-    ++h->opt_epoch;               // captured graphs bake kernel selection and precision in: drop them lazily
+    ++h->opt_epoch;               // captured graphs bake kernel selection and precision in: drop them lazily (whatever becomes of this call)
     KeepTune& t = h->tune;
-    if (n == "graphs") { h->use_graphs = v ? 1 : 0; return KEEP_OK; }
-    if (n == "label_margin") { if (!(value >= 0.0) || value > 2.0) return h->fail(KEEP_EINVAL, "label_margin must be in [0, 2]"); h->label_margin = (float)value; return KEEP_OK; }
-    if (n == "precision") { if (v != KEEP_PREC_FP16 && v != KEEP_PREC_STRICT && v != KEEP_PREC_COMP) return h->fail(KEEP_EINVAL, "precision %d", v); h->precision = v; }
-    else if (n == "strict_blocks") { if (v < 0) return h->fail(KEEP_EINVAL, "strict_blocks < 0"); h->strict_blocks = v; }
-    // the four prefix shorthands rewrite the whole per-block plan (a plan set block by block through keep_set_block_precision is replaced)
-    else if (n == "comp_full_blocks") { if (v < 0) return h->fail(KEEP_EINVAL, "comp_full_blocks < 0"); h->comp_full_blocks = v; h->plan_from_prefix(); }
-    else if (n == "comp_mlp_blocks") { if (v < 0) return h->fail(KEEP_EINVAL, "comp_mlp_blocks < 0"); h->comp_mlp_blocks = v; h->plan_from_prefix(); }
-    else if (n == "comp_qkv") { h->comp_qkv = v ? 1 : 0; h->plan_from_prefix(); }
-    else if (n == "comp_qkv_from") { if (v < 0) return h->fail(KEEP_EINVAL, "comp_qkv_from < 0"); h->comp_qkv_from = v; h->plan_from_prefix(); }
-    else if (n == "comp_min_tiles") { if (v < 24) return h->fail(KEEP_EINVAL, "comp_min_tiles must be >= 24 (the compensated product needs the 256x256 kernel)"); h->comp_min_tiles = v; }
-    else if (n == "fused_screening") { if (v < 0 || v > 2) return h->fail(KEEP_EINVAL, "fused_screening must be 0..2"); h->fused_screening = v; }
-    else if (n == "max_tiles") { if (v < 1) return h->fail(KEEP_EINVAL, "max_tiles < 1"); h->max_tiles = v; }
-    else if (n == "max_prompts") { if (v < 1) return h->fail(KEEP_EINVAL, "max_prompts < 1"); h->max_prompts = v; }
-    else if (n == "cls_tail") { h->cls_tail = v ? 1 : 0; if (h->bias_ready && h->cal_cls_tail != h->cls_tail) h->bias_ready = false; }   // (the mean-input biases of the last block were averaged under the other setting: recalibrate)
-    else if (n == "patch_split") { h->patch_split = v ? 1 : 0; }
-    else if (n == "grid_plan") { if (v < 0 || v > 2) return h->fail(KEEP_EINVAL, "grid_plan must be 0, 1 or 2"); h->grid_plan = v; }
-    else if (n == "bias_correction") { h->bias_correction = v ? 1 : 0; }
-    else if (n == "proj_impl") { if (v != 0 && v != 2128) return h->fail(KEEP_EINVAL, "proj_impl must be 0 or 2128"); h->proj_impl = v; }
-    else if (n == "streams") { if (v < 1 || v > 4) return h->fail(KEEP_EINVAL, "streams must be 1..4"); h->n_streams = v; }
-    else if (n == "gemm_persistent") { if (v < 0 || v > 1024) return h->fail(KEEP_EINVAL, "gemm_persistent must be 0..1024"); t.gemm_persistent = v; }
-    else if (n == "gemm_splitk_tiles") { if (v < 0 || v > 256) return h->fail(KEEP_EINVAL, "gemm_splitk_tiles must be 0..256"); t.gemm_splitk_tiles = v; }
-    else if (n == "sgemv_m") { if (v < 0 || v > 16) return h->fail(KEEP_EINVAL, "sgemv_m must be 0..16"); t.sgemv_m = v; }
-    else if (n == "skinny_wide") { t.skinny_wide = v ? 1 : 0; }
-    else if (n == "gemm_skinny_m") { if (v < 0 || v > SKINNY_MAX_M) return h->fail(KEEP_EINVAL, "gemm_skinny_m must be 0..%d", SKINNY_MAX_M); t.gemm_skinny_m = v; }
-    else if (n == "lane_min_tiles") { if (v < 6) return h->fail(KEEP_EINVAL, "lane_min_tiles must be >= 6"); h->lane_min_tiles = v; }
-    else if (n == "ln_impl") { if (v < 0 || v > 2) return h->fail(KEEP_EINVAL, "ln_impl must be 0, 1 or 2"); t.ln_impl = v; }
-    else if (n == "attn_waves") { if (v != 4 && v != 8 && v != 16) return h->fail(KEEP_EINVAL, "attn_waves must be 4, 8 or 16 (16: persistent double-buffered kernel for the image tower)"); t.attn_waves = v; }
-    else if (n == "gemm_impl") {
-        bool ok = v == 0 || v == 128 || v == 256;
-        if (!ok) return h->fail(KEEP_EINVAL, "gemm_impl %d (0, 128, 256)", v);
-        t.gemm_impl = v;
+    if (const Opt* o = find_opt(name)) {
+        if (!o->is_bool && (v < o->lo || v > o->hi)) return h->fail(KEEP_EINVAL, "%s", o->msg);
+        opt_value(h, *o) = o->is_bool ? (v ? 1 : 0) : v;
+        if (o->flags & OPT_REPLAN) h->plan_from_prefix();
+        // (the mean-input biases of the last block were averaged under the other setting: recalibrate)
+        if (o->hm == &keep_handle::cls_tail && h->bias_ready && h->cal_cls_tail != h->cls_tail) h->bias_ready = false;
     }
+    else if (n == "label_margin") { if (!(value >= 0.0) || value > 2.0) return h->fail(KEEP_EINVAL, "label_margin must be in [0, 2]"); h->label_margin = (float)value; }
+    else if (n == "precision") { if (v != KEEP_PREC_FP16 && v != KEEP_PREC_STRICT && v != KEEP_PREC_COMP) return h->fail(KEEP_EINVAL, "precision %d", v); h->precision = v; }
+    else if (n == "proj_impl") { if (v != 0 && v != 2128) return h->fail(KEEP_EINVAL, "proj_impl must be 0 or 2128"); h->proj_impl = v; }
+    else if (n == "attn_waves") { if (v != 4 && v != 8 && v != 16) return h->fail(KEEP_EINVAL, "attn_waves must be 4, 8 or 16 (16: persistent double-buffered kernel for the image tower)"); t.attn_waves = v; }
+    else if (n == "gemm_impl") { if (v != 0 && v != 128 && v != 256) return h->fail(KEEP_EINVAL, "gemm_impl %d (0, 128, 256)", v); t.gemm_impl = v; }
 #ifdef KEEP_DIAGNOSTICS
     // result-changing / timing diagnostics exist only in -DKEEP_DIAGNOSTICS builds (tools/gemm_timeline.py, tools/attn_timeline.py)
     else if (n == "gemm_ablate") { t.gemm_ablate = v; }
@@ -1142,33 +794,13 @@ int keep_set_option(keep_handle* h, const char* name, double value) {
 double keep_get_option(keep_handle* h, const char* name) {
     if (!h || !name) return -1;
     const std::string n(name);
-    const KeepTune& t = h->tune;
-    if (n == "precision") return h->precision;
+    if (const Opt* o = find_opt(name)) return (o->flags & OPT_WRITEONLY) ? -1 : opt_value(h, *o);
     if (n == "label_margin") return h->label_margin;
-    if (n == "strict_blocks") return h->strict_blocks;
-    if (n == "comp_full_blocks") return h->comp_full_blocks;
-    if (n == "comp_mlp_blocks") return h->comp_mlp_blocks;
-    if (n == "comp_min_tiles") return h->comp_min_tiles;
-    if (n == "comp_qkv") return h->comp_qkv;
-    if (n == "comp_qkv_from") return h->comp_qkv_from;
-    if (n == "plan_custom") return h->plan_custom ? 1 : 0;
-    if (n == "max_tiles") return h->max_tiles;
-    if (n == "max_prompts") return h->max_prompts;
-    if (n == "gemm_impl") return t.gemm_impl;
-    if (n == "streams") return h->n_streams;
-    if (n == "graphs") return h->use_graphs;
-    if (n == "gemm_skinny_m") return t.gemm_skinny_m;
-    if (n == "skinny_wide") return t.skinny_wide;
-    if (n == "sgemv_m") return t.sgemv_m;
-    if (n == "gemm_splitk_tiles") return t.gemm_splitk_tiles;
-    if (n == "gemm_persistent") return t.gemm_persistent;
-    if (n == "ln_impl") return t.ln_impl;
-    if (n == "attn_waves") return t.attn_waves;
-    if (n == "cls_tail") return h->cls_tail;
+    if (n == "precision") return h->precision;
     if (n == "proj_impl") return h->proj_impl;
-    if (n == "patch_split") return h->patch_split;
-    if (n == "grid_plan") return h->grid_plan;
-    if (n == "bias_correction") return h->bias_correction;
+    if (n == "attn_waves") return h->tune.attn_waves;
+    if (n == "gemm_impl") return h->tune.gemm_impl;
+    if (n == "plan_custom") return h->plan_custom ? 1 : 0;      // the two read-only names
     if (n == "bias_ready") return h->bias_ready ? 1 : 0;
     return -1;
 }
@@ -1194,23 +826,10 @@ int keep_get_block_precision(keep_handle* h, int block, int* attn_mode, int* mlp
 int keep_reserve(keep_handle* h, int64_t tiles, int64_t prompts, int64_t seq) {
     if (!h || !h->finalized) return h ? h->fail(KEEP_ESTATE, "weights not finalised") : KEEP_EINVAL;
     KEEP_ON_DEVICE(h);
+    // (an image call is sized for the 14 x 14 grid and, where it would be graph-replayed, for fp32 pixels: the widest staging)
     size_t need = 0;
-    if (tiles > 0 && h->vit_depth) {
-        int lanes = h->n_streams;
-        while (lanes > 1 && tiles < (int64_t)lanes * h->lane_min_tiles) --lanes;
-        int64_t per = (tiles + lanes - 1) / lanes;
-        if (per > h->max_tiles) per = h->max_tiles;
-        need = align_up(vit_ws_bytes(h, per, h->any_split())) * lanes;
-        if (tiles * 197 <= SKINNY_MAX_M)          // graph-replayed call: + staged pixels (fp32 at most) and outputs
-            need += align_up((size_t)tiles * 3 * 224 * 224 * 4) + align_up((size_t)tiles * h->proj_dim * 4);
-    }
-    if (prompts > 0 && seq > 0 && h->bert_layers) {
-        const int64_t pc = prompts < h->max_prompts ? prompts : h->max_prompts;
-        size_t t = align_up(txt_ws_bytes(h, pc, seq, h->any_split()));
-        if (prompts * seq <= TXT_GRAPH_ROWS)      // graph-replayed call: + staged ids / types / mask and outputs
-            t += 3 * align_up((size_t)prompts * seq * 8) + align_up((size_t)prompts * h->bert_H * 4);
-        need = t > need ? t : need;
-    }
+    if (tiles > 0 && h->vit_depth) need = vit_plan(h, tiles, 197, (size_t)3 * 224 * 224 * 4, tiles * 197 <= SKINNY_MAX_M).total;
+    if (prompts > 0 && seq > 0 && h->bert_layers) need = std::max(need, txt_plan(h, prompts, seq, prompts * seq <= TXT_GRAPH_ROWS).total);
     return ensure_arena(h, need);
 }
 int64_t keep_workspace_bytes(keep_handle* h) { return h ? (int64_t)h->arena_bytes : 0; }
@@ -1266,17 +885,18 @@ int keep_encode_text(keep_handle* h, const int64_t* ids, const int64_t* types, c
     if (P == 0) return KEEP_OK;
     KEEP_ON_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t pc_max = P < h->max_prompts ? P : h->max_prompts;
-    const size_t ws_bytes = align_up(txt_ws_bytes(h, pc_max, T, h->any_split()));
-    if (h->use_graphs && !h->prof_mode && P * T <= TXT_GRAPH_ROWS && P <= h->max_prompts) {
+    const bool graph = h->use_graphs && !h->prof_mode && P * T <= TXT_GRAPH_ROWS && P <= h->max_prompts;
+    const TxtPlan plan = txt_plan(h, P, T, graph);
+    const int64_t pc_max = plan.pc;
+    int rc = ensure_arena(h, plan.total);
+    if (rc) return rc;
+    if (graph) {
         // launch-bound size: stage the caller's tensors into fixed buffers and replay the whole tower as one graph
         const size_t nb = (size_t)P * T * sizeof(int64_t), ob = (size_t)P * h->bert_H * sizeof(float);
-        int rc = ensure_arena(h, ws_bytes + 3 * align_up(nb) + align_up(ob));
-        if (rc) return rc;
-        int64_t* st_ids = (int64_t*)(h->arena + ws_bytes);
-        int64_t* st_types = (int64_t*)(h->arena + ws_bytes + align_up(nb));
-        int64_t* st_mask = (int64_t*)(h->arena + ws_bytes + 2 * align_up(nb));
-        float* st_out = (float*)(h->arena + ws_bytes + 3 * align_up(nb));
+        int64_t* st_ids = (int64_t*)(h->arena + plan.o_ids);
+        int64_t* st_types = (int64_t*)(h->arena + plan.o_types);
+        int64_t* st_mask = (int64_t*)(h->arena + plan.o_mask);
+        float* st_out = (float*)(h->arena + plan.o_out);
         HIPCHK(h, hipMemcpyAsync(st_ids, ids, nb, hipMemcpyDeviceToDevice, s));
         if (types) HIPCHK(h, hipMemcpyAsync(st_types, types, nb, hipMemcpyDeviceToDevice, s));
         if (mask) HIPCHK(h, hipMemcpyAsync(st_mask, mask, nb, hipMemcpyDeviceToDevice, s));
@@ -1291,8 +911,6 @@ int keep_encode_text(keep_handle* h, const int64_t* ids, const int64_t* types, c
         HIPCHK(h, hipMemcpyAsync(out, st_out, ob, hipMemcpyDeviceToDevice, s));
         return KEEP_OK;
     }
-    int rc = ensure_arena(h, ws_bytes);
-    if (rc) return rc;
     for (int64_t p0 = 0; p0 < P; p0 += pc_max) {
         const int pc = (int)((P - p0) < pc_max ? (P - p0) : pc_max);
         rc = txt_chunk(h, ids + p0 * T, types ? types + p0 * T : nullptr, mask ? mask + p0 * T : nullptr, pc, (int)T,
@@ -1643,314 +1261,6 @@ int keep_profile_reset(keep_handle* h) {
     h->prof_collect();
     for (int i = 0; i < T_COUNT; ++i) { h->prof_ms[i] = 0; h->prof_n[i] = 0; h->prof_flops[i] = 0; }
     return KEEP_OK;
-}
-
-// ---------------------------------------------------------------- single-operator entry points
-int keep_op_linear(keep_handle* h, const float* a, const float* w, const float* bias, const float* ls, const float* resid,
-                   int64_t M, int64_t N, int64_t K, int epi, int split, float* out, void* stream) {
-    if (!h || !a || !w || !bias || !out) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
-    if (M < 1 || N % 128 || N < 128 || K < 64 || K % 32) return h->fail(KEEP_EUNSUPPORTED, "linear needs N%%128==0 and K%%32==0");
-    if (epi != EPI_F16 && epi != EPI_GELU_F16 && epi != EPI_RESID_LS && epi != EPI_RESID_F32) return h->fail(KEEP_EINVAL, "epilogue %d", epi);
-    if ((epi == EPI_RESID_LS && (!ls || !resid)) || (epi == EPI_RESID_F32 && !resid)) return h->fail(KEEP_EINVAL, "missing ls/resid");
-    KEEP_ON_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    Tmp t;
-    const size_t ae = blk_elems(M, K), we = blk_elems(N, K), oe = blk_elems(M, N);
-    f16* a_hi = t.get<f16>(ae); f16* a_lo = t.get<f16>(ae);
-    f16* w_hi = t.get<f16>(we); f16* w_lo = t.get<f16>(we);
-    f16* o_hi = t.get<f16>(oe); f16* o_lo = t.get<f16>(oe);
-    if (!a_hi || !a_lo || !w_hi || !w_lo || !o_hi || !o_lo) return h->fail(KEEP_ENOMEM, "temp alloc");
-    const bool comp = split == 2 || split == 3;          // 3: the W_lo term only (K >= 512)
-    unsigned char *a_q = nullptr, *a_sc = nullptr, *w_q = nullptr, *w_sc = nullptr;
-    if (comp) {
-        if (N % 256 || K % 128 || K < (split == 3 ? 512 : 256) || epi == EPI_RESID_F32) return h->fail(KEEP_EUNSUPPORTED, "compensated linear needs N%%256==0, K%%128==0, K>=256 (512 for the one-term form) and epilogue 0/1/2");
-        a_q = t.get<unsigned char>(keepk::q4_data_bytes(M, K)); a_sc = t.get<unsigned char>(keepk::q4_scale_bytes(M, K));
-        w_q = t.get<unsigned char>(keepk::q4_data_bytes(N, K)); w_sc = t.get<unsigned char>(keepk::q4_scale_bytes(N, K));
-        if (!a_q || !a_sc || !w_q || !w_sc) return h->fail(KEEP_ENOMEM, "temp alloc");
-        launch_quant_blockify(a, a_hi, a_lo, a_q, a_sc, (int)M, (int)K, s); launch_quant_blockify(w, w_hi, w_lo, w_q, w_sc, (int)N, (int)K, s);
-    }
-    else { launch_split_blockify(a, a_hi, a_lo, (int)M, (int)K, s); launch_split_blockify(w, w_hi, w_lo, (int)N, (int)K, s); }
-    GemmParams p{};
-    p.tune = &h->tune;
-    p.a_hi = a_hi; p.a_lo = a_lo; p.w_hi = w_hi; p.w_lo = w_lo; p.M = (int)M; p.N = (int)N; p.K = (int)K;
-    p.nseg = (split == 1) ? 3 : 1; p.bias = bias; p.ls = ls; p.patches_per_img = 196;
-    if (comp) { p.comp = split == 3 ? 1 : 2; p.a_q = a_q; p.a_sc = a_sc; p.w_q = w_q; p.w_sc = w_sc; }
-    p.splitk_ws = t.get<float>(SKINNY_WS_BYTES / 4); p.splitk_bytes = SKINNY_WS_BYTES;      // auto mode may take a split-K path (small or mid-size M), as the towers do
-    if (!p.splitk_ws) return h->fail(KEEP_ENOMEM, "temp alloc");
-    int launch_rc = 0;
-    auto launch = [&](const GemmParams& q) { launch_rc = launch_gemm_f16(q, epi, s); };
-    if (epi == EPI_F16 || epi == EPI_GELU_F16) {
-        p.out_hi = o_hi; p.out_lo = (split == 1 || split == 2) ? o_lo : nullptr;
-        // as in the towers: the GELU output feeds another GEMM (blk layout), the plain one feeds attention (row-major)
-        p.out_kt = (epi == EPI_GELU_F16) ? (int)(N / 32) : 0;
-        launch(p);
-        if (p.out_kt) launch_unblockify_f32(o_hi, p.out_lo, out, (int)M, (int)N, s);
-        else planes_to_f32(o_hi, p.out_lo, out, M * N, s);
-    } else if (epi == EPI_RESID_LS) {
-        HIPCHK(h, hipMemcpyAsync(out, resid, M * N * sizeof(float), hipMemcpyDeviceToDevice, s));
-        p.resid = out;
-        launch(p);
-    } else {
-        p.resid = const_cast<float*>(resid); p.out_f32 = out;
-        launch(p);
-    }
-    HIPCHK(h, hipStreamSynchronize(s));
-    if (launch_rc < 0) return h->fail(KEEP_EUNSUPPORTED, "op_linear: no kernel for this shape / mode");
-    return check_launch(h, "op_linear");
-}
-
-int keep_op_linear_ln(keep_handle* h, const float* a, const float* w, const float* bias, const float* ls, const float* resid,
-                      const float* ln_gamma, const float* ln_beta, float ln_eps, int64_t M, int64_t N, int64_t K, int epi, int split,
-                      float* out, float* ln_out, float* ln_hi, int* did_ln, void* stream) {
-    if (!h || !a || !w || !bias || !resid || !ln_gamma || !ln_beta || !out || !ln_out || !did_ln) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
-    if (M < 1 || (split != 0 && split != 1)) return h->fail(KEEP_EINVAL, "linear_ln needs M >= 1 and split 0 / 1");
-    if (epi != EPI_RESID_LS && epi != EPI_RESID_F32) return h->fail(KEEP_EINVAL, "epilogue %d (linear_ln takes the residual epilogues 2 and 4)", epi);
-    if (epi == EPI_RESID_LS && !ls) return h->fail(KEEP_EINVAL, "missing ls");
-    if ((N != 768 && N != 1024) || K < 64 || K % 32) return h->fail(KEEP_EUNSUPPORTED, "linear_ln needs N in {768, 1024} and K%%32==0");
-    KEEP_ON_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    Tmp t;
-    const size_t ae = blk_elems(M, K), we = blk_elems(N, K), oe = blk_elems(M, N);
-    f16* a_hi = t.get<f16>(ae); f16* a_lo = t.get<f16>(ae);
-    f16* w_hi = t.get<f16>(we); f16* w_lo = t.get<f16>(we);
-    f16* n_hi = t.get<f16>(oe); f16* n_lo = t.get<f16>(oe);
-    float* ws = t.get<float>(SKINNY_WS_BYTES / 4);
-    if (!a_hi || !a_lo || !w_hi || !w_lo || !n_hi || !n_lo || !ws) return h->fail(KEEP_ENOMEM, "temp alloc");
-    launch_split_blockify(a, a_hi, a_lo, (int)M, (int)K, s); launch_split_blockify(w, w_hi, w_lo, (int)N, (int)K, s);
-    // as in the towers: the residual stream is updated in place (ViT: resid += ...; BERT: out_f32 == resid), the LayerNorm that follows reads it there
-    HIPCHK(h, hipMemcpyAsync(out, resid, M * N * sizeof(float), hipMemcpyDeviceToDevice, s));
-    LnParams ln{};
-    ln.tune = &h->tune;
-    ln.x = out; ln.x_stride = N; ln.rows = (int)M; ln.D = (int)N; ln.eps = ln_eps; ln.gamma = ln_gamma; ln.beta = ln_beta;
-    ln.out_hi = n_hi; ln.out_lo = split ? n_lo : nullptr; ln.out_kt = (int)(N / 32);
-    if (epi == EPI_RESID_F32) { ln.out_f32 = out; ln.out_f32_stride = N; }      // BERT: the normalised row replaces the sum
-    GemmParams p{};
-    p.tune = &h->tune;
-    p.a_hi = a_hi; p.a_lo = a_lo; p.w_hi = w_hi; p.w_lo = w_lo; p.M = (int)M; p.N = (int)N; p.K = (int)K;
-    p.nseg = split ? 3 : 1; p.bias = bias; p.ls = ls; p.patches_per_img = 196;
-    p.splitk_ws = ws; p.splitk_bytes = SKINNY_WS_BYTES;
-    p.resid = out;
-    if (epi == EPI_RESID_F32) p.out_f32 = out;
-    offer_ln(p, ln);
-    const int rc = launch_gemm_f16(p, epi, s);
-    if (rc < 0) return h->fail(KEEP_EUNSUPPORTED, "op_linear_ln: no kernel for this shape / mode");
-    if (!(rc & GEMM_DID_LN) && launch_layernorm(ln, s)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %lld", (long long)N);
-    launch_unblockify_f32(n_hi, ln.out_lo, ln_out, (int)M, (int)N, s);
-    if (ln_hi) launch_unblockify_f32(n_hi, nullptr, ln_hi, (int)M, (int)N, s);      // the hi plane on its own: hi + lo does not tell the two planes apart
-    HIPCHK(h, hipStreamSynchronize(s));
-    *did_ln = (rc & GEMM_DID_LN) ? 1 : 0;
-    return check_launch(h, "op_linear_ln");
-}
-
-int keep_op_mlp(keep_handle* h, const float* x, const float* ln_w, const float* ln_b, const float* fc1_w, const float* fc1_b,
-                const float* fc2_w, const float* fc2_b, const float* ls, int64_t M, int64_t D, int64_t F, int mode, float* out, void* stream) {
-    if (!h || !x || !ln_w || !ln_b || !fc1_w || !fc1_b || !fc2_w || !fc2_b || !ls || !out) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
-    if (M < 1 || (D != 768 && D != 1024) || F % 256 || F < 256 || mode < 0 || mode > 3) return h->fail(KEEP_EUNSUPPORTED, "op_mlp: D in {768, 1024}, F %% 256 == 0, mode 0..3");
-    KEEP_ON_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    Tmp t;
-    const bool lo = mode == 1, q = mode == 2 || mode == 3;
-    const int cmode = mode == 3 ? 1 : 2;                 // GemmParams.comp: the W_lo term only | both terms
-    f16 *w1h = t.get<f16>(F * D), *w1l = t.get<f16>(F * D), *w2h = t.get<f16>(D * F), *w2l = t.get<f16>(D * F);
-    f16 *xh = t.get<f16>(blk_elems(M, D)), *xl = t.get<f16>(blk_elems(M, D)), *mh = t.get<f16>(blk_elems(M, F)), *ml = t.get<f16>(blk_elems(M, F));
-    unsigned char *w1q = t.get<unsigned char>(keepk::q4_data_bytes(F, D)), *w1s = t.get<unsigned char>(keepk::q4_scale_bytes(F, D));
-    unsigned char *w2q = t.get<unsigned char>(keepk::q4_data_bytes(D, F)), *w2s = t.get<unsigned char>(keepk::q4_scale_bytes(D, F));
-    unsigned char *xq = t.get<unsigned char>(keepk::q4_data_bytes(M, D)), *xs = t.get<unsigned char>(keepk::q4_scale_bytes(M, D));
-    unsigned char *mq = t.get<unsigned char>(keepk::q4_data_bytes(M, F)), *ms = t.get<unsigned char>(keepk::q4_scale_bytes(M, F));
-    float* ws = t.get<float>(SKINNY_WS_BYTES / 4);
-    if (!w1h || !w1l || !w2h || !w2l || !xh || !xl || !mh || !ml || !w1q || !w1s || !w2q || !w2s || !xq || !xs || !mq || !ms || !ws) return h->fail(KEEP_ENOMEM, "temp alloc");
-    launch_quant_blockify(fc1_w, w1h, w1l, w1q, w1s, (int)F, (int)D, s);
-    launch_quant_blockify(fc2_w, w2h, w2l, w2q, w2s, (int)D, (int)F, s);
-    HIPCHK(h, hipMemcpyAsync(out, x, M * D * sizeof(float), hipMemcpyDeviceToDevice, s));
-    LnParams ln{};
-    ln.tune = &h->tune;
-    ln.x = x; ln.x_stride = D; ln.rows = (int)M; ln.D = (int)D; ln.eps = 1e-6f; ln.gamma = ln_w; ln.beta = ln_b;
-    ln.out_hi = xh; ln.out_lo = lo ? xl : nullptr; ln.out_kt = (int)(D / 32); ln.out_q = q ? xq : nullptr; ln.out_sc = q ? xs : nullptr; ln.out_q_hi_only = mode == 3;
-    if (launch_layernorm(ln, s)) return h->fail(KEEP_EUNSUPPORTED, "op_mlp: layernorm");
-    GemmParams p{};
-    p.tune = &h->tune; p.patches_per_img = 196; p.splitk_ws = ws; p.splitk_bytes = SKINNY_WS_BYTES;
-    p.a_hi = xh; p.a_lo = xl; p.w_hi = w1h; p.w_lo = w1l; p.M = (int)M; p.N = (int)F; p.K = (int)D; p.nseg = lo ? 3 : 1; p.bias = fc1_b;
-    p.out_hi = mh; p.out_lo = lo ? ml : nullptr; p.out_kt = (int)(F / 32);
-    if (q) { p.comp = cmode; p.a_q = xq; p.a_sc = xs; p.w_q = w1q; p.w_sc = w1s; p.out_q = mq; p.out_sc = ms; }
-    if (launch_gemm_f16(p, EPI_GELU_F16, s) < 0) return h->fail(KEEP_EUNSUPPORTED, "op_mlp: fc1");
-    GemmParams r{};
-    r.tune = &h->tune; r.patches_per_img = 196; r.splitk_ws = ws; r.splitk_bytes = SKINNY_WS_BYTES;
-    r.a_hi = mh; r.a_lo = ml; r.w_hi = w2h; r.w_lo = w2l; r.M = (int)M; r.N = (int)D; r.K = (int)F; r.nseg = lo ? 3 : 1; r.bias = fc2_b;
-    r.ls = ls; r.resid = out;
-    if (q) { r.comp = cmode; r.a_q = mq; r.a_sc = ms; r.w_q = w2q; r.w_sc = w2s; }
-    if (launch_gemm_f16(r, EPI_RESID_LS, s) < 0) return h->fail(KEEP_EUNSUPPORTED, "op_mlp: fc2");
-    HIPCHK(h, hipStreamSynchronize(s));
-    return check_launch(h, "op_mlp");
-}
-
-int keep_op_attention(keep_handle* h, const float* qkv, const int64_t* mask, int64_t B, int64_t T, int heads, int split,
-                      float* out, void* stream) {
-    if (!h || !qkv || !out || B < 1 || T < 1 || heads < 1) return h ? h->fail(KEEP_EINVAL, "bad attention arguments") : KEEP_EINVAL;
-    KEEP_ON_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t M = B * T, D = (int64_t)heads * 64;
-    Tmp t;
-    f16* q_hi = t.get<f16>(M * 3 * D); f16* q_lo = t.get<f16>(M * 3 * D);
-    // the towers write the attention output in blk layout when the width allows it (D % 32 == 0 always holds)
-    const size_t oe = blk_elems(M, D);
-    f16* o_hi = t.get<f16>(oe); f16* o_lo = t.get<f16>(oe);
-    if (!q_hi || !q_lo || !o_hi || !o_lo) return h->fail(KEEP_ENOMEM, "temp alloc");
-    launch_split_f16(qkv, q_hi, q_lo, M * 3 * D, s);
-    AttnParams a{};
-    a.tune = &h->tune;
-    if (split && T > 256) {
-        a.part_bytes = (size_t)B * heads * T * ATT_PART_FLOATS * sizeof(float);
-        a.part_ws = t.get<float>(a.part_bytes / sizeof(float));
-        if (!a.part_ws) return h->fail(KEEP_ENOMEM, "temp alloc");
-    }
-    a.qkv_hi = q_hi; a.qkv_lo = q_lo; a.out_hi = o_hi; a.out_lo = split ? o_lo : nullptr; a.mask = mask;
-    a.batch = (int)B; a.ntok = (int)T; a.heads = heads; a.split = split; a.scale = 0.125f; a.out_kt = (int)(D / 32);
-    if (launch_attention(a, s)) return h->fail(KEEP_EUNSUPPORTED, "sequence length %lld unsupported", (long long)T);
-    launch_unblockify_f32(o_hi, split ? o_lo : nullptr, out, (int)M, (int)D, s);
-    HIPCHK(h, hipStreamSynchronize(s));
-    return check_launch(h, "op_attention");
-}
-
-int keep_op_attention_cls(keep_handle* h, const float* qkv, int64_t B, int64_t T, int heads, int split, int q_rows, float* out, float* cls_out,
-                          void* stream) {
-    if (!h || !qkv || !out || B < 1 || T < 1 || heads < 1 || q_rows < 0) return h ? h->fail(KEEP_EINVAL, "bad attention arguments") : KEEP_EINVAL;
-    KEEP_ON_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t M = B * T, D = (int64_t)heads * 64;
-    Tmp t;
-    f16* q_hi = t.get<f16>(M * 3 * D); f16* q_lo = t.get<f16>(M * 3 * D);
-    const size_t oe = blk_elems(M, D), ce = blk_elems(B, D);
-    f16* o_hi = t.get<f16>(oe); f16* o_lo = t.get<f16>(oe);
-    f16* c_hi = t.get<f16>(ce); f16* c_lo = t.get<f16>(ce);      // the compact [B, D] operand of KEEP_ATTN_PROJ_CLS
-    if (!q_hi || !q_lo || !o_hi || !o_lo || !c_hi || !c_lo) return h->fail(KEEP_ENOMEM, "temp alloc");
-    HIPCHK(h, hipMemsetAsync(o_hi, 0, oe * sizeof(f16), s));      // rows past q_rows read back as 0
-    HIPCHK(h, hipMemsetAsync(o_lo, 0, oe * sizeof(f16), s));
-    HIPCHK(h, hipMemsetAsync(c_hi, 0, ce * sizeof(f16), s));
-    HIPCHK(h, hipMemsetAsync(c_lo, 0, ce * sizeof(f16), s));
-    launch_split_f16(qkv, q_hi, q_lo, M * 3 * D, s);
-    AttnParams a{};
-    a.tune = &h->tune;
-    if (split && T > 256) {
-        a.part_bytes = (size_t)B * heads * T * ATT_PART_FLOATS * sizeof(float);
-        a.part_ws = t.get<float>(a.part_bytes / sizeof(float));
-        if (!a.part_ws) return h->fail(KEEP_ENOMEM, "temp alloc");
-    }
-    a.qkv_hi = q_hi; a.qkv_lo = q_lo; a.out_hi = o_hi; a.out_lo = split ? o_lo : nullptr; a.mask = nullptr;
-    a.batch = (int)B; a.ntok = (int)T; a.heads = heads; a.split = split; a.scale = 0.125f; a.out_kt = (int)(D / 32); a.q_rows = q_rows;
-    if (cls_out) { a.cls_hi = c_hi; a.cls_lo = c_lo; }           // (split: launch_attention refuses the planes -- reported, not worked round)
-    if (launch_attention(a, s)) return h->fail(KEEP_EUNSUPPORTED, "attention: T %lld%s unsupported", (long long)T, (cls_out && split) ? " with cls_out in split mode" : "");
-    launch_unblockify_f32(o_hi, split ? o_lo : nullptr, out, (int)M, (int)D, s);
-    if (cls_out) launch_unblockify_f32(c_hi, c_lo, cls_out, (int)B, (int)D, s);
-    HIPCHK(h, hipStreamSynchronize(s));
-    return check_launch(h, "op_attention_cls");
-}
-
-int keep_op_attention_long(keep_handle* h, const float* qkv, int64_t B, int64_t T, int heads, int split, int q_rows, float* out, void* stream) {
-    if (!h || !qkv || !out || B < 1 || T < 1 || heads < 1 || q_rows < 0) return h ? h->fail(KEEP_EINVAL, "bad attention arguments") : KEEP_EINVAL;
-    KEEP_ON_DEVICE(h);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t M = B * T, D = (int64_t)heads * 64;
-    Tmp t;
-    f16* q_hi = t.get<f16>(M * 3 * D); f16* q_lo = t.get<f16>(M * 3 * D);
-    const size_t oe = blk_elems(M, D);
-    f16* o_hi = t.get<f16>(oe); f16* o_lo = t.get<f16>(oe);
-    if (!q_hi || !q_lo || !o_hi || !o_lo) return h->fail(KEEP_ENOMEM, "temp alloc");
-    HIPCHK(h, hipMemsetAsync(o_hi, 0, oe * sizeof(f16), s));      // rows past q_rows read back as 0
-    HIPCHK(h, hipMemsetAsync(o_lo, 0, oe * sizeof(f16), s));
-    launch_split_f16(qkv, q_hi, q_lo, M * 3 * D, s);
-    AttnParams a{};
-    a.tune = &h->tune;
-    a.qkv_hi = q_hi; a.qkv_lo = q_lo; a.out_hi = o_hi; a.out_lo = split ? o_lo : nullptr; a.mask = nullptr;
-    a.batch = (int)B; a.ntok = (int)T; a.heads = heads; a.split = split; a.scale = 0.125f; a.out_kt = (int)(D / 32); a.q_rows = q_rows;
-    if (launch_attention_long(a, s)) return h->fail(KEEP_EUNSUPPORTED, "long attention: B %lld, T %lld, heads %d unsupported", (long long)B, (long long)T, heads);
-    launch_unblockify_f32(o_hi, split ? o_lo : nullptr, out, (int)M, (int)D, s);
-    HIPCHK(h, hipStreamSynchronize(s));
-    return check_launch(h, "op_attention_long");
-}
-
-// Matrix-pipe ceiling probe (keep_mfma_probe): no memory traffic inside the loop; every wave holds 2 A and 4 B fragments of the caller's data in registers and
-// issues 8 independent v_mfma_f32_32x32x16_f16 per iteration (all (i, j) pairs: the pipe's inputs change with every instruction); one 8-wave workgroup per CU,
-// two waves per SIMD, as the GEMM kernels run.
-__global__ __launch_bounds__(512, 2) void mfma_probe_kernel(const f16x8* __restrict__ src, float* __restrict__ sink, int iters) {
-    f16x8 a[2], b[4];
-    const int t = blockIdx.x * 512 + threadIdx.x;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) a[i] = src[(size_t)t * 6 + i];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) b[i] = src[(size_t)t * 6 + 2 + i];
-    f32x16 acc[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    for (int it = 0; it < iters; ++it) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i * 4 + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], acc[i * 4 + j], 0, 0, 0);
-    }
-    float v = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) v += acc[i][r];
-    sink[t] = v;
-}
-
-int keep_op_layernorm(keep_handle* h, const float* x, const float* add, const float* gamma, const float* beta, int64_t rows,
-                      int64_t D, float eps, float* out, void* stream) {
-    if (!h || !x || !gamma || !beta || !out || rows < 1) return h ? h->fail(KEEP_EINVAL, "bad layernorm arguments") : KEEP_EINVAL;
-    KEEP_ON_DEVICE(h);
-    LnParams p{};
-    p.tune = &h->tune;
-    p.x = x; p.x_stride = D; p.add = add; p.gamma = gamma; p.beta = beta; p.rows = (int)rows; p.D = (int)D; p.eps = eps;
-    p.out_f32 = out; p.out_f32_stride = D;
-    if (launch_layernorm(p, (hipStream_t)stream)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %lld", (long long)D);
-    return check_launch(h, "op_layernorm");
-}
-
-int keep_op_sgemm(keep_handle* h, const float* a, const float* b, const float* bias, int64_t M, int64_t N, int64_t K, float scale,
-                  int act, float* out, void* stream) {
-    if (!h || !a || !b || !out) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
-    KEEP_ON_DEVICE(h);
-    SgemmParams g{};
-    g.tune = &h->tune;
-    g.a = a; g.lda = K; g.b = b; g.ldb = K; g.out = out; g.ldo = N; g.bias = bias; g.M = (int)M; g.N = (int)N; g.K = (int)K;
-    g.scale = scale; g.act = act;
-    if (launch_sgemm_f32(g, (hipStream_t)stream)) return h->fail(KEEP_EUNSUPPORTED, "sgemm needs K%%16==0");
-    return check_launch(h, "op_sgemm");
-}
-
-int keep_debug_read(keep_handle* h, void* host_dst, int64_t bytes) {
-    if (!h || !host_dst || !h->tune.dbg || bytes > (int64_t)65536 * 4 * 8) return KEEP_EINVAL;      // diagnostics builds only
-    KEEP_ON_DEVICE(h);
-    HIPCHK(h, hipDeviceSynchronize());
-    HIPCHK(h, hipMemcpy(host_dst, h->tune.dbg, bytes, hipMemcpyDeviceToHost));
-    return KEEP_OK;
-}
-
-int keep_mfma_probe(keep_handle* h, const void* operands_f16, float* sink, int iters, double* flops_out, void* stream) {
-    if (!h || !operands_f16 || !sink || iters < 1 || iters > (1 << 24)) return h ? h->fail(KEEP_EINVAL, "bad mfma_probe arguments") : KEEP_EINVAL;
-    KEEP_ON_DEVICE(h);
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
-    hipLaunchKernelGGL(mfma_probe_kernel, dim3(cus), dim3(512), 0, (hipStream_t)stream, (const f16x8*)operands_f16, sink, iters);
-    if (flops_out) *flops_out = (double)cus * 8.0 * iters * 8.0 * 2.0 * 32 * 32 * 16;
-    return check_launch(h, "mfma_probe");
-}
-
-int keep_clock_probe(keep_handle* h, int spin_us, long long* device_out2, void* stream) {
-    if (!h || !device_out2 || spin_us < 1 || spin_us > 100000) return h ? h->fail(KEEP_EINVAL, "bad clock_probe arguments") : KEEP_EINVAL;
-    KEEP_ON_DEVICE(h);
-    hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, device_out2, spin_us * 100);
-    return check_launch(h, "clock_probe");
-}
-
-int keep_op_l2norm(keep_handle* h, float* x, int64_t rows, int64_t D, void* stream) {
-    if (!h || !x || rows < 1 || D < 1) return h ? h->fail(KEEP_EINVAL, "bad l2norm arguments") : KEEP_EINVAL;
-    KEEP_ON_DEVICE(h);
-    launch_l2norm_rows(x, (int)rows, (int)D, 1e-12f, (hipStream_t)stream);
-    return check_launch(h, "op_l2norm");
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
-// The engine handle: what keep_create returns and every extern "C" entry point receives.  engine.hip owns it (weights, arena,
-// towers, graphs, profile); slide_api.hip uses its device, error text, arena and error flag.
+// The engine handle: what keep_create returns and every extern "C" entry point receives.  engine.hip owns it (arena, towers,
+// graphs, options, profile); weights.hip fills its weight store and block tables; op_api.hip borrows its device and kernel
+// selection; slide_api.hip uses its device, error text, arena and error flag.
 #pragma once
 #include "common.h"
 #include "../../include/keep_hip.h"
@@ -262,3 +263,48 @@ struct keep_handle {
 // defined in engine.hip
 int ensure_arena(keep_handle* h, size_t bytes);            // grows the workspace arena to at least `bytes` (synchronises the device when it has to)
 int check_launch(keep_handle* h, const char* what);        // hipGetLastError after a launch, as a KEEP_E* code with the handle's error text set
+
+inline const WTensor* find_weight(const keep_handle* h, const std::string& k) {
+    auto it = h->w.find(k);
+    return it == h->w.end() ? nullptr : &it->second;
+}
+
+// temp device buffers of one call (op entry points, position-table resample): freed on return; a failed allocation clears `ok`
+struct Tmp {
+    std::vector<void*> ptrs; bool ok = true;
+    ~Tmp() { for (auto p : ptrs) hipFree(p); }
+    template <typename T> T* get(size_t n) { void* p = nullptr; if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) { ok = false; return nullptr; } ptrs.push_back(p); return (T*)p; }
+};
+
+// The launch parameter blocks as the towers and the op entry points fill them: the fields every site sets; outputs and epilogue inputs are the site's own.
+inline GemmParams gemm_params(const keep_handle* h, const f16* a_hi, const f16* a_lo, const f16* w_hi, const f16* w_lo, int M, int N, int K, bool split, const float* bias) {
+    GemmParams p{};
+    p.tune = &h->tune;
+    p.a_hi = a_hi; p.a_lo = a_lo; p.w_hi = w_hi; p.w_lo = w_lo;
+    p.M = M; p.N = N; p.K = K;
+    p.nseg = split ? 3 : 1;
+    p.bias = bias;
+    p.patches_per_img = 196;
+    return p;
+}
+inline GemmParams gemm_params(const keep_handle* h, const f16* a_hi, const f16* a_lo, const WTensor* w, int M, bool split, const float* bias) {
+    return gemm_params(h, a_hi, a_lo, w->hi, w->lo, M, (int)w->shape[0], (int)(w->numel / w->shape[0]), split, bias);
+}
+inline LnParams ln_params(const keep_handle* h, const float* x, int64_t x_stride, int rows, int D, float eps) {
+    LnParams p{};
+    p.tune = &h->tune;
+    p.x = x; p.x_stride = x_stride; p.rows = rows; p.D = D; p.eps = eps;
+    return p;
+}
+inline AttnParams attn_params(const keep_handle* h, const f16* qkv_hi, const f16* qkv_lo, f16* out_hi, f16* out_lo, int batch, int ntok, int heads, int split, int out_kt) {
+    AttnParams a{};
+    a.tune = &h->tune;
+    a.qkv_hi = qkv_hi; a.qkv_lo = qkv_lo; a.out_hi = out_hi; a.out_lo = out_lo;
+    a.batch = batch; a.ntok = ntok; a.heads = heads; a.split = split; a.scale = 0.125f; a.out_kt = out_kt;
+    return a;
+}
+// offer the LayerNorm that follows a residual GEMM to the GEMM itself (taken only on the small-M split-K path)
+inline void offer_ln(GemmParams& p, const LnParams& ln) {
+    p.ln_gamma = ln.gamma; p.ln_beta = ln.beta; p.ln_eps = ln.eps;
+    p.ln_out_hi = ln.out_hi; p.ln_out_lo = ln.out_lo; p.ln_out_f32 = ln.out_f32;
+}

@@ -1,0 +1,299 @@
+// Single-operator entry points (keep_op_*) and hardware probes of libkeep_hip: the kernels of the towers, one at a time, on fp32 tensors of the
+// caller.  They are the test surface of the kernels (tests/test_ops_gpu.py, tests/test_small_m_gpu.py): each packs its operands the way the
+// towers hold them (hi / lo planes, blk layout, MX-fp4 side planes), fills the launch parameters with the helpers the towers use (handle.h),
+// launches, and unpacks the result.  Temporaries are allocated per call; nothing here touches the arena.
+#include "handle.h"
+#include "quant4.h"
+
+namespace {
+
+// one wave: shader-clock cycles (s_memtime) against the constant 100 MHz counter (s_memrealtime) over ~`spin_us` microseconds
+__global__ void clock_probe_kernel(long long* out, int spin_ticks) {
+    if (threadIdx.x != 0) return;
+    const long long r0 = (long long)__builtin_amdgcn_s_memrealtime(), c0 = (long long)__builtin_readcyclecounter();
+    long long r1 = r0;
+    while (r1 - r0 < spin_ticks) { __builtin_amdgcn_s_sleep(32); r1 = (long long)__builtin_amdgcn_s_memrealtime(); }
+    const long long c1 = (long long)__builtin_readcyclecounter();
+    out[0] = c1 - c0; out[1] = r1 - r0;
+}
+
+__global__ void f16_planes_to_f32_kernel(const f16* hi, const f16* lo, float* out, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = (float)hi[i] + (lo ? (float)lo[i] : 0.f);
+}
+void planes_to_f32(const f16* hi, const f16* lo, float* out, int64_t n, hipStream_t s) {
+    int blocks = (int)((n + 255) / 256); if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(f16_planes_to_f32_kernel, dim3(blocks), dim3(256), 0, s, hi, lo, out, n);
+}
+
+// an operand of the op entry points: fp32 [rows][K] of the caller as hi + lo planes in blk layout, with the MX-fp4 side planes where asked for
+struct Planes { f16 *hi, *lo; unsigned char *q, *sc; };
+Planes alloc_planes(Tmp& t, int64_t rows, int64_t K, bool fp4) {
+    Planes p{t.get<f16>(blk_elems(rows, K)), t.get<f16>(blk_elems(rows, K)), nullptr, nullptr};
+    if (fp4) { p.q = t.get<unsigned char>(keepk::q4_data_bytes(rows, K)); p.sc = t.get<unsigned char>(keepk::q4_scale_bytes(rows, K)); }
+    return p;
+}
+void with_splitk(GemmParams& p, float* ws) { p.splitk_ws = ws; p.splitk_bytes = SKINNY_WS_BYTES; }   // auto mode may take a split-K path (small or mid-size M), as the towers do
+void with_fp4(GemmParams& p, int comp, const Planes& a, const Planes& w) { p.comp = comp; p.a_q = a.q; p.a_sc = a.sc; p.w_q = w.q; p.w_sc = w.sc; }
+
+// The three attention ops are this one body.  What they do differently, as they always did: the plain op takes a key mask and leaves rows it does
+// not compute alone (it computes all); the CLS op zero-fills the output (rows past q_rows read back as 0) and the compact [B, D] CLS operand of
+// KEEP_ATTN_PROJ_CLS; the long op zero-fills the output, runs the key-blocked kernel and allocates no two-window state.
+enum AttnOp { ATTN_OP_PLAIN, ATTN_OP_CLS, ATTN_OP_LONG };
+constexpr int ATTN_REFUSED = 1;      // the launcher took no kernel for the shape: the wrapper words its own message
+int attention_op(keep_handle* h, AttnOp kind, const char* what, const float* qkv, const int64_t* mask, int64_t B, int64_t T, int heads, int split,
+                 int q_rows, float* out, float* cls_out, hipStream_t s) {
+    const int64_t M = B * T, D = (int64_t)heads * 64;
+    // the towers write the attention output in blk layout when the width allows it (D % 32 == 0 always holds)
+    const size_t oe = blk_elems(M, D), ce = blk_elems(B, D);
+    Tmp t;
+    f16* q_hi = t.get<f16>(M * 3 * D); f16* q_lo = t.get<f16>(M * 3 * D);
+    f16* o_hi = t.get<f16>(oe); f16* o_lo = t.get<f16>(oe);
+    f16 *c_hi = nullptr, *c_lo = nullptr;
+    if (kind == ATTN_OP_CLS) { c_hi = t.get<f16>(ce); c_lo = t.get<f16>(ce); }
+    AttnParams a = attn_params(h, q_hi, q_lo, o_hi, split ? o_lo : nullptr, (int)B, (int)T, heads, split, (int)(D / 32));
+    a.mask = mask; a.q_rows = q_rows;
+    if (kind != ATTN_OP_LONG && split && T > 256) {
+        a.part_bytes = (size_t)B * heads * T * ATT_PART_FLOATS * sizeof(float);
+        a.part_ws = t.get<float>(a.part_bytes / sizeof(float));
+    }
+    if (!t.ok) return h->fail(KEEP_ENOMEM, "temp alloc");
+    if (kind != ATTN_OP_PLAIN) {
+        HIPCHK(h, hipMemsetAsync(o_hi, 0, oe * sizeof(f16), s));
+        HIPCHK(h, hipMemsetAsync(o_lo, 0, oe * sizeof(f16), s));
+    }
+    if (kind == ATTN_OP_CLS) {
+        HIPCHK(h, hipMemsetAsync(c_hi, 0, ce * sizeof(f16), s));
+        HIPCHK(h, hipMemsetAsync(c_lo, 0, ce * sizeof(f16), s));
+    }
+    launch_split_f16(qkv, q_hi, q_lo, M * 3 * D, s);
+    if (cls_out) { a.cls_hi = c_hi; a.cls_lo = c_lo; }           // (split: launch_attention refuses the planes -- reported, not worked round)
+    if (kind == ATTN_OP_LONG ? launch_attention_long(a, s) : launch_attention(a, s)) return ATTN_REFUSED;
+    launch_unblockify_f32(o_hi, split ? o_lo : nullptr, out, (int)M, (int)D, s);
+    if (cls_out) launch_unblockify_f32(c_hi, c_lo, cls_out, (int)B, (int)D, s);
+    HIPCHK(h, hipStreamSynchronize(s));
+    return check_launch(h, what);
+}
+
+}  // namespace
+
+extern "C" {
+
+int keep_op_linear(keep_handle* h, const float* a, const float* w, const float* bias, const float* ls, const float* resid,
+                   int64_t M, int64_t N, int64_t K, int epi, int split, float* out, void* stream) {
+    if (!h || !a || !w || !bias || !out) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
+    if (M < 1 || N % 128 || N < 128 || K < 64 || K % 32) return h->fail(KEEP_EUNSUPPORTED, "linear needs N%%128==0 and K%%32==0");
+    if (epi != EPI_F16 && epi != EPI_GELU_F16 && epi != EPI_RESID_LS && epi != EPI_RESID_F32) return h->fail(KEEP_EINVAL, "epilogue %d", epi);
+    if ((epi == EPI_RESID_LS && (!ls || !resid)) || (epi == EPI_RESID_F32 && !resid)) return h->fail(KEEP_EINVAL, "missing ls/resid");
+    const bool comp = split == 2 || split == 3;          // 3: the W_lo term only (K >= 512)
+    if (comp && (N % 256 || K % 128 || K < (split == 3 ? 512 : 256) || epi == EPI_RESID_F32)) return h->fail(KEEP_EUNSUPPORTED, "compensated linear needs N%%256==0, K%%128==0, K>=256 (512 for the one-term form) and epilogue 0/1/2");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    Tmp t;
+    const Planes A = alloc_planes(t, M, K, comp), W = alloc_planes(t, N, K, comp), O = alloc_planes(t, M, N, false);
+    float* ws = t.get<float>(SKINNY_WS_BYTES / 4);
+    if (!t.ok) return h->fail(KEEP_ENOMEM, "temp alloc");
+    if (comp) { launch_quant_blockify(a, A.hi, A.lo, A.q, A.sc, (int)M, (int)K, s); launch_quant_blockify(w, W.hi, W.lo, W.q, W.sc, (int)N, (int)K, s); }
+    else { launch_split_blockify(a, A.hi, A.lo, (int)M, (int)K, s); launch_split_blockify(w, W.hi, W.lo, (int)N, (int)K, s); }
+    GemmParams p = gemm_params(h, A.hi, A.lo, W.hi, W.lo, (int)M, (int)N, (int)K, split == 1, bias);
+    p.ls = ls;
+    if (comp) with_fp4(p, split == 3 ? 1 : 2, A, W);
+    with_splitk(p, ws);
+    int launch_rc = 0;
+    if (epi == EPI_F16 || epi == EPI_GELU_F16) {
+        p.out_hi = O.hi; p.out_lo = (split == 1 || split == 2) ? O.lo : nullptr;
+        // as in the towers: the GELU output feeds another GEMM (blk layout), the plain one feeds attention (row-major)
+        p.out_kt = (epi == EPI_GELU_F16) ? (int)(N / 32) : 0;
+        launch_rc = launch_gemm_f16(p, epi, s);
+        if (p.out_kt) launch_unblockify_f32(O.hi, p.out_lo, out, (int)M, (int)N, s);
+        else planes_to_f32(O.hi, p.out_lo, out, M * N, s);
+    } else if (epi == EPI_RESID_LS) {
+        HIPCHK(h, hipMemcpyAsync(out, resid, M * N * sizeof(float), hipMemcpyDeviceToDevice, s));
+        p.resid = out;
+        launch_rc = launch_gemm_f16(p, epi, s);
+    } else {
+        p.resid = const_cast<float*>(resid); p.out_f32 = out;
+        launch_rc = launch_gemm_f16(p, epi, s);
+    }
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (launch_rc < 0) return h->fail(KEEP_EUNSUPPORTED, "op_linear: no kernel for this shape / mode");
+    return check_launch(h, "op_linear");
+}
+
+int keep_op_linear_ln(keep_handle* h, const float* a, const float* w, const float* bias, const float* ls, const float* resid,
+                      const float* ln_gamma, const float* ln_beta, float ln_eps, int64_t M, int64_t N, int64_t K, int epi, int split,
+                      float* out, float* ln_out, float* ln_hi, int* did_ln, void* stream) {
+    if (!h || !a || !w || !bias || !resid || !ln_gamma || !ln_beta || !out || !ln_out || !did_ln) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
+    if (M < 1 || (split != 0 && split != 1)) return h->fail(KEEP_EINVAL, "linear_ln needs M >= 1 and split 0 / 1");
+    if (epi != EPI_RESID_LS && epi != EPI_RESID_F32) return h->fail(KEEP_EINVAL, "epilogue %d (linear_ln takes the residual epilogues 2 and 4)", epi);
+    if (epi == EPI_RESID_LS && !ls) return h->fail(KEEP_EINVAL, "missing ls");
+    if ((N != 768 && N != 1024) || K < 64 || K % 32) return h->fail(KEEP_EUNSUPPORTED, "linear_ln needs N in {768, 1024} and K%%32==0");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    Tmp t;
+    const Planes A = alloc_planes(t, M, K, false), W = alloc_planes(t, N, K, false), Nn = alloc_planes(t, M, N, false);
+    float* ws = t.get<float>(SKINNY_WS_BYTES / 4);
+    if (!t.ok) return h->fail(KEEP_ENOMEM, "temp alloc");
+    launch_split_blockify(a, A.hi, A.lo, (int)M, (int)K, s); launch_split_blockify(w, W.hi, W.lo, (int)N, (int)K, s);
+    // as in the towers: the residual stream is updated in place (ViT: resid += ...; BERT: out_f32 == resid), the LayerNorm that follows reads it there
+    HIPCHK(h, hipMemcpyAsync(out, resid, M * N * sizeof(float), hipMemcpyDeviceToDevice, s));
+    LnParams ln = ln_params(h, out, N, (int)M, (int)N, ln_eps);
+    ln.gamma = ln_gamma; ln.beta = ln_beta;
+    ln.out_hi = Nn.hi; ln.out_lo = split ? Nn.lo : nullptr; ln.out_kt = (int)(N / 32);
+    if (epi == EPI_RESID_F32) { ln.out_f32 = out; ln.out_f32_stride = N; }      // BERT: the normalised row replaces the sum
+    GemmParams p = gemm_params(h, A.hi, A.lo, W.hi, W.lo, (int)M, (int)N, (int)K, split != 0, bias);
+    p.ls = ls; p.resid = out;
+    with_splitk(p, ws);
+    if (epi == EPI_RESID_F32) p.out_f32 = out;
+    offer_ln(p, ln);
+    const int rc = launch_gemm_f16(p, epi, s);
+    if (rc < 0) return h->fail(KEEP_EUNSUPPORTED, "op_linear_ln: no kernel for this shape / mode");
+    if (!(rc & GEMM_DID_LN) && launch_layernorm(ln, s)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %lld", (long long)N);
+    launch_unblockify_f32(Nn.hi, ln.out_lo, ln_out, (int)M, (int)N, s);
+    if (ln_hi) launch_unblockify_f32(Nn.hi, nullptr, ln_hi, (int)M, (int)N, s);      // the hi plane on its own: hi + lo does not tell the two planes apart
+    HIPCHK(h, hipStreamSynchronize(s));
+    *did_ln = (rc & GEMM_DID_LN) ? 1 : 0;
+    return check_launch(h, "op_linear_ln");
+}
+
+int keep_op_mlp(keep_handle* h, const float* x, const float* ln_w, const float* ln_b, const float* fc1_w, const float* fc1_b,
+                const float* fc2_w, const float* fc2_b, const float* ls, int64_t M, int64_t D, int64_t F, int mode, float* out, void* stream) {
+    if (!h || !x || !ln_w || !ln_b || !fc1_w || !fc1_b || !fc2_w || !fc2_b || !ls || !out) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
+    if (M < 1 || (D != 768 && D != 1024) || F % 256 || F < 256 || mode < 0 || mode > 3) return h->fail(KEEP_EUNSUPPORTED, "op_mlp: D in {768, 1024}, F %% 256 == 0, mode 0..3");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    Tmp t;
+    const bool lo = mode == 1, q = mode == 2 || mode == 3;
+    const int cmode = mode == 3 ? 1 : 2;                 // GemmParams.comp: the W_lo term only | both terms
+    const Planes W1 = alloc_planes(t, F, D, true), W2 = alloc_planes(t, D, F, true), X = alloc_planes(t, M, D, true), H1 = alloc_planes(t, M, F, true);
+    float* ws = t.get<float>(SKINNY_WS_BYTES / 4);
+    if (!t.ok) return h->fail(KEEP_ENOMEM, "temp alloc");
+    launch_quant_blockify(fc1_w, W1.hi, W1.lo, W1.q, W1.sc, (int)F, (int)D, s);
+    launch_quant_blockify(fc2_w, W2.hi, W2.lo, W2.q, W2.sc, (int)D, (int)F, s);
+    HIPCHK(h, hipMemcpyAsync(out, x, M * D * sizeof(float), hipMemcpyDeviceToDevice, s));
+    LnParams ln = ln_params(h, x, D, (int)M, (int)D, 1e-6f);
+    ln.gamma = ln_w; ln.beta = ln_b;
+    ln.out_hi = X.hi; ln.out_lo = lo ? X.lo : nullptr; ln.out_kt = (int)(D / 32); ln.out_q = q ? X.q : nullptr; ln.out_sc = q ? X.sc : nullptr; ln.out_q_hi_only = mode == 3;
+    if (launch_layernorm(ln, s)) return h->fail(KEEP_EUNSUPPORTED, "op_mlp: layernorm");
+    GemmParams p = gemm_params(h, X.hi, X.lo, W1.hi, W1.lo, (int)M, (int)F, (int)D, lo, fc1_b);
+    with_splitk(p, ws);
+    p.out_hi = H1.hi; p.out_lo = lo ? H1.lo : nullptr; p.out_kt = (int)(F / 32);
+    if (q) { with_fp4(p, cmode, X, W1); p.out_q = H1.q; p.out_sc = H1.sc; }
+    if (launch_gemm_f16(p, EPI_GELU_F16, s) < 0) return h->fail(KEEP_EUNSUPPORTED, "op_mlp: fc1");
+    GemmParams r = gemm_params(h, H1.hi, H1.lo, W2.hi, W2.lo, (int)M, (int)D, (int)F, lo, fc2_b);
+    with_splitk(r, ws);
+    r.ls = ls; r.resid = out;
+    if (q) with_fp4(r, cmode, H1, W2);
+    if (launch_gemm_f16(r, EPI_RESID_LS, s) < 0) return h->fail(KEEP_EUNSUPPORTED, "op_mlp: fc2");
+    HIPCHK(h, hipStreamSynchronize(s));
+    return check_launch(h, "op_mlp");
+}
+
+int keep_op_attention(keep_handle* h, const float* qkv, const int64_t* mask, int64_t B, int64_t T, int heads, int split,
+                      float* out, void* stream) {
+    if (!h || !qkv || !out || B < 1 || T < 1 || heads < 1) return h ? h->fail(KEEP_EINVAL, "bad attention arguments") : KEEP_EINVAL;
+    KEEP_ON_DEVICE(h);
+    const int rc = attention_op(h, ATTN_OP_PLAIN, "op_attention", qkv, mask, B, T, heads, split, 0, out, nullptr, (hipStream_t)stream);
+    return rc == ATTN_REFUSED ? h->fail(KEEP_EUNSUPPORTED, "sequence length %lld unsupported", (long long)T) : rc;
+}
+
+int keep_op_attention_cls(keep_handle* h, const float* qkv, int64_t B, int64_t T, int heads, int split, int q_rows, float* out, float* cls_out,
+                          void* stream) {
+    if (!h || !qkv || !out || B < 1 || T < 1 || heads < 1 || q_rows < 0) return h ? h->fail(KEEP_EINVAL, "bad attention arguments") : KEEP_EINVAL;
+    KEEP_ON_DEVICE(h);
+    const int rc = attention_op(h, ATTN_OP_CLS, "op_attention_cls", qkv, nullptr, B, T, heads, split, q_rows, out, cls_out, (hipStream_t)stream);
+    return rc == ATTN_REFUSED ? h->fail(KEEP_EUNSUPPORTED, "attention: T %lld%s unsupported", (long long)T, (cls_out && split) ? " with cls_out in split mode" : "") : rc;
+}
+
+int keep_op_attention_long(keep_handle* h, const float* qkv, int64_t B, int64_t T, int heads, int split, int q_rows, float* out, void* stream) {
+    if (!h || !qkv || !out || B < 1 || T < 1 || heads < 1 || q_rows < 0) return h ? h->fail(KEEP_EINVAL, "bad attention arguments") : KEEP_EINVAL;
+    KEEP_ON_DEVICE(h);
+    const int rc = attention_op(h, ATTN_OP_LONG, "op_attention_long", qkv, nullptr, B, T, heads, split, q_rows, out, nullptr, (hipStream_t)stream);
+    return rc == ATTN_REFUSED ? h->fail(KEEP_EUNSUPPORTED, "long attention: B %lld, T %lld, heads %d unsupported", (long long)B, (long long)T, heads) : rc;
+}
+
+// Matrix-pipe ceiling probe (keep_mfma_probe): no memory traffic inside the loop; every wave holds 2 A and 4 B fragments of the caller's data in registers and
+// issues 8 independent v_mfma_f32_32x32x16_f16 per iteration (all (i, j) pairs: the pipe's inputs change with every instruction); one 8-wave workgroup per CU,
+// two waves per SIMD, as the GEMM kernels run.
+__global__ __launch_bounds__(512, 2) void mfma_probe_kernel(const f16x8* __restrict__ src, float* __restrict__ sink, int iters) {
+    f16x8 a[2], b[4];
+    const int t = blockIdx.x * 512 + threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) a[i] = src[(size_t)t * 6 + i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) b[i] = src[(size_t)t * 6 + 2 + i];
+    f32x16 acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i * 4 + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], acc[i * 4 + j], 0, 0, 0);
+    }
+    float v = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v += acc[i][r];
+    sink[t] = v;
+}
+
+int keep_op_layernorm(keep_handle* h, const float* x, const float* add, const float* gamma, const float* beta, int64_t rows,
+                      int64_t D, float eps, float* out, void* stream) {
+    if (!h || !x || !gamma || !beta || !out || rows < 1) return h ? h->fail(KEEP_EINVAL, "bad layernorm arguments") : KEEP_EINVAL;
+    KEEP_ON_DEVICE(h);
+    LnParams p = ln_params(h, x, D, (int)rows, (int)D, eps);
+    p.add = add; p.gamma = gamma; p.beta = beta;
+    p.out_f32 = out; p.out_f32_stride = D;
+    if (launch_layernorm(p, (hipStream_t)stream)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %lld", (long long)D);
+    return check_launch(h, "op_layernorm");
+}
+
+int keep_op_sgemm(keep_handle* h, const float* a, const float* b, const float* bias, int64_t M, int64_t N, int64_t K, float scale,
+                  int act, float* out, void* stream) {
+    if (!h || !a || !b || !out) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
+    KEEP_ON_DEVICE(h);
+    SgemmParams g{};
+    g.tune = &h->tune;
+    g.a = a; g.lda = K; g.b = b; g.ldb = K; g.out = out; g.ldo = N; g.bias = bias; g.M = (int)M; g.N = (int)N; g.K = (int)K;
+    g.scale = scale; g.act = act;
+    if (launch_sgemm_f32(g, (hipStream_t)stream)) return h->fail(KEEP_EUNSUPPORTED, "sgemm needs K%%16==0");
+    return check_launch(h, "op_sgemm");
+}
+
+int keep_debug_read(keep_handle* h, void* host_dst, int64_t bytes) {
+    if (!h || !host_dst || !h->tune.dbg || bytes > (int64_t)65536 * 4 * 8) return KEEP_EINVAL;      // diagnostics builds only
+    KEEP_ON_DEVICE(h);
+    HIPCHK(h, hipDeviceSynchronize());
+    HIPCHK(h, hipMemcpy(host_dst, h->tune.dbg, bytes, hipMemcpyDeviceToHost));
+    return KEEP_OK;
+}
+
+int keep_mfma_probe(keep_handle* h, const void* operands_f16, float* sink, int iters, double* flops_out, void* stream) {
+    if (!h || !operands_f16 || !sink || iters < 1 || iters > (1 << 24)) return h ? h->fail(KEEP_EINVAL, "bad mfma_probe arguments") : KEEP_EINVAL;
+    KEEP_ON_DEVICE(h);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 256;
+    hipLaunchKernelGGL(mfma_probe_kernel, dim3(cus), dim3(512), 0, (hipStream_t)stream, (const f16x8*)operands_f16, sink, iters);
+    if (flops_out) *flops_out = (double)cus * 8.0 * iters * 8.0 * 2.0 * 32 * 32 * 16;
+    return check_launch(h, "mfma_probe");
+}
+
+int keep_clock_probe(keep_handle* h, int spin_us, long long* device_out2, void* stream) {
+    if (!h || !device_out2 || spin_us < 1 || spin_us > 100000) return h ? h->fail(KEEP_EINVAL, "bad clock_probe arguments") : KEEP_EINVAL;
+    KEEP_ON_DEVICE(h);
+    hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, device_out2, spin_us * 100);
+    return check_launch(h, "clock_probe");
+}
+
+int keep_op_l2norm(keep_handle* h, float* x, int64_t rows, int64_t D, void* stream) {
+    if (!h || !x || rows < 1 || D < 1) return h ? h->fail(KEEP_EINVAL, "bad l2norm arguments") : KEEP_EINVAL;
+    KEEP_ON_DEVICE(h);
+    launch_l2norm_rows(x, (int)rows, (int)D, 1e-12f, (hipStream_t)stream);
+    return check_launch(h, "op_l2norm");
+}
+
+}  // extern "C"
