@@ -440,6 +440,42 @@ int keep_eval_mask_counts(keep_handle* h, const unsigned char* a, const unsigned
 int keep_eval_raster_hist(keep_handle* h, const int64_t* acc, const unsigned char* truth, const unsigned char* within, int64_t H, int64_t W,
                           int64_t* hist_out, void* stream);
 
+/* Lesion-level scoring: distance bands, peaks, candidates against lesions.  Beyond the reference, which stops
+ * at AUC and Dice (WSI_evaluation/segment_utils.py); the yardsticks are scipy and restatements of the published CAMELYON16 rule.
+ * keep_mask_dist2 replaces: rint(scipy.ndimage.distance_transform_edt(mask == 0) ** 2), capped.  mask uint8 [H,W] ON THE DEVICE,
+ * contiguous, non-zero = set, 1 <= H W <= 2^30; 1 <= radius R <= 1024.  out uint32 [H,W]: the squared Euclidean distance in pixels from
+ * every pixel to the nearest SET pixel (invert != 0: to the nearest ZERO pixel), exact where it is <= R^2 and the sentinel R^2 + 1
+ * elsewhere, a mask with no such pixel at all included.  Pixels outside the image do not exist: they are neither set nor zero.  Two
+ * passes: g(y, x) = min(rows to such a pixel in column x, R + 1) as uint16 (one thread per column and band of rows, an R-row halo on
+ * either side), then min over |dx| <= R of g(y, x + dx)^2 + dx^2 from a row segment of g with its 2 R halo in LDS, one thread per
+ * pixel walking outwards until dx^2 reaches its best.  Workspace from the arena: 2 H W bytes.  No host synchronisation.
+ * keep_raster_peaks replaces: non-maximum suppression of a heatmap with a rule that does not depend on thread order.  acc: the int64
+ * [H,W] accumulator of keep_heat_accumulate, 8-byte aligned, under the PRECONDITION S <= 65535 c stated at keep_regions_table; mask:
+ * uint8 [H,W] or NULL; 1 <= H W <= 2^30; 1 <= radius r <= 127; 0 <= min16 <= 65535.  A pixel is ELIGIBLE iff its count c > 0 and the
+ * mask, if given, is set there; its value is m = (2 S + c) / (2 c), peak16's rule.  An eligible pixel p with m >= min16 is a PEAK iff
+ * no other eligible pixel q of the window |dx|, |dy| <= r has m_q > m_p, or m_q == m_p and a lower row-major index: of a plateau the
+ * first pixel wins, and pixels below min16 still suppress.  Computed as a separable maximum (rows, then columns) of the 64-bit key
+ * (m + 1) << 32 | (0xFFFFFFFF - index), 0 for ineligible pixels: a peak's key equals its window's maximum.  peaks_out: int64
+ * [max_peaks,3] ON THE DEVICE, rows (x, y, m) in ascending row-major order (block counts, a scan and ranks from ballots: no atomic
+ * append); *n_out (int64 ON THE DEVICE): the true number of peaks, also when it exceeds max_peaks; the rows beyond the cap are not
+ * written (max_peaks = 0: peaks_out may be NULL).  Workspace: 8 H W bytes + 8 ceil(H W / 2048).  No host synchronisation.
+ * keep_lesion_hits replaces: the look-up of every detection in the evaluation mask and the per-lesion maximum of the CAMELYON16
+ * evaluation (computeITCList / compute_FP_TP_Probs as published).  xy int64 [N,2] level-0 (x, y) within +-2^62, scores fp32 [N],
+ * labels int32 [Hm,Wm] (1 <= Hm Wm <= 2^30), ignore uint8 [n_labels] or NULL, all ON THE DEVICE; 0 <= N <= 2^24 - 1; 1 <= downsample
+ * <= 2^30; origin within +-2^40; 0 <= n_labels <= 2^20.  Candidate i reads labels[floor((y - origin_y) / d)][floor((x - origin_x) / d)]
+ * (floor division also below zero); outside the array, or a value not in 1..n_labels, is background.  hit_out int32 [N]: the label, 0
+ * for background, -1 for a NaN score, which takes no part.  lesion_max_out uint32 [n_labels], zeroed at the head of the call: entry
+ * l - 1 is the maximum of the bit patterns of s = max(score, +0.0) (-0.0 read as +0.0; the patterns of non-negative floats order as
+ * the floats) over the candidates that hit label l; it stays 0 for a label whose ignore byte is set, while hit_out still reports that
+ * label, so that the caller does not count the hit as a false positive.  One returnless 32-bit atomicMax per distinct label of a
+ * wave: the lanes that share a label reduce first.  Maxima commute: the same from run to run.  No workspace, no host synchronisation. */
+int keep_mask_dist2(keep_handle* h, const unsigned char* mask, int64_t H, int64_t W, int radius, int invert, uint32_t* out, void* stream);
+int keep_raster_peaks(keep_handle* h, const int64_t* acc, const unsigned char* mask, int64_t H, int64_t W, int radius, int min16,
+                      int64_t max_peaks, int64_t* peaks_out, int64_t* n_out, void* stream);
+int keep_lesion_hits(keep_handle* h, const int64_t* xy, const float* scores, int64_t N, const int32_t* labels, int64_t Hm, int64_t Wm,
+                     int64_t downsample, int64_t origin_x, int64_t origin_y, int64_t n_labels, const unsigned char* ignore, int32_t* hit_out,
+                     uint32_t* lesion_max_out, void* stream);
+
 /* Pre-allocate workspace for calls of up to `tiles` tiles and `prompts` x `seq` tokens. */
 int keep_reserve(keep_handle* h, int64_t tiles, int64_t prompts, int64_t seq);
 int64_t keep_workspace_bytes(keep_handle* h);

@@ -461,3 +461,71 @@ int keep_eval_raster_hist(keep_handle* h, const int64_t* acc, const unsigned cha
 }
 
 }  // extern "C"
+
+// Lesion-level scoring (lesion.hip)
+constexpr int LESION_MAX_RADIUS = 1024;                  // g fits a uint16 and (R + 1)^2 a uint32; the LDS row of the row pass is 256 + 2 R entries
+constexpr int LESION_MAX_PEAK_RADIUS = 127;
+constexpr int64_t LESION_MAX_LABELS = (int64_t)1 << 20;
+size_t mask_dist2_workspace_bytes(int64_t npix);
+// ws: the uint16 plane of the column pass
+void launch_mask_dist2(const unsigned char* mask, int H, int W, int R, int invert, unsigned char* ws, unsigned* out, hipStream_t s);
+size_t raster_peaks_workspace_bytes(int64_t npix);
+// ws: the 64-bit plane of the row pass, then the blocks' counts and offsets; mask may be null; peaks may be null when max_peaks is 0
+void launch_raster_peaks(const int64_t* acc, const unsigned char* mask, int H, int W, int r, int min16, int64_t max_peaks, unsigned char* ws,
+                         int64_t* peaks, int64_t* n_out, hipStream_t s);
+// lesion_max: n_labels words, zeroed here; ignore may be null
+void launch_lesion_hits(const int64_t* xy, const float* scores, int64_t N, const int* labels, int Hm, int Wm, int64_t d, int64_t ox, int64_t oy,
+                        int n_labels, const unsigned char* ignore, int* hit, unsigned* lesion_max, hipStream_t s);
+
+extern "C" {
+
+int keep_mask_dist2(keep_handle* h, const unsigned char* mask, int64_t H, int64_t W, int radius, int invert, uint32_t* out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!mask) return h->fail(KEEP_EINVAL, "mask_dist2: mask is null");
+    if (!pixels_ok(H, W, TISSUE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "mask_dist2: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (radius < 1 || radius > LESION_MAX_RADIUS) return h->fail(KEEP_EINVAL, "mask_dist2: radius %d outside [1, %d]", radius, LESION_MAX_RADIUS);
+    if (!out || ((uintptr_t)out & 3)) return h->fail(KEEP_EINVAL, "mask_dist2: out is null or not 4-byte aligned");
+    KEEP_ON_DEVICE(h);
+    int rc = ensure_arena(h, mask_dist2_workspace_bytes(H * W));
+    if (rc) return rc;
+    launch_mask_dist2(mask, (int)H, (int)W, radius, invert != 0, (unsigned char*)h->arena, out, (hipStream_t)stream);
+    return check_launch(h, "mask_dist2");
+}
+
+int keep_raster_peaks(keep_handle* h, const int64_t* acc, const unsigned char* mask, int64_t H, int64_t W, int radius, int min16,
+                      int64_t max_peaks, int64_t* peaks_out, int64_t* n_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "raster_peaks: acc is null or not 8-byte aligned");
+    if (!pixels_ok(H, W, HEAT_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "raster_peaks: %lldx%lld: raster shape (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (radius < 1 || radius > LESION_MAX_PEAK_RADIUS) return h->fail(KEEP_EINVAL, "raster_peaks: radius %d outside [1, %d]", radius, LESION_MAX_PEAK_RADIUS);
+    if (min16 < 0 || min16 > 65535) return h->fail(KEEP_EINVAL, "raster_peaks: min16 %d outside [0, 65535]", min16);
+    if (max_peaks < 0) return h->fail(KEEP_EINVAL, "raster_peaks: max_peaks %lld < 0", (long long)max_peaks);
+    if (max_peaks > 0 && (!peaks_out || ((uintptr_t)peaks_out & 7))) return h->fail(KEEP_EINVAL, "raster_peaks: peaks_out is null or not 8-byte aligned");
+    if (!n_out || ((uintptr_t)n_out & 7)) return h->fail(KEEP_EINVAL, "raster_peaks: n_out is null or not 8-byte aligned");
+    KEEP_ON_DEVICE(h);
+    int rc = ensure_arena(h, raster_peaks_workspace_bytes(H * W));
+    if (rc) return rc;
+    launch_raster_peaks(acc, mask, (int)H, (int)W, radius, min16, max_peaks, (unsigned char*)h->arena, peaks_out, n_out, (hipStream_t)stream);
+    return check_launch(h, "raster_peaks");
+}
+
+int keep_lesion_hits(keep_handle* h, const int64_t* xy, const float* scores, int64_t N, const int32_t* labels, int64_t Hm, int64_t Wm,
+                     int64_t downsample, int64_t origin_x, int64_t origin_y, int64_t n_labels, const unsigned char* ignore, int32_t* hit_out,
+                     uint32_t* lesion_max_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (N < 0 || N > HEAT_MAX_TILES) return h->fail(KEEP_EINVAL, "lesion_hits: %lld candidates (0 .. 2^24 - 1)", (long long)N);
+    if (N > 0 && (!xy || !scores || !hit_out)) return h->fail(KEEP_EINVAL, "lesion_hits: null xy, scores or hit_out");
+    if (((uintptr_t)xy & 7) || ((uintptr_t)scores & 3) || ((uintptr_t)hit_out & 3)) return h->fail(KEEP_EINVAL, "lesion_hits: xy / scores / hit_out not aligned");
+    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "lesion_hits: labels is null or not 4-byte aligned");
+    if (!pixels_ok(Hm, Wm, TISSUE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "lesion_hits: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)Hm, (long long)Wm);
+    if (downsample < 1 || downsample > HEAT_MAX_PATCH) return h->fail(KEEP_EINVAL, "lesion_hits: downsample %lld outside [1, 2^30]", (long long)downsample);
+    if (int rc = origin_check(h, "lesion_hits", origin_x, origin_y)) return rc;
+    if (n_labels < 0 || n_labels > LESION_MAX_LABELS) return h->fail(KEEP_EINVAL, "lesion_hits: n_labels %lld outside [0, 2^20]", (long long)n_labels);
+    if (n_labels > 0 && (!lesion_max_out || ((uintptr_t)lesion_max_out & 3))) return h->fail(KEEP_EINVAL, "lesion_hits: lesion_max_out is null or not 4-byte aligned");
+    KEEP_ON_DEVICE(h);
+    launch_lesion_hits(xy, scores, N, labels, (int)Hm, (int)Wm, downsample, origin_x, origin_y, (int)n_labels, ignore, hit_out, lesion_max_out,
+                       (hipStream_t)stream);
+    return check_launch(h, "lesion_hits");
+}
+
+}  // extern "C"

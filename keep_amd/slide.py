@@ -16,6 +16,9 @@ from .components import NCOLS as REGION_COLS, RegionTable, check_raster, check_r
 from .evaluation import HIST_BINS, MaskOverlap, RocResult, check_mask, check_roc_args, check_same_geometry, plan_label_bands, sweep_from_hist
 from .heatmap import (MAX_TILES, ScoreReference, TileRaster, check_raster_args, check_tiles, check_values, colormap as colormap_table, render_args,
                       smooth_taps)
+from .heatmap import Q_ONE
+from .lesion import (MAX_LABELS, EvaluationMask, LesionCandidates, LesionHits, check_candidates, check_direction, check_peak_args, check_peak_count,
+                     check_radius, distance_threshold)
 from .outline import NCOLS as RING_COLS, RegionOutlines, check_draw_args, check_outline_args, check_ring_count, regions_labels, rgb_tensor
 from .region import (MASK_MODES, TILE, TissueMask, TissueSegmentation, check_downsample, check_grid_args, grid_shape, otsu_threshold, region_layout,
                      resize_tables, thumbnail_layout, tissue_params)
@@ -565,6 +568,133 @@ class SlideOps:
             counts = self.mask_tile_counts(mask, c[rows], patch, 1, origin)
             labels[rows] = (2 * counts[:, 1].to(torch.int64) > patch * patch).to(torch.uint8)
         return labels
+
+    # ------------------------------------------------------------------ lesion-level scoring
+    def _mask_dist2(self, m: torch.Tensor, R: int, invert: int) -> torch.Tensor:
+        """keep_mask_dist2 on a uint8 [h,w] device tensor -> uint32 [h,w] on the device."""
+        h, w = int(m.shape[0]), int(m.shape[1])
+        out = torch.empty((h, w), dtype=torch.uint32, device=self._device)
+        self._call("mask_dist2", _ptr(m), h, w, R, invert, _ptr(out))
+        return out
+
+    @torch.no_grad()
+    def mask_distance(self, mask, radius: int, to: str = "foreground") -> torch.Tensor:
+        """The squared Euclidean distance transform of a mask, capped at a radius, on the device -> uint32
+        ``[h,w]`` on the device: the squared distance in pixels from every pixel to the nearest set pixel (``to="background"``: to the
+        nearest zero pixel), exact where it is ``<= radius^2`` and ``radius^2 + 1`` elsewhere, a mask without such a pixel included.
+        ``mask``: bool / uint8 ``[h,w]``, numpy or torch, host or device, or a ``TissueMask``; ``1 <= radius <= 1024``.  Pixels outside the
+        image do not exist (scipy's behaviour): ``rint(distance_transform_edt(mask == 0) ** 2)`` capped.  No host synchronisation;
+        equal to ``keep_amd.lesion.dist2_numpy`` exactly."""
+        R, invert = check_radius(radius), check_direction(to)
+        m = check_mask(mask, "mask")
+        self._ready_device()
+        return self._mask_dist2(self._on_device(m), R, invert)
+
+    def _mask_band(self, mask, distance, invert: int):
+        R, k = distance_threshold(distance)
+        m = check_mask(mask, "mask")
+        self._ready_device()
+        d2 = self._mask_dist2(self._on_device(m), R, invert).view(torch.int32)          # <= 2^20 + 1: the sign bit is clear
+        out = (d2 > k) if invert else (d2 <= k)
+        if isinstance(mask, TissueMask):
+            return TissueMask(out, mask.downsample, mask.mode, mask.threshold)
+        return TissueMask(out, 1)
+
+    @torch.no_grad()
+    def dilate_mask(self, mask, distance: float):
+        """A mask dilated by a true disc -> ``TissueMask`` of the same geometry (downsample 1 for a bare array): a pixel is taken
+        iff its distance to the mask is ``< distance`` pixels, ``0 < distance <= 1024``, a float.  The comparison is scipy's float64
+        ``distance_transform_edt(mask == 0) < distance``, done exactly as an integer threshold on :meth:`mask_distance`
+        (``keep_amd.lesion.distance_threshold``)."""
+        return self._mask_band(mask, distance, 0)
+
+    @torch.no_grad()
+    def erode_mask(self, mask, distance: float):
+        """A mask eroded by a true disc: a pixel stays iff its distance to the background is ``>= distance`` pixels; the outside of
+        the image is not background.  Otherwise as :meth:`dilate_mask`."""
+        return self._mask_band(mask, distance, 1)
+
+    @torch.no_grad()
+    def evaluation_mask(self, truth, margin_px: float, connectivity: int = 8, fill_holes: bool = True, ignore_max_extent=None,
+                        downsample: Optional[int] = None, shape=None, order=None, rule: str = "union", max_regions: int = 1 << 20):
+        """The labelled lesions a detection may hit, as the CAMELYON16 evaluation describes its mask: the truth dilated by
+        ``margin_px`` (``keep_amd.lesion.camelyon16_margin``; 0 = as it is), holes filled, labelled with ``connectivity`` ->
+        ``keep_amd.lesion.EvaluationMask``.  ``truth``: a ``TissueMask``, or a ``PolygonSet`` with ``downsample=`` and ``shape=`` (through
+        :meth:`annotation_mask` with ``order`` / ``rule``).  Holes are the 4-connected background regions that touch no border.
+        ``ignore_max_extent``: lesions whose bounding box's longer side is below it get their ``ignore`` byte set -- a stand-in for the
+        challenge's isolated-tumour-cell rule (a major axis length from float moments), with which no parity is claimed; callers may
+        overwrite ``ignore``.  Two labellings, each with its one readback."""
+        if isinstance(truth, PolygonSet):
+            if downsample is None or shape is None:
+                raise ValueError("a PolygonSet needs downsample= and shape=, the geometry of the evaluation mask")
+            truth = self.annotation_mask(truth, downsample, shape, order=order, rule=rule)
+        if not isinstance(truth, TissueMask):
+            raise ValueError(f"truth must be a TissueMask or a PolygonSet, got {type(truth).__name__}")
+        if ignore_max_extent is not None and not ignore_max_extent >= 0:
+            raise ValueError(f"ignore_max_extent must be >= 0, got {ignore_max_extent!r}")
+        grown = self.dilate_mask(truth, margin_px) if margin_px else TissueMask(self._on_device(truth.mask), truth.downsample, truth.mode)
+        mask = grown.mask
+        if fill_holes:
+            bg = self.mask_regions(mask == 0, 4, max_regions=max_regions)
+            hole = torch.cat([torch.zeros((1,), dtype=torch.uint8, device=self._device), (bg.border == 0).to(torch.uint8)])
+            mask = mask | hole[bg.labels.to(torch.int64)]
+        table = self.mask_regions(TissueMask(mask, truth.downsample, truth.mode), connectivity, max_regions=max_regions)
+        ignore = torch.zeros((table.n,), dtype=torch.uint8, device=self._device)
+        if ignore_max_extent is not None:
+            ignore = (torch.maximum(table.x1 - table.x0, table.y1 - table.y0) < ignore_max_extent).to(torch.uint8)
+        return EvaluationMask(table.labels, table.n, table, ignore, truth.downsample, (0, 0))
+
+    @torch.no_grad()
+    def raster_peaks(self, raster, radius: int, min_score: float = 0.5, tissue=None, max_peaks: int = 1 << 20):
+        """The local maxima of a heatmap on the device -> ``keep_amd.lesion.LesionCandidates``.  A raster
+        pixel is eligible iff a tile covers it (and ``tissue``, a ``TissueMask`` of the raster's geometry, is set there); its value is
+        its mean in 16-bit fixed point; an eligible pixel at or above ``quantize(min_score)`` is a peak iff no other eligible pixel of
+        its ``(2 radius + 1)^2`` window is larger, or equal with a lower row-major index (``1 <= radius <= 127``).  Candidates come in
+        row-major order, the same from run to run.  Their number is read back once; more than ``max_peaks`` is a ValueError that
+        reports it.  Equal to ``keep_amd.lesion.peaks_numpy`` / ``candidates_numpy`` exactly."""
+        _check_tile_raster(raster)
+        r, min16, cap = check_peak_args(radius, min_score, max_peaks)
+        if tissue is not None:
+            _check_tissue(tissue, raster)
+        self._ready_device()
+        self._raster_here(raster)
+        h, w = raster.shape
+        md = None if tissue is None else self._on_device(tissue.mask)
+        rows = min(cap, h * w)
+        peaks = torch.empty((rows, 3), dtype=torch.int64, device=self._device)
+        n_dev = torch.empty((1,), dtype=torch.int64, device=self._device)
+        self._call("raster_peaks", _ptr(raster.acc), _ptr(md), h, w, r, min16, rows, _ptr(peaks if rows else None), _ptr(n_dev))
+        n = check_peak_count(int(n_dev.item()), cap)
+        peaks = peaks[:n]
+        d = raster.downsample
+        xy = peaks[:, :2] * d + (torch.tensor(raster.origin, dtype=torch.int64, device=self._device) + d // 2)
+        return LesionCandidates(xy, (peaks[:, 2].to(torch.float64) / float(Q_ONE)).to(torch.float32), peaks[:, 2].clone())
+
+    @torch.no_grad()
+    def lesion_hits(self, candidates, evaluation_mask):
+        """Which lesion does every candidate hit, and the best score on every lesion, on the device ->
+        ``keep_amd.lesion.LesionHits``.  ``candidates``: a ``LesionCandidates`` or a pair ``(xy integers [N,2] level-0, scores floating
+        [N])``, host or device, ``N <= 2^24 - 1``; ``evaluation_mask``: an ``EvaluationMask``.  A candidate reads the label under it
+        (floor division by the mask's downsample; outside the mask is background); a NaN score gives ``hit = -1`` and takes no part;
+        ``lesion_max`` is the maximum of ``max(score, 0)`` over a lesion's hits and stays 0 for an ignored lesion, whose hits are not
+        false positives either.  No host synchronisation but for ``fp_scores``; equal to ``keep_amd.lesion.lesion_hits_numpy`` exactly."""
+        if not isinstance(evaluation_mask, EvaluationMask):
+            raise ValueError(f"evaluation_mask must be an EvaluationMask, got {type(evaluation_mask).__name__}")
+        xy, s = (candidates.xy, candidates.scores) if isinstance(candidates, LesionCandidates) else candidates
+        xy = xy if isinstance(xy, torch.Tensor) else torch.as_tensor(np.asarray(xy))
+        s = s if isinstance(s, torch.Tensor) else torch.as_tensor(np.asarray(s))
+        N = check_candidates(xy, s)
+        em = evaluation_mask
+        if em.n > MAX_LABELS:
+            raise ValueError(f"the evaluation mask has {em.n} lesions, at most 2^20")
+        self._ready_device()
+        xy, s = self._on_device(xy, torch.int64), self._on_device(s, torch.float32)
+        lab, ignore = self._on_device(em.labels, torch.int32), self._on_device(em.ignore, torch.uint8)
+        hit = torch.empty((N,), dtype=torch.int32, device=self._device)
+        best = torch.empty((em.n,), dtype=torch.float32, device=self._device)
+        self._call("lesion_hits", _ptr(xy if N else None), _ptr(s if N else None), N, _ptr(lab), int(lab.shape[0]), int(lab.shape[1]), em.downsample,
+                   em.origin[0], em.origin[1], em.n, _ptr(ignore if em.n else None), _ptr(hit if N else None), _ptr(best if em.n else None))
+        return LesionHits(hit, best, em.n - int(ignore.sum()), s[hit == 0] + 0.0)
 
     @staticmethod
     def _cells_to_coords(cells: torch.Tensor, origin, coord_scale: int) -> torch.Tensor:

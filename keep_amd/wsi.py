@@ -429,6 +429,55 @@ def segment_evaluate(classifier, tile_features, tile_coords, annotation, patch_s
     return roc, ov, m.raster_sweep(m.tile_raster(coords, p, patch_size, 16, shape), mask16)
 
 
+# ------------------------------------------------------------------------------------------------ lesion-level scoring
+def segment_lesions(raster, radius, min_score=0.5, tissue=None, max_peaks=1 << 20, model=None):
+    """The detections a segmentation raster proposes: the local maxima of its mean within ``radius`` raster pixels that reach
+    ``min_score`` (``KEEPModel.raster_peaks``) -> ``keep_amd.lesion.LesionCandidates`` with level-0 coordinates.  ``raster``: the
+    ``TileRaster`` of :func:`segment_heatmap`; ``tissue``: a ``TissueMask`` of its geometry, optional."""
+    from .heatmap import TileRaster
+    if not isinstance(raster, TileRaster):
+        raise ValueError(f"raster must be a TileRaster, got {type(raster).__name__}")
+    return _engine(model, raster.acc).raster_peaks(raster, radius, min_score, tissue, max_peaks)
+
+
+def eval_seg_froc(slides, margin_px=None, radius=None, min_score=0.5, downsample=None, shape=None, rule="union", ignore_max_extent=None,
+                  model=None):
+    """Lesion-level FROC over slides, the score of a CAMELYON16-style challenge -> ``keep_amd.lesion.FrocCurve`` (``.score``: the mean
+    sensitivity at 1/4 ... 8 false positives per slide).  ``slides``: an iterable of ``(raster or candidates, annotation)``: a
+    ``TileRaster`` (its peaks are taken with ``radius`` / ``min_score``, see :func:`segment_lesions`) or a ``LesionCandidates``; the
+    annotation in the forms :func:`zero_shot_segment` takes.  A ``PolygonSet`` is filled in the raster's geometry (origin 0), or at
+    ``downsample`` / ``shape`` beside candidates.  Per slide: ``KEEPModel.evaluation_mask`` (``margin_px`` in mask pixels, default
+    ``keep_amd.lesion.camelyon16_margin()``: 75 um at downsample 32 of a 0.243 um slide), ``KEEPModel.lesion_hits``, then one
+    ``FrocAccumulator``.  Parity with the challenge's own script is not claimed."""
+    from .annotation import PolygonSet
+    from .heatmap import TileRaster
+    from .lesion import FrocAccumulator, LesionCandidates, camelyon16_margin
+    margin_px = camelyon16_margin() if margin_px is None else margin_px
+    froc, m = None, None
+    for found, annotation in slides:
+        truth, order = _annotation(annotation)
+        if isinstance(found, TileRaster):
+            if radius is None:
+                raise ValueError("a raster needs radius=, the suppression radius of its peaks in raster pixels")
+            m = _engine(model, found.acc)
+            d, hw = found.downsample, found.shape
+            found = m.raster_peaks(found, radius, min_score)
+        elif isinstance(found, LesionCandidates):
+            m = _engine(model, *(t for t in (found.xy, found.scores) if isinstance(t, torch.Tensor)))
+            d, hw = downsample, shape
+        else:
+            raise ValueError(f"a slide is (TileRaster or LesionCandidates, annotation), got {type(found).__name__}")
+        if isinstance(truth, PolygonSet):
+            em = m.evaluation_mask(truth, margin_px, ignore_max_extent=ignore_max_extent, downsample=d, shape=hw, order=order, rule=rule)
+        else:
+            em = m.evaluation_mask(truth, margin_px, ignore_max_extent=ignore_max_extent)
+        froc = FrocAccumulator(m) if froc is None else froc
+        froc.add(m.lesion_hits(found, em))
+    if froc is None:
+        raise ValueError("no slides")
+    return froc.curve()
+
+
 # ------------------------------------------------------------------------------------------------ heatmap (DESIGN.md section 12)
 def segment_heatmap(classifier, tile_features, tile_coords, downsample, shape, patch_size=224, overlap=True, cls=1, origin=(0, 0), model=None,
                     percentile=False, reference=None, blur_sigma=None, blur_radius=None, tissue=None):
