@@ -619,6 +619,21 @@ int keep_op_linear_ln(keep_handle* h, const float* a, const float* w, const floa
 int keep_op_mlp(keep_handle* h, const float* x, const float* ln_w, const float* ln_b, const float* fc1_w, const float* fc1_b,
                 const float* fc2_w, const float* fc2_b, const float* ls, int64_t M, int64_t D, int64_t F, int mode, float* out,
                 void* stream);
+/* One producer of the MX-fp4 side planes (the operands of the compensated product's correction terms) run on its own, and what it wrote read back:
+ *   KEEP_MX_BLOCKIFY   the weight / op-input conversion on x fp32 [M,K] (K % 32 == 0; always both planes: hi_only = 0)
+ *   KEEP_MX_LAYERNORM  LayerNorm(x [M,K]; gamma, beta [K], eps) with the side planes of its output; K in {768, 1024}
+ *   KEEP_MX_GELU       the compensated 256x256 GEMM gelu(x [M,K] @ w [N,K]^T + bias [N]) with the side planes of its output [M,N]
+ *                      (N % 256 == 0, K % 128 == 0, K >= 256; the one-term launch K >= 512)
+ *   hi_only 0: both planes, as a two-term consumer needs them; 1: Q(X_hi) and its scales only, as the producers of a one-term chain write them
+ *   (the GEMM then is a one-term launch itself); lo must then be NULL.
+ * With C = K (N for KEEP_MX_GELU) the width of the operand written: hi, lo fp32 [M,C] row-major, the fp16 planes converted back; q uint8
+ * [ceil(M/256)*256 * C] and sc uint8 [ceil(M/256)*256 * C/32 * 2]: the e2m1 bytes and the E8M0 scale bytes exactly as they lie on the device
+ * (both planes, padding rows included).  Every byte of q and sc is set to `sentinel` (0..255) before the producer runs: what still holds it was
+ * not written.  All pointers but h are device pointers. */
+enum { KEEP_MX_BLOCKIFY = 0, KEEP_MX_LAYERNORM = 1, KEEP_MX_GELU = 2 };
+int keep_op_mx_planes(keep_handle* h, int producer, int hi_only, const float* x, const float* w, const float* bias,
+                      const float* gamma, const float* beta, float eps, int64_t M, int64_t N, int64_t K, int sentinel,
+                      float* hi, float* lo, unsigned char* q, unsigned char* sc, void* stream);
 /* qkv fp32 [B*T, 3*heads*64] (q|k|v), mask int64 [B,T] or NULL -> out fp32 [B*T, heads*64] */
 int keep_op_attention(keep_handle* h, const float* qkv, const int64_t* mask, int64_t B, int64_t T, int heads,
                       int split, float* out, void* stream);

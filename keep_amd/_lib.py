@@ -86,6 +86,7 @@ SIGNATURES = {
     "keep_op_linear": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp]),
     "keep_op_linear_ln": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(_i32), _vp]),
     "keep_op_mlp": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp]),
+    "keep_op_mx_planes": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "keep_op_attention": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "keep_op_attention_cls": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "keep_op_attention_long": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),

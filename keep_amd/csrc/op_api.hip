@@ -101,7 +101,7 @@ int keep_op_linear(keep_handle* h, const float* a, const float* w, const float* 
     with_splitk(p, ws);
     int launch_rc = 0;
     if (epi == EPI_F16 || epi == EPI_GELU_F16) {
-        p.out_hi = O.hi; p.out_lo = (split == 1 || split == 2) ? O.lo : nullptr;
+        p.out_hi = O.hi; p.out_lo = split ? O.lo : nullptr;       // (split 3 too: what is read back is the accumulator to 2^-22, as the header says, not its fp16 rounding)
         // as in the towers: the GELU output feeds another GEMM (blk layout), the plain one feeds attention (row-major)
         p.out_kt = (epi == EPI_GELU_F16) ? (int)(N / 32) : 0;
         launch_rc = launch_gemm_f16(p, epi, s);
@@ -187,6 +187,56 @@ int keep_op_mlp(keep_handle* h, const float* x, const float* ln_w, const float* 
     if (launch_gemm_f16(r, EPI_RESID_LS, s) < 0) return h->fail(KEEP_EUNSUPPORTED, "op_mlp: fc2");
     HIPCHK(h, hipStreamSynchronize(s));
     return check_launch(h, "op_mlp");
+}
+
+int keep_op_mx_planes(keep_handle* h, int producer, int hi_only, const float* x, const float* w, const float* bias, const float* gamma,
+                      const float* beta, float eps, int64_t M, int64_t N, int64_t K, int sentinel, float* hi, float* lo, unsigned char* q,
+                      unsigned char* sc, void* stream) {
+    if (!h || !x || !hi || !q || !sc) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
+    if (producer < KEEP_MX_BLOCKIFY || producer > KEEP_MX_GELU || sentinel < 0 || sentinel > 255) return h->fail(KEEP_EINVAL, "mx_planes: producer %d, sentinel %d", producer, sentinel);
+    if (hi_only ? (lo != nullptr || producer == KEEP_MX_BLOCKIFY) : !lo) return h->fail(KEEP_EINVAL, "mx_planes: lo goes with both planes (the blockify kernel always writes both)");
+    if (M < 1 || M > (1 << 24)) return h->fail(KEEP_EINVAL, "mx_planes: M %lld", (long long)M);
+    if (producer == KEEP_MX_BLOCKIFY && (K < 32 || K % 32 || K > (1 << 20))) return h->fail(KEEP_EUNSUPPORTED, "mx_planes: blockify needs K%%32==0");
+    if (producer == KEEP_MX_LAYERNORM && (!gamma || !beta)) return h->fail(KEEP_EINVAL, "missing gamma/beta");
+    if (producer == KEEP_MX_LAYERNORM && K != 768 && K != 1024) return h->fail(KEEP_EUNSUPPORTED, "mx_planes: layernorm width %lld", (long long)K);
+    if (producer == KEEP_MX_GELU && (!w || !bias)) return h->fail(KEEP_EINVAL, "missing w/bias");
+    if (producer == KEEP_MX_GELU && (N < 256 || N % 256 || N > (1 << 20) || K % 128 || K < (hi_only ? 512 : 256) || K > (1 << 20)))
+        return h->fail(KEEP_EUNSUPPORTED, "compensated linear needs N%%256==0, K%%128==0, K>=256 (512 for the one-term form)");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t C = producer == KEEP_MX_GELU ? N : K;             // width of the operand the producer writes (the consumer's K)
+    Tmp t;
+    const Planes P = alloc_planes(t, M, C, true);
+    Planes A{}, W{};
+    float* ws = nullptr;
+    if (producer == KEEP_MX_GELU) { A = alloc_planes(t, M, K, true); W = alloc_planes(t, N, K, true); ws = t.get<float>(SKINNY_WS_BYTES / 4); }
+    if (!t.ok) return h->fail(KEEP_ENOMEM, "temp alloc");
+    const size_t qb = keepk::q4_data_bytes(M, C), sb = keepk::q4_scale_bytes(M, C);
+    HIPCHK(h, hipMemsetAsync(P.q, sentinel, qb, s));
+    HIPCHK(h, hipMemsetAsync(P.sc, sentinel, sb, s));
+    if (producer == KEEP_MX_BLOCKIFY) {
+        launch_quant_blockify(x, P.hi, P.lo, P.q, P.sc, (int)M, (int)K, s);
+    } else if (producer == KEEP_MX_LAYERNORM) {
+        LnParams ln = ln_params(h, x, K, (int)M, (int)K, eps);
+        ln.gamma = gamma; ln.beta = beta;
+        // (the towers leave out_lo null in both compensated modes; it is set here so that the lo plane the quantiser saw can be read back)
+        ln.out_hi = P.hi; ln.out_lo = hi_only ? nullptr : P.lo; ln.out_kt = (int)(K / 32); ln.out_q = P.q; ln.out_sc = P.sc; ln.out_q_hi_only = hi_only ? 1 : 0;
+        if (launch_layernorm(ln, s)) return h->fail(KEEP_EUNSUPPORTED, "mx_planes: layernorm");
+    } else {
+        launch_quant_blockify(x, A.hi, A.lo, A.q, A.sc, (int)M, (int)K, s);
+        launch_quant_blockify(w, W.hi, W.lo, W.q, W.sc, (int)N, (int)K, s);
+        GemmParams p = gemm_params(h, A.hi, A.lo, W.hi, W.lo, (int)M, (int)N, (int)K, false, bias);
+        with_fp4(p, hi_only ? 1 : 2, A, W);
+        with_splitk(p, ws);
+        p.out_hi = P.hi; p.out_lo = hi_only ? nullptr : P.lo; p.out_kt = (int)(N / 32); p.out_q = P.q; p.out_sc = P.sc;
+        if (launch_gemm_f16(p, EPI_GELU_F16, s) < 0) return h->fail(KEEP_EUNSUPPORTED, "mx_planes: no kernel for this shape / mode");
+    }
+    launch_unblockify_f32(P.hi, nullptr, hi, (int)M, (int)C, s);
+    if (lo) launch_unblockify_f32(P.lo, nullptr, lo, (int)M, (int)C, s);
+    HIPCHK(h, hipMemcpyAsync(q, P.q, qb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(sc, P.sc, sb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return check_launch(h, "op_mx_planes");
 }
 
 int keep_op_attention(keep_handle* h, const float* qkv, const int64_t* mask, int64_t B, int64_t T, int heads, int split,

@@ -14,6 +14,7 @@ from . import _lib
 from .model import _ptr, _stream
 
 EPI_F16, EPI_GELU_F16, EPI_RESID_LS, EPI_RESID_F32 = 0, 1, 2, 4
+MX_BLOCKIFY, MX_LAYERNORM, MX_GELU = 0, 1, 2             # keep_op_mx_planes: which producer of the MX-fp4 side planes runs
 
 
 class Ops:
@@ -87,6 +88,24 @@ class Ops:
                                      _ptr(ls), M, D, F, int(mode), _ptr(out), _stream(self.device))
         _lib.check(self._h, rc, "op_mlp")
         return out
+
+    def mx_planes(self, producer, x, w=None, bias=None, gamma=None, beta=None, eps=1e-6, hi_only=False, sentinel=0xFF):
+        """One producer of the MX-fp4 side planes on its own (MX_BLOCKIFY: x [M,K]; MX_LAYERNORM: x, gamma, beta, eps; MX_GELU: the compensated
+        GEMM gelu(x @ w^T + bias)) -> (hi, lo, q, sc): the fp16 planes it wrote as fp32 [M,C] (lo None with hi_only) and the raw e2m1 / E8M0 bytes
+        in device layout, padding rows included, every byte preset to `sentinel`."""
+        x, w, bias, gamma, beta = map(self._f, (x, w, bias, gamma, beta))
+        M, K = x.shape
+        N = w.shape[0] if w is not None else 0
+        Cw = N if producer == MX_GELU else K
+        Mp = (M + 255) // 256 * 256
+        hi = torch.empty((M, Cw), dtype=torch.float32, device=self.device)
+        lo = None if hi_only else torch.empty((M, Cw), dtype=torch.float32, device=self.device)
+        q = torch.empty(Mp * Cw, dtype=torch.uint8, device=self.device)
+        sc = torch.empty(Mp * (Cw // 32) * 2, dtype=torch.uint8, device=self.device)
+        rc = _lib.load().keep_op_mx_planes(self._h, int(producer), int(hi_only), _ptr(x), _ptr(w), _ptr(bias), _ptr(gamma), _ptr(beta), float(eps),
+                                           M, N, K, int(sentinel), _ptr(hi), _ptr(lo), _ptr(q), _ptr(sc), _stream(self.device))
+        _lib.check(self._h, rc, "op_mx_planes")
+        return hi, lo, q, sc
 
     def attention(self, qkv, B, T, heads, mask=None, split=False):
         qkv = self._f(qkv)

@@ -100,7 +100,10 @@ def _rel_rms(out, ref):
 def test_compensated_linear_recovers_the_fp16_rounding(ops, M, N, K, epi):
     """split=2: A_hi W_hi on the fp16 pipe + Q4(A_hi) Q4(W_lo) + Q4(A_lo) Q4(W_hi) on the MX-fp4 pipe.  The correction terms
     only need 2-3 bits: the result must sit >= 4x closer to the fp64 product than the plain fp16-operand product does
-    (tools/precision_study.py: ~96 % of the rounding variance removed), on every tile position incl. the ragged M edge."""
+    (tools/precision_study.py: ~96 % of the rounding variance removed), on every tile position incl. the ragged M edge.
+    What this can see: a correction term that is missing, transposed, or applied to the wrong tile.  What it cannot: these Gaussian operands
+    share 3 or 4 scale bytes per plane, so a neighbouring scale byte, a clipped block maximum or a truncating encoder still remove half of the
+    rounding error or more and may pass.  tests/test_mx_gpu.py pins the fp4 arithmetic itself (varying scales, host model, two-sided gate)."""
     a, w, b = rand(M, K, seed=21), rand(N, K, seed=22, std=0.04), rand(N, seed=23, std=0.1)
     ls = torch.rand(N, generator=torch.Generator().manual_seed(24)) * 0.45 + 0.05
     resid = rand(M, N, seed=25)
@@ -130,7 +133,8 @@ def test_compensated_linear_recovers_the_fp16_rounding(ops, M, N, K, epi):
 def test_one_term_compensated_linear_removes_the_weight_rounding(ops, M, N, K, epi):
     """split=3 (KEEP_MLP_COMP_W's GEMM): A_hi W_hi on the fp16 pipe + Q4(A_hi) Q4(W_lo) on the MX-fp4 pipe, K = 128 per chunk.  What it must
     deliver is the product of the fp16-ROUNDED activations with the UNROUNDED weights: against that reference the error has to be a small
-    fraction of the weight-rounding error it removes, on every 32 x 32 patch (a wrong plane, block order or scale byte adds error instead);
+    fraction of the weight-rounding error it removes, on every 32 x 32 patch (a wrong plane or block order adds error instead; a wrong scale
+    byte does NOT on these Gaussian operands, whose blocks share 3 or 4 scale bytes -- tests/test_mx_gpu.py covers that with varying scales);
     against the exact product it keeps the activation half of the fp16 rounding error -- no more, no less."""
     a, w, b = rand(M, K, seed=51), rand(N, K, seed=52, std=0.04), rand(N, seed=53, std=0.1)
     ls = torch.rand(N, generator=torch.Generator().manual_seed(54)) * 0.45 + 0.05
@@ -170,7 +174,8 @@ def test_compensated_linear_rejects_k_that_does_not_fill_the_ring(ops, K):
 
 def test_compensated_linear_is_not_transposed(ops):
     """Asymmetric operands whose fp16 rounding error is large and structured: a swapped / permuted correction operand
-    (rows, k blocks, scale bytes) would add error instead of removing it."""
+    (rows, k blocks) would add error instead of removing it.  The ramps are smooth and positive, so every block of a plane has the same
+    scale byte or its neighbour: permuted SCALE bytes go unnoticed here (tests/test_mx_gpu.py: operands with a power of two per row and block)."""
     M, N, K = 512, 512, 256
     g = torch.Generator().manual_seed(31)
     a = (torch.arange(M * K, dtype=torch.float32).reshape(M, K) % 977) / 977.0 + 1.0 + torch.rand(M, K, generator=g) * 1e-3
@@ -188,7 +193,9 @@ def test_mlp_block_modes(ops, D, F, M):
     """LayerNorm -> fc1 + GELU -> fc2 + LayerScale + residual through the tower's kernels.  Mode 2 consumes the MX-fp4 side
     planes written by the LayerNorm kernel and by the GELU epilogue (the producers of the compensated path): if either wrote
     a wrong layout the corrections would add noise, so the error must drop well below the plain fp16 mode's and approach the
-    split mode's."""
+    split mode's.  With N(0, 1) rows and gains near 1 the planes' block scales are almost constant, so this sees a wrong data layout but not a
+    wrong scale byte, plane-1 garbage in mode 3 or a rounding mistake of the encoder: tests/test_mx_gpu.py compares the producers' bytes with
+    the host encoding and the chain with its float64 emulation."""
     x = rand(M, D, seed=41)
     ln_w, ln_b = 1.0 + rand(D, seed=42, std=0.1), rand(D, seed=43, std=0.05)
     w1, b1 = rand(F, D, seed=44, std=0.025), rand(F, seed=45, std=0.02)
