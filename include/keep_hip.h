@@ -259,6 +259,16 @@ int keep_region_grid_mask(keep_handle* h, const unsigned char* mask, int64_t mh,
  * into the one in acc. */
 int keep_heat_accumulate(keep_handle* h, const int64_t* coords, const float* values, int64_t N, int64_t patch, int64_t downsample,
                          int64_t H, int64_t W, int64_t origin_x, int64_t origin_y, int zero_first, int64_t* acc, void* stream);
+/* keep_heat_accumulate with one value per cell of a gh x gw grid inside every tile (the token grid of the image
+ * tower, 14 x 14 cells of 16 pixels in a 224 tile): values fp32 [N, gh gw], row-major (y, x).  A tile's pixel footprint is exactly
+ * keep_heat_accumulate's; footprint pixel (X, Y) takes the cell cx = clamp(floor((X downsample + origin_x - x) / cw), 0, gw - 1), cy
+ * likewise, cw = patch / gw, ch = patch / gh: the cell under the pixel's upper-left corner in level-0 units.  Each (tile, pixel) adds
+ * (1 << 40) | q of that cell, so the count field still counts tiles and the 2^24 - 1 cap is a cap on tiles; a NaN cell adds nothing
+ * to its pixels, neither sum nor count.  Needs patch % gw == 0, patch % gh == 0, gh gw <= 2^24 and 1 <= downsample <= min(cw, ch);
+ * everything else as keep_heat_accumulate.  Integer arithmetic: the same however the tiles are split over calls. */
+int keep_heat_accumulate_cells(keep_handle* h, const int64_t* coords, const float* values, int64_t N, int64_t gh, int64_t gw, int64_t patch,
+                               int64_t downsample, int64_t H, int64_t W, int64_t origin_x, int64_t origin_y, int zero_first, int64_t* acc,
+                               void* stream);
 /* Replaces: reading the raster back as numbers (the probability map in slide geometry; the {0,255} pred_mask of
  * segment_utils.py:134-140 when the values were p > thd).  mean_out: fp32 [H,W] = float(double(sum) / double(65535 count)) where
  * count > 0, else `uncovered`; count_out: int32 [H,W]; pred_out: uint8 [H,W], 255 where sum > 0.  Any of the three may be null, not
@@ -498,6 +508,18 @@ int keep_encode_image(keep_handle* h, const void* pixels, int pix_dtype, int64_t
 int keep_encode_image_hw(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, int64_t H, int64_t W, float* out,
                          void* stream);
 
+/* keep_encode_image_hw with the CLS query's attention over the tokens of one block beside the feature: what a
+ *   DINO / UNI / HIPT figure shows per head, which the reference can only produce by hooking timm's Attention.forward
+ *   (quick_start/keep_inference.py:32-40 builds the tower).  out: fp32 [B,768], exactly what keep_encode_image_hw writes for the
+ *   same call made with option "graphs" = 0; attn_out: fp32 [B, heads, gh gw + 1], row (b, h) = softmax_k(q_{b,h,0} . k_{b,h,k} / 8)
+ *   of block `block` (0 .. depth - 1, or negative counting from the end), column 0 the CLS -> CLS weight, columns 1.. the patches in
+ *   row-major (y, x) order.  The operands are the block's own fp16 q / k planes (hi + lo where the block runs as split products),
+ *   products and sums in fp32.  The call runs the ordinary stream path (it is never captured or replayed as a graph) and leaves
+ *   the handle's options and graphs as they were.  KEEP_EINVAL: block out of range, a null pointer, H or W not a positive
+ *   multiple of 16. */
+int keep_encode_image_attn(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, int64_t H, int64_t W, int block, float* out,
+                           float* attn_out, void* stream);
+
 /* Replaces: timm.layers.resample_abs_pos_embed(visual.pos_embed, new_size=(gh, gw), old_size=(14, 14), num_prefix_tokens=1)
  *   (the step timm's dynamic_img_size takes per forward, quick_start/keep_inference.py:32-40).  out: fp32 [gh*gw+1, D], the table
  *   keep_encode_image_hw uses for that grid: visual.pos_embed itself at 14 x 14, else the CLS row + the patch rows through
@@ -647,6 +669,9 @@ int keep_op_attention_cls(keep_handle* h, const float* qkv, int64_t B, int64_t T
  * qkv fp32 [B*T, 3*heads*64] -> out fp32 [B*T, heads*64]; q_rows > 0: only the first q_rows queries of every sequence (other rows 0) */
 int keep_op_attention_long(keep_handle* h, const float* qkv, int64_t B, int64_t T, int heads, int split, int q_rows,
                            float* out, void* stream);
+/* The CLS query's attention probabilities (the kernel behind keep_encode_image_attn): qkv fp32 [B*T, 3*heads*64], turned into fp16 planes as
+ * keep_op_attention does (split != 0: hi + lo) -> out fp32 [B, heads, T] = softmax_k(q_{b,h,0} . k_{b,h,k} / 8), any T >= 1 */
+int keep_op_attention_cls_probs(keep_handle* h, const float* qkv, int64_t B, int64_t T, int heads, int split, float* out, void* stream);
 int keep_op_layernorm(keep_handle* h, const float* x, const float* add, const float* gamma, const float* beta,
                       int64_t rows, int64_t D, float eps, float* out, void* stream);
 /* out[M,N] = act(scale * A[M,K] @ B[N,K]^T + bias); act 0 none, 1 gelu, 2 tanh (exact fp32 MFMA) */

@@ -45,6 +45,7 @@ SIGNATURES = {
     "keep_workspace_bytes": (_i64, [_vp]),
     "keep_encode_image": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp]),
     "keep_encode_image_hw": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp]),
+    "keep_encode_image_attn": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
     "keep_vit_pos_embed": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "keep_encode_text": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "keep_resize_crop_u8": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp]),
@@ -54,6 +55,7 @@ SIGNATURES = {
     "keep_tissue_mask": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i64, _i64, _vp, _vp]),
     "keep_region_grid_mask": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
     "keep_heat_accumulate": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp]),
+    "keep_heat_accumulate_cells": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp]),
     "keep_heat_mean": (_i32, [_vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "keep_heat_render": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "keep_heat_smooth": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp]),
@@ -90,6 +92,7 @@ SIGNATURES = {
     "keep_op_attention": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "keep_op_attention_cls": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "keep_op_attention_long": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "keep_op_attention_cls_probs": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "keep_op_layernorm": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp]),
     "keep_op_sgemm": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _vp]),
     "keep_op_l2norm": (_i32, [_vp, _vp, _i64, _i64, _vp]),

@@ -734,6 +734,92 @@ int launch_long(const AttnParams& p, int qblocks, hipStream_t s) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The CLS query's attention probabilities on their own (launch_attention_cls_probs): out[b][h][k] =
+// softmax_k(scale q_{b,h,0} . k_{b,h,k}), fp32, read from the qkv planes the attention launch of the same block has just consumed.  0.1 GFLOP
+// at 256 tiles: no MFMA, no LDS, no barrier.  One wavefront per (tile, head); eight lanes share a key, each with 16 bytes of its row, so one
+// load instruction of the wave reads eight whole 128-byte key rows; the eight partial dot products (fp32 FMAs) meet in three shuffles.
+// Up to 8 NREG keys the log2-domain scores stay in registers (NREG > 0).  Beyond that (NREG == 0) the first lane of a key's eight parks its
+// scores in `out` and reads its own words back for the exponentials and again for the normalisation: program order of one lane, no fence.
+// A key index past the end reads the last row again (a valid address) and its score is replaced by -inf.
+template <bool SPLIT>
+__device__ __forceinline__ void cls_probs_load8(const f16* __restrict__ hi, const f16* __restrict__ lo, int64_t off, float (&v)[8]) {
+    const f16x8 a = *reinterpret_cast<const f16x8*>(hi + off);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = (float)a[i];
+    if (SPLIT) {
+        const f16x8 c = *reinterpret_cast<const f16x8*>(lo + off);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] += (float)c[i];
+    }
+}
+
+template <bool SPLIT, int NREG>
+__global__ __launch_bounds__(256)
+void attention_cls_probs_kernel(const f16* __restrict__ qkv_hi, const f16* __restrict__ qkv_lo, int batch, int ntok, int heads, float sc2,
+                                float* __restrict__ out) {
+    const int lane = threadIdx.x & 63, part = lane & 7, slot = lane >> 3;
+    const int pair = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (pair >= batch * heads) return;                      // the whole wave
+    const int b = pair / heads, h = pair - b * heads;
+    const int64_t ld = (int64_t)3 * heads * HD;
+    const int64_t qoff = (int64_t)b * ntok * ld + h * HD + part * 8;      // this lane's eight features of the CLS query ...
+    const int64_t koff = qoff + (int64_t)heads * HD;                       // ... and of key 0
+    float* __restrict__ o = out + (int64_t)pair * ntok;
+    float q[8];
+    cls_probs_load8<SPLIT>(qkv_hi, qkv_lo, qoff, q);
+    auto score = [&](int k) {                               // log2-domain score of key k in all eight lanes of its group; -inf past the end
+        float kv[8];
+        cls_probs_load8<SPLIT>(qkv_hi, qkv_lo, koff + (int64_t)(k < ntok ? k : ntok - 1) * ld, kv);
+        float acc = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc = fmaf(q[i], kv[i], acc);
+        acc += __shfl_xor(acc, 1);
+        acc += __shfl_xor(acc, 2);
+        acc += __shfl_xor(acc, 4);
+        return k < ntok ? acc * sc2 : -INFINITY;
+    };
+    float m = -INFINITY, l = 0.f;
+    if constexpr (NREG > 0) {
+        float s[NREG];
+#pragma unroll
+        for (int j = 0; j < NREG; ++j) {
+            s[j] = score(j * 8 + slot);
+            m = fmaxf(m, s[j]);
+        }
+        m = wave_max(m);                                    // finite: key 0 exists
+#pragma unroll
+        for (int j = 0; j < NREG; ++j) {
+            s[j] = __builtin_amdgcn_exp2f(s[j] - m);        // 0 past the end
+            l += part == 0 ? s[j] : 0.f;                    // every key once
+        }
+        const float inv = 1.f / wave_sum(l);
+#pragma unroll
+        for (int j = 0; j < NREG; ++j) {
+            const int k = j * 8 + slot;
+            if (part == 0 && k < ntok) o[k] = s[j] * inv;
+        }
+    } else {
+        for (int k0 = 0; k0 < ntok; k0 += 8) {
+            const int k = k0 + slot;
+            const float sk = score(k);
+            m = fmaxf(m, sk);
+            if (part == 0 && k < ntok) o[k] = sk;
+        }
+        m = wave_max(m);
+        if (part == 0)
+            for (int k = slot; k < ntok; k += 8) {
+                const float p = __builtin_amdgcn_exp2f(o[k] - m);
+                o[k] = p;
+                l += p;
+            }
+        const float inv = 1.f / wave_sum(l);
+        if (part == 0)
+            for (int k = slot; k < ntok; k += 8) o[k] *= inv;
+    }
+}
+constexpr int CLS_PROBS_NREG = 32;         // scores in registers up to 256 keys (the 197 of a 224 x 224 tile)
+
 }  // namespace keepk
 
 int launch_attention(const AttnParams& p_in, hipStream_t s) {
@@ -789,4 +875,22 @@ int launch_attention_long(const AttnParams& p_in, hipStream_t s) {
     const int nq = (p.q_rows > 0 && p.q_rows < p.ntok) ? p.q_rows : p.ntok;
     const int qblocks = (nq + ATL_QB - 1) / ATL_QB;
     return p.split ? launch_long<true>(p, qblocks, s) : launch_long<false>(p, qblocks, s);
+}
+
+int launch_attention_cls_probs(const f16* qkv_hi, const f16* qkv_lo, int batch, int ntok, int heads, float scale, float* out, hipStream_t s) {
+    using namespace keepk;
+    if (!qkv_hi || !out || batch < 1 || ntok < 1 || heads < 1) return -1;
+    if ((int64_t)batch * heads > (1ll << 30) || (int64_t)ntok * 3 * heads * HD >= (1ll << 31)) return -1;     // int pair index; qkv rows of one tile as in launch_attention
+    const int pairs = batch * heads;
+    const float sc2 = scale * 1.4426950408889634f;
+    const dim3 grid((pairs + 3) / 4), block(256);
+    const bool reg = ntok <= 8 * CLS_PROBS_NREG;
+    if (qkv_lo) {
+        if (reg) hipLaunchKernelGGL((attention_cls_probs_kernel<true, CLS_PROBS_NREG>), grid, block, 0, s, qkv_hi, qkv_lo, batch, ntok, heads, sc2, out);
+        else hipLaunchKernelGGL((attention_cls_probs_kernel<true, 0>), grid, block, 0, s, qkv_hi, qkv_lo, batch, ntok, heads, sc2, out);
+    } else {
+        if (reg) hipLaunchKernelGGL((attention_cls_probs_kernel<false, CLS_PROBS_NREG>), grid, block, 0, s, qkv_hi, qkv_lo, batch, ntok, heads, sc2, out);
+        else hipLaunchKernelGGL((attention_cls_probs_kernel<false, 0>), grid, block, 0, s, qkv_hi, qkv_lo, batch, ntok, heads, sc2, out);
+    }
+    return 0;
 }

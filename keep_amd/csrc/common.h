@@ -175,6 +175,10 @@ int launch_attention(const AttnParams& p, hipStream_t s);   // returns 0 or -1 (
 // (part_ws is not used).  A separate entry point: launch_attention's own dispatch is unchanged.  Returns 0 or -1.
 int launch_attention_long(const AttnParams& p, hipStream_t s);
 constexpr int ATT_PART_FLOATS = 66;       // 64 output features + maximum + sum
+// The CLS query's attention probabilities of one block: out fp32 [batch][heads][ntok] = softmax_k(scale q_{b,h,0} . k_{b,h,k}) from the
+// row-major qkv planes above (qkv_lo null: the hi plane alone; else every operand value is hi + lo), fp32 products and sums on the VALU.  Any ntok >= 1;
+// no LDS, no scratch, no atomics.  Returns 0 or -1.
+int launch_attention_cls_probs(const f16* qkv_hi, const f16* qkv_lo, int batch, int ntok, int heads, float scale, float* out, hipStream_t s);
 
 // LayerNorm over rows of D in {768,1024}; fp32 in, fp16 (hi[,lo]) and/or fp32 out.
 struct LnParams {
@@ -306,6 +310,11 @@ constexpr int64_t HEAT_MAX_PATCH = (int64_t)1 << 30;
 // adds every tile's footprint into acc (integer atomics; the caller zeroes acc when it starts a raster)
 void launch_heat_accumulate(const int64_t* coords, const float* values, int64_t n, int64_t patch, int64_t d, int h, int w, int64_t ox,
                             int64_t oy, int64_t* acc, hipStream_t s);
+// the same with one value per cell of every tile's gh x gw grid: values fp32 [n][gh gw], row-major (y, x); patch % gw == 0, patch % gh == 0 and
+// d <= min(patch / gw, patch / gh) are the caller's to check
+constexpr int64_t HEAT_MAX_CELLS = (int64_t)1 << 24;      // cells per tile
+void launch_heat_accumulate_cells(const int64_t* coords, const float* values, int64_t n, int gh, int gw, int64_t patch, int64_t d, int h, int w,
+                                  int64_t ox, int64_t oy, int64_t* acc, hipStream_t s);
 // any of mean / count / pred may be null
 void launch_heat_mean(const int64_t* acc, int h, int w, float uncovered, float* mean, int* count, unsigned char* pred, hipStream_t s);
 // thumb null: the constant bg (R | G << 8 | B << 16); mask null: every pixel

@@ -200,6 +200,7 @@ struct VitLane {
     const float* pos = nullptr;                           // position table of that grid, [ntok][D] (vit_pos_table)
     bool xn_ready = false;                                // the previous block's fc2 already wrote this block's LayerNorm-1 output
     bool c_resid_live = false;                            // ws.c_resid holds the CLS rows of ws.resid as they are NOW (left there by the previous block's CLS-row chain): no gather
+    int tap_block = -1; float* tap_out = nullptr;         // keep_encode_image_attn: the block whose CLS-row attention probabilities go to tap_out, this lane's [Bc][heads][ntok]
 };
 
 int vit_begin(keep_handle* h, VitLane& L) {
@@ -279,6 +280,8 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
         // beyond 512 tokens (grids past 22 x 22 patches) the key-blocked kernel; up to 512 the whole-sequence kernels of the 224 path
         if ((ntok > 512 ? launch_attention_long(a, s) : launch_attention(a, s))) return h->fail(KEEP_EUNSUPPORTED, "attention launch failed (%d tokens)", ntok);
     }
+    if (i == L.tap_block && launch_attention_cls_probs(ws.qkv_hi, sp ? ws.qkv_lo : nullptr, Bc, ntok, h->vit_heads, 0.125f, L.tap_out, s))
+        return h->fail(KEEP_EUNSUPPORTED, "CLS attention map launch failed (%d tokens)", ntok);
     const int Mr = cls_only ? Bc : M;
     float* resid = cls_only ? ws.c_resid : ws.resid;
     const f16 *att_hi = ws.att_hi, *att_lo = ws.att_lo;
@@ -568,7 +571,9 @@ int vit_pos_table(keep_handle* h, int gh, int gw, const float** out) {
 }
 
 // the image tower on B tiles of a gh x gw patch grid (arguments checked, device selected by the caller)
-int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, float* out, hipStream_t s, int gh = 14, int gw = 14) {
+// tap_out: fp32 [B][heads][ntok], the CLS-row attention probabilities of block tap_block (keep_encode_image_attn); such a call is never captured or replayed
+int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, float* out, hipStream_t s, int gh = 14, int gw = 14,
+                     int tap_block = -1, float* tap_out = nullptr) {
     const int ntok = gh * gw + 1;
     const bool g14 = gh == 14 && gw == 14;
     const float* pos = nullptr;
@@ -576,7 +581,7 @@ int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t 
     if (rc) return rc;
     const size_t px = pix_dtype == KEEP_PIX_F32 ? 4 : (pix_dtype == KEEP_PIX_U8_HWC ? 1 : 2);    // bytes per value; 3 * 16 gh * 16 gw values per tile in every layout
     const size_t tile_vals = (size_t)3 * (gh * 16) * (gw * 16);
-    const bool graph = h->use_graphs && !h->prof_mode && B * ntok <= SKINNY_MAX_M && B <= h->max_tiles;
+    const bool graph = h->use_graphs && !h->prof_mode && B * ntok <= SKINNY_MAX_M && B <= h->max_tiles && !tap_out;
     const VitPlan plan = vit_plan(h, B, ntok, tile_vals * px, graph);
     rc = ensure_arena(h, plan.total);
     if (rc) return rc;
@@ -625,6 +630,7 @@ int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t 
             x.out = out + lo * h->proj_dim;
             x.s = lanes > 1 ? h->aux[l] : s;
             x.gh = gh; x.gw = gw; x.ntok = ntok; x.pos = pos;
+            if (tap_out) { x.tap_block = tap_block; x.tap_out = tap_out + lo * h->vit_heads * ntok; }
             x.ws = carve_vit(h, h->arena + (size_t)l * plan.lane_bytes, x.Bc, plan.split, ntok);
         }
         for (int l = 0; l < nl; ++l) if ((rc = vit_begin(h, L[l]))) return rc;
@@ -859,6 +865,25 @@ int keep_encode_image_hw(keep_handle* h, const void* pixels, int pix_dtype, int6
     const int prec = h->precision;
     if (!(gh == 14 && gw == 14) && !h->grid_keeps_plan((int)(gh * gw + 1)) && prec == KEEP_PREC_COMP) h->precision = KEEP_PREC_STRICT;
     const int rc = encode_image_run(h, pixels, pix_dtype, B, out, (hipStream_t)stream, (int)gh, (int)gw);
+    h->precision = prec;
+    return rc;
+}
+
+int keep_encode_image_attn(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, int64_t H, int64_t W, int block, float* out,
+                           float* attn_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!h->finalized || !h->vit_depth) return h->fail(KEEP_ESTATE, "image tower not loaded / finalised");
+    if (!pixels || !out || !attn_out || B < 0) return h->fail(KEEP_EINVAL, "null pointer or negative batch");
+    if (pix_dtype < KEEP_PIX_F32 || pix_dtype > KEEP_PIX_U8_HWC) return h->fail(KEEP_EINVAL, "pixel dtype %d", pix_dtype);
+    if (H < 16 || W < 16 || H % 16 || W % 16) return h->fail(KEEP_EINVAL, "image size %lldx%lld: H and W must be positive multiples of 16", (long long)H, (long long)W);
+    if (block < -h->vit_depth || block >= h->vit_depth) return h->fail(KEEP_EINVAL, "block %d outside [-%d, %d)", block, h->vit_depth, h->vit_depth);
+    const int64_t gh = H / 16, gw = W / 16;
+    if (gh * gw + 1 > 65536) return h->fail(KEEP_EUNSUPPORTED, "image size %lldx%lld: more than 65536 patches", (long long)H, (long long)W);
+    if (B == 0) return KEEP_OK;
+    KEEP_ON_DEVICE(h);
+    const int prec = h->precision;                       // the grid rule of keep_encode_image_hw
+    if (!(gh == 14 && gw == 14) && !h->grid_keeps_plan((int)(gh * gw + 1)) && prec == KEEP_PREC_COMP) h->precision = KEEP_PREC_STRICT;
+    const int rc = encode_image_run(h, pixels, pix_dtype, B, out, (hipStream_t)stream, (int)gh, (int)gw, block < 0 ? block + h->vit_depth : block, attn_out);
     h->precision = prec;
     return rc;
 }

@@ -63,6 +63,48 @@ void heat_accumulate_kernel(const int64_t* __restrict__ coords, const float* __r
     }
 }
 
+// Token-cell values of the tiles (keep_heat_accumulate_cells): the footprint and the walk over it are heat_accumulate's, one wave per
+// tile; what a pixel adds is no longer the tile's one value but that of the cell of the tile's gh x gw grid (cells of cw x ch level-0 units) under the
+// pixel's upper-left corner, clamped into the grid: a footprint pixel may start up to d - 1 units before the tile.  Still ONE add of (1 << 40) | q per
+// (tile, pixel), so the count field counts tiles; a NaN cell adds nothing to its pixels.  rel = X d - x lies in (-d, P): 32 bits (P <= 2^30, d <= cw).
+__global__ __launch_bounds__(256)
+void heat_accumulate_cells_kernel(const int64_t* __restrict__ coords, const float* __restrict__ values, int64_t n, int gh, int gw, int cw, int ch,
+                                  int64_t P, int64_t d, int h, int w, int64_t ox, int64_t oy, heat_acc_t* __restrict__ acc) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < n; t += nwaves) {
+        const int64_t x = (int64_t)((uint64_t)coords[2 * t] - (uint64_t)ox), y = (int64_t)((uint64_t)coords[2 * t + 1] - (uint64_t)oy);
+        const int64_t x0 = heat_floor_div(x, d), x1 = heat_floor_div((int64_t)((uint64_t)x + (uint64_t)P), d);
+        const int64_t y0 = heat_floor_div(y, d), y1 = heat_floor_div((int64_t)((uint64_t)y + (uint64_t)P), d);
+        const int64_t c0 = x0 > 0 ? x0 : 0, c1 = x1 < w ? x1 : w, r0 = y0 > 0 ? y0 : 0, r1 = y1 < h ? y1 : h;
+        if (c1 <= c0 || r1 <= r0) continue;           // off the raster, or empty
+        const int fw = (int)(c1 - c0), fh = (int)(r1 - r0);
+        const int64_t npx = (int64_t)fw * fh;
+        const int dr = 64 / fw, dc = 64 - dr * fw;
+        int r = lane / fw, c = lane - r * fw;
+        const int relx0 = (int)(c0 * d - x), rely0 = (int)(r0 * d - y), di = (int)d;     // of footprint pixel (0, 0); > -d
+        const float* __restrict__ cells = values + t * ((int64_t)gh * gw);
+        heat_acc_t* base = acc + (r0 * (int64_t)w + c0);
+        for (int64_t i = lane; i < npx; i += 64) {    // i < npx <=> r < fh, and c < fw always: inside the clipped footprint
+            const int rx = relx0 + c * di, ry = rely0 + r * di;
+            const int cx = rx < 0 ? 0 : min(rx / cw, gw - 1), cy = ry < 0 ? 0 : min(ry / ch, gh - 1);
+            const float v = cells[cy * gw + cx];
+            if (v == v) {
+                const int q = __float2int_rn(fminf(fmaxf(v, 0.f), 1.f) * 65535.f);
+                (void)__hip_atomic_fetch_add(base + ((int64_t)r * w + c), ((heat_acc_t)1 << HEAT_COUNT_SHIFT) | (heat_acc_t)q, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT);
+            }
+            c += dc;
+            r += dr;
+            if (c >= fw) {
+                c -= fw;
+                ++r;
+            }
+        }
+    }
+}
+
 __device__ __forceinline__ void heat_mean_one(heat_acc_t a, float uncovered, float& mean, int& count, unsigned char& pred) {
     const heat_acc_t s = a & HEAT_SUM_MASK, c = a >> HEAT_COUNT_SHIFT;
     count = (int)c;
@@ -371,6 +413,13 @@ void launch_heat_accumulate(const int64_t* coords, const float* values, int64_t 
     if (n < 1) return;
     hipLaunchKernelGGL(heat_accumulate_kernel, dim3(heat_grid_for(n, 4)), dim3(256), 0, s, coords, values, n, patch, d, h, w, ox, oy,
                        (heat_acc_t*)acc);
+}
+
+void launch_heat_accumulate_cells(const int64_t* coords, const float* values, int64_t n, int gh, int gw, int64_t patch, int64_t d, int h, int w,
+                                  int64_t ox, int64_t oy, int64_t* acc, hipStream_t s) {
+    if (n < 1) return;
+    hipLaunchKernelGGL(heat_accumulate_cells_kernel, dim3(heat_grid_for(n, 4)), dim3(256), 0, s, coords, values, n, gh, gw, (int)(patch / gw),
+                       (int)(patch / gh), patch, d, h, w, ox, oy, (heat_acc_t*)acc);
 }
 
 void launch_heat_mean(const int64_t* acc, int h, int w, float uncovered, float* mean, int* count, unsigned char* pred, hipStream_t s) {

@@ -262,6 +262,22 @@ int keep_op_attention_long(keep_handle* h, const float* qkv, int64_t B, int64_t 
     return rc == ATTN_REFUSED ? h->fail(KEEP_EUNSUPPORTED, "long attention: B %lld, T %lld, heads %d unsupported", (long long)B, (long long)T, heads) : rc;
 }
 
+int keep_op_attention_cls_probs(keep_handle* h, const float* qkv, int64_t B, int64_t T, int heads, int split, float* out, void* stream) {
+    if (!h || !qkv || !out || B < 1 || T < 1 || heads < 1) return h ? h->fail(KEEP_EINVAL, "bad attention arguments") : KEEP_EINVAL;
+    if (B > INT32_MAX || T > INT32_MAX || B * T > INT32_MAX) return h->fail(KEEP_EINVAL, "attention_cls_probs: B %lld, T %lld", (long long)B, (long long)T);
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = B * T * 3 * heads * 64;
+    Tmp t;
+    f16* q_hi = t.get<f16>(n); f16* q_lo = t.get<f16>(n);
+    if (!t.ok) return h->fail(KEEP_ENOMEM, "temp alloc");
+    launch_split_f16(qkv, q_hi, q_lo, n, s);           // the planes as keep_op_attention makes them
+    if (launch_attention_cls_probs(q_hi, split ? q_lo : nullptr, (int)B, (int)T, heads, 0.125f, out, s))
+        return h->fail(KEEP_EUNSUPPORTED, "attention_cls_probs: B %lld, T %lld, heads %d unsupported", (long long)B, (long long)T, heads);
+    HIPCHK(h, hipStreamSynchronize(s));
+    return check_launch(h, "op_attention_cls_probs");
+}
+
 // Matrix-pipe ceiling probe (keep_mfma_probe): no memory traffic inside the loop; every wave holds 2 A and 4 B fragments of the caller's data in registers and
 // issues 8 independent v_mfma_f32_32x32x16_f16 per iteration (all (i, j) pairs: the pipe's inputs change with every instruction); one 8-wave workgroup per CU,
 // two waves per SIMD, as the GEMM kernels run.

@@ -197,6 +197,33 @@ int keep_heat_accumulate(keep_handle* h, const int64_t* coords, const float* val
     return check_launch(h, "heat_accumulate");
 }
 
+int keep_heat_accumulate_cells(keep_handle* h, const int64_t* coords, const float* values, int64_t N, int64_t gh, int64_t gw, int64_t patch,
+                               int64_t downsample, int64_t H, int64_t W, int64_t origin_x, int64_t origin_y, int zero_first, int64_t* acc,
+                               void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "heat_accumulate_cells: acc is null or not 8-byte aligned");
+    if (N < 0 || N > HEAT_MAX_TILES) return h->fail(KEEP_EINVAL, "heat_accumulate_cells: %lld tiles (0 .. 2^24 - 1)", (long long)N);
+    if (N > 0 && (!coords || !values)) return h->fail(KEEP_EINVAL, "heat_accumulate_cells: null coords or values");
+    if (!pixels_ok(H, W, HEAT_MAX_PIXELS))
+        return h->fail(KEEP_EINVAL, "heat_accumulate_cells: %lldx%lld: raster shape (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (patch < 1 || patch > HEAT_MAX_PATCH) return h->fail(KEEP_EINVAL, "heat_accumulate_cells: patch %lld outside [1, 2^30]", (long long)patch);
+    if (gh < 1 || gw < 1 || gh > patch || gw > patch || gh * gw > HEAT_MAX_CELLS || patch % gw || patch % gh)
+        return h->fail(KEEP_EINVAL, "heat_accumulate_cells: grid %lldx%lld: both sides must divide patch %lld (and gh gw <= 2^24)", (long long)gh,
+                       (long long)gw, (long long)patch);
+    const int64_t cmin = std::min(patch / gw, patch / gh);
+    if (downsample < 1 || downsample > cmin)
+        return h->fail(KEEP_EINVAL, "heat_accumulate_cells: downsample %lld outside [1, cell side = %lld]", (long long)downsample, (long long)cmin);
+    if (int rc = origin_check(h, "heat_accumulate_cells", origin_x, origin_y)) return rc;
+    if (origin_x % downsample || origin_y % downsample)
+        return h->fail(KEEP_EINVAL, "heat_accumulate_cells: origin (%lld, %lld) is not a multiple of downsample %lld", (long long)origin_x,
+                       (long long)origin_y, (long long)downsample);
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (zero_first) HIPCHK(h, hipMemsetAsync(acc, 0, (size_t)(H * W) * sizeof(int64_t), s));
+    launch_heat_accumulate_cells(coords, values, N, (int)gh, (int)gw, patch, downsample, (int)H, (int)W, origin_x, origin_y, acc, s);
+    return check_launch(h, "heat_accumulate_cells");
+}
+
 int keep_heat_mean(keep_handle* h, const int64_t* acc, int64_t H, int64_t W, float uncovered, float* mean_out, int32_t* count_out,
                    unsigned char* pred_out, void* stream) {
     if (!h) return KEEP_EINVAL;

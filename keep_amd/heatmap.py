@@ -12,7 +12,8 @@ The device kernels (``csrc/heatmap.hip``) equal the numpy restatements below exa
 a raster is the same however its tiles are split over calls.
 
 This module holds the host side: argument checks (ValueError before any device call), :class:`TileRaster`, the colour tables and
-the restatements ``raster_numpy`` / ``mean_numpy`` / ``pred_numpy`` / ``render_numpy``.
+the restatements ``raster_numpy`` / ``mean_numpy`` / ``pred_numpy`` / ``render_numpy``; ``cell_raster_numpy`` restates the token-cell
+raster of ``KEEPModel.cell_raster``.
 
 The two display steps of CLAM's heatmaps follow below: rank percentiles of the tile values
 (``KEEPModel.score_reference`` / ``percentiles``, :class:`ScoreReference`; ``sort_numpy`` / ``rank_numpy`` / ``percentiles_numpy``) and a
@@ -73,6 +74,36 @@ def check_tiles(coords, values) -> int:
     if not (vd.is_floating_point if isinstance(vd, torch.dtype) else vd.kind == "f"):
         raise ValueError(f"values must be floating point, got {vd}")
     return int(cs[0])
+
+
+MAX_CELLS = 1 << 24                            # cells per tile of a cell raster
+
+
+def check_cell_args(grid, patch, downsample, shape, origin=(0, 0)):
+    """The geometry of a cell raster (``KEEPModel.cell_raster``) on the host -> ((gh, gw), patch, downsample, (h, w), (ox, oy)):
+    :func:`check_raster_args`, a grid whose sides divide the patch, and a raster pixel no larger than a cell."""
+    if len(grid) != 2:
+        raise ValueError(f"grid must be (gh, gw), got {grid!r}")
+    gh, gw = _integer(grid[0], "grid[0]"), _integer(grid[1], "grid[1]")
+    patch = _integer(patch, "patch_size")
+    if gh < 1 or gw < 1 or gh * gw > MAX_CELLS:
+        raise ValueError(f"grid {(gh, gw)}: need gh, gw >= 1 and gh * gw <= 2^24")
+    if patch < 1 or patch % gw or patch % gh:
+        raise ValueError(f"patch_size {patch} must be a multiple of both sides of the grid {(gh, gw)}: cells are whole level-0 pixels")
+    cmin = min(patch // gw, patch // gh)
+    d = _integer(downsample, "downsample")
+    if d < 1 or d > cmin:
+        raise ValueError(f"downsample must lie in [1, cell side = {cmin}] (patch_size {patch}, grid {(gh, gw)}), got {d}")
+    patch, d, shape, origin = check_raster_args(patch, d, shape, origin)
+    return (gh, gw), patch, d, shape, origin
+
+
+def check_cells(coords, values, grid) -> int:
+    """Shapes of one call's tiles with cell values: coords [N,2] of an integer type, values [N, gh gw] of a floating type -> N."""
+    cs, vs = tuple(coords.shape), tuple(values.shape)
+    if len(vs) != 2 or vs[1] != grid[0] * grid[1]:
+        raise ValueError(f"cell values must be [N, gh gw = {grid[0] * grid[1]}], got {vs}")
+    return check_tiles(coords, values[:, 0])
 
 
 def quantize(value) -> int:
@@ -219,6 +250,31 @@ def raster_numpy(coords, values, patch: int, downsample: int, shape, origin=(0, 
     for n in np.nonzero(~skip & (fp[:, 1] > fp[:, 0]) & (fp[:, 3] > fp[:, 2]))[0]:
         c0, c1, r0, r1 = fp[n]
         acc[r0:r1, c0:c1] += np.uint64((1 << COUNT_SHIFT) | int(q[n]))
+    return into
+
+
+def cell_raster_numpy(coords, values, grid, patch: int, downsample: int, shape, origin=(0, 0), into: Optional[np.ndarray] = None) -> np.ndarray:
+    """``KEEPModel.cell_raster`` restated on the host -> the accumulator, int64 [h,w]; ``into`` adds to an earlier one (in place).  A tile's
+    footprint is :func:`footprints_numpy`'s; pixel (X, Y) of it takes cell ``(clip((Y d - y) // ch, 0, gh - 1), clip((X d - x) // cw, 0, gw - 1))``
+    with (x, y) the tile's corner relative to the origin, and adds ``(1 << 40) | q`` of that cell unless the cell is NaN."""
+    (gh, gw), patch, d, (h, w), origin = check_cell_args(grid, patch, downsample, shape, origin)
+    coords, values = np.asarray(coords), np.asarray(values)
+    check_cells(coords, values, (gh, gw))
+    if into is None:
+        into = np.zeros((h, w), np.int64)
+    elif into.dtype != np.int64 or into.shape != (h, w):
+        raise ValueError(f"into must be int64 {(h, w)}, got {into.dtype} {into.shape}")
+    acc = into.view(np.uint64)
+    q, skip = quantize_numpy(values)
+    add = np.where(skip, 0, (1 << COUNT_SHIFT) | q).astype(np.uint64).reshape(-1, gh, gw)
+    fp = footprints_numpy(coords, patch, d, (h, w), origin)
+    c = coords.astype(np.int64).reshape(-1, 2)
+    cw, ch = patch // gw, patch // gh
+    for n in np.nonzero((fp[:, 1] > fp[:, 0]) & (fp[:, 3] > fp[:, 2]))[0]:
+        c0, c1, r0, r1 = fp[n]
+        cx = np.clip((np.arange(c0, c1) * d - (c[n, 0] - origin[0])) // cw, 0, gw - 1)
+        cy = np.clip((np.arange(r0, r1) * d - (c[n, 1] - origin[1])) // ch, 0, gh - 1)
+        acc[r0:r1, c0:c1] += add[n][cy[:, None], cx[None, :]]
     return into
 
 

@@ -874,6 +874,54 @@ class KEEPModel(SlideOps):
             return lib.keep_encode_image(self._handle, _ptr(xd), pix, xd.shape[0], _ptr(out), _stream(self._device))
         return lib.keep_encode_image_hw(self._handle, _ptr(xd), pix, xd.shape[0], H, W, _ptr(out), _stream(self._device))
 
+    def _encode_tapped(self, xd: torch.Tensor, pix: int, H: int, W: int, block: int, what: str) -> Tuple[torch.Tensor, torch.Tensor]:
+        """keep_encode_image_attn on device tiles -> (features [B,768], attn [B, heads, T]) on the device."""
+        self._check_block(block)
+        B, heads, T = int(xd.shape[0]), self.config.vision.num_heads, (H // 16) * (W // 16) + 1
+        out = torch.empty((B, self.config.projection_dim), dtype=torch.float32, device=self._device)
+        attn = torch.empty((B, heads, T), dtype=torch.float32, device=self._device)
+        rc = _lib.load().keep_encode_image_attn(self._handle, _ptr(xd), pix, B, H, W, block, _ptr(out), _ptr(attn), _stream(self._device))
+        _lib.check(self._handle, rc, what)
+        self._queue_flag_check(_stream(self._device))
+        return out, attn
+
+    @torch.no_grad()
+    def encode_image_attention(self, image_inputs: torch.Tensor, block: int = -1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """:meth:`encode_image` with the CLS query's attention of one block beside it -> (features [B,768],
+        attn fp32 [B, heads, T]), T = H/16 * W/16 + 1.  ``attn[b, h]`` is the softmax over the keys of ``q_{b,h,0} . k_{b,h,k} / 8`` in
+        block ``block`` (``0 .. depth - 1``, negative from the end; ValueError outside): column 0 is CLS -> CLS, columns 1.. the patch
+        tokens in row-major (y, x) order, each row sums to 1.  ``keep_amd.attention.cls_attention_map`` turns it into the per-tile map
+        that is usually shown, ``keep_amd.wsi.attention_heatmap`` puts it on the slide raster.  Inputs and device handling as
+        :meth:`encode_image`.  The features equal :meth:`encode_image`'s with option ``graphs`` = 0 bit for bit: a tapped call is never
+        replayed as a graph, so small batches cost their launches."""
+        self._ready()
+        x = image_inputs
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"expected [B,3,H,W], got {tuple(x.shape)}")
+        H, W = int(x.shape[2]), int(x.shape[3])
+        self._check_hw(H, W, f"[B,3,H,W] = {tuple(x.shape)}")
+        if x.dtype not in _PIX:
+            x = x.to(torch.float32)
+        src_dev = x.device
+        if x.shape[0] == 0:
+            self._check_block(block)
+            return (torch.empty((0, self.config.projection_dim), dtype=torch.float32, device=src_dev),
+                    torch.empty((0, self.config.vision.num_heads, (H // 16) * (W // 16) + 1), dtype=torch.float32, device=src_dev))
+        xd = x.to(self._device, non_blocking=True).contiguous()
+        out, attn = self._encode_tapped(xd, _PIX[xd.dtype], H, W, block, "encode_image_attention")
+        if src_dev == self._device:
+            return out, attn
+        res = out.to(src_dev), attn.to(src_dev)
+        self.check_errors(wait=True)
+        return res
+
+    def _check_block(self, block) -> int:
+        """The rule keep_encode_image_attn applies, as a ValueError before any device work (and for calls without tiles)."""
+        depth = int(_lib.load().keep_vit_depth(self._handle))
+        if isinstance(block, bool) or not isinstance(block, int) or not -depth <= block < depth:
+            raise ValueError(f"block {block!r} outside [-{depth}, {depth})")
+        return block % depth
+
     @torch.no_grad()
     def encode_image_uint8(self, tiles_u8: torch.Tensor) -> torch.Tensor:
         """Raw RGB tiles, uint8 [B,224,224,3] (HWC, after the resize + centre crop of the reference transform):

@@ -136,6 +136,15 @@ class Ops:
         _lib.check(self._h, rc, "op_attention_long")
         return out
 
+    def attention_cls_probs(self, qkv, B, T, heads, split=False):
+        """The CLS query's attention probabilities, fp32 [B, heads, T]: softmax over the keys of q_{b,h,0} . k_{b,h,k} / 8 on the fp16 planes
+        of qkv (split: hi + lo), fp32 products and sums; any T >= 1."""
+        qkv = self._f(qkv)
+        out = torch.empty((B, heads, T), dtype=torch.float32, device=self.device)
+        rc = _lib.load().keep_op_attention_cls_probs(self._h, _ptr(qkv), B, T, heads, int(split), _ptr(out), _stream(self.device))
+        _lib.check(self._h, rc, "op_attention_cls_probs")
+        return out
+
     def layernorm(self, x, gamma, beta, eps, add=None):
         x, gamma, beta, add = map(self._f, (x, gamma, beta, add))
         out = torch.empty_like(x)

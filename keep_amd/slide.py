@@ -14,8 +14,8 @@ from . import _lib
 from .annotation import PolygonSet, check_fill_args, check_into, check_tile_args, polygon_arrays
 from .components import NCOLS as REGION_COLS, RegionTable, check_raster, check_region_count, check_regions_args, mask_tensor
 from .evaluation import HIST_BINS, MaskOverlap, RocResult, check_mask, check_roc_args, check_same_geometry, plan_label_bands, sweep_from_hist
-from .heatmap import (MAX_TILES, ScoreReference, TileRaster, check_raster_args, check_tiles, check_values, colormap as colormap_table, render_args,
-                      smooth_taps)
+from .heatmap import (MAX_TILES, ScoreReference, TileRaster, check_cell_args, check_cells, check_raster_args, check_tiles, check_values,
+                      colormap as colormap_table, render_args, smooth_taps)
 from .heatmap import Q_ONE
 from .lesion import (MAX_LABELS, EvaluationMask, LesionCandidates, LesionHits, check_candidates, check_direction, check_peak_args, check_peak_count,
                      check_radius, distance_threshold)
@@ -48,7 +48,8 @@ def _check_tissue(tissue, raster) -> None:
 
 class SlideOps:
     """Base of ``KEEPModel``, which supplies what these methods use of the engine: ``_handle``, ``_device``, ``_ready()``,
-    ``_ready_device()``, ``_queue_flag_check()``, ``encode_image_uint8()``, ``config`` and ``_heat_luts``."""
+    ``_ready_device()``, ``_queue_flag_check()``, ``encode_image_uint8()``, ``_encode_tapped()``, ``_check_block()``, ``config`` and
+    ``_heat_luts``."""
 
     def _call(self, name: str, *args) -> None:
         """``keep_<name>(handle, *args, current stream)``; a failure raises with the library's message, labelled ``name``."""
@@ -164,24 +165,52 @@ class SlideOps:
         c = coords if isinstance(coords, torch.Tensor) else torch.as_tensor(coords)
         v = values if isinstance(values, torch.Tensor) else torch.as_tensor(values)
         N = check_tiles(c, v)
+        into, zero = self._raster_into(N, patch, d, (h, w), origin, into)
+        c = c.to(self._device, torch.int64).contiguous()
+        v = v.to(self._device, torch.float32).contiguous()
+        self._call("heat_accumulate", _ptr(c), _ptr(v), N, patch, d, h, w, origin[0], origin[1], zero, _ptr(into.acc))
+        return into
+
+    def _raster_into(self, N: int, patch: int, d: int, shape, origin, into):
+        """The raster N more tiles go into -> (raster, zero_first): ``into`` after its geometry and device checks with the tiles claimed
+        (ValueError beyond the cap, before any device work), or a new one."""
         if into is not None:
             if not isinstance(into, TileRaster):
                 raise ValueError(f"into must be a TileRaster, got {type(into).__name__}")
-            into.check_geometry(patch, d, (h, w), origin)
+            into.check_geometry(patch, d, shape, origin)
             into.claim(N)                                           # raises beyond the cap, before any device work
         elif N > MAX_TILES:
             raise ValueError(f"a raster takes at most 2^24 - 1 = {MAX_TILES} tiles in all, got {N}")
         self._ready_device()
         if into is None:
-            into, zero = TileRaster(torch.empty((h, w), dtype=torch.int64, device=self._device), d, patch, origin, N, self), 1
-        elif into.acc.device != self._device:
+            return TileRaster(torch.empty(shape, dtype=torch.int64, device=self._device), d, patch, origin, N, self), 1
+        if into.acc.device != self._device:
             into.tiles -= N
             raise ValueError(f"into= raster lives on {into.acc.device}, this engine on {self._device}")
-        else:
-            zero = 0
+        return into, 0
+
+    @torch.no_grad()
+    def cell_raster(self, coords, cell_values, grid, patch_size: int, downsample: int, shape, origin=(0, 0), into=None):
+        """Values on a grid of cells inside every tile rasterised in slide geometry -> ``TileRaster``: the
+        token-level counterpart of :meth:`tile_raster`, made for the maps of ``keep_amd.attention.cls_attention_map``.
+
+        ``coords``: integers [N,2] as in :meth:`tile_raster`; ``cell_values``: floating point [N, gh gw], row-major (y, x) over the
+        ``grid = (gh, gw)`` cells of a tile, each ``patch_size / gw`` x ``patch_size / gh`` level-0 units (both divisions exact);
+        ``1 <= downsample <= min(cell width, cell height)``.  A tile covers exactly the pixels it covers in :meth:`tile_raster`; pixel
+        (X, Y) of them takes the cell ``cx = clamp((X d + ox - x) // cw, 0, gw - 1)``, ``cy`` likewise: the cell under the pixel's
+        upper-left corner.  It adds ``rint(clip(float32(v), 0, 1) * 65535)`` and a count of ONE, so the count, the cap of 2^24 - 1 and
+        ``into=`` are about tiles, as before; a NaN cell adds nothing to its pixels.  Tiles that are constant over their cells give
+        :meth:`tile_raster`'s raster bit for bit.  The result goes to ``mean()``, :meth:`render_heatmap`, :meth:`smooth_raster` and
+        :meth:`mask_regions` unchanged.  Integer arithmetic, the same however the tiles are split over calls; no host
+        synchronisation."""
+        (gh, gw), patch, d, (h, w), origin = check_cell_args(grid, patch_size, downsample, shape, origin)
+        c = coords if isinstance(coords, torch.Tensor) else torch.as_tensor(coords)
+        v = cell_values if isinstance(cell_values, torch.Tensor) else torch.as_tensor(cell_values)
+        N = check_cells(c, v, (gh, gw))
+        into, zero = self._raster_into(N, patch, d, (h, w), origin, into)
         c = c.to(self._device, torch.int64).contiguous()
         v = v.to(self._device, torch.float32).contiguous()
-        self._call("heat_accumulate", _ptr(c), _ptr(v), N, patch, d, h, w, origin[0], origin[1], zero, _ptr(into.acc))
+        self._call("heat_accumulate_cells", _ptr(c), _ptr(v), N, gh, gw, patch, d, h, w, origin[0], origin[1], zero, _ptr(into.acc))
         return into
 
     def _heat_read(self, raster, uncovered: float, mean: bool, count: bool, pred: bool):
@@ -754,6 +783,20 @@ class SlideOps:
         :meth:`region_patches_uint8` and :meth:`encode_image_uint8`, ``batch`` tiles at a time -> (features fp32 [N,768],
         coords int64 [N,2]) on the region's device; ``[0,768]`` / ``[0,2]`` when no cell is kept.  ``tissue`` as in
         :meth:`region_grid`: off, the per-pixel rule, or a ``TissueMask``."""
+        return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, None)[:2]
+
+    @torch.no_grad()
+    def encode_region_attention(self, region, patch_size: int = 224, step: Optional[int] = None, tissue=None, origin=(0, 0),
+                                coord_scale: int = 1, batch: int = 256, block: int = -1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """:meth:`encode_region` with the CLS query's attention of block ``block`` for every tile (``encode_image_attention``;
+        DESIGN.md section 19) -> (features [N,768], coords [N,2], attn fp32 [N, heads, 197]) on the region's device.  Same grid, same
+        tiles; the features equal :meth:`encode_region`'s with option ``graphs`` = 0 bit for bit."""
+        self._ready()
+        self._check_block(block)
+        return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, block)
+
+    def _encode_region(self, region, patch_size, step, tissue, origin, coord_scale, batch, block):
+        """The body of :meth:`encode_region`; ``block`` not None: the tiles go through the tapped encode -> (features, coords, attn)."""
         patch, step, origin, coord_scale = check_grid_args(patch_size, step, origin, coord_scale)
         by_mask = isinstance(tissue, TissueMask)
         sat_min, min_pixels = (0, 0) if by_mask else tissue_params(tissue, patch)
@@ -766,9 +809,14 @@ class SlideOps:
             self._region_cells(xd, H, W, C, row, patch, step, sat_min, min_pixels)
         N = int(cells.shape[0])
         feats = torch.empty((N, self.config.projection_dim), dtype=torch.float32, device=self._device)
+        attn = None if block is None else torch.empty((N, self.config.vision.num_heads, (TILE // 16) ** 2 + 1), dtype=torch.float32,
+                                                      device=self._device)
         for i in range(0, N, int(batch)):
-            feats[i:i + batch] = self.encode_image_uint8(self._region_tiles(xd, H, W, C, row, cells[i:i + batch], patch))
+            tiles = self._region_tiles(xd, H, W, C, row, cells[i:i + batch], patch)
+            if block is None:
+                feats[i:i + batch] = self.encode_image_uint8(tiles)
+            else:
+                feats[i:i + batch], attn[i:i + batch] = self._encode_tapped(tiles, _lib.PIX_U8_HWC, TILE, TILE, block, "encode_region_attention")
         coords = self._cells_to_coords(cells, origin, coord_scale)
-        if x.device == self._device:
-            return feats, coords
-        return feats.to(x.device), coords.to(x.device)
+        out = (feats, coords) if block is None else (feats, coords, attn)
+        return out if x.device == self._device else tuple(t.to(x.device) for t in out)

@@ -518,6 +518,16 @@ def segment_heatmap(classifier, tile_features, tile_coords, downsample, shape, p
     return raster if taps is None else m.smooth_raster(raster, taps=taps, tissue=tissue)
 
 
+def attention_heatmap(model, attn, coords, grid, patch_size, downsample, shape, heads=None, normalize="tile_max", origin=(0, 0), into=None):
+    """The CLS attention of a slide's tiles in slide geometry -> ``keep_amd.heatmap.TileRaster``:
+    ``keep_amd.attention.cls_attention_map(attn, heads, normalize)`` put on the raster by ``KEEPModel.cell_raster``.  ``attn`` [N, heads,
+    gh gw + 1] and ``coords`` [N,2] as ``KEEPModel.encode_region_attention`` returns them, ``grid = (gh, gw)`` the token grid of a tile
+    ((14, 14) at 224 x 224), ``patch_size`` a tile's footprint in the units of the coords; ``into=`` adds to an earlier raster."""
+    from .attention import cls_attention_map
+    m = _engine(model, attn)
+    return m.cell_raster(coords, cls_attention_map(attn, heads, normalize), grid, patch_size, downsample, shape, origin, into)
+
+
 def segment_regions(raster, thd=0.5, tissue=None, connectivity=8, min_area=1, model=None):
     """The lesion table of a segmentation raster: the connected regions of the pixels whose mean is above
     ``thd``, with area, box, centroid sums and mean / peak score -> ``keep_amd.components.RegionTable``.  ``raster``: the
