@@ -9,7 +9,9 @@ eval_seg_auc / eval_seg_coarse do against a mask: tile AUROC, the threshold of t
     python examples/slide_heatmap_synthetic.py [--rows 8] [--cols 10] [--depth 2] [--out slide_heatmap.png] [--geojson lesions.geojson]
 
 No dataset, weights or tokenizer exist offline, so the slide (stained tiles inside an ellipse, grey glass around it), the weights
-and the two prompts are seeded synthetic data: the picture shows the flow, not a tumour.
+and the two prompts are seeded synthetic data: the picture shows the flow, not a tumour.  With --attention the same region is encoded twice
+more, once with the last block's CLS attention and once with the attention rollout through every block (DESIGN.md sections 19, 20), and
+the two token-resolution heatmaps are written side by side.
 """
 import argparse
 import json
@@ -46,6 +48,7 @@ def main():
     ap.add_argument("--cols", type=int, default=10)
     ap.add_argument("--depth", type=int, default=2, help="ViT/BERT depth (24 = the real model's shape; small for a quick look)")
     ap.add_argument("--out", default=os.path.join(tempfile.gettempdir(), "slide_heatmap.png"))
+    ap.add_argument("--attention", default="", help="write the last-block CLS attention map and the rollout map, side by side, to this PNG")
     ap.add_argument("--geojson", default=os.path.join(tempfile.gettempdir(), "slide_lesions.geojson"))
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -93,6 +96,14 @@ def main():
     from PIL import Image
     Image.fromarray(picture.cpu().numpy()).save(a.out)
     print(f"wrote {a.out}")
+    if a.attention:                                                       # where inside the tiles the model looked: one block, and all of them
+        shape_t = tuple(thumb.shape[:2])
+        _, c, attn = model.encode_region_attention(slide, PATCH, tissue=tissue, block=-1)
+        _, _, rollout = model.encode_region_rollout(slide, PATCH, tissue=tissue, start_block=0, residual=0.5)
+        maps = [wsi.attention_heatmap(model, t, c, (14, 14), PATCH, DOWNSAMPLE, shape_t) for t in (attn, rollout)]
+        side = torch.cat([model.render_heatmap(r, thumb, alpha=0.6, colormap="jet", tissue=tissue) for r in maps], dim=1)
+        Image.fromarray(side.cpu().numpy()).save(a.attention)
+        print(f"wrote {a.attention}: last-block CLS attention (left) and attention rollout from block 0 (right), {c.shape[0]} tiles at token resolution")
     from keep_amd.annotation import PolygonSet
     truth = PolygonSet.from_geojson(a.geojson)                            # the polygons just written: what a pathologist would have drawn
     try:

@@ -127,6 +127,7 @@ int keep_bert_layers(keep_handle* h);
  *                     family.  A handle STARTS with another plan: block 0 KEEP_ATTN_SPLIT_COMPQKV + KEEP_MLP_COMP, every other block
  *                     KEEP_ATTN_PLAIN + KEEP_MLP_CLS -- until KEEPModel.calibrate / keep_set_block_precision replace it.
  *   "plan_custom"      (read only) 1 if keep_set_block_precision changed the plan since the last shorthand
+ *   "graph_count"      (read only) the captured graphs the handle holds; a graph made stale by an option change is dropped when its call comes again
  *   "comp_min_tiles"   sub-batches with fewer tiles use split products instead of compensated ones (default 32)
  *   "comp_qkv"         KEEP_PREC_COMP: 1 = the qkv GEMM of the split-attention blocks as a compensated product instead of a split one
  *                     (default 0: +0.9 % at equal settings, but calibrate() then needs more compensated MLP blocks -- a net loss)
@@ -520,6 +521,22 @@ int keep_encode_image_hw(keep_handle* h, const void* pixels, int pix_dtype, int6
 int keep_encode_image_attn(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, int64_t H, int64_t W, int block, float* out,
                            float* attn_out, void* stream);
 
+/* keep_encode_image_hw with the attention rollout of the tile beside the feature (Abnar & Zuidema 2020): the CLS
+ *   token's relevance over the tokens through every block from `start_block` on, which the reference can only produce by hooking all of
+ *   timm's Attention.forward calls (quick_start/keep_inference.py:32-40 builds the tower) and multiplying T x T matrices on the host.
+ *   With A_l the head mean of block l's softmax(q k^T / 8), all T query rows, and At_l = (1 - residual) A_l + residual I:
+ *   rollout_out[b] = row 0 of At_{depth-1} ... At_{start_block}, fp32 [B, gh gw + 1]; every row sums to 1, column 0 is CLS -> CLS, columns
+ *   1.. the patches in row-major (y, x) order.  start_block: 0 .. depth - 1, or negative counting from the end (depth - 1 and residual 0:
+ *   the head mean of keep_encode_image_attn's last block).  The scores are fp16 MFMA products of the block's own q / k planes (hi + lo
+ *   products where the block runs split) with fp32 sums, the matrix products exact fp32.  out: fp32 [B,768], exactly what
+ *   keep_encode_image_hw writes with option "graphs" = 0.  scratch: device memory of at least keep_rollout_scratch_bytes(h, B, H, W)
+ *   bytes, the caller's (nothing is taken from the handle's arena); the call is never captured or replayed as a graph and leaves options
+ *   and graphs as they were.  KEEP_EINVAL: start_block outside [-depth, depth), residual outside [0, 1) or not finite, a null pointer,
+ *   H or W not a positive multiple of 16, a scratch that is too small; KEEP_EUNSUPPORTED: more than 272 tokens per tile. */
+int keep_rollout_scratch_bytes(keep_handle* h, int64_t B, int64_t H, int64_t W, int64_t* bytes);
+int keep_encode_image_rollout(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, int64_t H, int64_t W, int start_block,
+                              float residual, float* out, float* rollout_out, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* Replaces: timm.layers.resample_abs_pos_embed(visual.pos_embed, new_size=(gh, gw), old_size=(14, 14), num_prefix_tokens=1)
  *   (the step timm's dynamic_img_size takes per forward, quick_start/keep_inference.py:32-40).  out: fp32 [gh*gw+1, D], the table
  *   keep_encode_image_hw uses for that grid: visual.pos_embed itself at 14 x 14, else the CLS row + the patch rows through
@@ -672,6 +689,11 @@ int keep_op_attention_long(keep_handle* h, const float* qkv, int64_t B, int64_t 
 /* The CLS query's attention probabilities (the kernel behind keep_encode_image_attn): qkv fp32 [B*T, 3*heads*64], turned into fp16 planes as
  * keep_op_attention does (split != 0: hi + lo) -> out fp32 [B, heads, T] = softmax_k(q_{b,h,0} . k_{b,h,k} / 8), any T >= 1 */
 int keep_op_attention_cls_probs(keep_handle* h, const float* qkv, int64_t B, int64_t T, int heads, int split, float* out, void* stream);
+/* One block's step of the attention rollout (the kernels behind keep_encode_image_rollout): qkv as above; with A the head mean of
+ * softmax(q k^T / 8) over all T query rows and At = (1 - residual) A + residual I, r_out = At r_in in fp32, or At itself when r_in is NULL.
+ * r_in, r_out: fp32 [B, T, T]; q_rows = 1: only the CLS row, r_out [B, T] (q_rows = 0: every row).  1 <= T <= 272, else KEEP_EUNSUPPORTED */
+int keep_op_attention_rollout_step(keep_handle* h, const float* qkv, int64_t B, int64_t T, int heads, int split, float residual,
+                                   const float* r_in, int q_rows, float* r_out, void* stream);
 int keep_op_layernorm(keep_handle* h, const float* x, const float* add, const float* gamma, const float* beta,
                       int64_t rows, int64_t D, float eps, float* out, void* stream);
 /* out[M,N] = act(scale * A[M,K] @ B[N,K]^T + bias); act 0 none, 1 gelu, 2 tanh (exact fp32 MFMA) */

@@ -46,6 +46,8 @@ SIGNATURES = {
     "keep_encode_image": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp]),
     "keep_encode_image_hw": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp]),
     "keep_encode_image_attn": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "keep_rollout_scratch_bytes": (_i32, [_vp, _i64, _i64, _i64, C.POINTER(_i64)]),
+    "keep_encode_image_rollout": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _i32, _f32, _vp, _vp, _vp, _i64, _vp]),
     "keep_vit_pos_embed": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "keep_encode_text": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "keep_resize_crop_u8": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp]),
@@ -93,6 +95,7 @@ SIGNATURES = {
     "keep_op_attention_cls": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "keep_op_attention_long": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
     "keep_op_attention_cls_probs": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
+    "keep_op_attention_rollout_step": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _i32, _vp, _vp]),
     "keep_op_layernorm": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp]),
     "keep_op_sgemm": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _vp]),
     "keep_op_l2norm": (_i32, [_vp, _vp, _i64, _i64, _vp]),

@@ -4,12 +4,19 @@ that is shown to a reader -- which patches of the tile the pooled feature's quer
 ``attn`` is fp32 ``[B, heads, T]``: row (b, h) is the softmax over the T = gh gw + 1 keys of the CLS query's scores in head h, column 0
 the CLS -> CLS weight, columns 1.. the patch tokens in row-major (y, x) order.  :func:`cls_attention_map` is plain elementwise torch
 on whatever device ``attn`` lives on; ``KEEPModel.cell_raster`` / ``keep_amd.wsi.attention_heatmap`` put its result on the slide raster.
-Not done here or anywhere in the engine: attention rollout across blocks, rows other than the CLS query's, the text tower."""
+
+Attention rollout: ``KEEPModel.encode_image_rollout`` returns the CLS row of the product of every block's
+head-mean attention matrix, each blended with the identity, as a ONE-head tensor ``[B, 1, T]`` of the same layout, so everything here
+and behind it takes it as it is.  Tiles of more than :data:`ROLLOUT_MAX_TOKENS` tokens are a ValueError there.
+
+Not done here or anywhere in the engine: head fusion by max / min, a discard ratio or gradient weighting in the rollout, rows other than
+the CLS query's as output, the text tower."""
 from typing import Optional, Sequence, Union
 
 import torch
 
 NORMALIZATIONS = ("tile_max", "sum", "none")
+ROLLOUT_MAX_TOKENS = 272        # tokens per tile the rollout kernels cover (17 key tiles of 16 in registers): every tile up to 256 x 256 pixels
 
 
 def cls_attention_map(attn: torch.Tensor, heads: Optional[Union[int, Sequence[int]]] = None, normalize: str = "tile_max") -> torch.Tensor:

@@ -179,6 +179,13 @@ constexpr int ATT_PART_FLOATS = 66;       // 64 output features + maximum + sum
 // row-major qkv planes above (qkv_lo null: the hi plane alone; else every operand value is hi + lo), fp32 products and sums on the VALU.  Any ntok >= 1;
 // no LDS, no scratch, no atomics.  Returns 0 or -1.
 int launch_attention_cls_probs(const f16* qkv_hi, const f16* qkv_lo, int batch, int ntok, int heads, float scale, float* out, hipStream_t s);
+// One block's step of the attention rollout (attention_rollout.hip): with A the block's head-mean softmax(scale q k^T) from the
+// planes above (fp16 MFMA products, fp32 sums) and At = (1 - residual) A + residual I, r_out = At r_in in exact fp32, or At itself when r_in is null.
+// r_in, r_out: fp32 [batch][ntok][ntok] row-major; q_rows = 1: only the CLS row, r_out [batch][ntok] (q_rows = 0: every row).  a_tmp: At's way from the
+// first kernel to the product, fp32 [batch][ntok or q_rows][ntok], needed when r_in is given.  1 <= ntok <= ROLLOUT_MAX_TOKENS.  Returns 0 or -1.
+constexpr int ROLLOUT_MAX_TOKENS = 272;   // 17 key tiles of 16 in registers: every tile up to 256 x 256 pixels (257 tokens)
+int launch_attention_rollout_step(const f16* qkv_hi, const f16* qkv_lo, int batch, int ntok, int heads, float scale, float residual,
+                                  const float* r_in, float* r_out, int q_rows, float* a_tmp, hipStream_t s);
 
 // LayerNorm over rows of D in {768,1024}; fp32 in, fp16 (hi[,lo]) and/or fp32 out.
 struct LnParams {

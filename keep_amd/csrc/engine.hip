@@ -201,6 +201,10 @@ struct VitLane {
     bool xn_ready = false;                                // the previous block's fc2 already wrote this block's LayerNorm-1 output
     bool c_resid_live = false;                            // ws.c_resid holds the CLS rows of ws.resid as they are NOW (left there by the previous block's CLS-row chain): no gather
     int tap_block = -1; float* tap_out = nullptr;         // keep_encode_image_attn: the block whose CLS-row attention probabilities go to tap_out, this lane's [Bc][heads][ntok]
+    // keep_encode_image_rollout: a step behind the attention launch of every block >= roll_start (-1: none).  roll_r: the lane's two
+    // [Bc][ntok][ntok] ping-pong buffers (roll_cur holds the running product), roll_a: the same size, At between the step's two kernels; roll_out: this
+    // lane's [Bc][ntok] of the result, written by the last block's step
+    int roll_start = -1; float roll_res = 0.5f; float* roll_r[2] = {nullptr, nullptr}; float* roll_a = nullptr; float* roll_out = nullptr; int roll_cur = 0;
 };
 
 int vit_begin(keep_handle* h, VitLane& L) {
@@ -282,6 +286,14 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
     }
     if (i == L.tap_block && launch_attention_cls_probs(ws.qkv_hi, sp ? ws.qkv_lo : nullptr, Bc, ntok, h->vit_heads, 0.125f, L.tap_out, s))
         return h->fail(KEEP_EUNSUPPORTED, "CLS attention map launch failed (%d tokens)", ntok);
+    if (L.roll_start >= 0 && i >= L.roll_start) {
+        const bool first = i == L.roll_start, last = i == h->vit_depth - 1;      // the last block's step: the CLS row only, whether or not cls_tail is on
+        float* r_out = last ? L.roll_out : L.roll_r[first ? L.roll_cur : L.roll_cur ^ 1];
+        if (launch_attention_rollout_step(ws.qkv_hi, sp ? ws.qkv_lo : nullptr, Bc, ntok, h->vit_heads, 0.125f, L.roll_res, first ? nullptr : L.roll_r[L.roll_cur],
+                                          r_out, last ? 1 : 0, L.roll_a, s))
+            return h->fail(KEEP_EUNSUPPORTED, "attention rollout launch failed (%d tokens, at most %d)", ntok, ROLLOUT_MAX_TOKENS);
+        if (!first && !last) L.roll_cur ^= 1;
+    }
     const int Mr = cls_only ? Bc : M;
     float* resid = cls_only ? ws.c_resid : ws.resid;
     const f16 *att_hi = ws.att_hi, *att_lo = ws.att_lo;
@@ -572,8 +584,20 @@ int vit_pos_table(keep_handle* h, int gh, int gw, const float** out) {
 
 // the image tower on B tiles of a gh x gw patch grid (arguments checked, device selected by the caller)
 // tap_out: fp32 [B][heads][ntok], the CLS-row attention probabilities of block tap_block (keep_encode_image_attn); such a call is never captured or replayed
+// roll: keep_encode_image_rollout's start block, residual weight, output [B][ntok] and scratch (rollout_scratch); never captured or replayed either
+struct RollArgs { int start; float residual; float* out; char* scratch; int64_t scratch_bytes; };
+// what the rollout of one call keeps live: per lane of a round, two ping-pong [per][ntok][ntok] and At of the same size
+struct RollPlan { size_t buf, lane, total; };
+RollPlan rollout_scratch(int64_t B, int ntok, const VitPlan& plan) {
+    RollPlan r{};
+    const int64_t live = std::min<int64_t>(B, plan.per * plan.lanes);             // only the tiles of one round of lanes are live at a time
+    r.buf = align_up((size_t)plan.per * ntok * ntok * sizeof(float));
+    r.lane = 3 * r.buf;
+    r.total = r.lane * (size_t)((live + plan.per - 1) / plan.per);
+    return r;
+}
 int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, float* out, hipStream_t s, int gh = 14, int gw = 14,
-                     int tap_block = -1, float* tap_out = nullptr) {
+                     int tap_block = -1, float* tap_out = nullptr, const RollArgs* roll = nullptr) {
     const int ntok = gh * gw + 1;
     const bool g14 = gh == 14 && gw == 14;
     const float* pos = nullptr;
@@ -581,8 +605,11 @@ int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t 
     if (rc) return rc;
     const size_t px = pix_dtype == KEEP_PIX_F32 ? 4 : (pix_dtype == KEEP_PIX_U8_HWC ? 1 : 2);    // bytes per value; 3 * 16 gh * 16 gw values per tile in every layout
     const size_t tile_vals = (size_t)3 * (gh * 16) * (gw * 16);
-    const bool graph = h->use_graphs && !h->prof_mode && B * ntok <= SKINNY_MAX_M && B <= h->max_tiles && !tap_out;
+    const bool graph = h->use_graphs && !h->prof_mode && B * ntok <= SKINNY_MAX_M && B <= h->max_tiles && !tap_out && !roll;
     const VitPlan plan = vit_plan(h, B, ntok, tile_vals * px, graph);
+    const RollPlan rp = roll ? rollout_scratch(B, ntok, plan) : RollPlan{};
+    if (roll && (int64_t)rp.total > roll->scratch_bytes)
+        return h->fail(KEEP_EINVAL, "rollout scratch of %lld bytes, %lld needed (keep_rollout_scratch_bytes)", (long long)roll->scratch_bytes, (long long)rp.total);
     rc = ensure_arena(h, plan.total);
     if (rc) return rc;
     if (graph) {
@@ -631,6 +658,11 @@ int encode_image_run(keep_handle* h, const void* pixels, int pix_dtype, int64_t 
             x.s = lanes > 1 ? h->aux[l] : s;
             x.gh = gh; x.gw = gw; x.ntok = ntok; x.pos = pos;
             if (tap_out) { x.tap_block = tap_block; x.tap_out = tap_out + lo * h->vit_heads * ntok; }
+            if (roll) {
+                float* base = (float*)(roll->scratch + (size_t)l * rp.lane);
+                x.roll_start = roll->start; x.roll_res = roll->residual; x.roll_out = roll->out + lo * ntok;
+                x.roll_r[0] = base; x.roll_r[1] = base + rp.buf / sizeof(float); x.roll_a = base + 2 * (rp.buf / sizeof(float));
+            }
             x.ws = carve_vit(h, h->arena + (size_t)l * plan.lane_bytes, x.Bc, plan.split, ntok);
         }
         for (int l = 0; l < nl; ++l) if ((rc = vit_begin(h, L[l]))) return rc;
@@ -808,6 +840,7 @@ double keep_get_option(keep_handle* h, const char* name) {
     if (n == "gemm_impl") return h->tune.gemm_impl;
     if (n == "plan_custom") return h->plan_custom ? 1 : 0;      // the two read-only names
     if (n == "bias_ready") return h->bias_ready ? 1 : 0;
+    if (n == "graph_count") return (double)h->graphs.size();     // read-only as well: the captured graphs the handle holds (stale ones are dropped lazily)
     return -1;
 }
 
@@ -884,6 +917,51 @@ int keep_encode_image_attn(keep_handle* h, const void* pixels, int pix_dtype, in
     const int prec = h->precision;                       // the grid rule of keep_encode_image_hw
     if (!(gh == 14 && gw == 14) && !h->grid_keeps_plan((int)(gh * gw + 1)) && prec == KEEP_PREC_COMP) h->precision = KEEP_PREC_STRICT;
     const int rc = encode_image_run(h, pixels, pix_dtype, B, out, (hipStream_t)stream, (int)gh, (int)gw, block < 0 ? block + h->vit_depth : block, attn_out);
+    h->precision = prec;
+    return rc;
+}
+
+// the argument rules keep_encode_image_rollout and keep_rollout_scratch_bytes share with keep_encode_image_attn
+static int rollout_grid(keep_handle* h, int64_t B, int64_t H, int64_t W, int64_t* gh, int64_t* gw) {
+    if (!h->finalized || !h->vit_depth) return h->fail(KEEP_ESTATE, "image tower not loaded / finalised");
+    if (B < 0) return h->fail(KEEP_EINVAL, "negative batch");
+    if (H < 16 || W < 16 || H % 16 || W % 16) return h->fail(KEEP_EINVAL, "image size %lldx%lld: H and W must be positive multiples of 16", (long long)H, (long long)W);
+    *gh = H / 16; *gw = W / 16;
+    if (*gh * *gw + 1 > ROLLOUT_MAX_TOKENS)
+        return h->fail(KEEP_EUNSUPPORTED, "image size %lldx%lld: %lld tokens, the rollout covers at most %d", (long long)H, (long long)W, (long long)(*gh * *gw + 1), ROLLOUT_MAX_TOKENS);
+    return KEEP_OK;
+}
+
+int keep_rollout_scratch_bytes(keep_handle* h, int64_t B, int64_t H, int64_t W, int64_t* bytes) {
+    if (!h) return KEEP_EINVAL;
+    if (!bytes) return h->fail(KEEP_EINVAL, "null pointer");
+    int64_t gh = 0, gw = 0;
+    const int rc = rollout_grid(h, B, H, W, &gh, &gw);
+    if (rc) return rc;
+    const int ntok = (int)(gh * gw + 1);
+    *bytes = B ? (int64_t)rollout_scratch(B, ntok, vit_plan(h, B, ntok, 0, false)).total : 0;
+    return KEEP_OK;
+}
+
+int keep_encode_image_rollout(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, int64_t H, int64_t W, int start_block, float residual,
+                              float* out, float* rollout_out, void* scratch, int64_t scratch_bytes, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!h->finalized || !h->vit_depth) return h->fail(KEEP_ESTATE, "image tower not loaded / finalised");
+    if (!pixels || !out || !rollout_out || B < 0) return h->fail(KEEP_EINVAL, "null pointer or negative batch");
+    if (pix_dtype < KEEP_PIX_F32 || pix_dtype > KEEP_PIX_U8_HWC) return h->fail(KEEP_EINVAL, "pixel dtype %d", pix_dtype);
+    if (start_block < -h->vit_depth || start_block >= h->vit_depth)
+        return h->fail(KEEP_EINVAL, "start_block %d outside [-%d, %d)", start_block, h->vit_depth, h->vit_depth);
+    if (!(residual >= 0.f && residual < 1.f)) return h->fail(KEEP_EINVAL, "residual %g outside [0, 1)", (double)residual);
+    int64_t gh = 0, gw = 0;
+    int rc = rollout_grid(h, B, H, W, &gh, &gw);
+    if (rc) return rc;
+    if (B == 0) return KEEP_OK;
+    if (!scratch || scratch_bytes < 0) return h->fail(KEEP_EINVAL, "rollout scratch missing (keep_rollout_scratch_bytes)");
+    KEEP_ON_DEVICE(h);
+    const int prec = h->precision;                       // the grid rule of keep_encode_image_hw
+    if (!(gh == 14 && gw == 14) && !h->grid_keeps_plan((int)(gh * gw + 1)) && prec == KEEP_PREC_COMP) h->precision = KEEP_PREC_STRICT;
+    const RollArgs roll{start_block < 0 ? start_block + h->vit_depth : start_block, residual, rollout_out, (char*)scratch, scratch_bytes};
+    rc = encode_image_run(h, pixels, pix_dtype, B, out, (hipStream_t)stream, (int)gh, (int)gw, -1, nullptr, &roll);
     h->precision = prec;
     return rc;
 }

@@ -278,6 +278,27 @@ int keep_op_attention_cls_probs(keep_handle* h, const float* qkv, int64_t B, int
     return check_launch(h, "op_attention_cls_probs");
 }
 
+int keep_op_attention_rollout_step(keep_handle* h, const float* qkv, int64_t B, int64_t T, int heads, int split, float residual, const float* r_in, int q_rows,
+                                   float* r_out, void* stream) {
+    if (!h || !qkv || !r_out || B < 1 || T < 1 || heads < 1) return h ? h->fail(KEEP_EINVAL, "bad attention arguments") : KEEP_EINVAL;
+    if (q_rows != 0 && q_rows != 1) return h->fail(KEEP_EINVAL, "attention_rollout_step: q_rows %d (0: every row, 1: the CLS row)", q_rows);
+    if (!(residual >= 0.f && residual < 1.f)) return h->fail(KEEP_EINVAL, "attention_rollout_step: residual %g outside [0, 1)", (double)residual);
+    if (B > INT32_MAX || T > INT32_MAX || B * T > INT32_MAX) return h->fail(KEEP_EINVAL, "attention_rollout_step: B %lld, T %lld", (long long)B, (long long)T);
+    if (T > ROLLOUT_MAX_TOKENS) return h->fail(KEEP_EUNSUPPORTED, "attention_rollout_step: T %lld, at most %d", (long long)T, ROLLOUT_MAX_TOKENS);
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = B * T * 3 * heads * 64;
+    Tmp t;
+    f16* q_hi = t.get<f16>(n); f16* q_lo = t.get<f16>(n);
+    float* a_tmp = r_in ? t.get<float>((size_t)B * (q_rows ? 1 : T) * T) : nullptr;
+    if (!t.ok) return h->fail(KEEP_ENOMEM, "temp alloc");
+    launch_split_f16(qkv, q_hi, q_lo, n, s);           // the planes as keep_op_attention makes them
+    if (launch_attention_rollout_step(q_hi, split ? q_lo : nullptr, (int)B, (int)T, heads, 0.125f, residual, r_in, r_out, q_rows, a_tmp, s))
+        return h->fail(KEEP_EUNSUPPORTED, "attention_rollout_step: B %lld, T %lld, heads %d unsupported", (long long)B, (long long)T, heads);
+    HIPCHK(h, hipStreamSynchronize(s));
+    return check_launch(h, "op_attention_rollout_step");
+}
+
 // Matrix-pipe ceiling probe (keep_mfma_probe): no memory traffic inside the loop; every wave holds 2 A and 4 B fragments of the caller's data in registers and
 // issues 8 independent v_mfma_f32_32x32x16_f16 per iteration (all (i, j) pairs: the pipe's inputs change with every instruction); one 8-wave workgroup per CU,
 // two waves per SIMD, as the GEMM kernels run.

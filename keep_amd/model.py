@@ -915,6 +915,66 @@ class KEEPModel(SlideOps):
         self.check_errors(wait=True)
         return res
 
+    def _check_rollout(self, start_block, residual, T: int):
+        """The rules keep_encode_image_rollout applies, as a ValueError before any device work (and for calls without tiles)."""
+        from .attention import ROLLOUT_MAX_TOKENS
+        depth = int(_lib.load().keep_vit_depth(self._handle))
+        if isinstance(start_block, bool) or not isinstance(start_block, int) or not -depth <= start_block < depth:
+            raise ValueError(f"start_block {start_block!r} outside [-{depth}, {depth})")
+        if isinstance(residual, bool) or not isinstance(residual, (int, float)) or not 0 <= residual < 1:      # (nan fails both comparisons)
+            raise ValueError(f"residual {residual!r} outside [0, 1)")
+        if T > ROLLOUT_MAX_TOKENS:
+            raise ValueError(f"{T} tokens per tile: the attention rollout covers at most {ROLLOUT_MAX_TOKENS}")
+
+    def _encode_rollout(self, xd: torch.Tensor, pix: int, H: int, W: int, start_block: int, residual: float, what: str) -> Tuple[torch.Tensor, torch.Tensor]:
+        """keep_encode_image_rollout on device tiles -> (features [B,768], rollout [B, 1, T]) on the device; the scratch lives for this call."""
+        B, T = int(xd.shape[0]), (H // 16) * (W // 16) + 1
+        self._check_rollout(start_block, residual, T)
+        lib = _lib.load()
+        need = C.c_int64(0)
+        _lib.check(self._handle, lib.keep_rollout_scratch_bytes(self._handle, B, H, W, C.byref(need)), what)
+        scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self._device)      # dropped on return; the allocator reuses it in stream order
+        out = torch.empty((B, self.config.projection_dim), dtype=torch.float32, device=self._device)
+        roll = torch.empty((B, 1, T), dtype=torch.float32, device=self._device)
+        rc = lib.keep_encode_image_rollout(self._handle, _ptr(xd), pix, B, H, W, start_block, float(residual), _ptr(out), _ptr(roll), _ptr(scratch),
+                                           scratch.numel(), _stream(self._device))
+        _lib.check(self._handle, rc, what)
+        self._queue_flag_check(_stream(self._device))
+        return out, roll
+
+    @torch.no_grad()
+    def encode_image_rollout(self, image_inputs: torch.Tensor, start_block: int = 0, residual: float = 0.5) -> Tuple[torch.Tensor, torch.Tensor]:
+        """:meth:`encode_image` with the tile's attention rollout beside it (Abnar & Zuidema 2020) -> (features
+        [B,768], rollout fp32 [B, 1, T]), T = H/16 * W/16 + 1.  With ``A_l`` the head mean of block l's softmax(q k^T / 8) over all T query
+        rows and ``At_l = (1 - residual) A_l + residual I``, ``rollout[b, 0]`` is row 0 (the CLS query) of ``At_{depth-1} ... At_{start_block}``:
+        it sums to 1, column 0 is CLS -> CLS, columns 1.. the patch tokens in row-major (y, x) order.  ``start_block``: ``0 .. depth - 1`` or
+        negative from the end; ``0 <= residual < 1`` (ValueError outside; also for more than
+        ``keep_amd.attention.ROLLOUT_MAX_TOKENS`` tokens per tile).  The singleton axis is the head axis of a one-head attention tensor:
+        ``cls_attention_map``, ``wsi.attention_heatmap`` and ``cell_raster`` take the result as they take
+        :meth:`encode_image_attention`'s.  Inputs and device handling as :meth:`encode_image`; the features equal its with option
+        ``graphs`` = 0 bit for bit (the call is never replayed as a graph)."""
+        self._ready()
+        x = image_inputs
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"expected [B,3,H,W], got {tuple(x.shape)}")
+        H, W = int(x.shape[2]), int(x.shape[3])
+        self._check_hw(H, W, f"[B,3,H,W] = {tuple(x.shape)}")
+        if x.dtype not in _PIX:
+            x = x.to(torch.float32)
+        src_dev = x.device
+        T = (H // 16) * (W // 16) + 1
+        if x.shape[0] == 0:
+            self._check_rollout(start_block, residual, T)
+            return (torch.empty((0, self.config.projection_dim), dtype=torch.float32, device=src_dev),
+                    torch.empty((0, 1, T), dtype=torch.float32, device=src_dev))
+        xd = x.to(self._device, non_blocking=True).contiguous()
+        out, roll = self._encode_rollout(xd, _PIX[xd.dtype], H, W, start_block, residual, "encode_image_rollout")
+        if src_dev == self._device:
+            return out, roll
+        res = out.to(src_dev), roll.to(src_dev)
+        self.check_errors(wait=True)
+        return res
+
     def _check_block(self, block) -> int:
         """The rule keep_encode_image_attn applies, as a ValueError before any device work (and for calls without tiles)."""
         depth = int(_lib.load().keep_vit_depth(self._handle))

@@ -145,6 +145,21 @@ class Ops:
         _lib.check(self._h, rc, "op_attention_cls_probs")
         return out
 
+    def attention_rollout_step(self, qkv, B, T, heads, split=False, residual=0.5, r_in=None, q_rows=0):
+        """One block's step of the attention rollout: with A the head mean of softmax(q k^T / 8) over all T query rows (fp16
+        planes of qkv, split: hi + lo products; fp32 sums) and At = (1 - residual) A + residual I, returns At @ r_in in fp32, or At when r_in is None
+        -> fp32 [B, T, T]; q_rows=1: the CLS row alone, [B, 1, T].  r_in: fp32 [B, T, T].  1 <= T <= keep_amd.attention.ROLLOUT_MAX_TOKENS."""
+        qkv = self._f(qkv)
+        if r_in is not None:
+            r_in = self._f(r_in)
+            if tuple(r_in.shape) != (B, T, T):
+                raise ValueError(f"r_in must be [B, T, T] = {(B, T, T)}, got {tuple(r_in.shape)}")
+        out = torch.empty((B, 1 if q_rows == 1 else T, T), dtype=torch.float32, device=self.device)
+        rc = _lib.load().keep_op_attention_rollout_step(self._h, _ptr(qkv), B, T, heads, int(split), float(residual), _ptr(r_in), int(q_rows),
+                                                        _ptr(out), _stream(self.device))
+        _lib.check(self._h, rc, "op_attention_rollout_step")
+        return out
+
     def layernorm(self, x, gamma, beta, eps, add=None):
         x, gamma, beta, add = map(self._f, (x, gamma, beta, add))
         out = torch.empty_like(x)

@@ -48,7 +48,7 @@ def _check_tissue(tissue, raster) -> None:
 
 class SlideOps:
     """Base of ``KEEPModel``, which supplies what these methods use of the engine: ``_handle``, ``_device``, ``_ready()``,
-    ``_ready_device()``, ``_queue_flag_check()``, ``encode_image_uint8()``, ``_encode_tapped()``, ``_check_block()``, ``config`` and
+    ``_ready_device()``, ``_queue_flag_check()``, ``encode_image_uint8()``, ``_encode_tapped()``, ``_check_block()``, ``_encode_rollout()``, ``_check_rollout()``, ``config`` and
     ``_heat_luts``."""
 
     def _call(self, name: str, *args) -> None:
@@ -795,8 +795,20 @@ class SlideOps:
         self._check_block(block)
         return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, block)
 
+    @torch.no_grad()
+    def encode_region_rollout(self, region, patch_size: int = 224, step: Optional[int] = None, tissue=None, origin=(0, 0), coord_scale: int = 1,
+                              batch: int = 256, start_block: int = 0, residual: float = 0.5) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """:meth:`encode_region` with every tile's attention rollout (``encode_image_rollout``) -> (features
+        [N,768], coords [N,2], rollout fp32 [N, 1, 197]) on the region's device.  Same grid, same tiles; the features equal
+        :meth:`encode_region`'s with option ``graphs`` = 0 bit for bit."""
+        self._ready()
+        self._check_rollout(start_block, residual, (TILE // 16) ** 2 + 1)
+        return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, ("rollout", start_block, residual))
+
     def _encode_region(self, region, patch_size, step, tissue, origin, coord_scale, batch, block):
-        """The body of :meth:`encode_region`; ``block`` not None: the tiles go through the tapped encode -> (features, coords, attn)."""
+        """The body of :meth:`encode_region`.  ``block`` an int: the tiles go through the tapped encode -> (features, coords, attn
+        [N, heads, 197]); ``("rollout", start_block, residual)``: through the rollout encode -> (features, coords, rollout [N, 1, 197])."""
+        rollout = isinstance(block, tuple)
         patch, step, origin, coord_scale = check_grid_args(patch_size, step, origin, coord_scale)
         by_mask = isinstance(tissue, TissueMask)
         sat_min, min_pixels = (0, 0) if by_mask else tissue_params(tissue, patch)
@@ -809,12 +821,14 @@ class SlideOps:
             self._region_cells(xd, H, W, C, row, patch, step, sat_min, min_pixels)
         N = int(cells.shape[0])
         feats = torch.empty((N, self.config.projection_dim), dtype=torch.float32, device=self._device)
-        attn = None if block is None else torch.empty((N, self.config.vision.num_heads, (TILE // 16) ** 2 + 1), dtype=torch.float32,
-                                                      device=self._device)
+        attn = None if block is None else torch.empty((N, 1 if rollout else self.config.vision.num_heads, (TILE // 16) ** 2 + 1),
+                                                      dtype=torch.float32, device=self._device)
         for i in range(0, N, int(batch)):
             tiles = self._region_tiles(xd, H, W, C, row, cells[i:i + batch], patch)
             if block is None:
                 feats[i:i + batch] = self.encode_image_uint8(tiles)
+            elif rollout:
+                feats[i:i + batch], attn[i:i + batch] = self._encode_rollout(tiles, _lib.PIX_U8_HWC, TILE, TILE, block[1], block[2], "encode_region_rollout")
             else:
                 feats[i:i + batch], attn[i:i + batch] = self._encode_tapped(tiles, _lib.PIX_U8_HWC, TILE, TILE, block, "encode_region_attention")
         coords = self._cells_to_coords(cells, origin, coord_scale)
