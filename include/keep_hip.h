@@ -342,6 +342,28 @@ int keep_regions_label(keep_handle* h, const unsigned char* mask, int64_t H, int
 int keep_regions_table(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, const int64_t* acc, int64_t* table_out,
                        void* stream);
 
+/* Region shape: second moments and the exact largest diameter of every region.
+ * Replaces: scikit-image's regionprops(...).major_axis_length, by which the CAMELYON16 evaluation sets isolated tumour cells aside,
+ * and the "largest dimension" a pathologist reads off a lesion; integer arithmetic on the device, exact, the same from run to run.
+ * labels: int32 [H,W] as keep_regions_label writes it (a value outside 1..n counts as background), 1 <= H W <= 2^30; table: the
+ * int64 [n,14] table of keep_regions_table ON THE DEVICE, of which only the box (x0, y0, x1, y1) is read.
+ * keep_regions_moments: moments_out int64 [n,3], row i - 1 for label i: sum_uu, sum_vv, sum_uv over the region's pixels with
+ * u = x - x0, v = y - y0 (the box origin; only x0, y0 are read).  A label no pixel carries gives a zero row.  The caller checks
+ * H W max(H, W)^2 < 3 * 2^63, under which no sum leaves int64.  No workspace, no host synchronisation.
+ * keep_regions_feret: needs (H + 1) (W + 1) <= 2^31 as well.  Region i is the union of the closed unit squares of its pixels;
+ * feret_out int64 [n,5], row i - 1: d2, ax, ay, bx, by: the largest squared distance between two corner-lattice points of the
+ * region and the pair that reaches it, a < b in lattice row-major order y (W + 1) + x, the smallest a first, then the smallest b.
+ * A label no pixel carries gives a zero row.  Candidates are the corners of the first and last pixel of every row of the region
+ * (every column where the box is taller than wide): 4 min(bw, bh) per region.  The candidate total and the pair total (the sum of
+ * c^2 / 2 over the regions) are read back once -- the call's one host synchronisation -- and written to totals_out (two int64 ON
+ * THE HOST, may be NULL); more than max_pairs (0 .. 2^50) pairs is KEEP_EINVAL and nothing is computed.  Workspace (16 bytes per
+ * region and 2 bytes per candidate) comes from the handle's arena.  A table that is not the labels' own gives wrong rows, never
+ * a write out of bounds. */
+int keep_regions_moments(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, const int64_t* table,
+                         int64_t* moments_out, void* stream);
+int keep_regions_feret(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, const int64_t* table, int64_t max_pairs,
+                       int64_t* feret_out, int64_t* totals_out, void* stream);
+
 /* Region outlines: the boundary rings of a label image, with holes, and an outline drawn into an image.
  * Replaces: the contour polygons with a hole list per contour that CLAM's segmentTissue hands back (cv2.findContours with
  * RETR_CCOMP; the step of README.md:74) and the polygon annotation a viewer takes a lesion of WSI_evaluation/segment_utils.py's

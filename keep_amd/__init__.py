@@ -14,6 +14,7 @@ from .model import KEEPModel, PROFILE_TAGS
 __all__ = ["KEEPModel", "KEEPShape", "VisionShape", "TextShape", "PROFILE_TAGS",
            "vit_flops_per_tile", "bert_flops_per_prompt"]
 from .lesion import FrocAccumulator, FrocCurve, camelyon16_margin
+from .morphometry import RegionShape, camelyon16_itc_axis
 
-__all__ += ["FrocAccumulator", "FrocCurve", "camelyon16_margin"]
+__all__ += ["FrocAccumulator", "FrocCurve", "camelyon16_margin", "RegionShape", "camelyon16_itc_axis"]
 __version__ = "0.1.0"

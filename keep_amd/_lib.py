@@ -65,6 +65,8 @@ SIGNATURES = {
     "keep_rank_f32": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "keep_regions_label": (_i32, [_vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp]),
     "keep_regions_table": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "keep_regions_moments": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "keep_regions_feret": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, C.POINTER(_i64), _vp]),
     "keep_outline_count": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp]),
     "keep_outline_trace": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "keep_outline_draw": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _vp]),

@@ -88,7 +88,8 @@ class RegionTable:
     mask pixel (None if neither the mask nor the raster said); ``origin``: the level-0 position of pixel (0, 0); ``ids``: the label of
     every row (1..n until :meth:`sort` permutes a copy).  Every column is an attribute (``.area``, ``.x0`` ...: int64 ``[n]`` views of
     the table); ``connectivity``: the connectivity ``mask_regions`` labelled with (None if unknown), which ``region_outlines`` takes as
-    its default.  The methods below convert on the host in float64 and are not part of the integer contract."""
+    its default; ``label_order``: row i - 1 belongs to label i (False for the copy :meth:`sort` returns, and for any table built with its
+    own ``ids``).  The methods below convert on the host in float64 and are not part of the integer contract."""
 
     def __init__(self, table: torch.Tensor, labels: Optional[torch.Tensor] = None, downsample: Optional[int] = None, origin=(0, 0),
                  ids: Optional[torch.Tensor] = None, connectivity: Optional[int] = None):
@@ -98,6 +99,7 @@ class RegionTable:
         self.origin = (int(origin[0]), int(origin[1]))
         self.connectivity = connectivity
         self.ids = torch.arange(1, table.shape[0] + 1, dtype=torch.int64, device=table.device) if ids is None else ids
+        self.label_order = ids is None
         self._host = None
 
     @property

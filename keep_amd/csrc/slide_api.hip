@@ -556,3 +556,71 @@ int keep_lesion_hits(keep_handle* h, const int64_t* xy, const float* scores, int
 }
 
 }  // extern "C"
+
+// Region shape (shape.hip)
+constexpr int64_t FERET_MAX_LATTICE = (int64_t)1 << 31;  // a lattice index y (W + 1) + x fits 32 bits
+constexpr int64_t FERET_MAX_PAIRS = (int64_t)1 << 50;
+// moments: n x 3 words, zeroed here
+void launch_regions_moments(const int* labels, int h, int w, int64_t n, const int64_t* table, int64_t* moments, hipStream_t s);
+size_t feret_plan_bytes(int64_t n);
+// plan: feret_plan_bytes(n) bytes; -> the three totals on the device: candidates, pairs, workgroups
+const int64_t* launch_feret_plan(const int64_t* table, int h, int w, int64_t n, unsigned char* plan, hipStream_t s);
+// lines: 2 total_lines ints after the plan
+void launch_regions_feret(const int* labels, int h, int w, int64_t n, const int64_t* table, const unsigned char* plan, int* lines,
+                          int64_t total_lines, int64_t total_wg, int64_t* feret, hipStream_t s);
+
+extern "C" {
+
+int keep_regions_moments(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, const int64_t* table, int64_t* moments_out,
+                         void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "regions_moments: labels is null or not 4-byte aligned");
+    if (!pixels_ok(H, W, TISSUE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "regions_moments: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (n < 0 || n > H * W) return h->fail(KEEP_EINVAL, "regions_moments: n = %lld outside [0, H W]", (long long)n);
+    if (n > 0 && (!table || ((uintptr_t)table & 7))) return h->fail(KEEP_EINVAL, "regions_moments: table is null or not 8-byte aligned");
+    if (n > 0 && (!moments_out || ((uintptr_t)moments_out & 7))) return h->fail(KEEP_EINVAL, "regions_moments: moments_out is null or not 8-byte aligned");
+    KEEP_ON_DEVICE(h);
+    launch_regions_moments(labels, (int)H, (int)W, n, table, moments_out, (hipStream_t)stream);
+    return check_launch(h, "regions_moments");
+}
+
+int keep_regions_feret(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, const int64_t* table, int64_t max_pairs,
+                       int64_t* feret_out, int64_t* totals_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (totals_out) totals_out[0] = totals_out[1] = 0;
+    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "regions_feret: labels is null or not 4-byte aligned");
+    if (!pixels_ok(H, W, TISSUE_MAX_PIXELS) || (H + 1) * (W + 1) > FERET_MAX_LATTICE)
+        return h->fail(KEEP_EINVAL, "regions_feret: %lldx%lld pixels (1 <= H W <= 2^30 and (H + 1) (W + 1) <= 2^31)", (long long)H, (long long)W);
+    if (n < 0 || n > H * W) return h->fail(KEEP_EINVAL, "regions_feret: n = %lld outside [0, H W]", (long long)n);
+    if (max_pairs < 0 || max_pairs > FERET_MAX_PAIRS) return h->fail(KEEP_EINVAL, "regions_feret: max_pairs %lld outside [0, 2^50]", (long long)max_pairs);
+    if (n > 0 && (!table || ((uintptr_t)table & 7))) return h->fail(KEEP_EINVAL, "regions_feret: table is null or not 8-byte aligned");
+    if (n > 0 && (!feret_out || ((uintptr_t)feret_out & 7))) return h->fail(KEEP_EINVAL, "regions_feret: feret_out is null or not 8-byte aligned");
+    if (n == 0) return KEEP_OK;
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t b_plan = align_up(feret_plan_bytes(n));
+    int rc = ensure_arena(h, b_plan);
+    if (rc) return rc;
+    const int64_t* t_dev = launch_feret_plan(table, (int)H, (int)W, n, (unsigned char*)h->arena, s);
+    rc = check_launch(h, "regions_feret (plan)");
+    if (rc) return rc;
+    int64_t t[3] = {0, 0, 0};
+    HIPCHK(h, hipMemcpyAsync(t, t_dev, sizeof t, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));                      // the one host synchronisation: the totals size the workspace and the grid
+    if (totals_out) { totals_out[0] = t[0]; totals_out[1] = t[1]; }
+    if (t[1] > max_pairs)
+        return h->fail(KEEP_EINVAL, "regions_feret: %lld candidates make %lld pairs, max_pairs is %lld", (long long)t[0], (long long)t[1],
+                       (long long)max_pairs);
+    const char* before = h->arena;
+    rc = ensure_arena(h, b_plan + align_up((size_t)t[0] / 2 * sizeof(int)));   // candidates / 4 lines, two ints each
+    if (rc) return rc;
+    if (h->arena != before) {                                // the arena moved: the plan again, from the same table
+        launch_feret_plan(table, (int)H, (int)W, n, (unsigned char*)h->arena, s);
+        rc = check_launch(h, "regions_feret (plan)");
+        if (rc) return rc;
+    }
+    launch_regions_feret(labels, (int)H, (int)W, n, table, (const unsigned char*)h->arena, (int*)(h->arena + b_plan), t[0] / 4, t[2], feret_out, s);
+    return check_launch(h, "regions_feret");
+}
+
+}  // extern "C"

@@ -13,8 +13,10 @@ the truth dilated by the margin, its holes (4-connected background that touches 
 pixel's value is its mean in 16-bit fixed point, ``m = (2 S + c) // (2 c)``; a pixel is a peak iff it is eligible (covered and inside
 the tissue mask), ``m >= min16`` and no other eligible pixel of its ``(2 r + 1)^2`` window has a larger ``m``, or the same ``m`` and a lower
 row-major index.  A candidate hits the label under it; a lesion's score is the largest ``max(score, 0)`` of its hits.  The FROC
-curve is the published rule of the CAMELYON16 evaluation restated (:func:`froc_numpy`); parity with that script itself is unpinned:
-it is not available here, and its isolated-tumour-cell rule (the major axis length of scikit-image) is replaced by a stated stand-in."""
+curve is the published rule of the CAMELYON16 evaluation restated (:func:`froc_numpy`), and its isolated-tumour-cell rule (a major
+axis length below 275 um) is ``evaluation_mask(ignore_major_axis=)`` on the device's integer moments (``keep_amd.morphometry``,
+DESIGN.md section 21).  Parity with that script itself and with scikit-image's ``major_axis_length`` is unpinned: neither is
+available here."""
 import math
 from typing import Iterable, Optional, Tuple
 

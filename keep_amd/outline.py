@@ -203,13 +203,16 @@ class RegionOutlines:
             raise ValueError("these outlines have no downsample: trace a RegionTable made from a TissueMask or a raster")
         return self.numpy()[1].astype(np.int64) * int(self.downsample) + np.asarray(self.origin, np.int64)
 
-    def to_geojson(self, table: Optional[RegionTable] = None, level0: bool = True, max_n_holes: Optional[int] = None, min_hole_area=0) -> dict:
+    def to_geojson(self, table: Optional[RegionTable] = None, level0: bool = True, max_n_holes: Optional[int] = None, min_hole_area=0,
+                   shape=None) -> dict:
         """A GeoJSON ``FeatureCollection`` (a dict that ``json.dumps`` takes): one ``Polygon`` feature per region that has pixels, in
         label order; its exterior ring first, then the holes that ``max_n_holes`` / ``min_hole_area`` keep (see :meth:`polygons`),
         every ring closed by repeating its first point.  Coordinates are level-0 pixels (``level0=True``, needs a downsample) or mask
         pixels.  ``properties``: ``label``, ``area`` (mask pixels), ``n_holes`` (all of the region's holes, cut or not), ``perimeter``
         (the outer ring's, in pixel sides); with the region's ``RegionTable`` also ``mean_score``, ``peak_score`` (None where no pixel
-        is covered) and ``border``.  Rings keep the orientation of the trace (region on the right with y down).  Under connectivity 8
+        is covered) and ``border``; with the regions' ``keep_amd.morphometry.RegionShape`` (``shape=``, made with its Feret columns)
+        also ``major_axis``, ``minor_axis``, ``feret`` and ``feret_line`` (the two end points of the largest diameter), in the units of
+        the coordinates.  Rings keep the orientation of the trace (region on the right with y down).  Under connectivity 8
         a ring that passes through a diagonal contact touches itself at that vertex; such pinched rings are left as they are, and a
         strict OGC validator may call them self-touching."""
         r, v = self.numpy()
@@ -220,6 +223,15 @@ class RegionOutlines:
             by_label = np.argsort(table.ids.cpu().numpy(), kind="stable")          # a table that sort() permuted still names its labels
             mean, peak = table.mean_score()[by_label], table.peak_score()[by_label]
             border, covered = (table.numpy()[by_label, TABLE_COLUMNS.index(c)] for c in ("border", "covered"))
+        if shape is not None:
+            from .morphometry import RegionShape
+            if not isinstance(shape, RegionShape) or shape.n != self.n or shape.feret is None:
+                raise ValueError(f"shape must be the RegionShape of these {self.n} regions, made with feret=True")
+            if level0:
+                sh = shape.to_level0()
+                axes, feret, line = sh["axis_lengths"], sh["feret"], shape.feret_points() * int(shape.downsample) + np.asarray(shape.origin, np.int64)
+            else:
+                axes, feret, line = shape.axis_lengths(), shape.feret_diameter(), shape.feret_points()
         area, holes, perim = self.area(), self.n_holes(), self.perimeter()
         features = []
         for lab in range(1, self.n + 1):
@@ -235,6 +247,9 @@ class RegionOutlines:
                 props["mean_score"] = float(mean[lab - 1]) if covered[lab - 1] > 0 else None
                 props["peak_score"] = float(peak[lab - 1]) if covered[lab - 1] > 0 else None
                 props["border"] = int(border[lab - 1])
+            if shape is not None:
+                props["major_axis"], props["minor_axis"] = float(axes[lab - 1, 0]), float(axes[lab - 1, 1])
+                props["feret"], props["feret_line"] = float(feret[lab - 1]), line[lab - 1].tolist()
             features.append({"type": "Feature", "properties": props, "geometry": {"type": "Polygon", "coordinates": coords}})
         return {"type": "FeatureCollection", "features": features}
 

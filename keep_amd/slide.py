@@ -1,5 +1,5 @@
 """The slide-analysis methods of ``KEEPModel``: patch grid and tiles of a region, tissue mask, heatmap raster, percentiles and
-smoothing, region table, outlines, polygon fill and segmentation evaluation (DESIGN.md sections 10-17).  Thin wrappers of the
+smoothing, region table, outlines, region shape, polygon fill and segmentation evaluation (DESIGN.md sections 10-21).  Thin wrappers of the
 entry points in csrc/slide_api.hip; the argument checks and the numpy references live in the feature modules imported below."""
 from __future__ import annotations
 
@@ -19,6 +19,7 @@ from .heatmap import (MAX_TILES, ScoreReference, TileRaster, check_cell_args, ch
 from .heatmap import Q_ONE
 from .lesion import (MAX_LABELS, EvaluationMask, LesionCandidates, LesionHits, check_candidates, check_direction, check_peak_args, check_peak_count,
                      check_radius, distance_threshold)
+from .morphometry import DEFAULT_MAX_PAIRS, RegionShape, check_shape_args
 from .outline import NCOLS as RING_COLS, RegionOutlines, check_draw_args, check_outline_args, check_ring_count, regions_labels, rgb_tensor
 from .region import (MASK_MODES, TILE, TissueMask, TissueSegmentation, check_downsample, check_grid_args, grid_shape, otsu_threshold, region_layout,
                      resize_tables, thumbnail_layout, tissue_params)
@@ -416,6 +417,49 @@ class SlideOps:
         self._call("outline_draw", _ptr(lab), h, w, _ptr(x), _ptr(out), packed, width)
         return out
 
+    # ------------------------------------------------------------------ region shape
+    @torch.no_grad()
+    def region_shape(self, regions, feret: bool = True, max_pairs: int = DEFAULT_MAX_PAIRS):
+        """The second moments and the exact largest diameter of every region, on the device ->
+        ``keep_amd.morphometry.RegionShape``: axis lengths, eccentricity, orientation, Feret diameter with its end points and the
+        isolated-cells / micro / macro size class follow from it on the host.
+
+        ``regions``: a ``RegionTable`` that kept its labels, in label order (``mask_regions`` / ``wsi.segment_regions``; not a copy that
+        ``sort`` permuted).  ``moments``: ``sum_uu, sum_vv, sum_uv`` over every region's pixels from its box origin, one pass over the
+        labels, no host synchronisation.  ``feret=True`` adds ``d2, ax, ay, bx, by``: the largest squared distance between two
+        corner-lattice points of the region and the first pair, in lattice row-major order, that reaches it.  Its candidates are the
+        corners of the first and last pixel of every row (or column, along the shorter box side): ``4 min(bw, bh)`` per region; the
+        candidate total and the pair total (the sum of ``c^2 / 2``) are read back once (the one host synchronisation; left in
+        ``last_feret_totals``), and more than ``max_pairs`` pairs is a ValueError.  The label image needs
+        ``h w max(h, w)^2 < 3 * 2^63`` and, with ``feret``, ``(h + 1) (w + 1) <= 2^31``.  Integer arithmetic, equal to
+        ``keep_amd.morphometry.shape_numpy`` exactly and the same from run to run."""
+        if not isinstance(regions, RegionTable):
+            raise ValueError(f"regions must be a RegionTable, got {type(regions).__name__}")
+        if regions.labels is None:
+            raise ValueError("this RegionTable has no labels: call mask_regions with labels=True")
+        if not regions.label_order:
+            raise ValueError("the table's rows are not in label order (a copy that sort() permuted): pass the table mask_regions returned")
+        h, w = int(regions.labels.shape[0]), int(regions.labels.shape[1])
+        max_pairs = check_shape_args(h, w, feret, max_pairs)
+        n = regions.n
+        if n == 0:
+            dev = regions.table.device
+            return RegionShape(torch.empty((0, 3), dtype=torch.int64, device=dev),
+                               torch.empty((0, 5), dtype=torch.int64, device=dev) if feret else None, regions)
+        self._ready_device()
+        lab, table = self._on_device(regions.labels, torch.int32), self._on_device(regions.table, torch.int64)
+        moments = torch.empty((n, 3), dtype=torch.int64, device=self._device)
+        self._call("regions_moments", _ptr(lab), h, w, n, _ptr(table), _ptr(moments))
+        out = None
+        if feret:
+            out = torch.empty((n, 5), dtype=torch.int64, device=self._device)
+            totals = (C.c_int64 * 2)(0, 0)
+            try:
+                self._call("regions_feret", _ptr(lab), h, w, n, _ptr(table), max_pairs, _ptr(out), totals)
+            finally:                                                    # also when the call raises over max_pairs
+                self.last_feret_totals = (int(totals[0]), int(totals[1]))
+        return RegionShape(moments, out, regions)
+
     # ------------------------------------------------------------------ polygon annotations (DESIGN.md section 16)
     @torch.no_grad()
     def fill_polygons(self, polys, downsample: int, shape, origin=(0, 0), rule: str = "union", value: int = 1, into=None) -> torch.Tensor:
@@ -645,14 +689,18 @@ class SlideOps:
 
     @torch.no_grad()
     def evaluation_mask(self, truth, margin_px: float, connectivity: int = 8, fill_holes: bool = True, ignore_max_extent=None,
-                        downsample: Optional[int] = None, shape=None, order=None, rule: str = "union", max_regions: int = 1 << 20):
+                        downsample: Optional[int] = None, shape=None, order=None, rule: str = "union", max_regions: int = 1 << 20,
+                        ignore_major_axis=None):
         """The labelled lesions a detection may hit, as the CAMELYON16 evaluation describes its mask: the truth dilated by
         ``margin_px`` (``keep_amd.lesion.camelyon16_margin``; 0 = as it is), holes filled, labelled with ``connectivity`` ->
         ``keep_amd.lesion.EvaluationMask``.  ``truth``: a ``TissueMask``, or a ``PolygonSet`` with ``downsample=`` and ``shape=`` (through
         :meth:`annotation_mask` with ``order`` / ``rule``).  Holes are the 4-connected background regions that touch no border.
-        ``ignore_max_extent``: lesions whose bounding box's longer side is below it get their ``ignore`` byte set -- a stand-in for the
-        challenge's isolated-tumour-cell rule (a major axis length from float moments), with which no parity is claimed; callers may
-        overwrite ``ignore``.  Two labellings, each with its one readback."""
+        ``ignore_major_axis``: lesions of this labelled mask whose major axis length (``RegionShape.axis_lengths()[:, 0]``, from the
+        device's integer moments; :meth:`region_shape`) is below it get their ``ignore`` byte set: the challenge's
+        isolated-tumour-cell rule, on the mask it is defined on (``keep_amd.morphometry.camelyon16_itc_axis``: 275 um, 35.4 pixels at
+        downsample 32).  ``ignore_max_extent``: the same by the longer side of the bounding box, the rule this method had before
+        the moments; giving both is a ValueError.  Callers may overwrite ``ignore``.  Parity with the challenge's script and with
+        scikit-image is unpinned (neither is available where this is built).  Two labellings, each with its one readback."""
         if isinstance(truth, PolygonSet):
             if downsample is None or shape is None:
                 raise ValueError("a PolygonSet needs downsample= and shape=, the geometry of the evaluation mask")
@@ -661,6 +709,11 @@ class SlideOps:
             raise ValueError(f"truth must be a TissueMask or a PolygonSet, got {type(truth).__name__}")
         if ignore_max_extent is not None and not ignore_max_extent >= 0:
             raise ValueError(f"ignore_max_extent must be >= 0, got {ignore_max_extent!r}")
+        if ignore_major_axis is not None:
+            if ignore_max_extent is not None:
+                raise ValueError("give ignore_major_axis (the challenge's rule) or ignore_max_extent (the bounding-box rule), not both")
+            if not ignore_major_axis >= 0:
+                raise ValueError(f"ignore_major_axis must be >= 0, got {ignore_major_axis!r}")
         grown = self.dilate_mask(truth, margin_px) if margin_px else TissueMask(self._on_device(truth.mask), truth.downsample, truth.mode)
         mask = grown.mask
         if fill_holes:
@@ -671,6 +724,9 @@ class SlideOps:
         ignore = torch.zeros((table.n,), dtype=torch.uint8, device=self._device)
         if ignore_max_extent is not None:
             ignore = (torch.maximum(table.x1 - table.x0, table.y1 - table.y0) < ignore_max_extent).to(torch.uint8)
+        if ignore_major_axis is not None:
+            major = self.region_shape(table, feret=False).axis_lengths()[:, 0]
+            ignore = torch.from_numpy((major < float(ignore_major_axis)).astype(np.uint8)).to(self._device)
         return EvaluationMask(table.labels, table.n, table, ignore, truth.downsample, (0, 0))
 
     @torch.no_grad()

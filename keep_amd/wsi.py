@@ -441,14 +441,16 @@ def segment_lesions(raster, radius, min_score=0.5, tissue=None, max_peaks=1 << 2
 
 
 def eval_seg_froc(slides, margin_px=None, radius=None, min_score=0.5, downsample=None, shape=None, rule="union", ignore_max_extent=None,
-                  model=None):
+                  model=None, ignore_major_axis=None):
     """Lesion-level FROC over slides, the score of a CAMELYON16-style challenge -> ``keep_amd.lesion.FrocCurve`` (``.score``: the mean
     sensitivity at 1/4 ... 8 false positives per slide).  ``slides``: an iterable of ``(raster or candidates, annotation)``: a
     ``TileRaster`` (its peaks are taken with ``radius`` / ``min_score``, see :func:`segment_lesions`) or a ``LesionCandidates``; the
     annotation in the forms :func:`zero_shot_segment` takes.  A ``PolygonSet`` is filled in the raster's geometry (origin 0), or at
     ``downsample`` / ``shape`` beside candidates.  Per slide: ``KEEPModel.evaluation_mask`` (``margin_px`` in mask pixels, default
     ``keep_amd.lesion.camelyon16_margin()``: 75 um at downsample 32 of a 0.243 um slide), ``KEEPModel.lesion_hits``, then one
-    ``FrocAccumulator``.  Parity with the challenge's own script is not claimed."""
+    ``FrocAccumulator``.  ``ignore_major_axis`` (``keep_amd.morphometry.camelyon16_itc_axis()``) sets the lesions aside whose major axis
+    length is below it, the challenge's isolated-tumour-cell rule; ``ignore_max_extent`` is the bounding-box rule; not both.  Parity
+    with the challenge's own script is not claimed (DESIGN.md sections 18 and 21)."""
     from .annotation import PolygonSet
     from .heatmap import TileRaster
     from .lesion import FrocAccumulator, LesionCandidates, camelyon16_margin
@@ -468,9 +470,10 @@ def eval_seg_froc(slides, margin_px=None, radius=None, min_score=0.5, downsample
         else:
             raise ValueError(f"a slide is (TileRaster or LesionCandidates, annotation), got {type(found).__name__}")
         if isinstance(truth, PolygonSet):
-            em = m.evaluation_mask(truth, margin_px, ignore_max_extent=ignore_max_extent, downsample=d, shape=hw, order=order, rule=rule)
+            em = m.evaluation_mask(truth, margin_px, ignore_max_extent=ignore_max_extent, downsample=d, shape=hw, order=order, rule=rule,
+                                   ignore_major_axis=ignore_major_axis)
         else:
-            em = m.evaluation_mask(truth, margin_px, ignore_max_extent=ignore_max_extent)
+            em = m.evaluation_mask(truth, margin_px, ignore_max_extent=ignore_max_extent, ignore_major_axis=ignore_major_axis)
         froc = FrocAccumulator(m) if froc is None else froc
         froc.add(m.lesion_hits(found, em))
     if froc is None:
