@@ -80,12 +80,17 @@ def main():
     ratio = wsi.zero_shot_detection(ens2, feats, coords256, 256, False)
     prob16 = model.similarity(torch.nn.functional.normalize(feats), ens2.t().contiguous(), scale=10.0, mode="softmax_f16")
     seg = wsi.zero_shot_segment(ens2, feats, coords224, None, 224, True)
+    # the subtyping call in slide geometry: where each class sits, how sure it is, the area share of each
+    shape16 = (grid * 256 // 16, grid * 256 // 16)
+    subtype = model.class_map(wsi.subtyping_map(ens, feats, coords256, 16, shape16, 256, True, vote=True))
+    picture = model.render_class_map(subtype, None, strength="top")
     torch.cuda.synchronize()
     t_slide = time.perf_counter() - t0
     if rank == 0:
         print(f"{args.tiles} tiles on {world} GPU(s){' (RCCL process group)' if use_dist else ''}: encode {t_enc:.3f}s ({args.tiles / t_enc:.0f} tiles/s incl. tile generation), "
               f"slide-level steps {t_slide * 1e3:.1f} ms; label={label} tumour_ratio={ratio:.4f} "
-              f"seg_map={len(seg)} tiles, fp16 prob map {tuple(prob16.shape)}")
+              f"seg_map={len(seg)} tiles, fp16 prob map {tuple(prob16.shape)}; subtype map {tuple(picture.shape)}: label by area "
+              f"{subtype.slide_label()}, class areas {subtype.counts().tolist()[:-1]} pixels")
     if use_dist:
         dist.destroy_process_group()
 

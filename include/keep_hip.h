@@ -364,6 +364,42 @@ int keep_regions_moments(keep_handle* h, const int32_t* labels, int64_t H, int64
 int keep_regions_feret(keep_handle* h, const int32_t* labels, int64_t H, int64_t W, int64_t n, const int64_t* table, int64_t max_pairs,
                        int64_t* feret_out, int64_t* totals_out, void* stream);
 
+/* ---- the subtype map ----------------------------------------------------------
+ * Replaces: nothing the reference draws; it gives the subtyping flow of WSI_evaluation/subtyping_utils.py:67-83 (refined tile
+ * probabilities -> argmax -> tile shares -> one slide label) the spatial output the other two flows have.  The class raster `acc`
+ * is int64 [C,H,W] contiguous on the device, 8-byte aligned, 1 <= C <= 64, C H W <= 2^30; plane c is an accumulator of
+ * keep_heat_accumulate (sum of q in bits 0..39, number of tiles in bits 40..63) over the tiles' values of class c.
+ *
+ * keep_heat_accumulate_classes (subtyping_utils.py:67-83: the [U,C] refined probabilities, kept where the reference reduces them):
+ * coords int64 [N,2], values fp32 [N,C] row-major; footprint, quantisation, limits and checks of keep_heat_accumulate; every (tile,
+ * pixel, class) adds (1 << 40) | q_c into plane c.  A tile whose row holds a NaN is skipped in every plane, so the count is the
+ * same in all planes.  It always adds into acc: the caller zeroes a new raster.  Integer sums: the same however the tiles are
+ * split over calls. */
+int keep_heat_accumulate_classes(keep_handle* h, const int64_t* coords, const float* values, int64_t N, int64_t C, int64_t patch,
+                                 int64_t downsample, int64_t H, int64_t W, int64_t origin_x, int64_t origin_y, int64_t* acc, void* stream);
+/* The per-pixel call of subtyping_utils.py:67-83 (`argmax(dim=1)` there per tile, here per pixel over the covering tiles' sums).  With
+ * n = the count of plane 0 and S_c the sums: n = 0, or a zero in mask (uint8 [H,W], may be null), gives label 255 and top = margin
+ * = 0.  Otherwise label = the smallest c with the largest S_c, S_second = the largest S_c over c != label (0 when C = 1), top =
+ * (n << 40) | S_label, margin = (n << 40) | (S_label - S_second), and the label becomes 254 (undecided) iff S_label < min16 n or
+ * S_label - S_second < margin16 n.  0 <= min16, margin16 <= 65535.  label_out uint8 [H,W], top_out / margin_out int64 [H,W] (8-byte
+ * aligned; both are accumulators every keep_heat_* call reads): any may be null, not all. */
+int keep_class_argmax(keep_handle* h, const int64_t* acc, int64_t C, int64_t H, int64_t W, const unsigned char* mask, int min16, int margin16,
+                      unsigned char* label_out, int64_t* top_out, int64_t* margin_out, void* stream);
+/* The confusion of two label maps, the multi-class counterpart of keep_eval_mask_counts for the labels of subtyping_utils.py:67-83.
+ * a, b: uint8 [H,W]; within: uint8 [H,W] or null (non-zero = counted); 1 <= C <= 64, 1 <= H W <= 2^30.  counts_out: int64
+ * [(C + 1)^2], 8-byte aligned, zeroed by the call; counts[i (C + 1) + j] = the pixels inside `within` with a = i and b = j, every
+ * label >= C (254 and 255 among them) counted at index C.  a and b may be the same map: the diagonal then holds the class areas. */
+int keep_class_confusion(keep_handle* h, const unsigned char* a, const unsigned char* b, const unsigned char* within, int64_t H, int64_t W,
+                         int64_t C, int64_t* counts_out, void* stream);
+/* The label map of subtyping_utils.py:67-83's classes as a picture.  labels: uint8 [H,W]; palette: uint8 [C,3]; thumb / row stride /
+ * pixel stride / background_rgb as keep_heat_render.  A pixel with label >= C passes `under` through.  Otherwise a_eff = alpha, or
+ * with strength (an int64 [H,W] accumulator, 8-byte aligned, or null) a_eff = (alpha idx + 127) / 255 with idx the colour index
+ * keep_heat_render gives that word in the window [lo16, hi16] (0 where its count is 0), and out = (a_eff palette[label] +
+ * (256 - a_eff) under + 128) >> 8 per channel.  0 <= alpha <= 256, 0 <= lo16 < hi16 <= 65535.  out: uint8 [H,W,3] contiguous. */
+int keep_class_render(keep_handle* h, const unsigned char* labels, int64_t H, int64_t W, int64_t C, const unsigned char* thumb,
+                      int64_t row_stride_bytes, int pix_stride, int background_rgb, const unsigned char* palette, int alpha,
+                      const int64_t* strength, int lo16, int hi16, unsigned char* out, void* stream);
+
 /* Region outlines: the boundary rings of a label image, with holes, and an outline drawn into an image.
  * Replaces: the contour polygons with a hole list per contour that CLAM's segmentTissue hands back (cv2.findContours with
  * RETR_CCOMP; the step of README.md:74) and the polygon annotation a viewer takes a lesion of WSI_evaluation/segment_utils.py's

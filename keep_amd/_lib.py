@@ -58,6 +58,10 @@ SIGNATURES = {
     "keep_region_grid_mask": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
     "keep_heat_accumulate": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp]),
     "keep_heat_accumulate_cells": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp]),
+    "keep_heat_accumulate_classes": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "keep_class_argmax": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "keep_class_confusion": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "keep_class_render": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
     "keep_heat_mean": (_i32, [_vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "keep_heat_render": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "keep_heat_smooth": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp]),

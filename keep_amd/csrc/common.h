@@ -334,6 +334,21 @@ constexpr int HEAT_SMOOTH_MAX_RADIUS = 127;
 void launch_heat_smooth(const int64_t* acc, int h, int w, const unsigned char* mask, const int* taps, int radius, unsigned* rowa,
                         unsigned short* rowb, int64_t* out, hipStream_t s);
 
+// The subtype map (classmap.hip).  acc: C planes of the accumulator word above, [C][h][w]
+constexpr int CLASS_MAX = 64;                           // one lane of a wave per class
+// adds every tile's footprint into all C planes (integer atomics; the caller zeroes acc when it starts a raster); values fp32 [n][C]
+void launch_class_accumulate(const int64_t* coords, const float* values, int64_t n, int C, int64_t patch, int64_t d, int h, int w, int64_t ox,
+                             int64_t oy, int64_t* acc, hipStream_t s);
+// mask may be null; any of label / top / margin may be null
+void launch_class_argmax(const int64_t* acc, int C, int h, int w, const unsigned char* mask, int min16, int margin16, unsigned char* label,
+                         int64_t* top, int64_t* margin, hipStream_t s);
+// out: int64 [(C + 1)^2], zeroed here; within may be null; a and b may be the same map
+void launch_class_confusion(const unsigned char* a, const unsigned char* b, const unsigned char* within, int h, int w, int C, int64_t* out,
+                            hipStream_t s);
+// thumb null: the constant bg (R | G << 8 | B << 16); strength null: the plain alpha; palette: uint8 [C][3]
+void launch_class_render(const unsigned char* label, int h, int w, int C, const unsigned char* thumb, int64_t row_stride, int ps, unsigned bg,
+                         const unsigned char* palette, int alpha, const int64_t* strength, int lo16, int hi16, unsigned char* out, hipStream_t s);
+
 // Sorted score population and rank percentiles (rank.hip)
 constexpr int SORT_TILE = 4096;                         // keys per block; up to this many are sorted by one block in LDS
 constexpr int SORT_SCAN_CHUNK = 2048;                   // entries of the digit table per block of the scan

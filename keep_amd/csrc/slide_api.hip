@@ -624,3 +624,84 @@ int keep_regions_feret(keep_handle* h, const int32_t* labels, int64_t H, int64_t
 }
 
 }  // extern "C"
+
+// The subtype map (classmap.hip)
+// 1 <= C <= CLASS_MAX, 1 <= H, W and C H W <= 2^30
+static bool class_planes_ok(int64_t C, int64_t H, int64_t W) {
+    return C >= 1 && C <= CLASS_MAX && pixels_ok(H, W, HEAT_MAX_PIXELS) && C * H * W <= HEAT_MAX_PIXELS;
+}
+
+extern "C" {
+
+int keep_heat_accumulate_classes(keep_handle* h, const int64_t* coords, const float* values, int64_t N, int64_t C, int64_t patch,
+                                 int64_t downsample, int64_t H, int64_t W, int64_t origin_x, int64_t origin_y, int64_t* acc, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "heat_accumulate_classes: acc is null or not 8-byte aligned");
+    if (N < 0 || N > HEAT_MAX_TILES) return h->fail(KEEP_EINVAL, "heat_accumulate_classes: %lld tiles (0 .. 2^24 - 1)", (long long)N);
+    if (N > 0 && (!coords || !values)) return h->fail(KEEP_EINVAL, "heat_accumulate_classes: null coords or values");
+    if (((uintptr_t)coords & 7) || ((uintptr_t)values & 3)) return h->fail(KEEP_EINVAL, "heat_accumulate_classes: coords / values not aligned");
+    if (!class_planes_ok(C, H, W))
+        return h->fail(KEEP_EINVAL, "heat_accumulate_classes: %lld planes of %lldx%lld (1 <= C <= 64, 1 <= C H W <= 2^30)", (long long)C, (long long)H,
+                       (long long)W);
+    if (patch < 1 || patch > HEAT_MAX_PATCH) return h->fail(KEEP_EINVAL, "heat_accumulate_classes: patch %lld outside [1, 2^30]", (long long)patch);
+    if (downsample < 1 || downsample > patch)
+        return h->fail(KEEP_EINVAL, "heat_accumulate_classes: downsample %lld outside [1, patch = %lld]", (long long)downsample, (long long)patch);
+    if (int rc = origin_check(h, "heat_accumulate_classes", origin_x, origin_y)) return rc;
+    if (origin_x % downsample || origin_y % downsample)
+        return h->fail(KEEP_EINVAL, "heat_accumulate_classes: origin (%lld, %lld) is not a multiple of downsample %lld", (long long)origin_x,
+                       (long long)origin_y, (long long)downsample);
+    KEEP_ON_DEVICE(h);
+    launch_class_accumulate(coords, values, N, (int)C, patch, downsample, (int)H, (int)W, origin_x, origin_y, acc, (hipStream_t)stream);
+    return check_launch(h, "heat_accumulate_classes");
+}
+
+int keep_class_argmax(keep_handle* h, const int64_t* acc, int64_t C, int64_t H, int64_t W, const unsigned char* mask, int min16, int margin16,
+                      unsigned char* label_out, int64_t* top_out, int64_t* margin_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "class_argmax: acc is null or not 8-byte aligned");
+    if (!class_planes_ok(C, H, W))
+        return h->fail(KEEP_EINVAL, "class_argmax: %lld planes of %lldx%lld (1 <= C <= 64, 1 <= C H W <= 2^30)", (long long)C, (long long)H, (long long)W);
+    if (min16 < 0 || min16 > 65535 || margin16 < 0 || margin16 > 65535)
+        return h->fail(KEEP_EINVAL, "class_argmax: min16 %d / margin16 %d outside [0, 65535]", min16, margin16);
+    if (!label_out && !top_out && !margin_out) return h->fail(KEEP_EINVAL, "class_argmax: no output");
+    if (((uintptr_t)top_out & 7) || ((uintptr_t)margin_out & 7)) return h->fail(KEEP_EINVAL, "class_argmax: top_out / margin_out not 8-byte aligned");
+    KEEP_ON_DEVICE(h);
+    launch_class_argmax(acc, (int)C, (int)H, (int)W, mask, min16, margin16, label_out, top_out, margin_out, (hipStream_t)stream);
+    return check_launch(h, "class_argmax");
+}
+
+int keep_class_confusion(keep_handle* h, const unsigned char* a, const unsigned char* b, const unsigned char* within, int64_t H, int64_t W,
+                         int64_t C, int64_t* counts_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!a || !b) return h->fail(KEEP_EINVAL, "class_confusion: a label map is null");
+    if (!pixels_ok(H, W, TISSUE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "class_confusion: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (C < 1 || C > CLASS_MAX) return h->fail(KEEP_EINVAL, "class_confusion: %lld classes (1 .. 64)", (long long)C);
+    if (!counts_out || ((uintptr_t)counts_out & 7)) return h->fail(KEEP_EINVAL, "class_confusion: counts_out is null or not 8-byte aligned");
+    KEEP_ON_DEVICE(h);
+    launch_class_confusion(a, b, within, (int)H, (int)W, (int)C, counts_out, (hipStream_t)stream);
+    return check_launch(h, "class_confusion");
+}
+
+int keep_class_render(keep_handle* h, const unsigned char* labels, int64_t H, int64_t W, int64_t C, const unsigned char* thumb,
+                      int64_t row_stride_bytes, int pix_stride, int background_rgb, const unsigned char* palette, int alpha,
+                      const int64_t* strength, int lo16, int hi16, unsigned char* out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!labels || !palette || !out) return h->fail(KEEP_EINVAL, "class_render: null labels, palette or output");
+    if (!pixels_ok(H, W, HEAT_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "class_render: %lldx%lld pixels (1 <= H W <= 2^30)", (long long)H, (long long)W);
+    if (C < 1 || C > CLASS_MAX) return h->fail(KEEP_EINVAL, "class_render: %lld classes (1 .. 64)", (long long)C);
+    if (thumb) {
+        if (int rc = pix_stride_check(h, "class_render", pix_stride)) return rc;
+        if (int rc = row_stride_check(h, "class_render", W, row_stride_bytes, pix_stride)) return rc;
+    } else if (background_rgb < 0 || background_rgb > 0xFFFFFF) {
+        return h->fail(KEEP_EINVAL, "class_render: background 0x%x outside [0, 0xFFFFFF]", background_rgb);
+    }
+    if (alpha < 0 || alpha > 256) return h->fail(KEEP_EINVAL, "class_render: alpha %d outside [0, 256]", alpha);
+    if ((uintptr_t)strength & 7) return h->fail(KEEP_EINVAL, "class_render: strength is not 8-byte aligned");
+    if (lo16 < 0 || hi16 > 65535 || lo16 >= hi16) return h->fail(KEEP_EINVAL, "class_render: window [%d, %d] (0 <= lo16 < hi16 <= 65535)", lo16, hi16);
+    KEEP_ON_DEVICE(h);
+    launch_class_render(labels, (int)H, (int)W, (int)C, thumb, row_stride_bytes, pix_stride, (unsigned)background_rgb, palette, alpha, strength, lo16,
+                        hi16, out, (hipStream_t)stream);
+    return check_launch(h, "class_render");
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 """The slide-analysis methods of ``KEEPModel``: patch grid and tiles of a region, tissue mask, heatmap raster, percentiles and
-smoothing, region table, outlines, region shape, polygon fill and segmentation evaluation (DESIGN.md sections 10-21).  Thin wrappers of the
+smoothing, region table, outlines, region shape, polygon fill, segmentation evaluation and the subtype map (DESIGN.md sections 10-22).  Thin wrappers of the
 entry points in csrc/slide_api.hip; the argument checks and the numpy references live in the feature modules imported below."""
 from __future__ import annotations
 
@@ -12,6 +12,8 @@ import torch
 
 from . import _lib
 from .annotation import PolygonSet, check_fill_args, check_into, check_tile_args, polygon_arrays
+from .classmap import (ClassMap, ClassRaster, check_class_names, check_class_tiles, check_classes, check_label_map, check_labels, check_palette,
+                       class_map_args)
 from .components import NCOLS as REGION_COLS, RegionTable, check_raster, check_region_count, check_regions_args, mask_tensor
 from .evaluation import HIST_BINS, MaskOverlap, RocResult, check_mask, check_roc_args, check_same_geometry, plan_label_bands, sweep_from_hist
 from .heatmap import (MAX_TILES, ScoreReference, TileRaster, check_cell_args, check_cells, check_raster_args, check_tiles, check_values,
@@ -333,6 +335,170 @@ class SlideOps:
         out = torch.empty((h, w), dtype=torch.int64, device=self._device)
         self._call("heat_smooth", _ptr(raster.acc), h, w, _ptr(md), _ptr(td), t.size // 2, _ptr(out))
         return TileRaster(out, raster.downsample, raster.patch, raster.origin, raster.tiles, self)
+
+    # ------------------------------------------------------------------ subtype map
+    @torch.no_grad()
+    def class_raster(self, coords, values, patch_size: int, downsample: int, shape, origin=(0, 0), into=None, labels=None, n_classes=None,
+                     classes=None):
+        """Per-tile class values rasterised in slide geometry, all classes in one launch ->
+        ``keep_amd.classmap.ClassRaster``.
+
+        ``coords``: integers [N,2] as in :meth:`tile_raster`; ``values``: floating point [N,C], ``1 <= C <= 64`` (the refined
+        probabilities of ``wsi.refine``); the geometry arguments are :meth:`tile_raster`'s, with ``C h w <= 2^30``.  Plane c of the result
+        is exactly ``tile_raster(coords, values[:, c], ...)`` over the tiles whose row holds no NaN: a NaN anywhere in a row skips the
+        tile in every plane, so all planes count the same tiles.  ``labels``: integers [N] given INSTEAD of ``values`` (``values=None``),
+        every one in ``0 .. C - 1`` (checked on the host: one read of their range), expanded to one-hot rows on the device: a vote
+        raster.  C is then ``n_classes``, the number of ``classes`` (optional names, kept on the result) or that of ``into``.
+        ``into``: an earlier ``ClassRaster`` of the same geometry and C to add to; the result is the same however the tiles are split
+        over calls.  At most 2^24 - 1 tiles go into one raster."""
+        patch, d, (h, w), origin = check_raster_args(patch_size, downsample, shape, origin)
+        if (values is None) == (labels is None):
+            raise ValueError("give values= [N,C] or labels= [N], one of the two")
+        if into is not None and not isinstance(into, ClassRaster):
+            raise ValueError(f"into must be a ClassRaster, got {type(into).__name__}")
+        names = check_class_names(classes)
+        c = coords if isinstance(coords, torch.Tensor) else torch.as_tensor(coords)
+        if values is not None:
+            v = values if isinstance(values, torch.Tensor) else torch.as_tensor(values)
+            N, C = check_class_tiles(c, v)
+            if n_classes is not None and check_classes(n_classes) != C:
+                raise ValueError(f"n_classes is {n_classes}, values has {C} columns")
+        else:
+            given = [k for k in (n_classes, None if names is None else len(names), None if into is None else into.n_classes) if k is not None]
+            if not given or any(k != given[0] for k in given):
+                raise ValueError("labels= needs the number of classes: n_classes=, classes= or into= (and they must agree)")
+            C = check_classes(given[0])
+            l = labels if isinstance(labels, torch.Tensor) else torch.as_tensor(labels)
+            N = check_labels(c, l, C)
+        check_class_names(names, C)
+        check_classes(C, (h, w))
+        if into is not None:
+            into.check_geometry(C, patch, d, (h, w), origin)
+            into.claim(N)                                           # raises beyond the cap, before any device work
+        elif N > MAX_TILES:
+            raise ValueError(f"a raster takes at most 2^24 - 1 = {MAX_TILES} tiles in all, got {N}")
+        try:
+            self._ready_device()
+            if into is not None and into.acc.device != self._device:
+                raise ValueError(f"into= raster lives on {into.acc.device}, this engine on {self._device}")
+        except Exception:
+            if into is not None:
+                into.tiles -= N
+            raise
+        if into is None:
+            into = ClassRaster(torch.zeros((C, h, w), dtype=torch.int64, device=self._device), d, patch, origin, N, names, self)
+        c = c.to(self._device, torch.int64).contiguous()
+        if values is not None:
+            v = v.to(self._device, torch.float32).contiguous()
+        else:
+            v = torch.zeros((N, C), dtype=torch.float32, device=self._device)
+            v.scatter_(1, l.to(self._device, torch.int64).reshape(N, 1), 1.0)
+        self._call("heat_accumulate_classes", _ptr(c), _ptr(v), N, C, patch, d, h, w, origin[0], origin[1], _ptr(into.acc))
+        return into
+
+    @torch.no_grad()
+    def class_map(self, raster, tissue=None, min_value: float = 0.0, min_margin: float = 0.0):
+        """The per-pixel call of a ``ClassRaster`` -> ``keep_amd.classmap.ClassMap``.
+
+        With n the number of tiles over a pixel and S_c the planes' sums there: the label is the smallest c with the largest S_c (the
+        argmax of the means, ties to the lowest class), 255 where n = 0 or outside ``tissue`` (a ``TissueMask`` of the raster's
+        geometry), and 254 where the winner's mean is below ``min_value`` or its lead over the runner-up below ``min_margin`` (both in
+        16-bit fixed point, compared as ``S < t16 * n``).  ``.top`` and ``.margin`` hold the winner's sum and its lead as
+        ``TileRaster``s.  Equal to ``keep_amd.classmap.class_argmax_numpy`` exactly; no host synchronisation."""
+        if not isinstance(raster, ClassRaster):
+            raise ValueError(f"raster must be a ClassRaster, got {type(raster).__name__}")
+        min16, margin16 = class_map_args(min_value, min_margin)
+        if tissue is not None:
+            _check_tissue(tissue, raster)
+        self._ready_device()
+        self._raster_here(raster)
+        C, (h, w) = raster.n_classes, raster.shape
+        md = None if tissue is None else self._on_device(tissue.mask)
+        labels = torch.empty((h, w), dtype=torch.uint8, device=self._device)
+        top, margin = (torch.empty((h, w), dtype=torch.int64, device=self._device) for _ in range(2))
+        self._call("class_argmax", _ptr(raster.acc), C, h, w, _ptr(md), min16, margin16, _ptr(labels), _ptr(top), _ptr(margin))
+        as_raster = lambda acc: TileRaster(acc, raster.downsample, raster.patch, raster.origin, raster.tiles, self)
+        return ClassMap(labels, as_raster(top), as_raster(margin), raster, self)
+
+    @torch.no_grad()
+    def label_confusion(self, a, b, n_classes: int, within=None) -> torch.Tensor:
+        """The confusion of two label maps on the device -> int64 ``[C+1, C+1]`` on the device: entry (i, j)
+        counts the pixels inside ``within`` with ``a = i`` and ``b = j``; every label ``>= C`` (254 and 255 among them) goes to index C.
+        ``a``, ``b``: uint8 ``[h,w]`` of one shape, numpy or torch, host or device, or ``ClassMap``s; ``within``: bool / uint8 ``[h,w]`` or a
+        ``TissueMask``.  ``keep_amd.classmap.overlap_from_confusion`` reads Dice, IoU, precision and recall per class off it.  Equal to
+        ``keep_amd.classmap.confusion_numpy`` exactly; no host synchronisation."""
+        C = check_classes(n_classes)
+        a = check_label_map(a, "a")
+        shape = (int(a.shape[0]), int(a.shape[1]))
+        b = check_label_map(b, "b", shape)
+        within = None if within is None else check_mask(within, "within", shape)
+        self._ready_device()
+        a, b, within = self._on_device(a), self._on_device(b), (None if within is None else self._on_device(within))
+        out = torch.empty((C + 1, C + 1), dtype=torch.int64, device=self._device)
+        self._call("class_confusion", _ptr(a), _ptr(b), _ptr(within), shape[0], shape[1], C, _ptr(out))
+        return out
+
+    @torch.no_grad()
+    def annotation_label_map(self, polygon_sets, downsample: int, shape, order=None, rule: str = "union") -> torch.Tensor:
+        """One ``PolygonSet`` per class -> a uint8 ``[h,w]`` label map on the device: class c where set c covers the pixel
+        (:meth:`annotation_mask` of that set, with the same ``order`` / ``rule``), later sets painted over earlier ones, 255 where no
+        set covers it.  What a multi-class ground truth is compared as in :meth:`label_confusion`."""
+        sets = list(polygon_sets)
+        check_classes(len(sets))
+        for p in sets:
+            if not isinstance(p, PolygonSet):
+                raise ValueError(f"polygon_sets must hold PolygonSets, got {type(p).__name__}")
+        check_fill_args(downsample, shape, (0, 0), rule, 1)
+        out = None
+        for c, p in enumerate(sets):
+            m = self.annotation_mask(p, downsample, shape, order, rule).mask
+            if out is None:
+                out = torch.full_like(m, 255)
+            out = torch.where(m != 0, torch.full_like(m, c), out)
+        return out
+
+    @torch.no_grad()
+    def render_class_map(self, cm, thumbnail=None, alpha: float = 0.5, palette=None, strength=None, window=(0.0, 1.0),
+                         background=(255, 255, 255)) -> torch.Tensor:
+        """A label map painted with a palette over the thumbnail -> uint8 [h,w,3] on the device.
+
+        ``cm``: a ``ClassMap``; ``thumbnail`` / ``background`` / ``alpha`` as in :meth:`render_heatmap`; ``palette``: uint8 [C,3]
+        (default ``keep_amd.classmap.palette(C)``).  Pixels labelled 254 or 255 show the underlay.  ``strength``: ``"margin"`` or
+        ``"top"`` (the map's own rasters) or a ``TileRaster`` of its shape: its mean, windowed by ``window`` to 0..255 with
+        :meth:`render_heatmap`'s index rule, scales alpha: ``a_eff = (a idx + 127) // 255``, so a confident call is painted stronger.
+        Equal to ``keep_amd.classmap.class_render_numpy`` exactly."""
+        if not isinstance(cm, ClassMap):
+            raise ValueError(f"cm must be a ClassMap, got {type(cm).__name__}")
+        a, lo16, hi16, _, bg = render_args(alpha, window, 0.0, background)
+        h, w = cm.shape
+        pal_host = check_palette(palette, cm.n_classes)
+        if isinstance(strength, str):
+            if strength not in ("margin", "top"):
+                raise ValueError(f"strength must be 'margin', 'top' or a TileRaster, got {strength!r}")
+            strength = cm.margin if strength == "margin" else cm.top
+        if strength is not None:
+            _check_tile_raster(strength)
+            if strength.shape != (h, w):
+                raise ValueError(f"strength is {strength.shape}, the label map {(h, w)}")
+        x = None
+        if thumbnail is not None:
+            x = torch.from_numpy(thumbnail) if not isinstance(thumbnail, torch.Tensor) else thumbnail
+            if region_layout(x)[:2] != (h, w):
+                raise ValueError(f"thumbnail is {tuple(x.shape[:2])}, the label map {(h, w)}")
+        self._ready_device()
+        if strength is not None:
+            self._raster_here(strength)
+        labels = self._on_device(cm.labels)
+        pal = torch.from_numpy(pal_host).to(self._device)
+        ps, row = 3, 0
+        if x is not None:
+            if x.device != self._device:
+                x = x.to(self._device)
+            _, _, ps, row = region_layout(x)
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=self._device)
+        self._call("class_render", _ptr(labels), h, w, cm.n_classes, _ptr(x), row, ps, bg[0] | bg[1] << 8 | bg[2] << 16, _ptr(pal), a,
+                   _ptr(None if strength is None else strength.acc), lo16, hi16, _ptr(out))
+        return out
 
     # ------------------------------------------------------------------ region table (DESIGN.md section 13)
     @torch.no_grad()

@@ -574,3 +574,50 @@ def segment_pred_mask(probs, thd, downsample, shape, patch_size=224, origin=(0, 
     m = _engine(model, p, coords)
     above = (p.to(m._device).to(torch.float32) > torch.tensor(float(thd), dtype=torch.float32, device=m._device)).to(torch.float32)
     return m.tile_raster(coords, above, patch_size, downsample, shape, origin).pred()
+
+
+# ------------------------------------------------------------------------------------------------ subtype map
+def subtyping_map(classifier, tile_features, tile_coords, downsample, shape, patch_size=256, overlap=True, origin=(0, 0), vote=False,
+                  classes=None, model=None):
+    """The subtyping flow (subtyping_utils.py:67-83) ending in slide geometry instead of one label: ``_probs`` -> :func:`refine`, as
+    :func:`zero_shot_subtyping` does, then ``KEEPModel.class_raster`` over the refined ``[U,C]`` probabilities ->
+    ``keep_amd.classmap.ClassRaster`` (``KEEPModel.class_map`` makes the per-pixel call of it, ``render_class_map`` the picture).
+    ``vote=True`` rasterises the tiles' argmax labels instead (one-hot rows): every pixel then counts the votes of its tiles, and on
+    tiles that do not overlap the area shares of the label map are the tile shares of :func:`zero_shot_subtyping`.  ``classes``:
+    optional names, one per column of the classifier.  ``downsample`` / ``shape`` / ``origin``: the raster's geometry."""
+    from .classmap import check_class_names, check_classes
+    from .heatmap import check_raster_args
+    _, _, shape, _ = check_raster_args(patch_size, downsample, shape, origin)
+    C_ = check_classes(classifier.shape[1], shape)
+    classes = check_class_names(classes, C_)
+    m = _engine(model, tile_features, classifier)
+    if isinstance(tile_coords, torch.Tensor):
+        tile_coords = tile_coords.cpu()                             # refine checks the coordinate range on the host
+    coords, mean, _ = refine(_probs(m, classifier, tile_features), tile_coords, patch_size, overlap, model=m)
+    if vote:
+        return m.class_raster(coords, None, patch_size, downsample, shape, origin, labels=mean.argmax(dim=1), n_classes=C_, classes=classes)
+    return m.class_raster(coords, mean, patch_size, downsample, shape, origin, classes=classes)
+
+
+def subtype_regions(class_map, tissue=None, connectivity=8, min_area=1, model=None):
+    """The region table of every class of a label map -> ``{c: keep_amd.components.RegionTable}``: the connected regions of the pixels
+    labelled c (inside ``tissue``, a ``TissueMask`` of the map's geometry, optional), scored on the class's own plane of the
+    ``ClassRaster`` the map came from, so a region's mean and peak are its own class's."""
+    from .classmap import ClassMap
+    from .region import TissueMask
+    if not isinstance(class_map, ClassMap):
+        raise ValueError(f"class_map must be a ClassMap, got {type(class_map).__name__}")
+    if tissue is not None:
+        if not isinstance(tissue, TissueMask):
+            raise ValueError(f"tissue must be a TissueMask, got {type(tissue).__name__}")
+        if tissue.downsample != class_map.downsample or tuple(tissue.mask.shape) != class_map.shape:
+            raise ValueError(f"tissue mask has downsample {tissue.downsample} and shape {tuple(tissue.mask.shape)}, the label map "
+                             f"{class_map.downsample} and {class_map.shape}")
+    m = _engine(model, class_map.labels)
+    out = {}
+    for c in range(class_map.n_classes):
+        mask = class_map.mask(c)
+        if tissue is not None:
+            mask = mask * (tissue.mask.to(mask.device) != 0).to(torch.uint8)
+        out[c] = m.mask_regions(mask, connectivity, min_area, raster=class_map.raster.plane(c))
+    return out
