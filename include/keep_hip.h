@@ -400,6 +400,42 @@ int keep_class_render(keep_handle* h, const unsigned char* labels, int64_t H, in
                       int64_t row_stride_bytes, int pix_stride, int background_rgb, const unsigned char* palette, int alpha,
                       const int64_t* strength, int lo16, int hi16, unsigned char* out, void* stream);
 
+/* ---- tile clustering -------------------------------------------------------------
+ * Replaces: nothing in the reference, which has no unsupervised path; on this engine the host round trip keep_similarity(ARGMAX) +
+ * an index_add of the feature rows + a normalise, which reads the features twice per iteration, writes an [N,K] matrix and sums the
+ * centroids in float in arrival order.  Spherical k-means: features fp32 [N,D] row-major unit rows, centroids fp32 [K,D] unit rows,
+ * both 16-byte aligned; 1 <= N <= 2^22 per call, D a multiple of 16 in 16 .. 1024, 1 <= K <= 64 (every result fits a class raster);
+ * at most 2^24 rows may be added into one set of accumulators (2^30 2^24 = 2^54 fits the word).  Anything else is KEEP_EINVAL and
+ * nothing is launched.
+ *
+ * keep_cluster_assign: score = x . c as a k-ordered fp32 fma chain (v_mfma_f32_16x16x4_f32) whose order does not depend on N, on the
+ * row's position or on the split over calls.  label_out int32 [N]: the smallest k with the largest score; best_out fp32 [N]: that
+ * score; margin_out fp32 [N]: best minus the largest score of the other centroids (0 when K = 1).  A row holding a non-finite value
+ * or an element with |x| > 1 is skipped: label -1, best = margin = 0, one added to *skipped, absent from every sum.  *changed +=
+ * the rows with label != prev_label[row] (prev_label int32 [N]; it may be label_out).  With accumulators the same launch adds every
+ * kept row: sums int64 [K,D] += llrint(x 2^30) into row `label`, counts int64 [K] += 1, *cos_sum += llrint(best 2^30).  Integer
+ * sums: the same words however the rows are ordered or split over calls.  The call ALWAYS ADDS into skipped, changed, sums, counts
+ * and cos_sum (int64, 8-byte aligned, on the device): the caller zeroes them.  May be null: best_out, margin_out, skipped; changed
+ * and prev_label (both or neither); sums, counts and cos_sum (all or none); label_out when the accumulators are given.
+ * two_launch = 1 runs the accumulate as a second launch over label_out / best_out (both then required): the same words, kept for
+ * measurement (tools/cluster_bench.py).
+ * keep_cluster_update: centroids[k] = (float)(s / sqrt(sum s^2)) with s_d = (double)sums[k,d] 2^-30, in fp64.  A cluster with
+ * counts[k] = 0 or a zero sum keeps its row of `centroids` bit for bit; empty_out uint8 [K] (may be null) is written 1 for those, 0 for
+ * the others.  One launch; sums and counts are only read.
+ * keep_cluster_seed_step: one step of farthest-point seeding.  The centre is `centre` (fp32 [D], 16-byte aligned) or, with centre
+ * null, row *centre_row of features (one int64 ON THE DEVICE, e.g. the index_out of the step before; clamped into 0 .. N - 1).
+ * first = 0: nearest[r] = max(nearest[r], x_r . c) (fp32 [N], the caller starts it at -inf) and *index_out = the row with the smallest
+ * nearest, the lowest row on a tie.  first = 1: nearest is not touched (may be null) and *index_out = the row with the LARGEST x_r . c,
+ * the lowest row on a tie.  Skipped rows (the rule above) take no part and keep their nearest; with every row skipped *index_out =
+ * -1.  index_out: one int64 ON THE DEVICE.  No host synchronisation; workspace: 8 bytes of the handle's arena. */
+int keep_cluster_assign(keep_handle* h, const float* features, int64_t N, int64_t D, const float* centroids, int64_t K, int32_t* label_out,
+                        float* best_out, float* margin_out, const int32_t* prev_label, int64_t* skipped, int64_t* changed, int64_t* sums,
+                        int64_t* counts, int64_t* cos_sum, int two_launch, void* stream);
+int keep_cluster_update(keep_handle* h, const int64_t* sums, const int64_t* counts, int64_t K, int64_t D, float* centroids,
+                        unsigned char* empty_out, void* stream);
+int keep_cluster_seed_step(keep_handle* h, const float* features, int64_t N, int64_t D, const float* centre, const int64_t* centre_row, int first,
+                           float* nearest, int64_t* index_out, void* stream);
+
 /* Region outlines: the boundary rings of a label image, with holes, and an outline drawn into an image.
  * Replaces: the contour polygons with a hole list per contour that CLAM's segmentTissue hands back (cv2.findContours with
  * RETR_CCOMP; the step of README.md:74) and the polygon annotation a viewer takes a lesion of WSI_evaluation/segment_utils.py's

@@ -62,7 +62,10 @@ SIGNATURES = {
     "keep_class_argmax": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "keep_class_confusion": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "keep_class_render": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
-    "keep_heat_mean": (_i32, [_vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "keep_cluster_assign": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "keep_cluster_update": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "keep_cluster_seed_step": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "keep_heat_mean":(_i32, [_vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "keep_heat_render": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "keep_heat_smooth": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp]),
     "keep_sort_f32": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),

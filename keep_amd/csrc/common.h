@@ -349,6 +349,21 @@ void launch_class_confusion(const unsigned char* a, const unsigned char* b, cons
 void launch_class_render(const unsigned char* label, int h, int w, int C, const unsigned char* thumb, int64_t row_stride, int ps, unsigned bg,
                          const unsigned char* palette, int alpha, const int64_t* strength, int lo16, int hi16, unsigned char* out, hipStream_t s);
 
+// Tile clustering (cluster.hip).  x: fp32 [N][D] unit rows, cen: fp32 [K][D]; sums int64 [K][D], counts int64 [K]
+constexpr int CLUSTER_MAX_K = 64;                       // every result fits a class raster (CLASS_MAX)
+constexpr int CLUSTER_MAX_D = 1024;                     // four columns per thread of the accumulate walk
+constexpr int64_t CLUSTER_MAX_ROWS = (int64_t)1 << 22;  // per call; 2^24 rows of |x| 2^30 <= 2^30 fit an int64 sum with room to spare
+constexpr int CLUSTER_MAX_GROUPS = 4;                   // groups of 64 rows per workgroup
+// label / best / margin / prev / skipped / changed may be null; sums, counts and cos_sum all or none; two_launch (with sums) needs label
+// and best.  Everything is added into skipped / changed / sums / counts / cos_sum: the caller zeroes them.
+void launch_cluster_assign(const float* x, int N, int D, const float* cen, int K, int32_t* label, float* best, float* margin, const int32_t* prev,
+                           int64_t* skipped, int64_t* changed, int64_t* sums, int64_t* counts, int64_t* cos_sum, int two_launch, hipStream_t s);
+// empty: uint8 [K], may be null
+void launch_cluster_update(const int64_t* sums, const int64_t* counts, int K, int D, float* cen, unsigned char* empty, hipStream_t s);
+// centre fp32 [D], or null and centre_row one int64 on the device; ws: 8 bytes
+void launch_cluster_seed_step(const float* x, int N, int D, const float* centre, const int64_t* centre_row, int first, float* nearest,
+                              unsigned char* ws, int64_t* index_out, hipStream_t s);
+
 // Sorted score population and rank percentiles (rank.hip)
 constexpr int SORT_TILE = 4096;                         // keys per block; up to this many are sorted by one block in LDS
 constexpr int SORT_SCAN_CHUNK = 2048;                   // entries of the digit table per block of the scan

@@ -1,5 +1,5 @@
 // The slide-geometry entry points of include/keep_hip.h: patch grid, tissue mask, heatmap, sort / rank, region table, outlines, polygon
-// fill and segmentation evaluation.  Host code only: each function validates its arguments, carves its workspace from the handle's
+// fill, segmentation evaluation, the subtype map and tile clustering.  Host code only: each function validates its arguments, carves its workspace from the handle's
 // arena, calls the launch_* of its kernel file (region / tissue / heatmap / rank / components / outline / annotation / eval .hip) and
 // reports the launch.  Of the handle (handle.h) they use the device, the error text, the arena and the sticky error flag.
 #include "handle.h"
@@ -702,6 +702,69 @@ int keep_class_render(keep_handle* h, const unsigned char* labels, int64_t H, in
     launch_class_render(labels, (int)H, (int)W, (int)C, thumb, row_stride_bytes, pix_stride, (unsigned)background_rgb, palette, alpha, strength, lo16,
                         hi16, out, (hipStream_t)stream);
     return check_launch(h, "class_render");
+}
+
+}  // extern "C"
+
+// Tile clustering (cluster.hip)
+static int cluster_shape_check(keep_handle* h, const char* who, int64_t N, int64_t D, int64_t K) {
+    if (N < 1 || N > CLUSTER_MAX_ROWS) return h->fail(KEEP_EINVAL, "%s: %lld rows (1 .. 2^22 per call)", who, (long long)N);
+    if (D < 16 || D > CLUSTER_MAX_D || D % 16) return h->fail(KEEP_EINVAL, "%s: D = %lld (a multiple of 16, 16 .. 1024)", who, (long long)D);
+    if (K < 1 || K > CLUSTER_MAX_K) return h->fail(KEEP_EINVAL, "%s: K = %lld (1 .. 64)", who, (long long)K);
+    return KEEP_OK;
+}
+
+extern "C" {
+
+int keep_cluster_assign(keep_handle* h, const float* features, int64_t N, int64_t D, const float* centroids, int64_t K, int32_t* label_out,
+                        float* best_out, float* margin_out, const int32_t* prev_label, int64_t* skipped, int64_t* changed, int64_t* sums,
+                        int64_t* counts, int64_t* cos_sum, int two_launch, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = cluster_shape_check(h, "cluster_assign", N, D, K)) return rc;
+    if (!features || !centroids) return h->fail(KEEP_EINVAL, "cluster_assign: null features or centroids");
+    if (((uintptr_t)features & 15) || ((uintptr_t)centroids & 15)) return h->fail(KEEP_EINVAL, "cluster_assign: features / centroids not 16-byte aligned");
+    const int nacc = (sums ? 1 : 0) + (counts ? 1 : 0) + (cos_sum ? 1 : 0);
+    if (nacc != 0 && nacc != 3) return h->fail(KEEP_EINVAL, "cluster_assign: sums, counts and cos_sum go together (%d of 3 given)", nacc);
+    if (!label_out && !sums) return h->fail(KEEP_EINVAL, "cluster_assign: no output (label_out and the accumulators are both null)");
+    if ((changed != nullptr) != (prev_label != nullptr)) return h->fail(KEEP_EINVAL, "cluster_assign: changed and prev_label go together");
+    if (two_launch != 0 && two_launch != 1) return h->fail(KEEP_EINVAL, "cluster_assign: two_launch %d (0 or 1)", two_launch);
+    if (two_launch && sums && (!label_out || !best_out)) return h->fail(KEEP_EINVAL, "cluster_assign: the two-launch form reads label_out and best_out");
+    if (((uintptr_t)label_out & 3) || ((uintptr_t)best_out & 3) || ((uintptr_t)margin_out & 3) || ((uintptr_t)prev_label & 3) ||
+        ((uintptr_t)skipped & 7) || ((uintptr_t)changed & 7) || ((uintptr_t)sums & 7) || ((uintptr_t)counts & 7) || ((uintptr_t)cos_sum & 7))
+        return h->fail(KEEP_EINVAL, "cluster_assign: an output is not aligned to its element size");
+    KEEP_ON_DEVICE(h);
+    launch_cluster_assign(features, (int)N, (int)D, centroids, (int)K, label_out, best_out, margin_out, prev_label, skipped, changed, sums, counts,
+                          cos_sum, two_launch, (hipStream_t)stream);
+    return check_launch(h, "cluster_assign");
+}
+
+int keep_cluster_update(keep_handle* h, const int64_t* sums, const int64_t* counts, int64_t K, int64_t D, float* centroids,
+                        unsigned char* empty_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = cluster_shape_check(h, "cluster_update", 1, D, K)) return rc;
+    if (!sums || !counts || !centroids) return h->fail(KEEP_EINVAL, "cluster_update: null sums, counts or centroids");
+    if (((uintptr_t)sums & 7) || ((uintptr_t)counts & 7) || ((uintptr_t)centroids & 3))
+        return h->fail(KEEP_EINVAL, "cluster_update: sums / counts / centroids not aligned to their element size");
+    KEEP_ON_DEVICE(h);
+    launch_cluster_update(sums, counts, (int)K, (int)D, centroids, empty_out, (hipStream_t)stream);
+    return check_launch(h, "cluster_update");
+}
+
+int keep_cluster_seed_step(keep_handle* h, const float* features, int64_t N, int64_t D, const float* centre, const int64_t* centre_row, int first,
+                           float* nearest, int64_t* index_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = cluster_shape_check(h, "cluster_seed_step", N, D, 1)) return rc;
+    if (!features || !index_out) return h->fail(KEEP_EINVAL, "cluster_seed_step: null features or index_out");
+    if ((centre != nullptr) == (centre_row != nullptr)) return h->fail(KEEP_EINVAL, "cluster_seed_step: give centre or centre_row, one of the two");
+    if (first != 0 && first != 1) return h->fail(KEEP_EINVAL, "cluster_seed_step: first %d (0 or 1)", first);
+    if (!first && !nearest) return h->fail(KEEP_EINVAL, "cluster_seed_step: null nearest");
+    if (((uintptr_t)features & 15) || ((uintptr_t)centre & 15) || ((uintptr_t)centre_row & 7) || ((uintptr_t)nearest & 3) || ((uintptr_t)index_out & 7))
+        return h->fail(KEEP_EINVAL, "cluster_seed_step: features / centre (16 bytes), centre_row / index_out (8) or nearest (4) not aligned");
+    KEEP_ON_DEVICE(h);
+    int rc = ensure_arena(h, 256);
+    if (rc) return rc;
+    launch_cluster_seed_step(features, (int)N, (int)D, centre, centre_row, first, nearest, (unsigned char*)h->arena, index_out, (hipStream_t)stream);
+    return check_launch(h, "cluster_seed_step");
 }
 
 }  // extern "C"

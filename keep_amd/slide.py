@@ -14,6 +14,8 @@ from . import _lib
 from .annotation import PolygonSet, check_fill_args, check_into, check_tile_args, polygon_arrays
 from .classmap import (ClassMap, ClassRaster, check_class_names, check_class_tiles, check_classes, check_label_map, check_labels, check_palette,
                        class_map_args)
+from .cluster import (ONE as CLUSTER_ONE, ClusterSums, TileClusters, check_centroids, check_dim, check_features, check_fit_args, check_init, check_k,
+                      check_prev)
 from .components import NCOLS as REGION_COLS, RegionTable, check_raster, check_region_count, check_regions_args, mask_tensor
 from .evaluation import HIST_BINS, MaskOverlap, RocResult, check_mask, check_roc_args, check_same_geometry, plan_label_bands, sweep_from_hist
 from .heatmap import (MAX_TILES, ScoreReference, TileRaster, check_cell_args, check_cells, check_raster_args, check_tiles, check_values,
@@ -499,6 +501,196 @@ class SlideOps:
         self._call("class_render", _ptr(labels), h, w, cm.n_classes, _ptr(x), row, ps, bg[0] | bg[1] << 8 | bg[2] << 16, _ptr(pal), a,
                    _ptr(None if strength is None else strength.acc), lo16, hi16, _ptr(out))
         return out
+
+    # ------------------------------------------------------------------ tile clustering
+    def _cluster_features(self, features, normalize: bool) -> torch.Tensor:
+        """fp32 ``[N, D]`` -> contiguous on the engine's device; ``normalize`` divides every row by max(its norm, 1e-12) on the engine
+        (keep_op_l2norm, the unit-row path of the WSI functions) in a copy."""
+        check_features(features)
+        self._ready_device()
+        x = self._on_device(features)
+        if normalize:
+            if isinstance(features, torch.Tensor) and x.data_ptr() == features.data_ptr():
+                x = x.clone()
+            self._call("op_l2norm", _ptr(x), x.shape[0], x.shape[1])
+        return x
+
+    def _cluster_assign(self, x, cen, labels, best, margin, prev, skipped, sums, fused: bool = True) -> None:
+        N, D = x.shape
+        acc = (None, None, None) if sums is None else (sums.sums, sums.counts, sums.cos_sum)
+        self._call("cluster_assign", _ptr(x), N, D, _ptr(cen), cen.shape[0], _ptr(labels), _ptr(best), _ptr(margin), _ptr(prev), _ptr(skipped),
+                   _ptr(None if prev is None else sums.changed), _ptr(acc[0]), _ptr(acc[1]), _ptr(acc[2]), 0 if fused else 1)
+
+    @torch.no_grad()
+    def cluster_assign(self, features, centroids, sums=None, prev=None, normalize=True, fused=True):
+        """Every tile's nearest centroid by cosine, in one pass over the features -> ``(labels, best, margin,
+        skipped)`` on the device: int32 ``[N]`` (the first maximum; -1 for a skipped tile), fp32 ``[N]`` twice (the winning cosine and its
+        lead over the runner-up, 0 when K = 1) and an int64 ``[1]`` count of skipped tiles.
+
+        ``features``: fp32 ``[N, D]``, ``1 <= N <= 2^22``, D a multiple of 16 up to 1024; ``centroids``: fp32 ``[K, D]`` unit rows, ``1 <= K
+        <= 64``.  ``normalize=True`` makes unit rows of the features first (the engine's row kernel); ``False`` takes them as they are.  A
+        tile with a non-finite value or an element beyond 1 in magnitude is skipped everywhere.  ``sums``: a
+        ``keep_amd.cluster.ClusterSums`` of the same K and D: the same launch adds every kept tile into its centroid's integer sums
+        (``skipped`` is then ``sums.skipped``, which keeps counting until ``sums.zero_()``); ``prev``: int32 ``[N]`` earlier labels,
+        with ``sums``: the tiles whose label differs are added to ``sums.changed``.  The scores are fp32 fma chains of one fixed order:
+        labels, best and margin of a tile do not depend on N, its row or the split over calls, and neither do the integer sums.
+        ``fused=False`` runs the accumulate as a second launch (the same words; for measurement).  No host synchronisation."""
+        N, D = check_features(features)
+        K, _ = check_centroids(centroids, D)
+        if sums is not None:
+            if not isinstance(sums, ClusterSums):
+                raise ValueError(f"sums must be a ClusterSums, got {type(sums).__name__}")
+            sums.check(K, D)
+        if prev is not None:
+            if sums is None:
+                raise ValueError("prev= needs sums=: the changed labels are counted in sums.changed")
+            check_prev(prev, N)
+        x = self._cluster_features(features, normalize)
+        if sums is not None:
+            if sums.buf.device != self._device:
+                raise ValueError(f"the accumulators live on {sums.buf.device}, this engine on {self._device}")
+            sums.claim(N)
+        cen = self._on_device(centroids)
+        labels = torch.empty(N, dtype=torch.int32, device=self._device)
+        best, margin = (torch.empty(N, dtype=torch.float32, device=self._device) for _ in range(2))
+        skipped = torch.zeros(1, dtype=torch.int64, device=self._device) if sums is None else sums.skipped
+        self._cluster_assign(x, cen, labels, best, margin, None if prev is None else self._on_device(prev), skipped, sums, fused)
+        return labels, best, margin, skipped
+
+    @torch.no_grad()
+    def cluster_update(self, sums, centroids):
+        """New centroids from the integer sums -> ``(centroids fp32 [K, D], empty uint8 [K])`` on the device: each
+        row its cluster's sum divided by its norm in float64, rounded once; a cluster without tiles (or with a zero sum) keeps its row of
+        ``centroids`` bit for bit and is flagged in ``empty``.  ``centroids`` itself is not written.  No host synchronisation."""
+        if not isinstance(sums, ClusterSums):
+            raise ValueError(f"sums must be a ClusterSums, got {type(sums).__name__}")
+        K, D = check_centroids(centroids)
+        sums.check(K, D)
+        self._ready_device()
+        if sums.buf.device != self._device:
+            raise ValueError(f"the accumulators live on {sums.buf.device}, this engine on {self._device}")
+        out = self._on_device(centroids).clone()
+        empty = torch.empty(K, dtype=torch.uint8, device=self._device)
+        self._call("cluster_update", _ptr(sums.sums), _ptr(sums.counts), K, D, _ptr(out), _ptr(empty))
+        return out, empty
+
+    def _cluster_seed(self, x: torch.Tensor, k: int) -> torch.Tensor:
+        N, D = x.shape
+        dev = self._device
+        sums = ClusterSums(1, D, dev)
+        zero = torch.zeros((1, D), dtype=torch.float32, device=dev)
+        self._cluster_assign(x, zero, None, None, None, None, None, sums)        # K = 1: the integer mean of the kept rows
+        mean, _ = self.cluster_update(sums, zero)
+        idx = torch.empty(k, dtype=torch.int64, device=dev)
+        nearest = torch.full((N,), float("-inf"), dtype=torch.float32, device=dev)
+        self._call("cluster_seed_step", _ptr(x), N, D, _ptr(mean), _ptr(None), 1, _ptr(None), C.c_void_p(idx.data_ptr()))
+        for i in range(1, k):
+            self._call("cluster_seed_step", _ptr(x), N, D, _ptr(None), C.c_void_p(idx.data_ptr() + 8 * (i - 1)), 0, _ptr(nearest),
+                       C.c_void_p(idx.data_ptr() + 8 * i))
+        return idx
+
+    @torch.no_grad()
+    def cluster_seed(self, features, k: int, normalize=True) -> torch.Tensor:
+        """Deterministic farthest-point seeding -> row indices int64 ``[k]`` on the device.  The first is the tile
+        with the largest cosine to the normalised integer mean of all tiles, every next one the tile whose largest cosine to the
+        centres chosen so far is the smallest; the lowest index wins every tie and skipped tiles are never chosen (-1 when every tile
+        is skipped).  No random numbers; k passes over the features, the index chain stays on the device (no host synchronisation)."""
+        check_features(features)
+        k = check_k(k)
+        return self._cluster_seed(self._cluster_features(features, normalize), k)
+
+    def _cluster_lloyd(self, batches, k: int, D: int, cen: torch.Tensor, max_iter: int, tol_changed: int):
+        """The Lloyd loop over ``batches()`` (an iterable of prepared device tensors, the same rows in the same order every time it is
+        called); ``cen`` fp32 ``[k, D]`` on the device."""
+        dev = self._device
+        sums = ClusterSums(k, D, dev)
+        bufs = []                                                       # per batch: [labels, previous labels, best, margin]
+
+        def one_pass():
+            sums.zero_()
+            first, seen = not bufs, 0
+            for i, x in enumerate(batches()):
+                seen += 1
+                if i == len(bufs):
+                    if not first:
+                        raise ValueError(f"batches() returned more than the {len(bufs)} batches of its first call")
+                    N = x.shape[0]
+                    bufs.append([torch.empty(N, dtype=torch.int32, device=dev), torch.full((N,), -1, dtype=torch.int32, device=dev),
+                                 torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev)])
+                b = bufs[i]
+                if b[0].shape[0] != x.shape[0]:
+                    raise ValueError(f"batch {i} has {x.shape[0]} rows, it had {b[0].shape[0]} in the first pass")
+                sums.claim(x.shape[0])
+                self._cluster_assign(x, cen, b[0], b[2], b[3], b[1], sums.skipped, sums)
+            if not bufs or seen != len(bufs):
+                raise ValueError(f"batches() returned {seen} batches, {len(bufs)} in its first call (at least one is needed)")
+
+        n_iter, converged = 0, False
+        for it in range(1, max_iter + 1):
+            one_pass()
+            n_iter = it
+            if int(sums.changed.item()) <= tol_changed:                  # the iteration's one host synchronisation
+                converged = True
+                break
+            cen, _ = self.cluster_update(sums, cen)
+            for b in bufs:
+                b[0], b[1] = b[1], b[0]
+        if not converged:
+            one_pass()
+        tail = sums.buf[k * D:].cpu()
+        counts, (cos_sum, changed, skipped) = tail[:k], (int(v) for v in tail[k:])
+        kept = int(counts.sum())
+        cat = lambda j: bufs[0][j] if len(bufs) == 1 else torch.cat([b[j] for b in bufs])
+        return TileClusters(cat(0), cat(2), cat(3), cen, sums.counts.clone(), skipped, sums.counts == 0, n_iter, changed,
+                            (cos_sum / CLUSTER_ONE / kept) if kept else 0.0, converged)
+
+    @torch.no_grad()
+    def cluster_tiles(self, features, k: int, init="farthest", max_iter: int = 50, tol_changed: int = 0):
+        """Spherical k-means of a slide's tiles on the device -> ``keep_amd.cluster.TileClusters``.
+
+        ``features``: fp32 ``[N, D]`` (made unit rows first); ``k`` in 1..64; ``init``: ``"farthest"`` (:meth:`cluster_seed`), fp32
+        centroids ``[k, D]`` (taken as they are: unit rows) or integer row indices ``[k]``.  Every iteration is one fused assign +
+        accumulate launch and one update launch; the host reads the number of changed labels once per iteration, the only
+        synchronisation, and stops when it is ``<= tol_changed`` or after ``max_iter`` iterations (then one more assign gives the labels of
+        the final centroids).  An empty cluster keeps its centroid.  No random numbers and integer sums: two runs give the same bits,
+        and :meth:`cluster_fit_batches` over any split of the same tiles gives them too.  Equal to ``keep_amd.cluster.kmeans_numpy``
+        wherever its float64 margins stay above the fp32 error of a length-D dot product."""
+        N, D = check_features(features)
+        k = check_k(k)
+        max_iter, tol_changed = check_fit_args(max_iter, tol_changed)
+        kind = check_init(init, k, N, D)
+        x = self._cluster_features(features, True)
+        if kind == "centroids":
+            cen = self._on_device(init if hasattr(init, "shape") else np.asarray(init, np.float32)).clone()
+        else:
+            idx = self._cluster_seed(x, k) if kind == "farthest" else self._on_device(torch.as_tensor(init), torch.int64)
+            cen = x[idx.clamp(min=0)].contiguous()
+        return self._cluster_lloyd(lambda: (x,), k, D, cen, max_iter, tol_changed)
+
+    @torch.no_grad()
+    def cluster_fit_batches(self, batches, k: int, init, max_iter: int = 50, tol_changed: int = 0):
+        """:meth:`cluster_tiles` for features that are never resident at once (a cohort of feature files) -> ``TileClusters`` over the
+        concatenation of the batches.  ``batches``: a callable returning an iterable of fp32 ``[n_i, D]`` tensors, called once per
+        iteration and returning the same rows in the same order each time; ``init``: fp32 centroids ``[k, D]`` (unit rows).  One
+        ``ClusterSums`` is accumulated over an iteration's batches (at most 2^24 tiles), so the result equals ``cluster_tiles`` on the
+        concatenation with the same ``init`` bit for bit."""
+        k = check_k(k)
+        max_iter, tol_changed = check_fit_args(max_iter, tol_changed)
+        if not callable(batches):
+            raise ValueError(f"batches must be a callable returning the feature tensors, got {type(batches).__name__}")
+        if isinstance(init, str) or not hasattr(init, "shape") or len(tuple(init.shape)) != 2:
+            raise ValueError(f"init must be centroids [k, D] here (seed on a resident sample with cluster_seed), got {init!r}")
+        D = check_dim(init.shape[1])
+        check_init(init, k, 1, D)
+        self._ready_device()
+        cen = self._on_device(init).clone()
+
+        def prepared():
+            for x in batches():
+                if check_features(x)[1] != D:
+                    raise ValueError(f"a batch has width {x.shape[1]}, the centroids {D}")
+                yield self._cluster_features(x, True)
+        return self._cluster_lloyd(prepared, k, D, cen, max_iter, tol_changed)
 
     # ------------------------------------------------------------------ region table (DESIGN.md section 13)
     @torch.no_grad()

@@ -599,6 +599,38 @@ def subtyping_map(classifier, tile_features, tile_coords, downsample, shape, pat
     return m.class_raster(coords, mean, patch_size, downsample, shape, origin, classes=classes)
 
 
+def cluster_map(tile_features, tile_coords, k_or_centroids, downsample, shape, patch_size=256, origin=(0, 0), model=None, **fit):
+    """The unsupervised morphology map: the tiles' features clustered by cosine and the cluster labels rasterised
+    as votes -> ``(keep_amd.classmap.ClassRaster, keep_amd.cluster.TileClusters)``.  ``k_or_centroids``: an integer k, which fits
+    ``KEEPModel.cluster_tiles(tile_features, k, **fit)`` (``init`` / ``max_iter`` / ``tol_changed``), or fp32 centroids ``[K, D]`` (of an
+    earlier fit), which only assigns.  Skipped tiles (a non-finite feature) are in no plane.  ``KEEPModel.class_map``,
+    ``render_class_map`` and :func:`subtype_regions` take the raster from there."""
+    from .cluster import TileClusters, check_centroids, check_features, check_k
+    from .heatmap import check_raster_args
+    check_raster_args(patch_size, downsample, shape, origin)
+    f = tile_features.squeeze(0) if isinstance(tile_features, torch.Tensor) and tile_features.dim() == 3 else tile_features
+    N, D = check_features(f)
+    coords = tile_coords if isinstance(tile_coords, torch.Tensor) else torch.as_tensor(np.asarray(tile_coords))
+    if tuple(coords.shape) != (N, 2):
+        raise ValueError(f"tile_coords must be [{N}, 2] beside {N} feature rows, got shape {tuple(coords.shape)}")
+    given = hasattr(k_or_centroids, "shape")
+    K = check_centroids(k_or_centroids, D)[0] if given else check_k(k_or_centroids)
+    if given and fit:
+        raise ValueError(f"centroids are given: nothing is fitted, so {sorted(fit)} have no meaning")
+    m = _engine(model, tile_features)
+    if given:
+        labels, best, margin, skipped = m.cluster_assign(f, k_or_centroids, normalize=True)
+        counts = torch.bincount(labels[labels >= 0].to(torch.int64), minlength=K)
+        kept = int(counts.sum())
+        res = TileClusters(labels, best, margin, m._on_device(k_or_centroids), counts, int(skipped), counts == 0, 0, 0,
+                           float(best.sum(dtype=torch.float64)) / kept if kept else 0.0, True)
+    else:
+        res = m.cluster_tiles(f, K, **fit)
+    keep = res.labels >= 0
+    raster = m.class_raster(coords.to(m._device)[keep], None, patch_size, downsample, shape, origin, labels=res.labels[keep], n_classes=K)
+    return raster, res
+
+
 def subtype_regions(class_map, tissue=None, connectivity=8, min_area=1, model=None):
     """The region table of every class of a label map -> ``{c: keep_amd.components.RegionTable}``: the connected regions of the pixels
     labelled c (inside ``tissue``, a ``TissueMask`` of the map's geometry, optional), scored on the class's own plane of the
