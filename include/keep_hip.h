@@ -545,6 +545,42 @@ int keep_eval_mask_counts(keep_handle* h, const unsigned char* a, const unsigned
 int keep_eval_raster_hist(keep_handle* h, const int64_t* acc, const unsigned char* truth, const unsigned char* within, int64_t H, int64_t W,
                           int64_t* hist_out, void* stream);
 
+/* Bootstrap resampling: the counts behind a confidence interval, B replicates per call.
+ * Replaces: nothing the reference runs (WSI_evaluation/zeroshot_subtyping_WSI.py:24 sets `bootstrapping = 1000` and never uses
+ * it); on the host, B calls of scikit-learn on B resampled copies, each with its own sort.
+ * The resampling.  All arithmetic modulo 2^64, G = 0x9E3779B97F4A7C15:
+ *   mix64(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *   key(seed, b) = mix64(seed ^ mix64((b + 1) G))                               b >= 0: the replicate
+ *   draw(seed, b, j, n) = (mix64(key(seed, b) + j G) n) >> 64                   the high half of the 128-bit product, j = 0..n-1
+ * Replicate b >= 0 of a sample of n items is the multiset { item[draw(seed, b, j, n)] : j = 0..n-1 }; replicate -1 is the sample
+ * itself.  A replicate depends on (seed, b, n) alone: not on B, on the split of the replicates over calls, on the launch or on the
+ * order of the atomics; two calls with equal seed and n draw the same positions (paired replicates).  The index bias is below
+ * n / 2^64.  Row r of `out` holds replicate first_replicate + r; first_replicate >= -1, 0 <= B <= 2^20, 0 <= N <= 2^24 - 1.
+ * keep_boot_roc: scores fp32 [N] (4-byte aligned), labels uint8 [N] (non-zero = positive), ON THE DEVICE; NaN and -0.0 as in
+ * keep_eval_roc.  The sample is the n scored items in their original order.  out: int64 [B,4] ON THE DEVICE, 8-byte aligned:
+ *   0 n (the same in every row)    1 P_b, 2 Nn_b  the drawn positives / negatives
+ *   3 U2_b  over the drawn positives the sum of 2 less + eq, less / eq the drawn negatives below / equal to the positive's score,
+ *           each with its multiplicity: keep_eval_roc's U2 of the resampled arrays (<= 2 n^2 < 2^49)
+ * A replicate with one class only is reported as it is (P_b = 0 or Nn_b = 0).  Row b = -1 equals scalars 0..3 of keep_eval_roc.
+ * One sort per call gives every scored item the rank g of its score among the K distinct ones; a replicate is then n x (hash,
+ * 4-byte gather, integer add into a histogram of 2 K counters) and one scan over K.  The counters live in LDS up to
+ * K = KEEP_BOOT_LDS_GROUPS, above it in one slab of 8 N bytes per resident workgroup.
+ * Workspace from the handle's arena: 8 N bytes + the sort's (4 N + its digit tables, none up to 4096 values) + 8 (2048 ceil(N /
+ * 2048)) + 8 ceil(N / 2048) + 16 and, for N > KEEP_BOOT_LDS_GROUPS, the slabs: min(B, 2 x the CUs, 256 MiB / 8 N, at least 1) x
+ * 8 N bytes (each part rounded up to 256).
+ * keep_boot_confusion: truth, pred uint8 [N] ON THE DEVICE, 2 <= C <= 16.  PRECONDITION: every truth[i], pred[i] < C (not read on
+ * the host; a larger label counts as C - 1, no index leaves the table).  out: int64 [B,C,C] ON THE DEVICE, 8-byte aligned:
+ * out[r][t][p] = the draws of replicate first_replicate + r that landed on an item with truth t and pred p; every row sums to N and
+ * row b = -1 is the plain confusion matrix.  Workspace: N bytes.
+ * Both: no host synchronisation; integer adds only: the same from run to run.  N = 0 writes zeros; B = 0 writes nothing.
+ * KEEP_EINVAL, nothing written: N or B or first_replicate or C outside the ranges above, a null array with N > 0, a null or
+ * misaligned out with B > 0. */
+enum { KEEP_BOOT_LDS_GROUPS = 8192 };
+int keep_boot_roc(keep_handle* h, const float* scores, const unsigned char* labels, int64_t N, uint64_t seed, int64_t first_replicate,
+                  int64_t B, int64_t* out, void* stream);
+int keep_boot_confusion(keep_handle* h, const unsigned char* truth, const unsigned char* pred, int64_t N, int64_t C, uint64_t seed,
+                        int64_t first_replicate, int64_t B, int64_t* out, void* stream);
+
 /* Lesion-level scoring: distance bands, peaks, candidates against lesions.  Beyond the reference, which stops
  * at AUC and Dice (WSI_evaluation/segment_utils.py); the yardsticks are scipy and restatements of the published CAMELYON16 rule.
  * keep_mask_dist2 replaces: rint(scipy.ndimage.distance_transform_edt(mask == 0) ** 2), capped.  mask uint8 [H,W] ON THE DEVICE,

@@ -17,4 +17,7 @@ from .lesion import FrocAccumulator, FrocCurve, camelyon16_margin
 from .morphometry import RegionShape, camelyon16_itc_axis
 
 __all__ += ["FrocAccumulator", "FrocCurve", "camelyon16_margin", "RegionShape", "camelyon16_itc_axis"]
+from .bootstrap import BootstrapResult
+
+__all__ += ["BootstrapResult"]
 __version__ = "0.1.0"

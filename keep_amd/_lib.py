@@ -82,6 +82,8 @@ SIGNATURES = {
     "keep_eval_roc": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "keep_eval_mask_counts": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "keep_eval_raster_hist": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "keep_boot_roc": (_i32, [_vp, _vp, _vp, _i64, C.c_uint64, _i64, _i64, _vp, _vp]),
+    "keep_boot_confusion": (_i32, [_vp, _vp, _vp, _i64, _i64, C.c_uint64, _i64, _i64, _vp, _vp]),
     "keep_mask_dist2": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "keep_raster_peaks": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i64, _vp, _vp, _vp]),
     "keep_lesion_hits": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),

@@ -199,4 +199,53 @@ def run_segmentation(classifier, dataloader, device, model=None):
     return l, c
 
 
+def _per_slide(values, targets, what: str):
+    """One value and one target per slide, aligned -> two lists.  ``targets``: the ``{slide_id: label}`` a ``run_*`` returns, or a
+    sequence; ``values``: a mapping with the same slide ids, or a sequence in the same order.  Every entry is one number."""
+    def number(x):
+        a = np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x)
+        if a.size != 1:
+            raise ValueError(f"{what}: one number per slide is needed, got an array of shape {a.shape} (reduce a slide's tiles to its "
+                             "call or score first, e.g. with wsi.zero_shot_subtyping / zero_shot_detection)")
+        return a.reshape(()).item()
+    if isinstance(targets, Mapping):
+        ids = list(targets)
+        t = [targets[i] for i in ids]
+        if isinstance(values, Mapping):
+            missing = [i for i in ids if i not in values]
+            if missing:
+                raise ValueError(f"{what}: no value for slide {missing[0]!r}")
+            v = [values[i] for i in ids]
+        else:
+            v = list(values)
+    else:
+        t = list(targets)
+        v = list(values.values()) if isinstance(values, Mapping) else list(values)
+    if len(v) != len(t):
+        raise ValueError(f"{what}: {len(v)} values for {len(t)} targets")
+    if not t:
+        raise ValueError(f"{what}: no slides")
+    return [number(x) for x in v], [number(x) for x in t]
+
+
+def bootstrap_subtyping(preds, targets, n_classes: int, n_boot: int = 1000, seed: int = 0, model=None, device=None):
+    """The cohort's balanced accuracy and weighted F1 with bootstrap replicates -> ``{"balanced_accuracy":
+    BootstrapResult, "weighted_f1": BootstrapResult}`` (``.estimate``, ``.ci()``), both from the same resamples of the slides.
+    ``targets``: what ``run_subtyping`` returns third, ``{slide_id: class index}``; ``preds``: the called class index per slide, a
+    mapping with those ids or a sequence in their order."""
+    from . import bootstrap
+    p, t = _per_slide(preds, targets, "bootstrap_subtyping")
+    m = _engine(model, device=device)
+    rows, seed, first = m._boot_confusions(np.asarray(t, dtype=np.int64), np.asarray(p, dtype=np.int64), n_classes, n_boot, seed, 0)
+    return {name: bootstrap.result_from_confusions(rows, name, seed, first) for name in ("balanced_accuracy", "weighted_f1")}
+
+
+def bootstrap_detection(scores, targets, n_boot: int = 1000, seed: int = 0, model=None, device=None):
+    """The cohort's AUROC with bootstrap replicates -> ``BootstrapResult``.  ``targets``: what ``run_detection`` returns third (non-zero =
+    positive); ``scores``: one score per slide, a mapping with those ids or a sequence in their order."""
+    s, t = _per_slide(scores, targets, "bootstrap_detection")
+    m = _engine(model, device=device)
+    return m.bootstrap_roc(np.asarray(s, dtype=np.float64), np.asarray(t, dtype=np.int64) != 0, n_boot, seed)[1]
+
+
 WSI_Classification_Dataset = WSIClassificationDataset        # the reference's spelling (utils.py:11)

@@ -389,6 +389,20 @@ void launch_eval_mask_counts(const unsigned char* a, const unsigned char* b, con
 // hist: int64 [2][EVAL_HIST_BINS], zeroed here; within may be null
 void launch_eval_raster_hist(const int64_t* acc, const unsigned char* truth, const unsigned char* within, int64_t n, int64_t* hist, hipStream_t s);
 
+// Bootstrap resampling (bootstrap.hip)
+constexpr int BOOT_LDS_GROUPS = 8192;                   // = KEEP_BOOT_LDS_GROUPS: distinct scores up to which a replicate's 2 K counters live in LDS (64 KiB)
+constexpr size_t BOOT_SLAB_BYTES = (size_t)256 << 20;   // above it: all the workgroups' slabs of 8 N bytes together (never less than one slab)
+constexpr int64_t BOOT_MAX_REPLICATES = (int64_t)1 << 20;
+constexpr int BOOT_MAX_CLASSES = 16;                    // C^2 <= 256: a draw's (truth, pred) is one byte
+size_t boot_roc_workspace_bytes(int64_t N, int64_t B);
+// out: int64 [B][4] (n, P_b, Nn_b, U2_b), row r = replicate first + r (first >= -1; -1 = the sample itself)
+void launch_boot_roc(const float* scores, const unsigned char* labels, int64_t N, unsigned long long seed, int64_t first, int64_t B,
+                     unsigned char* ws, int64_t* out, hipStream_t s);
+size_t boot_confusion_workspace_bytes(int64_t N);
+// out: int64 [B][C][C]; labels >= C are clamped to C - 1 (the entry point's precondition rules them out)
+void launch_boot_confusion(const unsigned char* truth, const unsigned char* pred, int64_t N, int C, unsigned long long seed, int64_t first,
+                           int64_t B, unsigned char* ws, int64_t* out, hipStream_t s);
+
 // Row-wise helpers (rowops.hip)
 // pixels [B,3,16 gh,16 gw] (or uint8 [B,16 gh,16 gw,3]) -> patches [B * gh * gw][768], row-major (y, x) patch order; CLS rows of resid
 void launch_im2col(const void* pixels, int dtype, int B, int gh, int gw, f16* out_hi, f16* out_lo,      // out in blk layout (KT = 24)

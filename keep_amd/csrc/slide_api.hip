@@ -1,6 +1,6 @@
 // The slide-geometry entry points of include/keep_hip.h: patch grid, tissue mask, heatmap, sort / rank, region table, outlines, polygon
-// fill, segmentation evaluation, the subtype map and tile clustering.  Host code only: each function validates its arguments, carves its workspace from the handle's
-// arena, calls the launch_* of its kernel file (region / tissue / heatmap / rank / components / outline / annotation / eval .hip) and
+// fill, segmentation evaluation, bootstrap resampling, the subtype map and tile clustering.  Host code only: each function validates its arguments, carves its workspace from the handle's
+// arena, calls the launch_* of its kernel file (region / tissue / heatmap / rank / components / outline / annotation / eval / bootstrap .hip) and
 // reports the launch.  Of the handle (handle.h) they use the device, the error text, the arena and the sticky error flag.
 #include "handle.h"
 
@@ -485,6 +485,43 @@ int keep_eval_raster_hist(keep_handle* h, const int64_t* acc, const unsigned cha
     KEEP_ON_DEVICE(h);
     launch_eval_raster_hist(acc, truth, within, H * W, hist_out, (hipStream_t)stream);
     return check_launch(h, "eval_raster_hist");
+}
+
+// what keep_boot_roc and keep_boot_confusion ask of the sample size, the replicates and the output alike
+static int boot_check(keep_handle* h, const char* who, int64_t N, int64_t first_replicate, int64_t B, const int64_t* out) {
+    if (N < 0 || N > SORT_MAX) return h->fail(KEEP_EINVAL, "%s: %lld items (0 .. 2^24 - 1)", who, (long long)N);
+    if (B < 0 || B > BOOT_MAX_REPLICATES) return h->fail(KEEP_EINVAL, "%s: %lld replicates (0 .. 2^20)", who, (long long)B);
+    if (first_replicate < -1) return h->fail(KEEP_EINVAL, "%s: first replicate %lld < -1", who, (long long)first_replicate);
+    if (B > 0 && (!out || ((uintptr_t)out & 7))) return h->fail(KEEP_EINVAL, "%s: out is null or not 8-byte aligned", who);
+    return KEEP_OK;
+}
+
+int keep_boot_roc(keep_handle* h, const float* scores, const unsigned char* labels, int64_t N, uint64_t seed, int64_t first_replicate,
+                  int64_t B, int64_t* out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = boot_check(h, "boot_roc", N, first_replicate, B, out)) return rc;
+    if (N > 0 && (!scores || !labels)) return h->fail(KEEP_EINVAL, "boot_roc: null scores or labels");
+    if ((uintptr_t)scores & 3) return h->fail(KEEP_EINVAL, "boot_roc: scores not 4-byte aligned");
+    if (B == 0) return KEEP_OK;
+    KEEP_ON_DEVICE(h);
+    int rc = ensure_arena(h, boot_roc_workspace_bytes(N, B));
+    if (rc) return rc;
+    launch_boot_roc(scores, labels, N, (unsigned long long)seed, first_replicate, B, (unsigned char*)h->arena, out, (hipStream_t)stream);
+    return check_launch(h, "boot_roc");
+}
+
+int keep_boot_confusion(keep_handle* h, const unsigned char* truth, const unsigned char* pred, int64_t N, int64_t C, uint64_t seed,
+                        int64_t first_replicate, int64_t B, int64_t* out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = boot_check(h, "boot_confusion", N, first_replicate, B, out)) return rc;
+    if (C < 2 || C > BOOT_MAX_CLASSES) return h->fail(KEEP_EINVAL, "boot_confusion: %lld classes (2 .. 16)", (long long)C);
+    if (N > 0 && (!truth || !pred)) return h->fail(KEEP_EINVAL, "boot_confusion: null truth or pred");
+    if (B == 0) return KEEP_OK;
+    KEEP_ON_DEVICE(h);
+    int rc = ensure_arena(h, boot_confusion_workspace_bytes(N));
+    if (rc) return rc;
+    launch_boot_confusion(truth, pred, N, (int)C, (unsigned long long)seed, first_replicate, B, (unsigned char*)h->arena, out, (hipStream_t)stream);
+    return check_launch(h, "boot_confusion");
 }
 
 }  // extern "C"

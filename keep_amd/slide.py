@@ -1,5 +1,5 @@
 """The slide-analysis methods of ``KEEPModel``: patch grid and tiles of a region, tissue mask, heatmap raster, percentiles and
-smoothing, region table, outlines, region shape, polygon fill, segmentation evaluation and the subtype map (DESIGN.md sections 10-22).  Thin wrappers of the
+smoothing, region table, outlines, region shape, polygon fill, segmentation evaluation, the subtype map and bootstrap resampling (DESIGN.md sections 10-24).  Thin wrappers of the
 entry points in csrc/slide_api.hip; the argument checks and the numpy references live in the feature modules imported below."""
 from __future__ import annotations
 
@@ -10,7 +10,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, bootstrap
 from .annotation import PolygonSet, check_fill_args, check_into, check_tile_args, polygon_arrays
 from .classmap import (ClassMap, ClassRaster, check_class_names, check_class_tiles, check_classes, check_label_map, check_labels, check_palette,
                        class_map_args)
@@ -913,6 +913,96 @@ class SlideOps:
         if not curve:
             return RocResult(n, P, Nn, u2, best)
         return RocResult(n, P, Nn, u2, best, outs[0][:K], outs[1][:K], outs[2][:K], outs[3][:K].to(torch.bool))
+
+    # ------------------------------------------------------------------ bootstrap confidence intervals
+    def _boot_rows(self, name: str, args: tuple, row_shape: tuple, B: int, seed: int, first: int) -> torch.Tensor:
+        """int64 ``[1 + B, *row_shape]`` on the device: the sample's own row (replicate -1), then replicates ``first .. first + B - 1`` of
+        ``keep_boot_<name>``.  One launch when the replicates start at 0 (the estimate rides in it), else two."""
+        out = torch.empty((1 + B,) + row_shape, dtype=torch.int64, device=self._device)
+        if first == 0 and B < bootstrap.MAX_REPLICATES:
+            self._call(name, *args, seed, -1, 1 + B, _ptr(out))
+        else:
+            self._call(name, *args, seed, -1, 1, _ptr(out))
+            if B:
+                self._call(name, *args, seed, first, B, _ptr(out[1:]))
+        return out
+
+    @torch.no_grad()
+    def bootstrap_roc(self, scores, labels, n_boot: int = 1000, seed: int = 0, first_replicate: int = 0):
+        """``n_boot`` bootstrap replicates of the tile ROC on the device -> ``(counts, result)``: ``counts`` int64
+        ``[n_boot, 4]`` on the device, rows ``n, P_b, Nn_b, U2_b`` of replicates ``first_replicate ..``, and the AUROC's
+        ``keep_amd.bootstrap.BootstrapResult`` (``estimate``, ``values``, ``ci()``, ``se``, ``minus()``).  Arguments as :meth:`tile_roc`;
+        ``seed``: an integer in ``[0, 2^64)``.  A replicate that drew one class only has a NaN value and counts in ``n_undefined``; so
+        does the estimate of a one-class sample.  Two score vectors with NaNs in the same places and equal ``seed`` give paired
+        replicates.  One sort, then one workgroup per replicate; one read of the counts.  Equal to
+        ``keep_amd.bootstrap.boot_roc_numpy`` exactly."""
+        s = scores if isinstance(scores, torch.Tensor) else torch.as_tensor(np.asarray(scores))
+        l = labels if isinstance(labels, torch.Tensor) else torch.as_tensor(np.asarray(labels))
+        N = check_roc_args(s, l)
+        seed = bootstrap.check_seed(seed)
+        B, first = bootstrap.check_replicates(n_boot, first_replicate)
+        if first < 0:
+            raise ValueError("first_replicate must be >= 0 here: the sample's own row is the result's estimate")
+        self._ready_device()
+        s = s.to(self._device, torch.float32).contiguous()
+        l = (l.to(self._device) != 0).to(torch.uint8).contiguous()
+        rows = self._boot_rows("boot_roc", (_ptr(s), _ptr(l), N), (4,), B, seed, first)
+        return rows[1:], bootstrap.result_from_roc_counts(rows, seed, first)
+
+    def _boot_confusions(self, truth, pred, n_classes, n_boot, seed, first_replicate):
+        """-> (int64 ``[1 + B, C, C]`` on the device, the sample's confusion first; seed; first replicate)."""
+        t = truth if isinstance(truth, torch.Tensor) else torch.as_tensor(np.asarray(truth))
+        p = pred if isinstance(pred, torch.Tensor) else torch.as_tensor(np.asarray(pred))
+        N, C = bootstrap.check_confusion_args(t, p, n_classes)
+        seed = bootstrap.check_seed(seed)
+        B, first = bootstrap.check_replicates(n_boot, first_replicate)
+        if first < 0:
+            raise ValueError("first_replicate must be >= 0 here: the sample's own row is the result's estimate")
+        self._ready_device()
+        t, p = t.to(self._device, torch.uint8).contiguous(), p.to(self._device, torch.uint8).contiguous()
+        return self._boot_rows("boot_confusion", (_ptr(t), _ptr(p), N, C), (C, C), B, seed, first), seed, first
+
+    @torch.no_grad()
+    def bootstrap_confusion(self, truth, pred, n_classes: int, n_boot: int = 1000, seed: int = 0, first_replicate: int = 0) -> torch.Tensor:
+        """``n_boot`` bootstrap replicates of a confusion matrix on the device -> int64 ``[n_boot, C, C]`` on the device:
+        ``counts[r, t, p]`` = the draws of replicate ``first_replicate + r`` that landed on an item with truth ``t`` and prediction
+        ``p``; every ``counts[r]`` sums to N.  ``truth`` / ``pred``: bool or integers ``[N]`` with values in ``[0, n_classes)``, host or
+        device, numpy or torch; ``2 <= n_classes <= 16``; anything else is a ``ValueError``.  Equal to
+        ``keep_amd.bootstrap.boot_confusion_numpy`` exactly."""
+        return self._boot_confusions(truth, pred, n_classes, n_boot, seed, first_replicate)[0][1:]
+
+    @torch.no_grad()
+    def bootstrap_metric(self, truth, pred, n_classes: int, metric, n_boot: int = 1000, seed: int = 0, first_replicate: int = 0):
+        """A metric of the confusion matrix with its bootstrap replicates -> ``keep_amd.bootstrap.BootstrapResult``.  ``metric``:
+        ``"accuracy"``, ``"balanced_accuracy"``, ``"weighted_f1"``, for two classes ``"sensitivity"`` / ``"specificity"``, or a callable that
+        takes the int64 ``[1 + n_boot, C, C]`` confusions (numpy) and returns one float64 per confusion
+        (``lambda m: bootstrap.recall(m, 2)``).  The counts come from one launch of :meth:`bootstrap_confusion`'s kernel; the
+        metric runs on the host in float64."""
+        fn = bootstrap.resolve_metric(metric)
+        rows, seed, first = self._boot_confusions(truth, pred, n_classes, n_boot, seed, first_replicate)
+        return bootstrap.result_from_confusions(rows, fn, seed, first)
+
+    @torch.no_grad()
+    def bootstrap_ovr_roc(self, probs, labels, n_boot: int = 1000, seed: int = 0, first_replicate: int = 0):
+        """One-vs-rest AUROC per class with bootstrap replicates, and their macro mean -> ``(per_class, macro)``: a list of C
+        ``BootstrapResult`` and one more.  ``probs``: floating ``[N,C]``; ``labels``: integers ``[N]`` in ``[0, C)``.  A row of ``probs``
+        with any NaN is dropped for every class (``class_raster``'s rule), so every class resamples the same items with the same
+        draws; a replicate undefined for any class is undefined for the macro mean."""
+        p = probs if isinstance(probs, torch.Tensor) else torch.as_tensor(np.asarray(probs))
+        l = labels if isinstance(labels, torch.Tensor) else torch.as_tensor(np.asarray(labels))
+        if p.ndim != 2 or not p.dtype.is_floating_point or p.shape[1] < 2:
+            raise ValueError(f"probs must be floating point [N, C] with C >= 2, got {p.dtype} {tuple(p.shape)}")
+        if l.ndim != 1 or l.shape[0] != p.shape[0] or l.dtype.is_floating_point or l.dtype.is_complex:
+            raise ValueError(f"labels must be integers [N] beside probs [N, C], got {l.dtype} {tuple(l.shape)}")
+        C = int(p.shape[1])
+        if l.numel() and (int(l.min()) < 0 or int(l.max()) >= C):
+            raise ValueError(f"labels outside [0, {C})")
+        self._ready_device()
+        p, l = p.to(self._device, torch.float32), l.to(self._device)
+        keep = ~torch.isnan(p).any(dim=1)
+        p, l = p[keep], l[keep]
+        per_class = [self.bootstrap_roc(p[:, c].contiguous(), l == c, n_boot, seed, first_replicate)[1] for c in range(C)]
+        return per_class, bootstrap.macro_mean(per_class)
 
     @torch.no_grad()
     def mask_overlap(self, a, b, within=None):

@@ -47,13 +47,8 @@ def weighted_f1_from_confusion(conf: np.ndarray) -> float:
     return float(np.average(f, weights=tp + fn))
 
 
-def classification_rounds(model, image_embeddings: torch.Tensor, cap_embeddings: Mapping[str, torch.Tensor],
-                          label_list: Sequence) -> np.ndarray:
-    """zero_shot.py:118-139 -> WF1 of each of the 50 prompt rounds (float64 [50]).
-
-    ``cap_embeddings[type_name]`` is ``[50, D]`` (row i = the class's caption of round i); ``label_list`` holds the
-    true class names (any label outside the caption classes counts as never predicted, as in sklearn)."""
-    m = _engine(model)
+def _round_predictions(m, image_embeddings: torch.Tensor, cap_embeddings: Mapping[str, torch.Tensor], label_list: Sequence):
+    """-> (true int64 [N], pred int32 [N,50] on the host, A = the number of class names, caption classes first)."""
     names = list(cap_embeddings.keys())
     C = len(names)
     img = _normalized(m, torch.as_tensor(image_embeddings))
@@ -72,12 +67,35 @@ def classification_rounds(model, image_embeddings: torch.Tensor, cap_embeddings:
     true = np.array([index[t] for t in label_list], dtype=np.int64)
     if true.shape[0] != N:
         raise ValueError(f"{N} embeddings but {true.shape[0]} labels")
-    A = len(all_names)
+    return true, pred, len(all_names)
+
+
+def classification_rounds(model, image_embeddings: torch.Tensor, cap_embeddings: Mapping[str, torch.Tensor],
+                          label_list: Sequence) -> np.ndarray:
+    """zero_shot.py:118-139 -> WF1 of each of the 50 prompt rounds (float64 [50]).
+
+    ``cap_embeddings[type_name]`` is ``[50, D]`` (row i = the class's caption of round i); ``label_list`` holds the
+    true class names (any label outside the caption classes counts as never predicted, as in sklearn)."""
+    true, pred, A = _round_predictions(_engine(model), image_embeddings, cap_embeddings, label_list)
+    K = pred.shape[1]
     out = np.empty(K)
     for k in range(K):
         conf = np.bincount(true * A + pred[:, k], minlength=A * A).reshape(A, A)
         out[k] = weighted_f1_from_confusion(conf)
     return out
+
+
+def classification_rounds_ci(model, image_embeddings: torch.Tensor, cap_embeddings: Mapping[str, torch.Tensor], label_list: Sequence,
+                             round: int = 0, n_boot: int = 1000, seed: int = 0):        # noqa: A002 -- the protocol's word for a prompt set
+    """The weighted F1 of one prompt round with its bootstrap replicates -> ``keep_amd.bootstrap.BootstrapResult``:
+    ``estimate`` is ``classification_rounds(...)[round]``, ``ci()`` its percentile interval over ``n_boot`` resamples of the tiles.
+    Arguments as :func:`classification_rounds`; at most 16 class names in all (the confusion kernel's limit).  Two rounds with equal
+    ``seed`` resample the same tiles: ``a.minus(b)`` is the interval of their difference."""
+    m = _engine(model)
+    true, pred, A = _round_predictions(m, image_embeddings, cap_embeddings, label_list)
+    if not 0 <= int(round) < pred.shape[1]:
+        raise ValueError(f"round must be in 0 .. {pred.shape[1] - 1}, got {round!r}")
+    return m.bootstrap_metric(true, pred[:, int(round)].astype(np.int64), max(A, 2), "weighted_f1", n_boot, seed)
 
 
 def retrieval_ranks(model, image_embeddings: torch.Tensor, text_embeddings: torch.Tensor,

@@ -379,6 +379,18 @@ def eval_seg_auc(probs_all_refined, mask_path, patch_size=224, save_path='./', m
     return roc.auc, roc.best_threshold
 
 
+def bootstrap_seg_auc(probs_all_refined, mask_path, patch_size=224, save_path='./', model=None, rule="union", max_band_bytes=1 << 28,
+                      n_boot=1000, seed=0):
+    """:func:`eval_seg_auc`'s tile-level AUROC with its bootstrap replicates ->
+    ``keep_amd.bootstrap.BootstrapResult``: ``estimate`` is the ``auc`` ``eval_seg_auc`` returns, ``ci()`` its percentile interval over
+    ``n_boot`` resamples of the slide's tiles (``KEEPModel.bootstrap_roc``).  The first arguments are ``eval_seg_auc``'s."""
+    truth, order = _annotation(mask_path)
+    coords, p = _tile_probs(probs_all_refined)
+    m = _engine(model, p, coords)
+    labels = m.annotation_tile_labels(truth, coords, patch_size, order=order, rule=rule, max_band_bytes=max_band_bytes)
+    return m.bootstrap_roc(p.to(torch.float32), labels, n_boot, seed)[1]
+
+
 def _truth_mask16(m: KEEPModel, truth, order, shape, rule: str, d: int = 16) -> torch.Tensor:
     from .region import TissueMask
     if isinstance(truth, TissueMask):
