@@ -9,6 +9,9 @@ are handed to the C ABI as raw device pointers; torch supplies storage, streams 
 
 There is no CPU execution path.  Inputs that live on the CPU are copied to the engine's GPU and the
 result is copied back; without a GPU (or without libkeep_hip.so) every call raises.
+
+How the 'comp' mode's per-block plan is chosen -- the rule, the statistics, the search -- is ``keep_amd.calibration`` (pure functions, testable on a
+CPU); ``KEEPModel.calibrate`` only drives it: it encodes the probe and applies what comes back.
 """
 from __future__ import annotations
 
@@ -23,138 +26,18 @@ import numpy as np
 import torch
 
 from . import _lib
+# how the 'comp' plan is chosen lives in keep_amd.calibration; its public names stay importable from here
+from .calibration import (ATTN_RESIDUAL, CALIBRATION_POPULATION, COMP_LADDER, CONFIDENCE, DEFAULT_KNOBS, KNOB_COST_MS, MLP_RESIDUAL,  # noqa: F401
+                          PROBE_RMS_MARGIN, TOLERANCE, Plan, calibration_report, default_probe, exceedance_probability, expected_max_sigmas,
+                          greedy_walk, label_margin_unit, ladder_candidates, max_sigmas_gumbel, max_sigmas_quantile, measure_shares,
+                          mixture_exceedance, mixture_max_quantile, plan_prefix, plan_string, prefix_plan, probe_members, probe_statistics,
+                          search, share_probe, walk_candidates)
 from .config import KEEPShape
 from .slide import SlideOps, _ptr, _stream
 
 _PIX = {torch.float32: _lib.PIX_F32, torch.float16: _lib.PIX_F16, torch.bfloat16: _lib.PIX_BF16}
 _PRECISIONS = {"fp16": _lib.PREC_FP16, "strict": _lib.PREC_STRICT, "comp": _lib.PREC_COMP}
 DEFAULT_PRECISION = "comp"     # the mode that meets the reference tolerance (cosines within 1e-4) at the lowest cost
-# 'comp' spends its precision budget block by block (keep_set_block_precision): a PLAN is one (attention-side mode, MLP mode) pair per ViT block,
-# modes as in include/keep_hip.h (KEEP_ATTN_*, KEEP_MLP_*).  The prefix shorthand (comp_full_blocks, comp_mlp_blocks) = the first blocks' attention
-# side as split products / the first blocks' MLP GEMMs with both MX-fp4 correction terms is one family of plans; calibrate() walks it from the
-# cheapest rung up (budget="ladder") or builds a plan from variance shares measured on the loaded weights (budget="measured").
-COMP_LADDER = ((0, 0), (0, 4), (1, 4), (1, 6), (1, 8), (2, 8), (1, 10), (2, 10), (1, 12), (2, 12), (2, 14), (2, 16), (2, 24), (4, 24), (8, 24), (24, 24))
-# calibrate() keeps the cheapest plan whose probe statistics predict, with probability CONFIDENCE, a worst cosine error inside TOLERANCE over the
-# POPULATION the model will be used on (tiles x distinct prompts): rms x max_sigmas_quantile(population, CONFIDENCE) x tail factor <= TOLERANCE.
-CALIBRATION_POPULATION = 100_000 * 264      # BASELINE config 4: a 100 000-tile slide against the 264 distinct prompt strings of the RCC bank
-TOLERANCE = 1e-4
-CONFIDENCE = 0.99
-# The probe's rms is itself an estimate: 256 tiles x 64 prompts are 16 384 cosines, >= 4 096 effective samples once the correlation of one tile's
-# cosines is allowed for, i.e. a relative standard error <= 1.1 %.  The rule holds the tolerance against rms x this factor (two standard errors).
-PROBE_RMS_MARGIN = 1.02
-# Milliseconds a knob adds to a 256-tile encode step on an MI355X (two lanes; tools/precision_budget.py measures them, profiles/r05_precision_budget.md):
-# what the greedy of budget="measured" divides a knob's variance share by.  Only the RATIOS matter.
-KNOB_COST_MS = {"attn_split": 0.92, "attn_split_compqkv": 0.56, "attn_compqkv": 0.22, "attn_proj_cls": 0.012, "attn_compqkv_proj_cls": 0.18, "mlp_comp": 0.52, "mlp_comp_w": 0.29, "mlp_cls": 0.07}
-# Share of a site's rounding variance that survives a treatment when it is not measured on the loaded weights (same tool, bench weights): both
-# MX-fp4 correction terms remove ~96 % of an MLP's share, the W_lo term alone 40-55 %; a compensated qkv inside a split attention side leaves 1-2 %
-MLP_RESIDUAL = {_lib.MLP_PLAIN: 1.0, _lib.MLP_CLS: 0.1, _lib.MLP_COMP_W: 0.55, _lib.MLP_COMP: 0.04, _lib.MLP_SPLIT: 0.0}
-ATTN_RESIDUAL = {_lib.ATTN_PLAIN: 1.0, _lib.ATTN_COMPQKV: 0.6, _lib.ATTN_PROJ_CLS: 0.55, _lib.ATTN_COMPQKV_PROJ_CLS: 0.25, _lib.ATTN_SPLIT_COMPQKV: 0.015, _lib.ATTN_SPLIT: 0.0}
-# The treatments the greedy of budget="measured" may use.  Measured on the bench weights (profiles/r05_precision_budget.md): the W_lo-only MLP form
-# removes ~45 % of a block's MLP share for 57 % of the cost of both terms, and a compensated qkv alone ~35 % of an attention side's share at 1 ms per
-# percent of variance against 0.45 for MLP blocks -- neither ever wins a greedy step, so they are off by default (``knobs=`` switches them on).
-# KEEP_MLP_CLS (every row plain, the CLS row of every tile again as split products) is the cheap one: the feature is pooled from the CLS rows, whose
-# own rounding errors reach it directly while the other 196 rows' only arrive through attention averages -- what it leaves of a block's MLP share is
-# measured per block (0.5-2 % on the bench weights).
-# KEEP_ATTN_PROJ_CLS (round 6) is the attention side's counterpart: on spatially correlated tiles ~70 % of an attention side's rounding error is its proj
-# GEMM's (tools/attn_site_study.py), and redoing the CLS row's proj as a split product on its fp32-grade attention output removes what a full CLS-row
-# treatment of the attention side would -- for one more small GEMM in the CLS-row chain (measured per block and tile group, like KEEP_MLP_CLS).
-DEFAULT_KNOBS = {"attn": (_lib.ATTN_PROJ_CLS, _lib.ATTN_COMPQKV_PROJ_CLS, _lib.ATTN_SPLIT_COMPQKV, _lib.ATTN_SPLIT), "mlp": (_lib.MLP_CLS, _lib.MLP_COMP)}
-
-Plan = List[Tuple[int, int]]
-
-
-def prefix_plan(depth: int, full_blocks: int, mlp_blocks: int) -> Plan:
-    """The plan the (comp_full_blocks, comp_mlp_blocks) shorthand stands for."""
-    return [(_lib.ATTN_SPLIT if i < full_blocks else _lib.ATTN_PLAIN, _lib.MLP_COMP if i < mlp_blocks else _lib.MLP_PLAIN) for i in range(depth)]
-
-
-def plan_string(plan: Plan) -> str:
-    """'attn:1000... mlp:2222...' -- one digit per block (KEEP_ATTN_* / KEEP_MLP_*)."""
-    return "attn:" + "".join(str(a) for a, _ in plan) + " mlp:" + "".join(str(m) for _, m in plan)
-
-
-def plan_prefix(plan: Plan) -> Optional[Tuple[int, int]]:
-    """(comp_full_blocks, comp_mlp_blocks) if the plan is one of the prefix family, else None."""
-    full = sum(1 for a, _ in plan if a == _lib.ATTN_SPLIT)
-    mlp = sum(1 for _, m in plan if m == _lib.MLP_COMP)
-    return (full, mlp) if plan == prefix_plan(len(plan), full, mlp) else None
-
-
-def max_sigmas_gumbel(n: float) -> Tuple[float, float]:
-    """(a, b) of the extreme-value (Gumbel) law of M = max_i |x_i| / sigma over n independent N(0, sigma) samples (2n one-sided samples):
-    P(M <= z) ~ exp(-exp(-a (z - b))).  b is the LOCATION (the mode; M exceeds it 63 % of the time), the mean is b + 0.5772 / a."""
-    n2 = 2.0 * max(float(n), 2.0)
-    a = math.sqrt(2.0 * math.log(n2))
-    return a, a - (math.log(math.log(n2)) + math.log(4.0 * math.pi)) / (2.0 * a)
-
-
-def expected_max_sigmas(n: float) -> float:
-    """LOCATION b_n of the maximum of n |N(0, sigma)| samples in units of sigma -- the value the worst of n cosine errors exceeds about 63 % of
-    the time (NOT its mean, which is 0.58 / a_n higher, and not a bound): 16 384 -> 4.03, 262 144 -> 4.63, 6.4e6 -> 5.26, 2.6e7 -> 5.51.
-    Measured max / rms sits 1-5 % below it at every size (bench.py configs.c4).  A tolerance has to be held against a QUANTILE of the maximum:
-    ``max_sigmas_quantile``."""
-    return max_sigmas_gumbel(n)[1]
-
-
-def max_sigmas_quantile(n: float, q: float = CONFIDENCE) -> float:
-    """z with P(max_i |x_i| <= z sigma) = q over n independent N(0, sigma) samples, exactly: erfc(z / sqrt 2) = 1 - q^(1/n).  q = 0.99:
-    2.64e7 -> 6.26 (the location of the maximum is 5.51), 262 144 -> 5.50, 16 384 -> 4.99; the extreme-value asymptote b_n - ln(-ln q) / a_n is
-    0.02-0.05 higher.  Cosine errors of one tile against different prompts are positively correlated (one error vector, projected on the
-    prompts), which only lowers the maximum: treating them as independent is the conservative side."""
-    n = max(float(n), 1.0)
-    q = min(max(q, 1e-300), 1.0 - 1e-15)
-    p = -math.expm1(math.log(q) / n)          # 1 - q^(1/n), accurate for tiny values
-    lo, hi = 0.0, 40.0
-    for _ in range(200):                      # erfc is monotone: bisection to the last bit
-        mid = 0.5 * (lo + hi)
-        if math.erfc(mid / math.sqrt(2.0)) > p:
-            lo = mid
-        else:
-            hi = mid
-    return 0.5 * (lo + hi)
-
-
-def exceedance_probability(rms: float, n: float, tolerance: float = TOLERANCE) -> float:
-    """P(at least one of n independent N(0, rms) cosine errors exceeds ``tolerance``) = 1 - (1 - erfc(tolerance / (rms sqrt 2)))^n."""
-    if not rms > 0.0:
-        return 0.0
-    tail = math.erfc(tolerance / (rms * math.sqrt(2.0)))
-    if tail >= 1.0:
-        return 1.0
-    return float(-math.expm1(max(float(n), 1.0) * math.log1p(-tail)))
-
-
-def mixture_exceedance(sigmas: Sequence[float], n: float, x: float) -> float:
-    """P(at least one of n independent zero-mean Gaussian errors exceeds x in magnitude) when the errors' standard deviations are spread like
-    ``sigmas`` (each value standing for n / len(sigmas) samples): 1 - prod_i (1 - erfc(x / (sigma_i sqrt 2)))^(n / len).  Tiles are not equally hard
-    (a tile with more texture carries a larger error vector): the worst of a population is set by its hardest tiles, not by the rms over all."""
-    sig = [s for s in sigmas if s > 0.0]
-    if not sig:
-        return 0.0
-    w = max(float(n), 1.0) / len(sigmas)
-    acc = 0.0
-    for s in sig:
-        tail = math.erfc(x / (s * math.sqrt(2.0)))
-        if tail >= 1.0:
-            return 1.0
-        acc += w * math.log1p(-tail)
-    return float(-math.expm1(acc))
-
-
-def mixture_max_quantile(sigmas: Sequence[float], n: float, q: float = CONFIDENCE) -> float:
-    """x with P(max of the n errors <= x) = q under the mixture of ``mixture_exceedance`` (bisection); for equal sigmas this is
-    sigma x max_sigmas_quantile(n, q)."""
-    top = max(sigmas) if len(sigmas) else 0.0
-    if not top > 0.0:
-        return 0.0
-    lo, hi = 0.0, 40.0 * top
-    for _ in range(100):
-        mid = 0.5 * (lo + hi)
-        if mixture_exceedance(sigmas, n, mid) > 1.0 - q:
-            lo = mid
-        else:
-            hi = mid
-    return 0.5 * (lo + hi)
 
 
 class KEEPModel(SlideOps):
@@ -207,6 +90,7 @@ class KEEPModel(SlideOps):
         # (about 2 s at load for ViT-L); "ladder": the prefix family COMP_LADDER only (under 1 s, up to 12 % slower plans -- profiles/r05_precision_budget.md)
         self.calibration_budget = os.environ.get("KEEP_CALIBRATION_BUDGET", "measured")
         self.calibration: Optional[dict] = None
+        self._label_margin_unit: Optional[float] = None      # calibrate(): classify's second-look margin per unit of prompt distance
         # what calibrate() / calibrate_bias() probe when the caller passes no tiles: "mixture" = N(0,1) pixels AND the structured tile families of
         # keep_amd.synth.calibration_probe, the plan being held to the WORST family; "gaussian" = N(0,1) pixels only (round 5's probe: it does not
         # hold the tolerance on structured tiles -- profiles/r06_offdist_parity_before_repair_gaussian_probe.json)
@@ -452,15 +336,7 @@ class KEEPModel(SlideOps):
         self._ready()
         dev = self._device
         if tiles is None:
-            probe = probe or self.calibration_probe
-            if probe == "gaussian":
-                g = torch.Generator(device=dev).manual_seed(seed)
-                tiles = torch.randn(n_tiles, 3, 224, 224, device=dev, generator=g, dtype=torch.float32).to(torch.bfloat16)
-            elif probe == "mixture":
-                from .synth import PROBE_FAMILIES, calibration_probe
-                tiles = calibration_probe(max(n_tiles // len(PROBE_FAMILIES), 1), dev, seed=seed)[0]
-            else:
-                raise ValueError("probe must be 'mixture' or 'gaussian'")
+            tiles = default_probe(probe or self.calibration_probe, n_tiles, dev, seed)[0]
         x = tiles.to(dev)
         if x.dtype not in _PIX and x.dtype != torch.uint8:
             x = x.to(torch.float32)
@@ -525,28 +401,9 @@ class KEEPModel(SlideOps):
         probe_name = "caller's tiles"
         if tiles is None:
             probe_name = probe or self.calibration_probe
-            if probe_name == "gaussian":
-                g = torch.Generator(device=dev).manual_seed(seed)
-                tiles = torch.randn(n_tiles, 3, 224, 224, device=dev, generator=g, dtype=torch.float32).to(torch.bfloat16)
-                groups, group_names = None, ("gaussian",)
-            elif probe_name == "mixture":
-                from .synth import PROBE_FAMILIES, calibration_probe
-                tiles, groups, group_names = calibration_probe(max(n_tiles // len(PROBE_FAMILIES), 1), dev, seed=seed)
-            else:
-                raise ValueError("probe must be 'mixture' or 'gaussian'")
+            tiles, groups, group_names = default_probe(probe_name, n_tiles, dev, seed)
         tiles = tiles.to(dev)
-        n_t = int(tiles.shape[0])
-        if groups is None:
-            groups = torch.zeros(n_t, dtype=torch.int64)
-        groups = torch.as_tensor(groups, dtype=torch.int64).cpu()
-        if groups.numel() != n_t or (n_t and int(groups.min()) < 0):
-            raise ValueError("groups: one non-negative group index per probe tile")
-        n_groups = int(groups.max()) + 1 if n_t else 1
-        names = tuple(group_names) if group_names is not None else tuple(f"group{i}" for i in range(n_groups))
-        if len(names) < n_groups:
-            raise ValueError("group_names: one name per group index")
-        members = [torch.nonzero(groups == gi).flatten().to(dev) for gi in range(n_groups)]
-        members = [(names[gi], m) for gi, m in enumerate(members) if m.numel() > 0]
+        members = probe_members(groups, group_names, int(tiles.shape[0]), dev)
         if text_features is None:
             if lib.keep_bert_layers(h) > 0:
                 from .synth import synth_prompts
@@ -557,110 +414,39 @@ class KEEPModel(SlideOps):
                 text_features = torch.randn(64, self.config.projection_dim, generator=g).to(dev)
                 _lib.check(h, lib.keep_op_l2norm(h, _ptr(text_features), 64, self.config.projection_dim, _stream(dev)), "l2norm")
         bank = text_features.to(dev, torch.float32).contiguous()
-        z_pop = max_sigmas_quantile(population, confidence)
-        rms_target = tolerance / (z_pop * PROBE_RMS_MARGIN)
         saved_opts, saved_plan = dict(self._options), (list(self._plan) if self._plan is not None else None)
         strict_blocks = int(saved_opts.get("strict_blocks") or 0)
         was, self.auto_calibrate = self.auto_calibrate, False
-        tried, chosen, chosen_stats, shares = [], None, None, None
+        shares = None
         done = False
 
-        def encode_probe(x):
-            return torch.cat([self.encode_image(x[i:i + 256]) for i in range(0, x.shape[0], 256)]) if x.shape[0] > 256 else self.encode_image(x)
-
-        def probe_stats(plan: Plan):
-            """Encode the probe under `plan`; per group: max, isotropic and bank rms, margin, tail -> the governing group's figures."""
+        def verify(plan: Plan):
             self.set_plan(plan)
-            f = encode_probe(tiles)
-            d2 = self.similarity(f, bank).sub_(ref).pow_(2)                    # [n, P] squared cosine errors
-            e2 = (f - ref_f).pow(2).sum(dim=1).div_(f.shape[1])               # [n] isotropic squared error per tile
-            rows = []
-            for name, idx in members:
-                dg, eg = d2[idx], e2[idx]
-                nt = int(idx.numel())
-                mx = float(dg.max().sqrt())
-                rms_bank, ms_iso = math.sqrt(float(dg.mean())), float(eg.mean())
-                rms_iso = math.sqrt(ms_iso)
-                # relative standard error of the group's mean squared error from its tile-to-tile spread (one tile's cosines share ONE error vector:
-                # the tile is the sample); the rule holds the plan to two of them, at least PROBE_RMS_MARGIN
-                se = float(eg.std()) / math.sqrt(nt) / ms_iso if nt > 1 and ms_iso > 0 else 0.0
-                margin = max(PROBE_RMS_MARGIN, math.sqrt(1.0 + 2.0 * se))
-                rows.append([name, mx, rms_bank, rms_iso, margin, 1.0, nt])
-            # error vectors are not isotropic: against a bank of real prompts the rms can sit 5-10 % above (or below) the isotropic figure.  ONE
-            # factor for the plan, the MEDIAN over the groups of bank rms / isotropic rms, at least 1: a group of near-identical tiles (glass) has
-            # near-identical error vectors, and against a bank of similar prompts its bank rms is a single random draw, not an rms
-            ratios = sorted(r[2] / r[3] for r in rows if r[3] > 0)
-            aniso = max(1.0, 0.5 * (ratios[(len(ratios) - 1) // 2] + ratios[len(ratios) // 2])) if ratios else 1.0
-            per_group, worst = {}, None
-            for (name, mx, rms_bank, rms_iso, margin, tail, nt), (_, idx) in zip(rows, members):
-                rms = rms_iso * aniso
-                # heavier tails than the model assumes show as a probe maximum above what the SAME per-tile mixture allows a sample of the probe's
-                # size at 99 %: then every sigma is stretched by the ratio (measured against the isotropic per-tile figures, not against the
-                # group's bank rms -- for a group of near-identical tiles that is a single random draw)
-                allowed = mixture_max_quantile((e2[idx].double().sqrt() * aniso).tolist(), nt * bank.shape[0], 0.99)
-                tail = max(1.0, mx / allowed) if allowed > 0 else 1.0
-                # the group's tiles are not equally hard: the population maximum is predicted from the per-tile spread (mixture_max_quantile),
-                # every tile's isotropic error standing for population / nt cosines; `eff` = the homoscedastic rms that predicts the same maximum
-                sig = (e2[idx].double().sqrt() * (aniso * margin * tail)).tolist()
-                pred_g = mixture_max_quantile(sig, population, confidence)
-                eff = pred_g / z_pop
-                per_group[name] = {"max_abs_dcos": float(f"{mx:.3e}"), "rms_dcos_vs_bank": float(f"{rms_bank:.3e}"), "rms_dcos_isotropic": float(f"{rms_iso:.3e}"),
-                                   "margin": round(margin, 4), "tail_factor": round(tail, 3), "effective_rms": float(f"{eff:.3e}"),
-                                   "hardest_tile_over_rms": round(max(sig) / (rms * margin * tail), 3) if rms > 0 else 0.0, "tiles": nt,
-                                   "exceedance_probability": float(f"{mixture_exceedance(sig, population, tolerance):.3e}")}
-                if worst is None or eff > worst[1]:
-                    worst = (name, eff, mx, rms, margin, tail, rms_bank, rms_iso, sig)
-            per_group["anisotropy_factor"] = round(aniso, 4)
-            err_all = max(r[1] for r in rows)
-            return err_all, worst, per_group
+            f = self._encode_probe(tiles)
+            return probe_statistics(f, ref_f, self.similarity(f, bank), ref, members, population, confidence, tolerance)
 
-        def consider(plan: Plan) -> bool:
-            nonlocal chosen, chosen_stats
-            err, worst, per_group = probe_stats(plan)
-            name, eff, _, rms, margin, tail, rms_bank, rms_iso, sig = worst
-            pred = eff * z_pop
-            pre = plan_prefix(plan)
-            tried.append({"comp_full_blocks": pre[0] if pre else None, "comp_mlp_blocks": pre[1] if pre else None, "plan": plan_string(plan),
-                          "max_abs_dcos": float(f"{err:.3e}"), "rms_dcos": float(f"{rms:.3e}"), "rms_dcos_vs_bank": float(f"{rms_bank:.3e}"),
-                          "rms_dcos_isotropic": float(f"{rms_iso:.3e}"), "governing_group": name, "predicted_max_abs_dcos": float(f"{pred:.3e}"),
-                          "isotropic_rms_by_group": {k: v["rms_dcos_isotropic"] for k, v in per_group.items() if isinstance(v, dict)},
-                          "anisotropy_factor": per_group["anisotropy_factor"]})
-            if pred <= tolerance:                 # (NaN compares False: falls through to the next candidate)
-                chosen, chosen_stats = plan, (err, rms, pred, tail, margin, name, per_group, sig)
-                return True
-            return False
+        def iso_var(plan: Plan):              # isotropic error variance per group of the share probe under `plan`
+            self.set_plan(plan)
+            f = self._encode_probe(sh_tiles)
+            e2 = (f - sh_ref_f).pow(2).sum(dim=1).div_(f.shape[1])
+            return [float(e2[idx].mean()) for _, idx in sh_members]
 
         try:
             self.set_precision("strict", strict_blocks)
-            ref_f = encode_probe(tiles)
+            ref_f = self._encode_probe(tiles)
             ref = self.similarity(ref_f, bank)                              # cosines on the engine's exact-fp32 similarity kernel
             self.set_precision("comp", strict_blocks)
             if not bool(torch.isfinite(ref).all()):
                 self._raise_flags(2)
             if budget == "ladder":
-                for full, mlp in dict.fromkeys((min(a, depth), min(b, depth)) for a, b in COMP_LADDER):
-                    if consider(prefix_plan(depth, full, mlp)):
-                        break
+                candidates = ladder_candidates(depth)
             else:
-                # the shares only rank the knobs: a sixteenth of the probe (at least 16 tiles of every group) is enough
-                sel = torch.cat([idx[:max(16, int(idx.numel()) // 16)] for _, idx in members])
-                sh_members = []
-                at = 0
-                for name, idx in members:
-                    k = min(max(16, int(idx.numel()) // 16), int(idx.numel()))
-                    sh_members.append((name, torch.arange(at, at + k, device=dev)))
-                    at += k
-                shares = self._measure_shares(tiles[sel], ref_f[sel], depth, sh_members)
-                walk = self._greedy_walk(shares, depth, knobs or DEFAULT_KNOBS)
-                # the sum of measured shares over-predicts the rms of a plan by 3-11 % (variances of neighbouring sites do not quite add): start the
-                # verification a little before the predicted crossing and walk up one knob at a time until a plan verifies
-                start = next((i for i, (_, v) in enumerate(walk) if v <= (1.06 * rms_target) ** 2), len(walk) - 1)
-                # verified from there upwards, ONE knob at a time, until a plan passes.  (Not by bisection: the prediction is not monotone along the walk --
-                # the anisotropy factor moves between 1.0 and 2.0 once the isotropic error is small -- and a bisection that lands in that region keeps a
-                # plan several times dearer than the first one that verifies: round 6 saw 47.8 instead of 35.4 ms per step.)
-                for plan, _ in walk[start:]:
-                    if consider(plan):
-                        break
+                sel, sh_members = share_probe(members)
+                sh_tiles, sh_ref_f = tiles[sel], ref_f[sel]
+                shares = measure_shares(iso_var, depth, sh_members)
+                rms_target = tolerance / (max_sigmas_quantile(population, confidence) * PROBE_RMS_MARGIN)
+                candidates = walk_candidates(greedy_walk(shares, depth, knobs or DEFAULT_KNOBS), rms_target)
+            chosen, stats, tried = search(candidates, verify, tolerance)
             if chosen is None:
                 self.set_precision("strict", strict_blocks)
             self.check_errors(wait=True)
@@ -674,147 +460,21 @@ class KEEPModel(SlideOps):
                         self._apply_options()
                     except Exception:
                         pass
-        pre = plan_prefix(chosen) if chosen else None
-        self.calibration = {"precision": "comp" if chosen else "strict", "comp_full_blocks": pre[0] if pre else None,
-                            "comp_mlp_blocks": pre[1] if pre else None, "plan": plan_string(chosen) if chosen else None, "budget": budget,
-                            "population": population, "confidence": confidence, "max_sigmas_quantile": round(z_pop, 3),
-                            "expected_max_sigmas": round(expected_max_sigmas(population), 3),
-                            "target_rms_dcos": float(f"{rms_target:.3e}"), "strict_blocks": strict_blocks,
-                            "probe": f"{tiles.shape[0]} tiles x {bank.shape[0]} prompts vs the split-product arithmetic", "probe_distribution": probe_name,
-                            "probe_groups": [name for name, _ in members], "tried": tried,
-                            "bias_correction": bool(lib.keep_get_option(h, b"bias_ready") > 0 and lib.keep_get_option(h, b"bias_correction") > 0)}
+        unit, n_margins = 0.0, 0.0
         if chosen:
-            err, rms, pred, tail, margin_g, gov, per_group, sig = chosen_stats
-            # keep_classify looks a second time at tiles whose top-2 cosine margin could hide a flipped label.  A margin is the difference of two
-            # cosines of ONE tile, i.e. its error vector projected on t1 - t2: standard deviation |t1 - t2| x rms, and there is ONE margin per tile:
-            # the quantile is taken over the tiles of the population (`label_population`; default: the 100 000 tiles of the default population, the
-            # whole population for a caller's own), at the same confidence.  |t1 - t2| <= 2 in general; the engine's default is sqrt 2 (prompts
-            # with a non-negative cosine -- every pair of the banks this repository has seen); ``classify`` scales it by the caller's own bank.
-            n_margins = float(label_population) if label_population else (100_000.0 if population == float(CALIBRATION_POPULATION) else population)
-            unit = mixture_max_quantile(sig, n_margins, confidence)
-            margin = math.sqrt(2.0) * unit
-            self.set_option("label_margin", margin)
+            unit, n_margins = label_margin_unit(stats.governing.sigmas, population, label_population, confidence)
+            self.set_option("label_margin", math.sqrt(2.0) * unit)
             self._label_margin_unit = unit
-            self.calibration.update({"probe_max_abs_dcos": float(f"{err:.3e}"), "probe_rms_dcos": float(f"{rms:.3e}"), "tail_factor": round(tail, 3),
-                                     "rms_margin": round(margin_g, 4), "governing_group": gov, "per_group": per_group,
-                                     "predicted_max_abs_dcos": float(f"{pred:.3e}"),
-                                     "exceedance_probability": float(f"{mixture_exceedance(sig, population, tolerance):.3e}"),
-                                     "label_margin": float(f"{margin:.3e}"), "label_margin_per_unit_prompt_distance": float(f"{unit:.3e}"),
-                                     "label_population": n_margins})
-        if shares is not None:
-            self.calibration["variance_shares"] = shares
+        self.calibration = calibration_report(
+            chosen=chosen, stats=stats, tried=tried, shares=shares, budget=budget, population=population, confidence=confidence, tolerance=tolerance,
+            strict_blocks=strict_blocks, probe_tiles=int(tiles.shape[0]), prompts=int(bank.shape[0]), probe_name=probe_name,
+            group_names=[name for name, _ in members], label_unit=unit, label_population=n_margins,
+            bias_correction=bool(lib.keep_get_option(h, b"bias_ready") > 0 and lib.keep_get_option(h, b"bias_correction") > 0))
         return self.calibration
 
-    def _measure_shares(self, tiles, ref_f, depth: int, members=None) -> dict:
-        """Cosine-error variance each block's attention side / MLP contributes when it alone runs single fp16 passes and everything else split
-        products (so the figure is that site's own rounding error, not the re-drawn rounding of everything downstream), plus what is left of a
-        site's share under the cheaper treatments -- per tile group (``members``: [(name, indices into ``tiles``)]).  Variances are the isotropic
-        ones -- |feature error|^2 / D, the mean squared cosine error over random prompt directions -- which ranks the knobs independently of any
-        prompt bank.  Top-level ``attn`` / ``mlp`` / ``floor`` / ``residual_*`` hold the worst group's value per entry; ``by_group`` everything."""
-        split = [(_lib.ATTN_SPLIT, _lib.MLP_SPLIT)] * depth
-        if members is None:
-            members = [("all", torch.arange(tiles.shape[0], device=tiles.device))]
-        G = len(members)
-
-        def iso_var():
-            f = self.encode_image(tiles) if tiles.shape[0] <= 256 else torch.cat([self.encode_image(tiles[i:i + 256]) for i in range(0, tiles.shape[0], 256)])
-            e2 = (f - ref_f).pow(2).sum(dim=1).div_(f.shape[1])
-            return [float(e2[idx].mean()) for _, idx in members]
-
-        def var_of(i, mode):
-            p = list(split)
-            p[i] = mode
-            self.set_plan(p)
-            return iso_var()
-
-        def minus_floor(v):
-            return [max(v[g] - floor[g], 0.0) for g in range(G)]
-
-        def ratio(v, base):
-            return [min(v[g] / base[g], 1.0) if base[g] > 0 else 0.0 for g in range(G)]
-
-        self.set_plan(split)
-        floor = iso_var()
-        attn = [minus_floor(var_of(i, (_lib.ATTN_PLAIN, _lib.MLP_SPLIT))) for i in range(depth)]          # [depth][G]
-        mlp = [minus_floor(var_of(i, (_lib.ATTN_SPLIT, _lib.MLP_PLAIN))) for i in range(depth)]
-        res_m = {k: [v] * G for k, v in MLP_RESIDUAL.items()}
-        res_a = {k: [v] * G for k, v in ATTN_RESIDUAL.items()}
-        # what the CLS-rows-only treatment leaves differs from block to block (most in the first, where every row's error is amplified by all the
-        # attention layers that follow) and from group to group (on correlated tiles the other rows carry the SAME error): measured for every block
-        cls_left = [ratio(minus_floor(var_of(i, (_lib.ATTN_SPLIT, _lib.MLP_CLS))), mlp[i]) for i in range(depth)]
-        for mode in (_lib.MLP_COMP, _lib.MLP_COMP_W):
-            fr = [ratio(minus_floor(var_of(i, (_lib.ATTN_SPLIT, mode))), mlp[i]) for i in sorted({0, depth // 2})]
-            res_m[mode] = [sum(f[g] for f in fr) / len(fr) for g in range(G)]
-        for mode in (_lib.ATTN_SPLIT_COMPQKV, _lib.ATTN_COMPQKV, _lib.ATTN_COMPQKV_PROJ_CLS):
-            fr = [ratio(minus_floor(var_of(i, (mode, _lib.MLP_SPLIT))), attn[i]) for i in sorted({0, min(1, depth - 1), depth // 2})]
-            res_a[mode] = [max(f[g] for f in fr) for g in range(G)]
-        # ... and so does what the CLS-row proj leaves of an attention side (nearly all of it in block 0 of N(0,1) tiles, under half on correlated tiles)
-        pcls_left = [ratio(minus_floor(var_of(i, (_lib.ATTN_PROJ_CLS, _lib.MLP_SPLIT))), attn[i]) for i in range(depth)]
-        r3 = lambda v: float(f"{v:.3e}")
-        r4 = lambda v: float(f"{v:.4f}")
-        by_group = {}
-        for g, (name, idx) in enumerate(members):
-            rm = {int(k): r4(v[g]) for k, v in res_m.items()}
-            rm[int(_lib.MLP_CLS)] = [r4(cls_left[i][g]) for i in range(depth)]
-            ra = {int(k): r4(v[g]) for k, v in res_a.items()}
-            ra[int(_lib.ATTN_PROJ_CLS)] = [r4(pcls_left[i][g]) for i in range(depth)]
-            by_group[name] = {"attn": [r3(attn[i][g]) for i in range(depth)], "mlp": [r3(mlp[i][g]) for i in range(depth)], "floor": r3(floor[g]),
-                              "residual_mlp": rm, "residual_attn": ra, "probe_tiles": int(idx.numel())}
-        worst_m = {int(k): r4(max(v)) for k, v in res_m.items()}
-        worst_m[int(_lib.MLP_CLS)] = [r4(max(cls_left[i])) for i in range(depth)]
-        worst_a = {int(k): r4(max(v)) for k, v in res_a.items()}
-        worst_a[int(_lib.ATTN_PROJ_CLS)] = [r4(max(pcls_left[i])) for i in range(depth)]
-        return {"attn": [r3(max(attn[i])) for i in range(depth)], "mlp": [r3(max(mlp[i])) for i in range(depth)], "floor": r3(max(floor)),
-                "residual_mlp": worst_m, "residual_attn": worst_a, "probe_tiles": int(tiles.shape[0]),
-                "groups": [name for name, _ in members], "by_group": by_group}
-
-    @staticmethod
-    def _greedy_walk(shares: dict, depth: int, knobs: Mapping) -> List[Tuple[Plan, float]]:
-        """[(plan, predicted cosine-error variance of the WORST tile group)] from the all-plain plan upwards: every step takes the ONE upgrade (a
-        block's attention side or MLP to one of the allowed treatments) that lowers the worst group's predicted variance most per millisecond
-        (KNOB_COST_MS); when no upgrade moves the worst group any more, the one with the largest summed reduction.  The last entry has every site
-        at its best allowed treatment.  ``shares`` without ``by_group`` (one group) are read from the top level."""
-        groups = list(shares["by_group"].values()) if shares.get("by_group") else [shares]
-        G = len(groups)
-        res_a = [{int(k): v for k, v in g["residual_attn"].items()} for g in groups]
-        res_m = [{int(k): v for k, v in g["residual_mlp"].items()} for g in groups]
-        left_m = lambda g, i, mode: (res_m[g][mode][i] if isinstance(res_m[g][mode], (list, tuple)) else res_m[g][mode])
-        left_a = lambda g, i, mode: (res_a[g][mode][i] if isinstance(res_a[g][mode], (list, tuple)) else res_a[g][mode])
-        cost_a = {_lib.ATTN_PLAIN: 0.0, _lib.ATTN_PROJ_CLS: KNOB_COST_MS["attn_proj_cls"], _lib.ATTN_COMPQKV: KNOB_COST_MS["attn_compqkv"],
-                  _lib.ATTN_COMPQKV_PROJ_CLS: KNOB_COST_MS["attn_compqkv_proj_cls"],
-                  _lib.ATTN_SPLIT_COMPQKV: KNOB_COST_MS["attn_split_compqkv"], _lib.ATTN_SPLIT: KNOB_COST_MS["attn_split"]}
-        cost_m = {_lib.MLP_PLAIN: 0.0, _lib.MLP_CLS: KNOB_COST_MS["mlp_cls"], _lib.MLP_COMP_W: KNOB_COST_MS["mlp_comp_w"], _lib.MLP_COMP: KNOB_COST_MS["mlp_comp"],
-                  _lib.MLP_SPLIT: 3.0 * KNOB_COST_MS["mlp_comp"]}
-        am, mm = [_lib.ATTN_PLAIN] * depth, [_lib.MLP_PLAIN] * depth
-
-        def predicted():
-            return [groups[g]["floor"] + sum(groups[g]["attn"][i] * left_a(g, i, am[i]) + groups[g]["mlp"][i] * left_m(g, i, mm[i]) for i in range(depth))
-                    for g in range(G)]
-
-        cur = predicted()
-        walk = [(list(zip(am, mm)), max(cur))]
-        while True:
-            best, gain, best_sum, gain_sum = None, 0.0, None, 0.0
-            top = max(cur)
-            for i in range(depth):
-                cands = [(am, a, cost_a[a] - cost_a[am[i]], [groups[g]["attn"][i] * (left_a(g, i, am[i]) - left_a(g, i, a)) for g in range(G)]) for a in knobs.get("attn", ())
-                         if a in res_a[0]]
-                cands += [(mm, m, cost_m[m] - cost_m[mm[i]], [groups[g]["mlp"][i] * (left_m(g, i, mm[i]) - left_m(g, i, m)) for g in range(G)]) for m in knobs.get("mlp", ())]
-                for target, mode, dc, dv in cands:
-                    if dc <= 0:
-                        continue
-                    drop = top - max(cur[g] - dv[g] for g in range(G))
-                    if drop > 0 and drop / dc > gain:
-                        best, gain = (target, i, mode), drop / dc
-                    if sum(dv) > 0 and sum(dv) / dc > gain_sum:
-                        best_sum, gain_sum = (target, i, mode), sum(dv) / dc
-            best = best or best_sum
-            if best is None:
-                break
-            best[0][best[1]] = best[2]
-            cur = predicted()
-            walk.append((list(zip(am, mm)), max(cur)))
-        return walk
+    def _encode_probe(self, x: torch.Tensor) -> torch.Tensor:
+        """``encode_image`` in chunks of 256 tiles (the probes of ``calibrate``)."""
+        return torch.cat([self.encode_image(x[i:i + 256]) for i in range(0, x.shape[0], 256)]) if x.shape[0] > 256 else self.encode_image(x)
 
     def get_option(self, name: str) -> float:
         self._ready_device()
@@ -1221,7 +881,7 @@ class KEEPModel(SlideOps):
         if txt.dim() != 2 or txt.shape[1] != D:
             raise ValueError(f"text_features must be [P,{D}], got {tuple(txt.shape)}")
         B, P = x.shape[0], txt.shape[0]
-        if margin is None and getattr(self, "_label_margin_unit", None):
+        if margin is None and self._label_margin_unit:
             margin = self._label_margin_unit * self._bank_diameter(txt)
         self.last_margin = float(margin) if margin is not None else (self.get_option("label_margin") if self._handle.value else None)
         sim = torch.empty((B, P), dtype=torch.float32, device=self._device)

@@ -84,13 +84,13 @@ def test_greedy_walk_serves_the_worst_group():
     """Two tile groups whose error lives in different places: every step of the walk lowers the WORST group's predicted variance, and the plan that
     ends the walk treats both."""
     from keep_amd import _lib
-    from keep_amd.model import DEFAULT_KNOBS, KEEPModel
+    from keep_amd.calibration import DEFAULT_KNOBS, greedy_walk
     depth = 4
     res_m = {0: 1.0, 1: 0.0, 2: 0.04, 3: 0.5, 4: [0.05] * depth}
     res_a = {0: 1.0, 1: 0.0, 2: 0.015, 3: 0.6}
     g1 = {"attn": [8.0, 0.1, 0.1, 0.1], "mlp": [1.0, 1.0, 0.5, 0.5], "floor": 0.01, "residual_mlp": res_m, "residual_attn": res_a}      # block 0's attention side
     g2 = {"attn": [0.5, 0.5, 0.5, 0.5], "mlp": [3.0, 3.0, 3.0, 3.0], "floor": 0.01, "residual_mlp": res_m, "residual_attn": res_a}      # every MLP
-    walk = KEEPModel._greedy_walk({"by_group": {"a": g1, "b": g2}}, depth, DEFAULT_KNOBS)
+    walk = greedy_walk({"by_group": {"a": g1, "b": g2}}, depth, DEFAULT_KNOBS)
     worst = [v for _, v in walk]
     assert worst[0] == pytest.approx(max(0.01 + 8.3 + 3.0, 0.01 + 2.0 + 12.0))
     assert all(b <= a + 1e-12 for a, b in zip(worst, worst[1:])) and worst[-1] < 0.05 * worst[0]
@@ -98,7 +98,7 @@ def test_greedy_walk_serves_the_worst_group():
     assert any(m != _lib.MLP_PLAIN for _, m in first) and all(a == _lib.ATTN_PLAIN for a, _ in first)      # group b governs at the start: an MLP knob goes first
     assert walk[-1][0][0][0] != _lib.ATTN_PLAIN                                                             # ... and group a's block-0 attention side is treated before the end
     # one group, read from the top level (the pre-round-6 form of the shares)
-    solo = KEEPModel._greedy_walk(g1, depth, DEFAULT_KNOBS)
+    solo = greedy_walk(g1, depth, DEFAULT_KNOBS)
     assert solo[1][0][0][0] != _lib.ATTN_PLAIN
 
 
