@@ -245,6 +245,43 @@ int keep_region_grid_mask(keep_handle* h, const unsigned char* mask, int64_t mh,
                           int64_t patch, int64_t step, int64_t origin_x, int64_t origin_y, int mode, int32_t* cell_xy_out, int64_t* n_out,
                           void* stream);
 
+/* ---- Macenko stain normalisation ---------------------------------------------
+ * Replaces: nothing the reference runs (its WSI scripts read features of tiles as they were scanned); it stands where a host
+ * library (torchstain, staintools) would otherwise sit between the patch cut and quick_start/keep_inference.py:54-58's
+ * encode_image.  Macenko et al. 2009 restated in fixed point, integer arithmetic, exact against keep_amd.stain's numpy restatements;
+ * the dense algebra between the passes (3 x 3 eigh, 3 x 2 pinv, percentiles off the histograms) is the caller's, in float64.
+ * image: uint8 [H,W,C] RGB / RGBA with the layout contract of keep_region_grid, H W <= 2^30.  mask: NULL (every pixel) or uint8
+ * [mh,mw] contiguous on the device, one pixel = downsample x downsample image pixels: pixel (x, y) reads
+ * mask[y / downsample][x / downsample], outside the mask it is not allowed.  od_q: int32 [256] on the device,
+ * rint(-ln((v + 1) / Io) * 2^12), |od_q| < 2^15.  A pixel is KEPT iff the mask allows it and all three od_q >= beta_q.
+ * moments_out: int64 [10] on the device, 8-byte aligned: n, S_r, S_g, S_b, S_rr, S_rg, S_rb, S_gg, S_gb, S_bb over the kept pixels.
+ * zero_first != 0 starts a new sum, 0 adds to the one there: integer sums, so the result is the same however the pixels are split
+ * over calls (bands of a region, slides of a cohort). */
+int keep_stain_moments(keep_handle* h, const unsigned char* image, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
+                       const unsigned char* mask, int64_t mh, int64_t mw, int64_t downsample, const int32_t* od_q, int beta_q, int zero_first,
+                       int64_t* moments_out, void* stream);
+/* Replaces: numpy.arctan2 of the kept pixels' plane coordinates + the histogram behind numpy.percentile.  v_q: int32 [3][2] ON THE
+ * HOST, |v_q| <= 2^14 (rint(V * 2^14) of two unit vectors); t = od_q . v_q per kept pixel, |t| < 2^31.  hist_out: int32 [4096] on
+ * the device: the bin of atan2(t1, t0) among 4096 equal bins of [-pi, pi), decided by integer comparisons against dirs: int32
+ * [1024][2] on the device, (rint(2^30 cos), rint(2^30 sin)) of j 2 pi / 4096; t = (0, 0) counts as the angle 0, the angle pi as -pi.
+ * zero_first as above; at most 2^31 - 1 pixels may ever be added into one histogram. */
+int keep_stain_angle_hist(keep_handle* h, const unsigned char* image, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
+                          const unsigned char* mask, int64_t mh, int64_t mw, int64_t downsample, const int32_t* od_q, int beta_q,
+                          const int32_t* v_q, const int32_t* dirs, int zero_first, int32_t* hist_out, void* stream);
+/* Replaces: numpy.linalg.lstsq(HE, OD) over every pixel the mask allows (no beta rule, as the float method has none there) + the
+ * histograms behind the 99th percentiles.  minv_q: int32 [2][3] ON THE HOST, rint(pinv(HE) * 2^14), |minv_q| <= 2^24; c_s = od_q .
+ * minv_q[s] in Q26; hist_out: int32 [2][4096] on the device, bin clamp(c_s >> 17, 0, 4095) (1 / 512 wide, 0 .. 8). */
+int keep_stain_conc_hist(keep_handle* h, const unsigned char* image, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
+                         const unsigned char* mask, int64_t mh, int64_t mw, int64_t downsample, const int32_t* od_q, const int32_t* minv_q,
+                         int zero_first, int32_t* hist_out, void* stream);
+/* Replaces: Io * exp(-HERef . (C * maxCRef / maxC)) of the float method, and its colour deconvolution images, as ONE 3 x 3 matrix
+ * between two tables.  src, dst: uint8 [n,3] contiguous on the device, dst == src allowed (no other overlap).  t_q: int32 [3][3] ON
+ * THE HOST, rint(T * 2^14), |T| <= 64 or KEEP_EINVAL.  Per pixel and output channel o = (sum_d t_q[c][d] od_q[src_d] + 2^15) >> 16
+ * (Q10, arithmetic shift) and dst_c = exp_lut[clamp(o - lo, 0, lut_len - 1)]; exp_lut: uint8 [lut_len] on the device, 4-byte aligned,
+ * 1 <= lut_len <= 8192. */
+int keep_stain_apply_u8(keep_handle* h, const unsigned char* src, int64_t n, const int32_t* od_q, const int32_t* t_q,
+                        const unsigned char* exp_lut, int lut_len, int lo, unsigned char* dst, void* stream);
+
 /* ---- tile scores rasterised onto the slide thumbnail -------------------------
  * The accumulator `acc` is int64 [H,W] contiguous on the device, 8-byte aligned, H W <= 2^30, one word per raster pixel read as
  * unsigned: bits 0..39 hold the sum of q over the tiles that cover the pixel, bits 40..63 their number, q = rint(clip(value, 0, 1) *

@@ -20,4 +20,7 @@ __all__ += ["FrocAccumulator", "FrocCurve", "camelyon16_margin", "RegionShape", 
 from .bootstrap import BootstrapResult
 
 __all__ += ["BootstrapResult"]
+from .stain import StainFit, StainTarget
+
+__all__ += ["StainFit", "StainTarget"]
 __version__ = "0.1.0"

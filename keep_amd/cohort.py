@@ -84,7 +84,7 @@ def save_slide_features(data_source: str, slide_id: str, features: torch.Tensor,
 @torch.no_grad()
 def extract_slide_features(read_region, width: int, height: int, slide_id: str, data_source: str, patch_size: int = 256,
                            step: Optional[int] = None, tissue=None, band_rows: int = 8, coord_scale: int = 1, use_h5: bool = False,
-                           model=None, thumbnail=None, thumbnail_downsample: Optional[int] = None, segmentation=None) -> str:
+                           model=None, thumbnail=None, thumbnail_downsample: Optional[int] = None, segmentation=None, stain=None) -> str:
     """The feature files the WSI scripts read, made on the device (replaces the CLAM extraction step of README.md:74).
 
     ``read_region(x, y, w, h)`` returns uint8 [h, w, 3 | 4] pixels of the slide level being tiled, ``width`` x ``height`` pixels
@@ -110,9 +110,16 @@ def extract_slide_features(read_region, width: int, height: int, slide_id: str, 
     With a mask the cells of every band are decided BEFORE ``read_region``: a band with no kept cell is not read at all, of the
     others only the columns ``[min kept x, max kept x + patch_size)`` (keep_amd.region.plan_mask_reads), and that window is cut
     with ``origin=(x0, y0)``.  Rows and coords come out in the same slide row-major order, and the tiles are encoded in the batches
-    ``encode_region(whole slide, tissue=mask)`` would form, so the features equal its features exactly."""
+    ``encode_region(whole slide, tissue=mask)`` would form, so the features equal its features exactly.
+
+    ``stain``: a ``keep_amd.stain.StainFit`` (``model.stain_fit(...)``) normalises every batch of cut tiles on the device before it is
+    encoded (``encode_region(..., stain=fit)``); ``"macenko"`` fits one first on ``thumbnail`` under the tissue mask
+    made from it, and so needs ``thumbnail=``; ``None`` (the default) changes nothing."""
     from .model import engine_for
     from .region import TissueMask, check_grid_args, plan_bands, plan_mask_reads
+    from .stain import check_stain
+    if check_stain(stain, allow_name=True) == "macenko" and thumbnail is None:
+        raise ValueError('stain="macenko" fits on the thumbnail: give thumbnail= (or a StainFit of your own)')
     patch, step, _, coord_scale = check_grid_args(patch_size, step, (0, 0), coord_scale)
     bands = plan_bands(width, height, patch, step, band_rows)
     if thumbnail is not None and (tissue is not None or thumbnail_downsample is None):
@@ -122,6 +129,8 @@ def extract_slide_features(read_region, width: int, height: int, slide_id: str, 
     m = engine_for(model=model)
     if thumbnail is not None:
         tissue = m.tissue_mask(thumbnail, thumbnail_downsample, segmentation)
+        if isinstance(stain, str):                                 # the mask lies on the thumbnail pixel for pixel
+            stain = m.stain_fit(thumbnail, TissueMask(tissue.mask, 1))
     feats, coords = [], []
     if isinstance(tissue, TissueMask):
         # every kept cell of the slide, decided on the mask alone; then per band only the window that holds kept cells is read.
@@ -143,7 +152,7 @@ def extract_slide_features(read_region, width: int, height: int, slide_id: str, 
             if band.dim() != 3 or tuple(band.shape[:2]) != (h, w):
                 raise ValueError(f"read_region({x0}, {y0}, {w}, {h}) returned {tuple(band.shape)}, expected [{h}, {w}, 3|4]")
             xy = torch.from_numpy(cells[(cells[:, 1] >= y0) & (cells[:, 1] + patch <= y0 + h)] * coord_scale)
-            pending.append(m.region_patches_uint8(band.to(m._device), xy, patch, origin=(x0, y0), coord_scale=coord_scale))
+            pending.append(m.region_patches_uint8(band.to(m._device), xy, patch, origin=(x0, y0), coord_scale=coord_scale, stain=stain))
             n_pending += len(xy)
             coords.append(xy)
             encode(final=False)
@@ -154,7 +163,7 @@ def extract_slide_features(read_region, width: int, height: int, slide_id: str, 
             band = torch.from_numpy(np.ascontiguousarray(band)) if not isinstance(band, torch.Tensor) else band
             if band.dim() != 3 or tuple(band.shape[:2]) != (h, width):
                 raise ValueError(f"read_region(0, {y0}, {width}, {h}) returned {tuple(band.shape)}, expected [{h}, {width}, 3|4]")
-            f, c = m.encode_region(band, patch, step, tissue, origin=(0, y0), coord_scale=coord_scale)
+            f, c = m.encode_region(band, patch, step, tissue, origin=(0, y0), coord_scale=coord_scale, stain=stain)
             feats.append(f.cpu())
             coords.append(c.cpu())
     features = torch.cat(feats) if feats else torch.empty((0, m.config.projection_dim), dtype=torch.float32)

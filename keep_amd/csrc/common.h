@@ -258,6 +258,23 @@ void launch_tissue_mask(const unsigned char* med, int h, int w, int thr, int clo
 void launch_tissue_grid_cells(const unsigned char* mask, int64_t mh, int64_t mw, int64_t ds, int gx, int64_t ncells, int patch, int step,
                               int64_t ox, int64_t oy, int mode, unsigned char* keep, hipStream_t s);
 
+// Macenko stain normalisation (stain.hip).  img / mask as above: a strided RGB / RGBA view and a nullable {0,1}
+// mask [mh,mw] one pixel of which covers ds x ds image pixels (outside the mask: not allowed).  od_q: int32 [256] on the device.
+constexpr int STAIN_MOMENTS = 10;                       // n, S_r, S_g, S_b, S_rr, S_rg, S_rb, S_gg, S_gb, S_bb
+constexpr int STAIN_ANGLE_BINS = 4096;                  // equal bins of [-pi, pi); the direction table holds the first quarter
+constexpr int STAIN_CONC_BINS = 4096, STAIN_CONC_SHIFT = 17;   // Q26 >> 17: bins 1 / 512 wide over 0 .. 8
+constexpr int STAIN_LUT_MAX = 8192;                     // bytes of the exp table in LDS (8 OD units in Q10) beside the 3 KiB of od tables
+constexpr int64_t STAIN_T_MAX = (int64_t)64 << 14;      // |T_q|: keeps the apply's split products inside an int32
+// all three add into their output (the caller zeroes it); v_q [3][2], minv_q [2][3] and t_q [3][3] are HOST arrays, passed by value
+void launch_stain_moments(const unsigned char* img, int64_t row_stride, int ps, int h, int w, const unsigned char* mask, int64_t mh, int64_t mw,
+                          int64_t ds, const int* od_q, int beta_q, int64_t* out, hipStream_t s);
+void launch_stain_angle_hist(const unsigned char* img, int64_t row_stride, int ps, int h, int w, const unsigned char* mask, int64_t mh,
+                             int64_t mw, int64_t ds, const int* od_q, int beta_q, const int* v_q, const int* dirs, int* hist, hipStream_t s);
+void launch_stain_conc_hist(const unsigned char* img, int64_t row_stride, int ps, int h, int w, const unsigned char* mask, int64_t mh,
+                            int64_t mw, int64_t ds, const int* od_q, const int* minv_q, int* hist, hipStream_t s);
+void launch_stain_apply_u8(const unsigned char* src, unsigned char* dst, int64_t n, const int* od_q, const int* t_q, const unsigned char* exp_lut,
+                           int lut_len, int lo, hipStream_t s);
+
 // the labelling alone: foreground components of img, 8- or 4-connected -> labels[p] = the component's smallest pixel index (-1 on the
 // background), info[root] = area | CC_BORDER (labelling.h)
 void launch_cc_label(const unsigned char* img, int h, int w, int conn8, int* labels, int* info, int* err, hipStream_t s);

@@ -1,6 +1,6 @@
-// The slide-geometry entry points of include/keep_hip.h: patch grid, tissue mask, heatmap, sort / rank, region table, outlines, polygon
+// The slide-geometry entry points of include/keep_hip.h: patch grid, tissue mask, stain normalisation, heatmap, sort / rank, region table, outlines, polygon
 // fill, segmentation evaluation, bootstrap resampling, the subtype map and tile clustering.  Host code only: each function validates its arguments, carves its workspace from the handle's
-// arena, calls the launch_* of its kernel file (region / tissue / heatmap / rank / components / outline / annotation / eval / bootstrap .hip) and
+// arena, calls the launch_* of its kernel file (region / tissue / stain / heatmap / rank / components / outline / annotation / eval / bootstrap .hip) and
 // reports the launch.  Of the handle (handle.h) they use the device, the error text, the arena and the sticky error flag.
 #include "handle.h"
 
@@ -802,6 +802,84 @@ int keep_cluster_seed_step(keep_handle* h, const float* features, int64_t N, int
     if (rc) return rc;
     launch_cluster_seed_step(features, (int)N, (int)D, centre, centre_row, first, nearest, (unsigned char*)h->arena, index_out, (hipStream_t)stream);
     return check_launch(h, "cluster_seed_step");
+}
+
+// the image, mask and od table that the three fit passes of the stain normalisation share
+static int stain_view_check(keep_handle* h, const char* who, const unsigned char* image, int64_t H, int64_t W, int64_t row_stride_bytes,
+                            int pix_stride, const unsigned char* mask, int64_t mh, int64_t mw, int64_t downsample, const int32_t* od_q) {
+    if (!image || H < 1 || W < 1) return h->fail(KEEP_EINVAL, "%s: null pointer or empty shape %lldx%lld", who, (long long)H, (long long)W);
+    if (int rc = pix_stride_check(h, who, pix_stride)) return rc;
+    if (!pixels_ok(H, W, TISSUE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "%s: %lldx%lld pixels (limit H W <= 2^30)", who, (long long)H, (long long)W);
+    if (int rc = row_stride_check(h, who, W, row_stride_bytes, pix_stride)) return rc;
+    if (mask && (mh < 1 || mw < 1 || mh > INT32_MAX || mw > INT32_MAX))
+        return h->fail(KEEP_EINVAL, "%s: bad mask shape %lldx%lld", who, (long long)mh, (long long)mw);
+    if (mask && (downsample < 1 || downsample > INT32_MAX)) return h->fail(KEEP_EINVAL, "%s: downsample %lld < 1", who, (long long)downsample);
+    if (!od_q || ((uintptr_t)od_q & 3)) return h->fail(KEEP_EINVAL, "%s: null or unaligned od_q", who);
+    return KEEP_OK;
+}
+
+int keep_stain_moments(keep_handle* h, const unsigned char* image, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
+                       const unsigned char* mask, int64_t mh, int64_t mw, int64_t downsample, const int32_t* od_q, int beta_q, int zero_first,
+                       int64_t* moments_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = stain_view_check(h, "stain_moments", image, H, W, row_stride_bytes, pix_stride, mask, mh, mw, downsample, od_q)) return rc;
+    if (!moments_out || ((uintptr_t)moments_out & 7)) return h->fail(KEEP_EINVAL, "stain_moments: null or unaligned moments_out");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (zero_first) HIPCHK(h, hipMemsetAsync(moments_out, 0, STAIN_MOMENTS * sizeof(int64_t), s));
+    launch_stain_moments(image, row_stride_bytes, pix_stride, (int)H, (int)W, mask, mh, mw, mask ? downsample : 1, od_q, beta_q, moments_out, s);
+    return check_launch(h, "stain_moments");
+}
+
+int keep_stain_angle_hist(keep_handle* h, const unsigned char* image, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
+                          const unsigned char* mask, int64_t mh, int64_t mw, int64_t downsample, const int32_t* od_q, int beta_q,
+                          const int32_t* v_q, const int32_t* dirs, int zero_first, int32_t* hist_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = stain_view_check(h, "stain_angle_hist", image, H, W, row_stride_bytes, pix_stride, mask, mh, mw, downsample, od_q)) return rc;
+    if (!v_q || !dirs || ((uintptr_t)dirs & 7) || !hist_out || ((uintptr_t)hist_out & 3))
+        return h->fail(KEEP_EINVAL, "stain_angle_hist: null v_q, dirs or hist_out, or dirs / hist_out unaligned");
+    for (int i = 0; i < 6; ++i)
+        if (v_q[i] < -(1 << 14) || v_q[i] > (1 << 14)) return h->fail(KEEP_EINVAL, "stain_angle_hist: v_q[%d] = %d outside +-2^14", i, v_q[i]);
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (zero_first) HIPCHK(h, hipMemsetAsync(hist_out, 0, STAIN_ANGLE_BINS * sizeof(int32_t), s));
+    launch_stain_angle_hist(image, row_stride_bytes, pix_stride, (int)H, (int)W, mask, mh, mw, mask ? downsample : 1, od_q, beta_q, v_q, dirs,
+                            hist_out, s);
+    return check_launch(h, "stain_angle_hist");
+}
+
+int keep_stain_conc_hist(keep_handle* h, const unsigned char* image, int64_t H, int64_t W, int64_t row_stride_bytes, int pix_stride,
+                         const unsigned char* mask, int64_t mh, int64_t mw, int64_t downsample, const int32_t* od_q, const int32_t* minv_q,
+                         int zero_first, int32_t* hist_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = stain_view_check(h, "stain_conc_hist", image, H, W, row_stride_bytes, pix_stride, mask, mh, mw, downsample, od_q)) return rc;
+    if (!minv_q || !hist_out || ((uintptr_t)hist_out & 3)) return h->fail(KEEP_EINVAL, "stain_conc_hist: null minv_q or hist_out, or hist_out unaligned");
+    for (int i = 0; i < 6; ++i)
+        if (minv_q[i] < -(1 << 24) || minv_q[i] > (1 << 24))
+            return h->fail(KEEP_EINVAL, "stain_conc_hist: minv_q[%d] = %d outside +-2^24", i, minv_q[i]);
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (zero_first) HIPCHK(h, hipMemsetAsync(hist_out, 0, 2 * STAIN_CONC_BINS * sizeof(int32_t), s));
+    launch_stain_conc_hist(image, row_stride_bytes, pix_stride, (int)H, (int)W, mask, mh, mw, mask ? downsample : 1, od_q, minv_q, hist_out, s);
+    return check_launch(h, "stain_conc_hist");
+}
+
+int keep_stain_apply_u8(keep_handle* h, const unsigned char* src, int64_t n, const int32_t* od_q, const int32_t* t_q,
+                        const unsigned char* exp_lut, int lut_len, int lo, unsigned char* dst, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (n < 0 || n > ((int64_t)1 << 40) || (n > 0 && (!src || !dst))) return h->fail(KEEP_EINVAL, "stain_apply_u8: bad n %lld or null pointer", (long long)n);
+    if (!od_q || ((uintptr_t)od_q & 3) || !t_q || !exp_lut || ((uintptr_t)exp_lut & 3))
+        return h->fail(KEEP_EINVAL, "stain_apply_u8: null t_q, or od_q / exp_lut null or not 4-byte aligned");
+    if (lut_len < 1 || lut_len > STAIN_LUT_MAX) return h->fail(KEEP_EINVAL, "stain_apply_u8: lut_len %d outside [1, %d]", lut_len, STAIN_LUT_MAX);
+    if (lo < -(1 << 24) || lo > (1 << 24)) return h->fail(KEEP_EINVAL, "stain_apply_u8: lo %d outside +-2^24", lo);
+    for (int i = 0; i < 9; ++i)
+        if (t_q[i] < -STAIN_T_MAX || t_q[i] > STAIN_T_MAX)
+            return h->fail(KEEP_EINVAL, "stain_apply_u8: t_q[%d] = %d: |T| > 64", i, t_q[i]);
+    if (src != dst && src < dst + 3 * n && dst < src + 3 * n) return h->fail(KEEP_EINVAL, "stain_apply_u8: src and dst overlap without being equal");
+    if (n == 0) return KEEP_OK;
+    KEEP_ON_DEVICE(h);
+    launch_stain_apply_u8(src, dst, n, od_q, t_q, exp_lut, lut_len, lo, (hipStream_t)stream);
+    return check_launch(h, "stain_apply_u8");
 }
 
 }  // extern "C"

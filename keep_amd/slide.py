@@ -27,6 +27,8 @@ from .morphometry import DEFAULT_MAX_PAIRS, RegionShape, check_shape_args
 from .outline import NCOLS as RING_COLS, RegionOutlines, check_draw_args, check_outline_args, check_ring_count, regions_labels, rgb_tensor
 from .region import (MASK_MODES, TILE, TissueMask, TissueSegmentation, check_downsample, check_grid_args, grid_shape, otsu_threshold, region_layout,
                      resize_tables, thumbnail_layout, tissue_params)
+from . import stain as _stain
+from .stain import StainFit, StainTarget, check_stain
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -1229,6 +1231,124 @@ class SlideOps:
                    em.origin[0], em.origin[1], em.n, _ptr(ignore if em.n else None), _ptr(hit if N else None), _ptr(best if em.n else None))
         return LesionHits(hit, best, em.n - int(ignore.sum()), s[hit == 0] + 0.0)
 
+    # ------------------------------------------------------------------ stain normalisation
+    def _stain_const(self, key, make) -> torch.Tensor:
+        """A host-made table on the device, uploaded once per engine and key."""
+        cache = self.__dict__.setdefault("_stain_consts", {})
+        if key not in cache:
+            cache[key] = torch.from_numpy(make()).to(self._device)
+        return cache[key]
+
+    def _stain_view(self, image, mask, ds):
+        """-> the arguments the three fit passes share: image view, mask (or null) and downsample."""
+        if isinstance(image, np.ndarray):                          # an image of a fit begun with stain_fit_numpy and continued here
+            image = torch.from_numpy(np.ascontiguousarray(image))
+        image = image.to(self._device)
+        H, W, C, row = thumbnail_layout(image)
+        md = None if mask is None else mask.to(self._device, torch.uint8).contiguous()
+        return (_ptr(image), H, W, row, C, _ptr(md), 0 if md is None else int(md.shape[0]), 0 if md is None else int(md.shape[1]), ds), (image, md)
+
+    class _StainPasses:
+        """keep_amd.stain.run_fit's three passes on the device: the accumulators are device tensors, read back by ``to_numpy``."""
+
+        def __init__(self, ops):
+            self.ops = ops
+
+        def _acc(self, acc, shape, dtype):
+            return (torch.empty(shape, dtype=dtype, device=self.ops._device), 1) if acc is None else (acc, 0)
+
+        def moments(self, image, mask, ds, od_q, beta_q, acc):
+            o = self.ops
+            acc, zero = self._acc(acc, (10,), torch.int64)
+            view, _md = o._stain_view(image, mask, ds)
+            o._call("stain_moments", *view, _ptr(o._stain_const(("od", od_q.tobytes()), lambda: od_q)), beta_q, zero, _ptr(acc))
+            return acc
+
+        def angle_hist(self, image, mask, ds, od_q, beta_q, v_q, acc):
+            o = self.ops
+            acc, zero = self._acc(acc, (_stain.ANGLE_BINS,), torch.int32)
+            view, _md = o._stain_view(image, mask, ds)
+            v = np.ascontiguousarray(v_q, dtype=np.int32)
+            o._call("stain_angle_hist", *view, _ptr(o._stain_const(("od", od_q.tobytes()), lambda: od_q)), beta_q, v.ctypes.data_as(C.c_void_p),
+                    _ptr(o._stain_const("dirs", _stain.angle_dirs)), zero, _ptr(acc))
+            return acc
+
+        def conc_hist(self, image, mask, ds, od_q, minv_q, acc):
+            o = self.ops
+            acc, zero = self._acc(acc, (2, _stain.CONC_BINS), torch.int32)
+            view, _md = o._stain_view(image, mask, ds)
+            m = np.ascontiguousarray(minv_q, dtype=np.int32)
+            o._call("stain_conc_hist", *view, _ptr(o._stain_const(("od", od_q.tobytes()), lambda: od_q)), m.ctypes.data_as(C.c_void_p), zero,
+                    _ptr(acc))
+            return acc
+
+        @staticmethod
+        def to_numpy(acc):
+            return acc.cpu().numpy().astype(np.int64)
+
+    @torch.no_grad()
+    def stain_fit(self, image, tissue=None, alpha: float = 1, beta: float = 0.15, io: float = 240, into: Optional[StainFit] = None) -> StainFit:
+        """Macenko fit of the H & E stain of ``image`` on the device -> ``keep_amd.stain.StainFit``.
+
+        ``image``: a thumbnail or region, uint8 [h,w,3] (RGB) or [h,w,4] (RGBA, alpha ignored), host or device, numpy or torch, any
+        row stride, ``h w <= 2^30``.  ``tissue``: a ``TissueMask`` whose pixel covers ``downsample`` x ``downsample`` pixels of ``image``
+        (a mask made from this very thumbnail: ``TissueMask(mask.mask, 1)``) or ``None`` (every pixel).  Three integer passes on the
+        device (moments of the optical density over pixels with every channel ``OD >= beta``; the histogram of their angles in the
+        plane of the two leading eigenvectors; the histograms of the least-squares concentrations over every allowed pixel) with the
+        3 x 3 ``eigh``, the 3 x 2 ``pinv`` and the percentiles (``alpha``, ``100 - alpha``, 99) in float64 on the host between them;
+        equal to ``keep_amd.stain.stain_fit_numpy`` bit for bit.  ``into``: a fit to continue with this image (bands of a region, slides
+        of a cohort); the result is the fit of all its images however they were split.  Fewer than 2 kept pixels, or pixels that span
+        no plane, raise ValueError naming the count."""
+        x = torch.from_numpy(image) if not isinstance(image, torch.Tensor) else image
+        thumbnail_layout(x)
+        _stain.mask_split(tissue)
+        self._ready_device()
+        if x.device != self._device:
+            x = x.to(self._device)
+        return _stain.run_fit(self._StainPasses(self), x, tissue, alpha, beta, io, into)
+
+    def _stain_plan(self, fit, target=None, keep=_stain.STAINS):
+        """A fit (+ target, stains kept) -> what ``keep_stain_apply_u8`` takes: (od_q on the device, t_q on the host, exp table on the
+        device, its length, lo)."""
+        if not isinstance(fit, StainFit):
+            raise ValueError(f"fit must be a StainFit, got {type(fit).__name__}")
+        t = fit.tables(target, keep)
+        return (self._stain_const(("od", t["od_q"].tobytes()), lambda: t["od_q"]), np.ascontiguousarray(t["t_q"], dtype=np.int32),
+                self._stain_const(("exp", t["exp_lut"].tobytes()), lambda: t["exp_lut"]), int(len(t["exp_lut"])), int(t["lo"]))
+
+    def _stain_apply(self, src: torch.Tensor, dst: torch.Tensor, plan) -> None:
+        """keep_stain_apply_u8 on contiguous device uint8 [..., 3]; ``dst`` may be ``src``."""
+        od, t_q, lut, n_lut, lo = plan
+        self._call("stain_apply_u8", _ptr(src), src.numel() // 3, _ptr(od), t_q.ctypes.data_as(C.c_void_p), _ptr(lut), n_lut, lo, _ptr(dst))
+
+    @torch.no_grad()
+    def stain_normalize(self, pixels_u8, fit: StainFit, target: Optional[StainTarget] = None, keep=_stain.STAINS, out=None):
+        """Map uint8 ``[..., 3]`` pixels (``[..., 4]``: the alpha is dropped, the result is ``[..., 3]``) of the stain ``fit`` describes
+        to ``target`` (default: the customary Macenko reference) on the device -> uint8 of the same shape on the input's device, a
+        numpy array for a numpy input.  One kernel: table -> 3 x 3 integer matrix -> table per pixel, equal to
+        ``keep_amd.stain.stain_apply_numpy`` with ``fit.tables(target, keep)`` bit for bit.  ``keep=("H",)`` / ``("E",)`` gives the
+        haematoxylin-only / eosin-only image.  ``out``: a contiguous uint8 tensor of the result's shape on the engine's device; it may
+        be ``pixels_u8`` itself (in place)."""
+        as_numpy = isinstance(pixels_u8, np.ndarray)
+        x = torch.from_numpy(pixels_u8) if as_numpy else pixels_u8
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() < 1 or x.shape[-1] not in (3, 4):
+            raise ValueError(f"pixels must be uint8 [..., 3] or [..., 4], got {getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+        self._ready_device()
+        plan = self._stain_plan(fit, target, keep)
+        src = x.to(self._device)[..., :3].contiguous()
+        if out is None:
+            dst = torch.empty_like(src)
+        else:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self._device or out.shape != src.shape \
+                    or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous uint8 tensor {tuple(src.shape)} on {self._device}")
+            dst = out
+        if src.numel():
+            self._stain_apply(src, dst, plan)
+        if out is not None:
+            return out
+        return dst.cpu().numpy() if as_numpy else (dst if x.device == self._device else dst.to(x.device))
+
     @staticmethod
     def _cells_to_coords(cells: torch.Tensor, origin, coord_scale: int) -> torch.Tensor:
         o = torch.tensor(origin, dtype=torch.int64, device=cells.device)
@@ -1263,53 +1383,60 @@ class SlideOps:
         return coords if x.device == self._device else coords.to(x.device)
 
     @torch.no_grad()
-    def region_patches_uint8(self, region, coords: torch.Tensor, patch_size: int, origin=(0, 0), coord_scale: int = 1) -> torch.Tensor:
+    def region_patches_uint8(self, region, coords: torch.Tensor, patch_size: int, origin=(0, 0), coord_scale: int = 1, stain=None) -> torch.Tensor:
         """The tiles of ``coords`` (as :meth:`region_grid` returns them, same ``origin`` / ``coord_scale``) cut from ``region`` on the
         device -> uint8 [N,224,224,3]: the patches themselves at ``patch_size == 224``, else the reference transform's
-        ``Resize(224, BICUBIC)`` + ``CenterCrop(224)`` of each patch, bit-identical to PIL.  A coord outside the region is a ValueError."""
+        ``Resize(224, BICUBIC)`` + ``CenterCrop(224)`` of each patch, bit-identical to PIL.  A coord outside the region is a ValueError.
+        ``stain``: a ``StainFit`` (:meth:`stain_fit`) maps the cut tiles to the default stain target (:meth:`stain_normalize`, after
+        the resize); ``None`` leaves them as cut."""
         patch, _, origin, coord_scale = check_grid_args(patch_size, None, origin, coord_scale)
+        check_stain(stain)
         coords = torch.as_tensor(coords)
         if coords.dim() != 2 or coords.shape[1] != 2:
             raise ValueError(f"coords must be [N,2] (x, y), got {tuple(coords.shape)}")
         x = self._region_tensor(region)
         self._ready_device()
+        plan = None if stain is None else self._stain_plan(stain)
         xd, H, W, C, row = self._region_on_device(x)
         c = coords.to(self._device, torch.int64)
         cells = (torch.div(c, coord_scale, rounding_mode="floor") - torch.tensor(origin, dtype=torch.int64, device=self._device))
         cells = cells.clamp(-(1 << 31), (1 << 31) - 1).to(torch.int32)          # out of int32 range stays outside the region
         out = self._region_tiles(xd, H, W, C, row, cells, patch)
+        if plan is not None and out.numel():
+            self._stain_apply(out, out, plan)
         return out if x.device == self._device else out.to(x.device)
 
     @torch.no_grad()
     def encode_region(self, region, patch_size: int = 224, step: Optional[int] = None, tissue=None, origin=(0, 0), coord_scale: int = 1,
-                      batch: int = 256) -> Tuple[torch.Tensor, torch.Tensor]:
+                      batch: int = 256, stain=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Slide pixels in, what the WSI functions take out: the grid of :meth:`region_grid`, the tiles of
         :meth:`region_patches_uint8` and :meth:`encode_image_uint8`, ``batch`` tiles at a time -> (features fp32 [N,768],
         coords int64 [N,2]) on the region's device; ``[0,768]`` / ``[0,2]`` when no cell is kept.  ``tissue`` as in
-        :meth:`region_grid`: off, the per-pixel rule, or a ``TissueMask``."""
-        return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, None)[:2]
+        :meth:`region_grid`: off, the per-pixel rule, or a ``TissueMask``.  ``stain``: a ``StainFit`` normalises every batch of cut tiles
+        (after the resize to 224, before the encoder) as :meth:`stain_normalize` does; ``None`` changes nothing."""
+        return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, None, stain)[:2]
 
     @torch.no_grad()
     def encode_region_attention(self, region, patch_size: int = 224, step: Optional[int] = None, tissue=None, origin=(0, 0),
-                                coord_scale: int = 1, batch: int = 256, block: int = -1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                                coord_scale: int = 1, batch: int = 256, block: int = -1, stain=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """:meth:`encode_region` with the CLS query's attention of block ``block`` for every tile (``encode_image_attention``;
         DESIGN.md section 19) -> (features [N,768], coords [N,2], attn fp32 [N, heads, 197]) on the region's device.  Same grid, same
         tiles; the features equal :meth:`encode_region`'s with option ``graphs`` = 0 bit for bit."""
         self._ready()
         self._check_block(block)
-        return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, block)
+        return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, block, stain)
 
     @torch.no_grad()
     def encode_region_rollout(self, region, patch_size: int = 224, step: Optional[int] = None, tissue=None, origin=(0, 0), coord_scale: int = 1,
-                              batch: int = 256, start_block: int = 0, residual: float = 0.5) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                              batch: int = 256, start_block: int = 0, residual: float = 0.5, stain=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """:meth:`encode_region` with every tile's attention rollout (``encode_image_rollout``) -> (features
         [N,768], coords [N,2], rollout fp32 [N, 1, 197]) on the region's device.  Same grid, same tiles; the features equal
         :meth:`encode_region`'s with option ``graphs`` = 0 bit for bit."""
         self._ready()
         self._check_rollout(start_block, residual, (TILE // 16) ** 2 + 1)
-        return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, ("rollout", start_block, residual))
+        return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, ("rollout", start_block, residual), stain)
 
-    def _encode_region(self, region, patch_size, step, tissue, origin, coord_scale, batch, block):
+    def _encode_region(self, region, patch_size, step, tissue, origin, coord_scale, batch, block, stain=None):
         """The body of :meth:`encode_region`.  ``block`` an int: the tiles go through the tapped encode -> (features, coords, attn
         [N, heads, 197]); ``("rollout", start_block, residual)``: through the rollout encode -> (features, coords, rollout [N, 1, 197])."""
         rollout = isinstance(block, tuple)
@@ -1319,7 +1446,9 @@ class SlideOps:
         if isinstance(batch, bool) or int(batch) != batch or batch < 1:
             raise ValueError(f"batch must be an integer >= 1, got {batch!r}")
         x = self._region_tensor(region)
+        check_stain(stain)
         self._ready()
+        plan = None if stain is None else self._stain_plan(stain)
         xd, H, W, C, row = self._region_on_device(x)
         cells = self._mask_cells(tissue, H, W, patch, step, origin) if by_mask else \
             self._region_cells(xd, H, W, C, row, patch, step, sat_min, min_pixels)
@@ -1329,6 +1458,8 @@ class SlideOps:
                                                       dtype=torch.float32, device=self._device)
         for i in range(0, N, int(batch)):
             tiles = self._region_tiles(xd, H, W, C, row, cells[i:i + batch], patch)
+            if plan is not None:
+                self._stain_apply(tiles, tiles, plan)
             if block is None:
                 feats[i:i + batch] = self.encode_image_uint8(tiles)
             elif rollout:
