@@ -282,6 +282,31 @@ int keep_stain_conc_hist(keep_handle* h, const unsigned char* image, int64_t H, 
 int keep_stain_apply_u8(keep_handle* h, const unsigned char* src, int64_t n, const int32_t* od_q, const int32_t* t_q,
                         const unsigned char* exp_lut, int lut_len, int lo, unsigned char* dst, void* stream);
 
+/* ---- tile quality control: pen ink, dark, glass, tissue share and focus -----
+ * Replaces: nothing the reference runs (its WSI scripts take the tiles CLAM kept); it stands where HistoQC-style filters sit in the
+ * pipelines around it, between the patch grid and quick_start/keep_inference.py:54-58's encode_image.  Integer arithmetic, exact
+ * against keep_amd.quality's numpy restatements.
+ * rules: int32 [776] ON THE DEVICE, 4-byte aligned (keep_amd.quality.QualityRules.blob()): sat_min, white_min, dark_max, the number
+ * of pen boxes (0..32), the index of the first box of class 1, of class 2 and of class 3 (the boxes sorted by class), 0, then three
+ * tables of 256 words for r, g and b: bit i of word v is set iff box i holds the value v in that channel.  Every pixel has ONE class,
+ * the first that applies of: pen ink of the lowest class with a box that holds it; dark, max(r,g,b) <= dark_max; glass,
+ * min(r,g,b) >= white_min; tissue, max > 0 and 255 (max - min) >= sat_min max (keep_region_grid's rule); other.
+ * region, H, W, pix_stride, row_stride_bytes: the layout contract of keep_region_grid; cell_xy: int32 [N][2] (x, y) offsets of N
+ * cells of side patch, 1 <= patch <= 1024, as keep_region_patches_u8 takes them (overlapping cells are fine; a cell outside the
+ * region is KEEP_EINVAL: checked on the device, one stream synchronisation per call); 0 <= N <= 2^24 - 1.  A contiguous batch of tiles
+ * [N][S][S][3] is the region H = N S, W = S with the cells (0, i S).
+ * out: int64 [N][12] on the device, 8-byte aligned; zero_first != 0 starts new sums, 0 adds to the words there.  Columns: 0-3 the
+ * pixels of pen class 0..3, 4 dark, 5 glass, 6 tissue (P^2 minus their sum is "other"); with g = (77 r + 150 g + 29 b + 128) >> 8 and
+ * L = 4 g(x,y) - g(x-1,y) - g(x+1,y) - g(x,y-1) - g(x,y+1) over the (patch - 2)^2 interior pixels of the cell itself (no pixel
+ * outside the cell is read): 7 sum L, 8 sum L^2; 9 the interior pixels whose own class is tissue, 10 and 11 sum L and sum L^2 over
+ * those.  patch < 3: columns 7-11 are 0. */
+int keep_region_quality(keep_handle* h, const unsigned char* region, int64_t H, int64_t W, int pix_stride, int64_t row_stride_bytes,
+                        const int32_t* cell_xy, int64_t N, int64_t patch, const int32_t* rules, int zero_first, int64_t* out, void* stream);
+/* The class of every pixel of a thumbnail, with the classifier above.  thumb: uint8 [H,W,pix_stride] as keep_tissue_median_hist takes
+ * it, H W <= 2^30; out: uint8 [H][W] contiguous on the device: 0 none, 1-4 pen class + 1, 5 dark, 6 glass, 7 tissue. */
+int keep_pen_mask(keep_handle* h, const unsigned char* thumb, int64_t H, int64_t W, int pix_stride, int64_t row_stride_bytes,
+                  const int32_t* rules, unsigned char* out, void* stream);
+
 /* ---- tile scores rasterised onto the slide thumbnail -------------------------
  * The accumulator `acc` is int64 [H,W] contiguous on the device, 8-byte aligned, H W <= 2^30, one word per raster pixel read as
  * unsigned: bits 0..39 hold the sum of q over the tiles that cover the pixel, bits 40..63 their number, q = rint(clip(value, 0, 1) *

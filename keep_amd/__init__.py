@@ -23,4 +23,7 @@ __all__ += ["BootstrapResult"]
 from .stain import StainFit, StainTarget
 
 __all__ += ["StainFit", "StainTarget"]
+from .quality import QualityGate, QualityRules, TileQuality
+
+__all__ += ["QualityGate", "QualityRules", "TileQuality"]
 __version__ = "0.1.0"

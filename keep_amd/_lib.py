@@ -60,6 +60,8 @@ SIGNATURES = {
     "keep_stain_angle_hist": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "keep_stain_conc_hist": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp]),
     "keep_stain_apply_u8": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "keep_region_quality": (_i32, [_vp, _vp, _i64, _i64, _i32, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp]),
+    "keep_pen_mask": (_i32, [_vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp]),
     "keep_heat_accumulate": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp]),
     "keep_heat_accumulate_cells": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp]),
     "keep_heat_accumulate_classes": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),

@@ -84,7 +84,7 @@ def save_slide_features(data_source: str, slide_id: str, features: torch.Tensor,
 @torch.no_grad()
 def extract_slide_features(read_region, width: int, height: int, slide_id: str, data_source: str, patch_size: int = 256,
                            step: Optional[int] = None, tissue=None, band_rows: int = 8, coord_scale: int = 1, use_h5: bool = False,
-                           model=None, thumbnail=None, thumbnail_downsample: Optional[int] = None, segmentation=None, stain=None) -> str:
+                           model=None, thumbnail=None, thumbnail_downsample: Optional[int] = None, segmentation=None, stain=None, quality=None) -> str:
     """The feature files the WSI scripts read, made on the device (replaces the CLAM extraction step of README.md:74).
 
     ``read_region(x, y, w, h)`` returns uint8 [h, w, 3 | 4] pixels of the slide level being tiled, ``width`` x ``height`` pixels
@@ -114,10 +114,17 @@ def extract_slide_features(read_region, width: int, height: int, slide_id: str, 
 
     ``stain``: a ``keep_amd.stain.StainFit`` (``model.stain_fit(...)``) normalises every batch of cut tiles on the device before it is
     encoded (``encode_region(..., stain=fit)``); ``"macenko"`` fits one first on ``thumbnail`` under the tissue mask
-    made from it, and so needs ``thumbnail=``; ``None`` (the default) changes nothing."""
+    made from it, and so needs ``thumbnail=``; ``None`` (the default) changes nothing.
+
+    ``quality``: a ``keep_amd.quality.QualityGate``; the cells of every band are measured in the band as read (class counts and focus,
+    ``model.region_quality``) and those the gate rejects are neither cut nor encoded nor written; ``None`` (the
+    default) changes nothing."""
     from .model import engine_for
     from .region import TissueMask, check_grid_args, plan_bands, plan_mask_reads
+    from .quality import check_gate, check_patch
     from .stain import check_stain
+    if check_gate(quality) is not None:
+        check_patch(patch_size)
     if check_stain(stain, allow_name=True) == "macenko" and thumbnail is None:
         raise ValueError('stain="macenko" fits on the thumbnail: give thumbnail= (or a StainFit of your own)')
     patch, step, _, coord_scale = check_grid_args(patch_size, step, (0, 0), coord_scale)
@@ -152,7 +159,12 @@ def extract_slide_features(read_region, width: int, height: int, slide_id: str, 
             if band.dim() != 3 or tuple(band.shape[:2]) != (h, w):
                 raise ValueError(f"read_region({x0}, {y0}, {w}, {h}) returned {tuple(band.shape)}, expected [{h}, {w}, 3|4]")
             xy = torch.from_numpy(cells[(cells[:, 1] >= y0) & (cells[:, 1] + patch <= y0 + h)] * coord_scale)
-            pending.append(m.region_patches_uint8(band.to(m._device), xy, patch, origin=(x0, y0), coord_scale=coord_scale, stain=stain))
+            band = band.to(m._device)
+            if quality is not None:
+                xy = xy[quality.keep(m.region_quality(band, xy, patch, origin=(x0, y0), coord_scale=coord_scale, rules=quality.rules)).cpu()]
+                if len(xy) == 0:
+                    continue
+            pending.append(m.region_patches_uint8(band, xy, patch, origin=(x0, y0), coord_scale=coord_scale, stain=stain))
             n_pending += len(xy)
             coords.append(xy)
             encode(final=False)
@@ -163,7 +175,7 @@ def extract_slide_features(read_region, width: int, height: int, slide_id: str, 
             band = torch.from_numpy(np.ascontiguousarray(band)) if not isinstance(band, torch.Tensor) else band
             if band.dim() != 3 or tuple(band.shape[:2]) != (h, width):
                 raise ValueError(f"read_region(0, {y0}, {width}, {h}) returned {tuple(band.shape)}, expected [{h}, {width}, 3|4]")
-            f, c = m.encode_region(band, patch, step, tissue, origin=(0, y0), coord_scale=coord_scale, stain=stain)
+            f, c = m.encode_region(band, patch, step, tissue, origin=(0, y0), coord_scale=coord_scale, stain=stain, quality=quality)
             feats.append(f.cpu())
             coords.append(c.cpu())
     features = torch.cat(feats) if feats else torch.empty((0, m.config.projection_dim), dtype=torch.float32)

@@ -275,6 +275,21 @@ void launch_stain_conc_hist(const unsigned char* img, int64_t row_stride, int ps
 void launch_stain_apply_u8(const unsigned char* src, unsigned char* dst, int64_t n, const int* od_q, const int* t_q, const unsigned char* exp_lut,
                            int lut_len, int lo, hipStream_t s);
 
+// Tile quality control (quality.hip).  blob: int32 [QUAL_BLOB_WORDS] on the device: sat_min, white_min, dark_max, the
+// number of pen boxes, the index of the first box of class 1, 2 and 3 (the boxes are sorted by class), 0, then three tables of 256 words:
+// bit i of table c's word v is set iff box i holds the value v in channel c.
+constexpr int QUAL_COLS = 12;                           // pen 0..3, dark, glass, tissue, S L, S L^2, n_t, S L and S L^2 over tissue
+constexpr int QUAL_BLOB_HEAD = 8, QUAL_BLOB_WORDS = QUAL_BLOB_HEAD + 3 * 256;
+constexpr int QUAL_MAX_PATCH = 1024, QUAL_MAX_BOXES = 32;
+constexpr int QUAL_BAND_PIXELS = 16384;                 // a workgroup's band of rows holds at most this many pixels (or one row)
+constexpr int QUAL_GREY_BYTES = 19456, QUAL_TIS_BYTES = 4352;   // LDS of the largest band: (R + 2) (4 G + 8) <= 18720 (patch 1024), R G <= 4224 (patch 128)
+constexpr int64_t QUAL_MAX_CELLS = ((int64_t)1 << 24) - 1;     // cells x bands (<= 128) is the grid
+// adds into out [n][QUAL_COLS] (the caller zeroes it); every cell lies inside the region (the caller checks); -1: the patch does not fit the LDS plan
+int launch_region_quality(const unsigned char* region, int64_t row_stride, int ps, const int32_t* cells, int64_t n, int patch, const int* blob,
+                          int64_t* out, hipStream_t s);
+// one class byte per pixel: 0 none, 1..4 pen class + 1, 5 dark, 6 glass, 7 tissue
+void launch_pen_mask(const unsigned char* img, int64_t row_stride, int ps, int h, int w, const int* blob, unsigned char* out, hipStream_t s);
+
 // the labelling alone: foreground components of img, 8- or 4-connected -> labels[p] = the component's smallest pixel index (-1 on the
 // background), info[root] = area | CC_BORDER (labelling.h)
 void launch_cc_label(const unsigned char* img, int h, int w, int conn8, int* labels, int* info, int* err, hipStream_t s);

@@ -1,6 +1,6 @@
-// The slide-geometry entry points of include/keep_hip.h: patch grid, tissue mask, stain normalisation, heatmap, sort / rank, region table, outlines, polygon
+// The slide-geometry entry points of include/keep_hip.h: patch grid, tissue mask, stain normalisation, tile quality, heatmap, sort / rank, region table, outlines, polygon
 // fill, segmentation evaluation, bootstrap resampling, the subtype map and tile clustering.  Host code only: each function validates its arguments, carves its workspace from the handle's
-// arena, calls the launch_* of its kernel file (region / tissue / stain / heatmap / rank / components / outline / annotation / eval / bootstrap .hip) and
+// arena, calls the launch_* of its kernel file (region / tissue / stain / quality / heatmap / rank / components / outline / annotation / eval / bootstrap .hip) and
 // reports the launch.  Of the handle (handle.h) they use the device, the error text, the arena and the sticky error flag.
 #include "handle.h"
 
@@ -880,6 +880,56 @@ int keep_stain_apply_u8(keep_handle* h, const unsigned char* src, int64_t n, con
     KEEP_ON_DEVICE(h);
     launch_stain_apply_u8(src, dst, n, od_q, t_q, exp_lut, lut_len, lo, (hipStream_t)stream);
     return check_launch(h, "stain_apply_u8");
+}
+
+int keep_region_quality(keep_handle* h, const unsigned char* region, int64_t H, int64_t W, int pix_stride, int64_t row_stride_bytes,
+                        const int32_t* cell_xy, int64_t N, int64_t patch, const int32_t* rules, int zero_first, int64_t* out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!region || H < 1 || W < 1 || H > INT32_MAX || W > INT32_MAX)
+        return h->fail(KEEP_EINVAL, "region_quality: null region or bad shape %lldx%lld", (long long)H, (long long)W);
+    if (int rc = pix_stride_check(h, "region_quality", pix_stride)) return rc;
+    if (int rc = row_stride_check(h, "region_quality", W, row_stride_bytes, pix_stride)) return rc;
+    if (patch < 1 || patch > QUAL_MAX_PATCH) return h->fail(KEEP_EINVAL, "region_quality: patch %lld outside [1, %d]", (long long)patch, QUAL_MAX_PATCH);
+    if (patch > H || patch > W)
+        return h->fail(KEEP_EINVAL, "region_quality: patch %lld larger than the region %lldx%lld", (long long)patch, (long long)W, (long long)H);
+    if (N < 0 || N > QUAL_MAX_CELLS) return h->fail(KEEP_EINVAL, "region_quality: %lld cells (0 .. 2^24 - 1)", (long long)N);
+    if (N > 0 && (!cell_xy || ((uintptr_t)cell_xy & 3))) return h->fail(KEEP_EINVAL, "region_quality: cell_xy is null or not 4-byte aligned");
+    if (N > 0 && (!out || ((uintptr_t)out & 7))) return h->fail(KEEP_EINVAL, "region_quality: out is null or not 8-byte aligned");
+    if (!rules || ((uintptr_t)rules & 3)) return h->fail(KEEP_EINVAL, "region_quality: rules is null or not 4-byte aligned");
+    if (N == 0) return KEEP_OK;
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    // the flag is read back before any pixel is touched (the one synchronisation of this call), as in keep_region_patches_u8
+    int rc = ensure_arena(h, align_up(sizeof(int)));
+    if (rc) return rc;
+    int* bad = (int*)h->arena;
+    HIPCHK(h, hipMemsetAsync(bad, 0, sizeof(int), s));
+    launch_region_check_cells(cell_xy, (int)N, H, W, (int)patch, bad, s);
+    rc = check_launch(h, "region_check_cells");
+    if (rc) return rc;
+    int bad_h = 0;
+    HIPCHK(h, hipMemcpyAsync(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (bad_h) return h->fail(KEEP_EINVAL, "region_quality: a cell (x, y) has x < 0, y < 0, x + %lld > %lld or y + %lld > %lld", (long long)patch,
+                              (long long)W, (long long)patch, (long long)H);
+    if (zero_first) HIPCHK(h, hipMemsetAsync(out, 0, (size_t)N * QUAL_COLS * sizeof(int64_t), s));
+    if (launch_region_quality(region, row_stride_bytes, pix_stride, cell_xy, N, (int)patch, rules, out, s))
+        return h->fail(KEEP_EUNSUPPORTED, "region_quality: no launch plan for patch %lld", (long long)patch);
+    return check_launch(h, "region_quality");
+}
+
+int keep_pen_mask(keep_handle* h, const unsigned char* thumb, int64_t H, int64_t W, int pix_stride, int64_t row_stride_bytes,
+                  const int32_t* rules, unsigned char* out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!thumb || H < 1 || W < 1) return h->fail(KEEP_EINVAL, "pen_mask: null pointer or empty shape %lldx%lld", (long long)H, (long long)W);
+    if (int rc = pix_stride_check(h, "pen_mask", pix_stride)) return rc;
+    if (!pixels_ok(H, W, TISSUE_MAX_PIXELS)) return h->fail(KEEP_EINVAL, "pen_mask: %lldx%lld pixels (limit H W <= 2^30)", (long long)H, (long long)W);
+    if (int rc = row_stride_check(h, "pen_mask", W, row_stride_bytes, pix_stride)) return rc;
+    if (!rules || ((uintptr_t)rules & 3)) return h->fail(KEEP_EINVAL, "pen_mask: rules is null or not 4-byte aligned");
+    if (!out) return h->fail(KEEP_EINVAL, "pen_mask: out is null");
+    KEEP_ON_DEVICE(h);
+    launch_pen_mask(thumb, row_stride_bytes, pix_stride, (int)H, (int)W, rules, out, (hipStream_t)stream);
+    return check_launch(h, "pen_mask");
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@ from .outline import NCOLS as RING_COLS, RegionOutlines, check_draw_args, check_
 from .region import (MASK_MODES, TILE, TissueMask, TissueSegmentation, check_downsample, check_grid_args, grid_shape, otsu_threshold, region_layout,
                      resize_tables, thumbnail_layout, tissue_params)
 from . import stain as _stain
+from .quality import NCOLS as QUALITY_COLS, MAX_CELLS as QUALITY_MAX_CELLS, QualityGate, TileQuality, check_gate, check_patch, check_rules
 from .stain import StainFit, StainTarget, check_stain
 
 
@@ -1349,6 +1350,95 @@ class SlideOps:
             return out
         return dst.cpu().numpy() if as_numpy else (dst if x.device == self._device else dst.to(x.device))
 
+    # ------------------------------------------------------------------ tile quality control
+    def _quality_table(self, xd: torch.Tensor, H: int, W: int, C: int, row: int, cells: torch.Tensor, patch: int, rules) -> torch.Tensor:
+        """keep_region_quality: int32 [N,2] cells of a device region -> the int64 [N,12] table on the device (one sync: the cell check)."""
+        cells = cells.to(self._device, torch.int32).contiguous()
+        N = int(cells.shape[0])
+        if N > QUALITY_MAX_CELLS:
+            raise ValueError(f"at most 2^24 - 1 cells go into one table, got {N}")
+        out = torch.empty((N, QUALITY_COLS), dtype=torch.int64, device=self._device)
+        if N:
+            self._call("region_quality", _ptr(xd), H, W, C, row, _ptr(cells), N, patch, _ptr(self._quality_blob(rules)), 1, _ptr(out))
+        return out
+
+    def _quality_blob(self, rules) -> torch.Tensor:
+        """The rules' words on the device, uploaded once per engine and set of rules; the 16 sets used last are kept."""
+        cache = self.__dict__.setdefault("_quality_blobs", {})
+        blob = cache.pop(rules, None)
+        if blob is None or blob.device != self._device:
+            blob = torch.from_numpy(rules.blob()).to(self._device)
+        cache[rules] = blob                                         # dicts keep insertion order: the first key is the one used longest ago
+        while len(cache) > 16:
+            del cache[next(iter(cache))]
+        return blob
+
+    def _quality_cells(self, xd: torch.Tensor, H: int, W: int, C: int, row: int, cells: torch.Tensor, patch: int, gate: QualityGate) -> torch.Tensor:
+        """The cells of a grid that ``gate`` keeps, in grid order (measured in the region at its own resolution)."""
+        if cells.shape[0] == 0:
+            return cells
+        return cells[gate.keep(TileQuality(self._quality_table(xd, H, W, C, row, cells, patch, gate.rules), patch))]
+
+    @torch.no_grad()
+    def tile_quality(self, tiles_u8, rules=None) -> TileQuality:
+        """Class counts and focus of every tile of a batch on the device -> ``keep_amd.quality.TileQuality``.
+        ``tiles_u8``: uint8 ``[N,S,S,3]`` (or ``[N,S,S,4]``, alpha ignored), ``1 <= S <= 1024``, host or device, numpy or torch; ``rules``: a
+        ``keep_amd.quality.QualityRules`` (default: its defaults).  The batch is read as a region of height ``N S`` with the cells
+        ``(0, i S)``: the kernel, and the numbers, are :meth:`region_quality`'s.  Equal to ``keep_amd.quality.tile_quality_numpy`` exactly."""
+        rules = check_rules(rules)
+        x = torch.from_numpy(tiles_u8) if isinstance(tiles_u8, np.ndarray) else tiles_u8
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 4 or x.shape[1] != x.shape[2] or x.shape[3] not in (3, 4):
+            raise ValueError(f"tiles must be uint8 [N,S,S,3], got {getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+        N, S, C = int(x.shape[0]), int(x.shape[1]), int(x.shape[3])
+        check_patch(S)
+        if N * S >= 1 << 31:
+            raise ValueError(f"{N} tiles of {S} rows: a batch holds fewer than 2^31 rows")
+        self._ready_device()
+        if N == 0:
+            return TileQuality(torch.empty((0, QUALITY_COLS), dtype=torch.int64, device=self._device), S)
+        xd = x.to(self._device).contiguous().view(N * S, S, C)
+        cells = torch.zeros((N, 2), dtype=torch.int32, device=self._device)
+        cells[:, 1] = torch.arange(N, dtype=torch.int32, device=self._device) * S
+        return TileQuality(self._quality_table(xd, N * S, S, C, S * C, cells, S, rules), S)
+
+    @torch.no_grad()
+    def region_quality(self, region, coords, patch_size: int, origin=(0, 0), coord_scale: int = 1, rules=None) -> TileQuality:
+        """Class counts and focus of the tiles of ``coords`` measured IN the region, at its own resolution and before any resize to 224
+         -> ``keep_amd.quality.TileQuality`` on the engine's device.  ``region``, ``coords``, ``origin`` and
+        ``coord_scale`` as in :meth:`region_patches_uint8` (a coord outside the region is the same ValueError); ``1 <= patch_size <= 1024``;
+        overlapping tiles are fine.  Per tile: the pixels of each pen class, of dark, glass and tissue (every pixel has one class;
+        ``keep_amd.quality``), and the sums behind the variance of the integer Laplacian over the tile's interior pixels, over all
+        of them and over the tissue ones.  Integer arithmetic, equal to ``keep_amd.quality.tile_quality_numpy`` exactly."""
+        rules, patch = check_rules(rules), check_patch(patch_size)
+        _, _, origin, coord_scale = check_grid_args(TILE, None, origin, coord_scale)
+        coords = torch.as_tensor(coords)
+        if coords.dim() != 2 or coords.shape[1] != 2:
+            raise ValueError(f"coords must be [N,2] (x, y), got {tuple(coords.shape)}")
+        x = self._region_tensor(region)
+        self._ready_device()
+        xd, H, W, C, row = self._region_on_device(x)
+        c = coords.to(self._device, torch.int64)
+        cells = (torch.div(c, coord_scale, rounding_mode="floor") - torch.tensor(origin, dtype=torch.int64, device=self._device))
+        cells = cells.clamp(-(1 << 31), (1 << 31) - 1).to(torch.int32)          # out of int32 range stays outside the region
+        return TileQuality(self._quality_table(xd, H, W, C, row, cells, patch, rules), patch)
+
+    @torch.no_grad()
+    def pen_mask(self, thumbnail, rules=None):
+        """The class of every pixel of a thumbnail on the device -> uint8 ``[h,w]`` on the input's device (a numpy
+        array for a numpy input): 0 none, 1-4 pen class + 1 (``keep_amd.quality.PEN_CLASSES``), 5 dark, 6 glass, 7 tissue.
+        ``thumbnail``: the layout contract of :meth:`tissue_mask`.  ``keep_amd.quality.exclude`` takes chosen classes out of a
+        ``TissueMask`` with it.  Equal to ``keep_amd.quality.pen_mask_numpy`` exactly; no host synchronisation."""
+        rules = check_rules(rules)
+        as_numpy = isinstance(thumbnail, np.ndarray)
+        x = torch.from_numpy(thumbnail) if as_numpy else thumbnail
+        thumbnail_layout(x)
+        self._ready_device()
+        xd = x if x.device == self._device else x.to(self._device)
+        h, w, C, row = thumbnail_layout(xd)
+        out = torch.empty((h, w), dtype=torch.uint8, device=self._device)
+        self._call("pen_mask", _ptr(xd), h, w, C, row, _ptr(self._quality_blob(rules)), _ptr(out))
+        return out.cpu().numpy() if as_numpy else (out if x.device == self._device else out.to(x.device))
+
     @staticmethod
     def _cells_to_coords(cells: torch.Tensor, origin, coord_scale: int) -> torch.Tensor:
         o = torch.tensor(origin, dtype=torch.int64, device=cells.device)
@@ -1356,7 +1446,7 @@ class SlideOps:
 
     @torch.no_grad()
     def region_grid(self, region, patch_size: int = 224, step: Optional[int] = None, tissue=None, origin=(0, 0),
-                    coord_scale: int = 1) -> torch.Tensor:
+                    coord_scale: int = 1, quality: Optional[QualityGate] = None) -> torch.Tensor:
         """Patch grid over a uint8 region [H,W,3] (RGB) or [H,W,4] (RGBA, alpha ignored as PIL's ``convert("RGB")`` drops it), host or
         device, any row stride -> the level-0 coords int64 [N,2] ``(x, y)`` of the kept cells, on the region's device.
 
@@ -1367,18 +1457,26 @@ class SlideOps:
         is kept iff it holds ``>= ceil(min_fraction patch^2)`` of them.  That rule is deliberately NOT CLAM's contour segmentation;
         a ``keep_amd.region.TissueMask`` (from :meth:`tissue_mask`, or a caller's own) is the other choice: a cell is then tested at
         CLAM's ``four_pt`` / ``four_pt_hard`` / ``center`` points, in level coordinates including ``origin``, against the mask
-        (DESIGN.md section 11), and the region's pixels are not read."""
+        (DESIGN.md section 11), and the region's pixels are not read.  ``quality``: a ``keep_amd.quality.QualityGate``; the cells of the
+        grid (by rule or by mask) are then measured in the region (:meth:`region_quality`, ``patch_size <= 1024``) and those the gate
+        rejects are dropped, the rest staying in grid order; ``None`` changes nothing."""
         patch, step, origin, coord_scale = check_grid_args(patch_size, step, origin, coord_scale)
+        if check_gate(quality) is not None:
+            check_patch(patch)
         x = self._region_tensor(region)
         if isinstance(tissue, TissueMask):                         # decided by the mask: the region gives its shape, no pixel is read
             self._ready_device()
             H, W, _, _ = region_layout(x)
             cells = self._mask_cells(tissue, H, W, patch, step, origin)
+            if quality is not None:
+                xd, H, W, C, row = self._region_on_device(x)
         else:
             sat_min, min_pixels = tissue_params(tissue, patch)
             self._ready_device()
             xd, H, W, C, row = self._region_on_device(x)
             cells = self._region_cells(xd, H, W, C, row, patch, step, sat_min, min_pixels)
+        if quality is not None:
+            cells = self._quality_cells(xd, H, W, C, row, cells, patch, quality)
         coords = self._cells_to_coords(cells, origin, coord_scale)
         return coords if x.device == self._device else coords.to(x.device)
 
@@ -1408,35 +1506,39 @@ class SlideOps:
 
     @torch.no_grad()
     def encode_region(self, region, patch_size: int = 224, step: Optional[int] = None, tissue=None, origin=(0, 0), coord_scale: int = 1,
-                      batch: int = 256, stain=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                      batch: int = 256, stain=None, quality: Optional[QualityGate] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Slide pixels in, what the WSI functions take out: the grid of :meth:`region_grid`, the tiles of
         :meth:`region_patches_uint8` and :meth:`encode_image_uint8`, ``batch`` tiles at a time -> (features fp32 [N,768],
         coords int64 [N,2]) on the region's device; ``[0,768]`` / ``[0,2]`` when no cell is kept.  ``tissue`` as in
         :meth:`region_grid`: off, the per-pixel rule, or a ``TissueMask``.  ``stain``: a ``StainFit`` normalises every batch of cut tiles
-        (after the resize to 224, before the encoder) as :meth:`stain_normalize` does; ``None`` changes nothing."""
-        return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, None, stain)[:2]
+        (after the resize to 224, before the encoder) as :meth:`stain_normalize` does; ``None`` changes nothing.  ``quality``: a
+        ``QualityGate`` drops the cells it rejects as in :meth:`region_grid`, before any tile is cut or encoded and on the pixels as
+        scanned (not stain-normalised); features and coords come back for the kept cells only, in grid order; ``None`` changes nothing."""
+        return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, None, stain, quality)[:2]
 
     @torch.no_grad()
     def encode_region_attention(self, region, patch_size: int = 224, step: Optional[int] = None, tissue=None, origin=(0, 0),
-                                coord_scale: int = 1, batch: int = 256, block: int = -1, stain=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                                coord_scale: int = 1, batch: int = 256, block: int = -1, stain=None,
+                                quality: Optional[QualityGate] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """:meth:`encode_region` with the CLS query's attention of block ``block`` for every tile (``encode_image_attention``;
         DESIGN.md section 19) -> (features [N,768], coords [N,2], attn fp32 [N, heads, 197]) on the region's device.  Same grid, same
         tiles; the features equal :meth:`encode_region`'s with option ``graphs`` = 0 bit for bit."""
         self._ready()
         self._check_block(block)
-        return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, block, stain)
+        return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, block, stain, quality)
 
     @torch.no_grad()
     def encode_region_rollout(self, region, patch_size: int = 224, step: Optional[int] = None, tissue=None, origin=(0, 0), coord_scale: int = 1,
-                              batch: int = 256, start_block: int = 0, residual: float = 0.5, stain=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                              batch: int = 256, start_block: int = 0, residual: float = 0.5, stain=None,
+                              quality: Optional[QualityGate] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """:meth:`encode_region` with every tile's attention rollout (``encode_image_rollout``) -> (features
         [N,768], coords [N,2], rollout fp32 [N, 1, 197]) on the region's device.  Same grid, same tiles; the features equal
         :meth:`encode_region`'s with option ``graphs`` = 0 bit for bit."""
         self._ready()
         self._check_rollout(start_block, residual, (TILE // 16) ** 2 + 1)
-        return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, ("rollout", start_block, residual), stain)
+        return self._encode_region(region, patch_size, step, tissue, origin, coord_scale, batch, ("rollout", start_block, residual), stain, quality)
 
-    def _encode_region(self, region, patch_size, step, tissue, origin, coord_scale, batch, block, stain=None):
+    def _encode_region(self, region, patch_size, step, tissue, origin, coord_scale, batch, block, stain=None, quality=None):
         """The body of :meth:`encode_region`.  ``block`` an int: the tiles go through the tapped encode -> (features, coords, attn
         [N, heads, 197]); ``("rollout", start_block, residual)``: through the rollout encode -> (features, coords, rollout [N, 1, 197])."""
         rollout = isinstance(block, tuple)
@@ -1447,11 +1549,15 @@ class SlideOps:
             raise ValueError(f"batch must be an integer >= 1, got {batch!r}")
         x = self._region_tensor(region)
         check_stain(stain)
+        if check_gate(quality) is not None:
+            check_patch(patch)
         self._ready()
         plan = None if stain is None else self._stain_plan(stain)
         xd, H, W, C, row = self._region_on_device(x)
         cells = self._mask_cells(tissue, H, W, patch, step, origin) if by_mask else \
             self._region_cells(xd, H, W, C, row, patch, step, sat_min, min_pixels)
+        if quality is not None:
+            cells = self._quality_cells(xd, H, W, C, row, cells, patch, quality)
         N = int(cells.shape[0])
         feats = torch.empty((N, self.config.projection_dim), dtype=torch.float32, device=self._device)
         attn = None if block is None else torch.empty((N, 1 if rollout else self.config.vision.num_heads, (TILE // 16) ** 2 + 1),
