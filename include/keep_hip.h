@@ -498,6 +498,36 @@ int keep_cluster_update(keep_handle* h, const int64_t* sums, const int64_t* coun
 int keep_cluster_seed_step(keep_handle* h, const float* features, int64_t N, int64_t D, const float* centre, const int64_t* centre_row, int first,
                            float* nearest, int64_t* index_out, void* stream);
 
+/* ---- linear probe ----------------------------------------------------------------
+ * Replaces: nothing in the reference, which scores frozen features against prompts only; on this engine the round trip through
+ * sklearn.linear_model.LogisticRegression on the host, or per iteration x @ W.T + b, softmax and (p - onehot).T @ x in torch, which
+ * reads the features twice, writes two [N,C] matrices and sums the gradient in float in an order the library picks.  Multinomial
+ * logistic regression: features fp32 [N,D] row-major unit rows and weight fp32 [C,D], both 16-byte aligned, bias fp32 [C];
+ * 1 <= N <= 2^22 per call, D a multiple of 16 in 16 .. 1024, 2 <= C <= 64; at most 2^24 rows may be added into one set of
+ * accumulators.  groups: 0, or 1 / 2 / 4 groups of 64 rows per workgroup (any value gives the same words; for measurement), with
+ * groups ceil(C / 16) <= 8 in keep_probe_loss_grad.  Anything else is KEEP_EINVAL and nothing is launched.
+ *
+ * keep_probe_forward: z_c = x . w_c as a k-ordered fp32 fma chain (v_mfma_f32_16x16x4_f32) plus bias[c]; a row's logits do not depend
+ * on N, on its position or on the split over calls.  probs_out fp32 [N,C]: exp(z_c - max z) / sum, fp32, the sum in one fixed order;
+ * label_out int32 [N]: the smallest c with the largest logit; best_out fp32 [N]: its probability; margin_out fp32 [N]: best minus the
+ * runner-up's probability.  A row holding a non-finite value or an element with |x| > 1 (or whose logits are not finite) is skipped:
+ * label -1, best = margin = 0, a zero row of probs, one added to *skipped (int64 on the device, ADDED into).  Every output may be
+ * null, not all of them.  No host synchronisation.
+ * keep_probe_loss_grad: the same forward (its outputs optional) and the integer sums of F = (1/S) sum_i w[y_i] loss_i with loss_i =
+ * logsumexp(z_i) - z_i[y_i].  labels int32 [N]: -1 (unlabelled: in no sum, still predicted) or 0 .. C - 1; class_weight fp32 [C] in
+ * (0, 1], or null for 1.  A label or weight outside that is KEEP_EINVAL, found by one check launch and a 4-byte read-back (the one
+ * host synchronisation) before a label is used.  With r_ic = w[y_i] (p_ic - [c = y_i]) (the subtraction, then the product, single
+ * fp32 operations) every kept row adds grad[c,d] += llrint(fp32(r_ic x_id) 2^30), gbias[c] += llrint(r_ic 2^30), *loss +=
+ * llrint(fp32(w[y_i] loss_i) 2^24), counts[y_i] += 1; a skipped row adds one to *skipped.  grad int64 [C,D], gbias int64 [C], loss
+ * int64 [1], counts int64 [C], skipped int64 [1], 8-byte aligned on the device, all required: the call ALWAYS ADDS, the caller
+ * zeroes.  Every term is rounded before it is added, so the words are the same however the rows are ordered, grouped or split over
+ * calls.  loss_i < 2^15 keeps the loss word exact: the caller holds max_c(|w_c| + |b_c|) under 8192. */
+int keep_probe_forward(keep_handle* h, const float* features, int64_t N, int64_t D, const float* weight, const float* bias, int64_t C,
+                       float* probs_out, int32_t* label_out, float* best_out, float* margin_out, int64_t* skipped, int groups, void* stream);
+int keep_probe_loss_grad(keep_handle* h, const float* features, int64_t N, int64_t D, const int32_t* labels, const float* weight, const float* bias,
+                         int64_t C, const float* class_weight, int64_t* grad, int64_t* gbias, int64_t* loss, int64_t* counts, int64_t* skipped,
+                         float* probs_out, int32_t* label_out, float* best_out, float* margin_out, int groups, void* stream);
+
 /* Region outlines: the boundary rings of a label image, with holes, and an outline drawn into an image.
  * Replaces: the contour polygons with a hole list per contour that CLAM's segmentTissue hands back (cv2.findContours with
  * RETR_CCOMP; the step of README.md:74) and the polygon annotation a viewer takes a lesion of WSI_evaluation/segment_utils.py's

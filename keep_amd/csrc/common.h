@@ -396,6 +396,21 @@ void launch_cluster_update(const int64_t* sums, const int64_t* counts, int K, in
 void launch_cluster_seed_step(const float* x, int N, int D, const float* centre, const int64_t* centre_row, int first, float* nearest,
                               unsigned char* ws, int64_t* index_out, hipStream_t s);
 
+// Linear probe (probe.hip).  x: fp32 [N][D] unit rows, w: fp32 [C][D], bias: fp32 [C]; the limits on N and D are
+// those of the clustering above.
+constexpr int PROBE_MAX_C = 64;
+constexpr int PROBE_MAX_GROUPS = 4;                     // groups of 64 rows per workgroup
+constexpr int PROBE_MAX_GROUP_TILES = 8;                // groups x ceil(C / 16) of a gradient launch: its residuals have 32 KB of LDS
+// groups: 0 (probe_groups chooses), 1, 2 or 4.  grad null: the forward alone (labels, class_weight, gbias, loss, counts unused); otherwise
+// labels int32 [N], class_weight fp32 [C] or null, and grad int64 [C][D], gbias int64 [C], loss int64 [1], counts int64 [C] are ADDED
+// into.  probs / label / best / margin / skipped may be null.
+int probe_groups(int N, int C, bool grad);
+void launch_probe(const float* x, int N, int D, const float* w, const float* bias, int C, int groups, const int32_t* labels,
+                  const float* class_weight, float* probs, int32_t* label, float* best, float* margin, int64_t* skipped, int64_t* grad,
+                  int64_t* gbias, int64_t* loss, int64_t* counts, hipStream_t s);
+// *bad = 1 for a label outside -1 .. C - 1 or a class weight (may be null) outside (0, 1]
+void launch_probe_check(const int32_t* labels, int N, int C, const float* class_weight, int* bad, hipStream_t s);
+
 // Sorted score population and rank percentiles (rank.hip)
 constexpr int SORT_TILE = 4096;                         // keys per block; up to this many are sorted by one block in LDS
 constexpr int SORT_SCAN_CHUNK = 2048;                   // entries of the digit table per block of the scan

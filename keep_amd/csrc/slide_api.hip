@@ -1,5 +1,5 @@
 // The slide-geometry entry points of include/keep_hip.h: patch grid, tissue mask, stain normalisation, tile quality, heatmap, sort / rank, region table, outlines, polygon
-// fill, segmentation evaluation, bootstrap resampling, the subtype map and tile clustering.  Host code only: each function validates its arguments, carves its workspace from the handle's
+// fill, segmentation evaluation, bootstrap resampling, the subtype map, tile clustering and the linear probe.  Host code only: each function validates its arguments, carves its workspace from the handle's
 // arena, calls the launch_* of its kernel file (region / tissue / stain / quality / heatmap / rank / components / outline / annotation / eval / bootstrap .hip) and
 // reports the launch.  Of the handle (handle.h) they use the device, the error text, the arena and the sticky error flag.
 #include "handle.h"
@@ -802,6 +802,71 @@ int keep_cluster_seed_step(keep_handle* h, const float* features, int64_t N, int
     if (rc) return rc;
     launch_cluster_seed_step(features, (int)N, (int)D, centre, centre_row, first, nearest, (unsigned char*)h->arena, index_out, (hipStream_t)stream);
     return check_launch(h, "cluster_seed_step");
+}
+
+}  // extern "C"
+
+// Linear probe (probe.hip)
+static int probe_args_check(keep_handle* h, const char* who, const float* features, int64_t N, int64_t D, const float* weight, const float* bias,
+                            int64_t C, int groups, bool grad, const float* probs_out, const int32_t* label_out, const float* best_out,
+                            const float* margin_out, const int64_t* skipped) {
+    if (int rc = cluster_shape_check(h, who, N, D, 1)) return rc;
+    if (C < 2 || C > PROBE_MAX_C) return h->fail(KEEP_EINVAL, "%s: C = %lld (2 .. 64)", who, (long long)C);
+    if (!features || !weight || !bias) return h->fail(KEEP_EINVAL, "%s: null features, weight or bias", who);
+    if (((uintptr_t)features & 15) || ((uintptr_t)weight & 15)) return h->fail(KEEP_EINVAL, "%s: features / weight not 16-byte aligned", who);
+    if (groups != 0 && groups != 1 && groups != 2 && groups != 4) return h->fail(KEEP_EINVAL, "%s: groups %d (0 = chosen here, 1, 2 or 4)", who, groups);
+    if (grad && groups * ((C + 15) / 16) > PROBE_MAX_GROUP_TILES)
+        return h->fail(KEEP_EINVAL, "%s: groups %d with C = %lld (groups x ceil(C / 16) <= %d)", who, groups, (long long)C, PROBE_MAX_GROUP_TILES);
+    if (((uintptr_t)bias & 3) || ((uintptr_t)probs_out & 3) || ((uintptr_t)label_out & 3) || ((uintptr_t)best_out & 3) || ((uintptr_t)margin_out & 3) ||
+        ((uintptr_t)skipped & 7))
+        return h->fail(KEEP_EINVAL, "%s: bias or an output is not aligned to its element size", who);
+    return KEEP_OK;
+}
+
+extern "C" {
+
+int keep_probe_forward(keep_handle* h, const float* features, int64_t N, int64_t D, const float* weight, const float* bias, int64_t C,
+                       float* probs_out, int32_t* label_out, float* best_out, float* margin_out, int64_t* skipped, int groups, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = probe_args_check(h, "probe_forward", features, N, D, weight, bias, C, groups, false, probs_out, label_out, best_out, margin_out,
+                                  skipped))
+        return rc;
+    if (!probs_out && !label_out && !best_out && !margin_out && !skipped) return h->fail(KEEP_EINVAL, "probe_forward: no output (every pointer is null)");
+    KEEP_ON_DEVICE(h);
+    launch_probe(features, (int)N, (int)D, weight, bias, (int)C, groups, nullptr, nullptr, probs_out, label_out, best_out, margin_out, skipped, nullptr,
+                 nullptr, nullptr, nullptr, (hipStream_t)stream);
+    return check_launch(h, "probe_forward");
+}
+
+int keep_probe_loss_grad(keep_handle* h, const float* features, int64_t N, int64_t D, const int32_t* labels, const float* weight, const float* bias,
+                         int64_t C, const float* class_weight, int64_t* grad, int64_t* gbias, int64_t* loss, int64_t* counts, int64_t* skipped,
+                         float* probs_out, int32_t* label_out, float* best_out, float* margin_out, int groups, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = probe_args_check(h, "probe_loss_grad", features, N, D, weight, bias, C, groups, true, probs_out, label_out, best_out, margin_out,
+                                  skipped))
+        return rc;
+    if (!labels || ((uintptr_t)labels & 3)) return h->fail(KEEP_EINVAL, "probe_loss_grad: labels is null or not 4-byte aligned");
+    if ((uintptr_t)class_weight & 3) return h->fail(KEEP_EINVAL, "probe_loss_grad: class_weight is not 4-byte aligned");
+    if (!grad || !gbias || !loss || !counts || !skipped) return h->fail(KEEP_EINVAL, "probe_loss_grad: null grad, gbias, loss, counts or skipped");
+    if (((uintptr_t)grad & 7) || ((uintptr_t)gbias & 7) || ((uintptr_t)loss & 7) || ((uintptr_t)counts & 7))
+        return h->fail(KEEP_EINVAL, "probe_loss_grad: an accumulator is not 8-byte aligned");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    // the flag is read back before a label is used (the one synchronisation of this call), as in keep_region_quality
+    int rc = ensure_arena(h, align_up(sizeof(int)));
+    if (rc) return rc;
+    int* bad = (int*)h->arena;
+    HIPCHK(h, hipMemsetAsync(bad, 0, sizeof(int), s));
+    launch_probe_check(labels, (int)N, (int)C, class_weight, bad, s);
+    rc = check_launch(h, "probe_check");
+    if (rc) return rc;
+    int bad_h = 0;
+    HIPCHK(h, hipMemcpyAsync(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (bad_h) return h->fail(KEEP_EINVAL, "probe_loss_grad: a label outside -1 .. %lld or a class weight outside (0, 1]", (long long)(C - 1));
+    launch_probe(features, (int)N, (int)D, weight, bias, (int)C, groups, labels, class_weight, probs_out, label_out, best_out, margin_out, skipped, grad,
+                 gbias, loss, counts, s);
+    return check_launch(h, "probe_loss_grad");
 }
 
 // the image, mask and od table that the three fit passes of the stain normalisation share

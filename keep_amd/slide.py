@@ -1,5 +1,5 @@
 """The slide-analysis methods of ``KEEPModel``: patch grid and tiles of a region, tissue mask, heatmap raster, percentiles and
-smoothing, region table, outlines, region shape, polygon fill, segmentation evaluation, the subtype map and bootstrap resampling (DESIGN.md sections 10-24).  Thin wrappers of the
+smoothing, region table, outlines, region shape, polygon fill, segmentation evaluation, the subtype map, bootstrap resampling and the linear probe (DESIGN.md sections 10-27).  Thin wrappers of the
 entry points in csrc/slide_api.hip; the argument checks and the numpy references live in the feature modules imported below."""
 from __future__ import annotations
 
@@ -27,6 +27,7 @@ from .morphometry import DEFAULT_MAX_PAIRS, RegionShape, check_shape_args
 from .outline import NCOLS as RING_COLS, RegionOutlines, check_draw_args, check_outline_args, check_ring_count, regions_labels, rgb_tensor
 from .region import (MASK_MODES, TILE, TissueMask, TissueSegmentation, check_downsample, check_grid_args, grid_shape, otsu_threshold, region_layout,
                      resize_tables, thumbnail_layout, tissue_params)
+from . import probe as _probe
 from . import stain as _stain
 from .quality import NCOLS as QUALITY_COLS, MAX_CELLS as QUALITY_MAX_CELLS, QualityGate, TileQuality, check_gate, check_patch, check_rules
 from .stain import StainFit, StainTarget, check_stain
@@ -694,6 +695,168 @@ class SlideOps:
                     raise ValueError(f"a batch has width {x.shape[1]}, the centroids {D}")
                 yield self._cluster_features(x, True)
         return self._cluster_lloyd(prepared, k, D, cen, max_iter, tol_changed)
+
+    # ------------------------------------------------------------------ linear probe
+    def _probe_params(self, weight, bias, D: int, values: bool = True):
+        """fp32 weight ``[C, D]`` / bias ``[C]`` checked on the host (shapes; with ``values`` finite and the norm limit, which reads
+        device tensors back) -> (C, device weight, device bias)."""
+        C_, _ = _probe.check_weights(weight, bias, D, values)
+        return C_, self._on_device(weight), self._on_device(bias)
+
+    @torch.no_grad()
+    def probe_loss_grad(self, features, labels, weight, bias, sums, class_weight=None, normalize=True, forward=False, groups=0):
+        """One loss + gradient evaluation of the linear probe on the device: every kept row's softmax residual
+        is added into ``sums`` (a ``keep_amd.probe.ProbeSums`` of the same C and D) in one pass over the features.
+
+        ``features``: fp32 ``[N, D]`` as in :meth:`cluster_assign` (``normalize=True`` makes unit rows first); ``labels``: int32 ``[N]``,
+        -1 for an unlabelled row (in no sum) or ``0 .. C - 1``, anything else is an error the call reports after one 4-byte read-back;
+        ``weight`` fp32 ``[C, D]``, ``bias`` fp32 ``[C]``, ``2 <= C <= 64``; ``class_weight``: None or fp32 ``[C]`` in (0, 1]
+        (``keep_amd.probe.check_class_weight`` makes one).  The sums are integers, every term rounded before it is added: the same words
+        however the rows are split over calls; ``keep_amd.probe.objective_from_words`` turns them into the objective and its gradient.
+        ``forward=True`` returns ``(labels, probs, best, margin)`` of the same launch as :meth:`probe_predict` would, otherwise None.
+        ``groups``: 0, or 1 / 2 / 4 groups of 64 rows per workgroup (the same words; for measurement)."""
+        N, D = check_features(features)
+        _probe.check_labels(labels, N)
+        C_, w, b = self._probe_params(weight, bias, D)
+        if not isinstance(sums, _probe.ProbeSums):
+            raise ValueError(f"sums must be a ProbeSums, got {type(sums).__name__}")
+        sums.check(C_, D)
+        cw = None
+        if class_weight is not None:
+            cw = class_weight if isinstance(class_weight, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(class_weight))
+            if tuple(cw.shape) != (C_,) or cw.dtype != torch.float32:
+                raise ValueError(f"class_weight must be float32 [{C_}], got {cw.dtype} {tuple(cw.shape)}")
+        x = self._cluster_features(features, normalize)
+        if sums.buf.device != self._device:
+            raise ValueError(f"the accumulators live on {sums.buf.device}, this engine on {self._device}")
+        sums.claim(N)
+        y = self._on_device(labels)
+        cw = None if cw is None else self._on_device(cw)
+        out = (None, None, None, None)
+        if forward:
+            out = (torch.empty(N, dtype=torch.int32, device=self._device), torch.empty((N, C_), dtype=torch.float32, device=self._device),
+                   torch.empty(N, dtype=torch.float32, device=self._device), torch.empty(N, dtype=torch.float32, device=self._device))
+        self._call("probe_loss_grad", _ptr(x), N, D, _ptr(y), _ptr(w), _ptr(b), C_, _ptr(cw), _ptr(sums.grad), _ptr(sums.gbias), _ptr(sums.loss),
+                   _ptr(sums.counts), _ptr(sums.skipped), _ptr(out[1]), _ptr(out[0]), _ptr(out[2]), _ptr(out[3]), int(groups))
+        return out if forward else None
+
+    @torch.no_grad()
+    def probe_predict(self, probe, features, normalize=True, groups=0):
+        """The linear probe's forward on the device -> ``(labels, probs, margin, skipped)``: int32 ``[N]`` (the
+        first maximum of the logits; -1 for a skipped tile), fp32 ``[N, C]`` (softmax; a zero row for a skipped tile), fp32 ``[N]`` (the
+        winner's probability minus the runner-up's) and an int64 ``[1]`` count of skipped tiles.  ``probe``: a
+        ``keep_amd.probe.LinearProbe`` or a ``(weight fp32 [C, D], bias fp32 [C])`` pair; ``features`` as in :meth:`cluster_assign`.  The
+        logits are fp32 fma chains of one fixed order plus the bias: a tile's outputs do not depend on N, its row or the split over
+        calls.  No host synchronisation."""
+        N, D = check_features(features)
+        weight, bias = (probe.weight, probe.bias) if isinstance(probe, _probe.LinearProbe) else probe
+        C_, w, b = self._probe_params(weight, bias, D, values=False)
+        x = self._cluster_features(features, normalize)
+        labels = torch.empty(N, dtype=torch.int32, device=self._device)
+        probs = torch.empty((N, C_), dtype=torch.float32, device=self._device)
+        margin = torch.empty(N, dtype=torch.float32, device=self._device)
+        skipped = torch.zeros(1, dtype=torch.int64, device=self._device)
+        self._call("probe_forward", _ptr(x), N, D, _ptr(w), _ptr(b), C_, _ptr(probs), _ptr(labels), _ptr(None), _ptr(margin), _ptr(skipped),
+                   int(groups))
+        return labels, probs, margin, skipped
+
+    def _probe_fit(self, batches, C_: int, D: int, l2: float, cw: np.ndarray, gtol: float, max_iter: int, init, classes):
+        """L-BFGS on the host over ``batches()`` (an iterable of prepared device ``(features, labels)`` pairs, the same rows in the
+        same order every time it is called).  Every evaluation streams all batches into one ``ProbeSums`` and reads it back once."""
+        dev = self._device
+        sums = _probe.ProbeSums(C_, D, dev)
+        cwd = torch.from_numpy(cw).to(dev)
+        cd = C_ * D
+        last = {}
+
+        def split(theta):
+            return theta[:cd].reshape(C_, D), theta[cd:]
+
+        def fun(theta):
+            w64, b64 = split(theta)
+            w32, b32 = w64.astype(np.float32), b64.astype(np.float32)
+            _probe.check_weights(w32, b32, D)
+            wd, bd = torch.from_numpy(w32).to(dev), torch.from_numpy(b32).to(dev)
+            sums.zero_()
+            for x, y in batches():
+                sums.claim(x.shape[0])
+                self._call("probe_loss_grad", _ptr(x), x.shape[0], D, _ptr(y), _ptr(wd), _ptr(bd), C_, _ptr(cwd), _ptr(sums.grad), _ptr(sums.gbias),
+                           _ptr(sums.loss), _ptr(sums.counts), _ptr(sums.skipped), _ptr(None), _ptr(None), _ptr(None), _ptr(None), 0)
+            if sums.tiles == 0:
+                raise ValueError("batches() returned no rows")
+            words = sums.host()                                          # the evaluation's one read of the sums
+            f, gw, gb = _probe.objective_from_words(words, cw, w64, b64, l2)
+            last.update(words=words, weight=wd, bias=bd, theta=theta.copy())
+            return f, np.concatenate([gw.ravel(), gb])
+
+        w0, b0 = _probe.check_init(init, C_, D)
+        res = _probe.lbfgs(fun, np.concatenate([w0.ravel(), b0]), gtol, max_iter, noise=lambda th: _probe.loss_noise(*split(th)))
+        if not np.array_equal(last["theta"], res.theta):                # a stall: the accepted point is not the last one tried
+            fun(res.theta)
+        words = last["words"]
+        return _probe.LinearProbe(last["weight"], last["bias"], l2, cw, classes, res.n_iter, res.n_eval, res.converged, res.stop_reason,
+                                  float(res.f), float(np.abs(res.g).max()), torch.from_numpy(words["counts"].copy()).to(dev),
+                                  int(words["skipped"]))
+
+    def _probe_labels(self, labels, n: int) -> torch.Tensor:
+        """Integer labels ``[n]`` of any integer type, numpy or torch -> int32 on the device."""
+        y = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.array(labels))       # a copy: the caller's may be read-only
+        if tuple(y.shape) != (n,) or y.dtype.is_floating_point or y.dtype.is_complex or y.dtype == torch.bool:
+            raise ValueError(f"labels must be integers [{n}], got {y.dtype} {tuple(y.shape)}")
+        return y.to(self._device, torch.int32).contiguous()
+
+    @torch.no_grad()
+    def probe_fit(self, features, labels, n_classes: int, l2: float = 1e-3, class_weight=None, gtol: float = 1e-4, max_iter: int = 1000,
+                  init=None, classes=None):
+        """Fit a linear probe on frozen features -> ``keep_amd.probe.LinearProbe``: multinomial logistic
+        regression with L2, ``F = (1/S) sum_i w[y_i] (logsumexp(z_i) - z_i[y_i]) + (l2/2) |W|^2``, the bias not penalised; with
+        ``class_weight=None`` and C >= 3 this is sklearn's ``LogisticRegression(C=1 / (l2 n))``.
+
+        ``features``: fp32 ``[N, D]`` (made unit rows first); ``labels``: integers ``[N]``, -1 for a tile to leave out; ``n_classes`` in
+        2..64; ``class_weight``: None, ``"balanced"`` or ``[C]`` positive numbers (divided by their maximum).  The parameters live on the
+        host in float64 and L-BFGS (memory 10) runs there; every evaluation is one pass over the features on the device and one
+        read of the integer sums.  It stops when the gradient's largest magnitude is ``<= gtol``, after ``max_iter`` iterations, or when
+        the line search stalls in the fp32 evaluation noise (``stop_reason="stalled"``, not an error).  Integer sums and no random
+        numbers: two fits give the same bits, and :meth:`probe_fit_batches` over any split of the same tiles gives them too."""
+        N, D = check_features(features)
+        C_ = _probe.check_n_classes(n_classes)
+        l2, gtol, max_iter = _probe.check_fit(l2, gtol, max_iter)
+        classes = check_class_names(classes, C_)
+        self._ready_device()
+        y = self._probe_labels(labels, N)
+        counts = torch.bincount(y[y >= 0].to(torch.int64), minlength=C_)[:C_] if isinstance(class_weight, str) else None
+        cw = _probe.check_class_weight(class_weight, C_, counts)
+        x = self._cluster_features(features, True)
+        return self._probe_fit(lambda: ((x, y),), C_, D, l2, cw, gtol, max_iter, init, classes)
+
+    @torch.no_grad()
+    def probe_fit_batches(self, batches, n_classes: int, dim: int, l2: float = 1e-3, class_weight=None, gtol: float = 1e-4,
+                          max_iter: int = 1000, init=None, classes=None):
+        """:meth:`probe_fit` for features that are never resident at once (a cohort of feature files) -> ``LinearProbe`` over the
+        concatenation of the batches.  ``batches``: a callable returning an iterable of ``(features fp32 [n_i, dim], labels [n_i])``
+        pairs, called once per evaluation (and once more for ``class_weight="balanced"``) and returning the same rows in the same order
+        each time.  One ``ProbeSums`` is accumulated over an evaluation's batches (at most 2^24 tiles); the sums are integers, so the
+        result equals ``probe_fit`` on the concatenation bit for bit."""
+        C_, D = _probe.check_n_classes(n_classes), check_dim(dim)
+        l2, gtol, max_iter = _probe.check_fit(l2, gtol, max_iter)
+        classes = check_class_names(classes, C_)
+        if not callable(batches):
+            raise ValueError(f"batches must be a callable returning (features, labels) pairs, got {type(batches).__name__}")
+        self._ready_device()
+
+        def prepared():
+            for x, y in batches():
+                if check_features(x)[1] != D:
+                    raise ValueError(f"a batch has width {x.shape[1]}, dim is {D}")
+                yield self._cluster_features(x, True), self._probe_labels(y, x.shape[0])
+        counts = None
+        if isinstance(class_weight, str):
+            counts = torch.zeros(C_, dtype=torch.int64, device=self._device)
+            for _, y in batches():
+                y = self._probe_labels(y, len(y))
+                counts += torch.bincount(y[y >= 0].to(torch.int64), minlength=C_)[:C_]
+        cw = _probe.check_class_weight(class_weight, C_, counts)
+        return self._probe_fit(prepared, C_, D, l2, cw, gtol, max_iter, init, classes)
 
     # ------------------------------------------------------------------ region table (DESIGN.md section 13)
     @torch.no_grad()

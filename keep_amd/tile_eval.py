@@ -98,6 +98,39 @@ def classification_rounds_ci(model, image_embeddings: torch.Tensor, cap_embeddin
     return m.bootstrap_metric(true, pred[:, int(round)].astype(np.int64), max(A, 2), "weighted_f1", n_boot, seed)
 
 
+def linear_probe(model, train_x, train_y, test_x, test_y, n_classes: int, l2: float = 1e-3, class_weight=None, gtol: float = 1e-4,
+                 max_iter: int = 1000, n_boot: int = 1000, seed: int = 0, roc: bool = True) -> dict:
+    """The linear-probe protocol on frozen features: ``KEEPModel.probe_fit`` on the training tiles, then
+    ``probe_predict`` on the test tiles, scored as sklearn scores predicted labels -> a dict with ``probe`` (the
+    ``keep_amd.probe.LinearProbe``), ``labels`` / ``probs`` (the test predictions on the device), ``confusion`` (int64 ``[C, C]``,
+    ``confusion[true, pred]``), ``balanced_accuracy`` and ``weighted_f1`` (float64 on the host, sklearn's definitions), ``skipped``
+    (test tiles the skip rule left out; they are in no metric, as are test tiles labelled -1), and, for ``C <= 16`` (the confusion
+    kernel's limit) and ``n_boot > 0``, ``balanced_accuracy_ci`` / ``weighted_f1_ci`` (``bootstrap_metric`` results, paired by
+    ``seed``), else None; with ``roc=True`` also ``ovr_roc``: ``bootstrap_ovr_roc``'s ``(per_class, macro)`` on the probabilities."""
+    from . import bootstrap
+    m = _engine(model)
+    probe = m.probe_fit(train_x, train_y, n_classes, l2=l2, class_weight=class_weight, gtol=gtol, max_iter=max_iter)
+    C = probe.n_classes
+    labels, probs, _, _ = m.probe_predict(probe, test_x)
+    truth = m._probe_labels(test_y, int(labels.shape[0]))
+    if int(truth.max()) >= C or int(truth.min()) < -1:
+        raise ValueError(f"test labels must lie in -1..{C - 1}")
+    keep = (labels >= 0) & (truth >= 0)
+    t, p = truth[keep].to(torch.int64), labels[keep].to(torch.int64)
+    if t.numel() == 0:
+        raise ValueError("no labelled test tile is kept")
+    conf = torch.bincount(t * C + p, minlength=C * C).reshape(C, C).cpu().numpy()
+    out = dict(probe=probe, labels=labels, probs=probs, confusion=conf, balanced_accuracy=float(bootstrap.balanced_accuracy(conf)),
+               weighted_f1=weighted_f1_from_confusion(conf), skipped=int((labels < 0).sum()), balanced_accuracy_ci=None,
+               weighted_f1_ci=None, ovr_roc=None)
+    if n_boot > 0 and C <= 16:
+        out["balanced_accuracy_ci"] = m.bootstrap_metric(t, p, C, "balanced_accuracy", n_boot, seed)
+        out["weighted_f1_ci"] = m.bootstrap_metric(t, p, C, "weighted_f1", n_boot, seed)
+    if n_boot > 0 and roc:
+        out["ovr_roc"] = m.bootstrap_ovr_roc(probs[keep], t, n_boot, seed)
+    return out
+
+
 def retrieval_ranks(model, image_embeddings: torch.Tensor, text_embeddings: torch.Tensor,
                     targets: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Position of each caption's target image in its descending similarity list (int32 [P] on the device)."""

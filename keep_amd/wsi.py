@@ -643,6 +643,33 @@ def cluster_map(tile_features, tile_coords, k_or_centroids, downsample, shape, p
     return raster, res
 
 
+def probe_map(probe, tile_features, tile_coords, downsample, shape, patch_size=256, origin=(0, 0), vote=False, classes=None, model=None):
+    """The supervised morphology map: a fitted linear probe's probabilities of every tile rasterised in slide
+    geometry -> ``keep_amd.classmap.ClassRaster``.  ``probe``: a ``keep_amd.probe.LinearProbe`` (of ``KEEPModel.probe_fit``) or a
+    ``(weight [C, D], bias [C])`` pair; ``vote=True`` rasterises the predicted labels as one-hot rows instead.  ``classes``: optional
+    names, by default the probe's.  Skipped tiles (a non-finite feature) are in no plane.  ``KEEPModel.class_map``,
+    ``render_class_map`` and :func:`subtype_regions` take the raster from there."""
+    from .cluster import check_features
+    from .heatmap import check_raster_args
+    from .probe import LinearProbe
+    check_raster_args(patch_size, downsample, shape, origin)
+    f = tile_features.squeeze(0) if isinstance(tile_features, torch.Tensor) and tile_features.dim() == 3 else tile_features
+    N, _ = check_features(f)
+    coords = tile_coords if isinstance(tile_coords, torch.Tensor) else torch.as_tensor(np.asarray(tile_coords))
+    if tuple(coords.shape) != (N, 2):
+        raise ValueError(f"tile_coords must be [{N}, 2] beside {N} feature rows, got shape {tuple(coords.shape)}")
+    if classes is None and isinstance(probe, LinearProbe):
+        classes = probe.classes
+    m = _engine(model, tile_features)
+    labels, probs, _, _ = m.probe_predict(probe, f, normalize=True)
+    keep = labels >= 0
+    coords = coords.to(m._device)[keep]
+    if vote:
+        return m.class_raster(coords, None, patch_size, downsample, shape, origin, labels=labels[keep], n_classes=int(probs.shape[1]),
+                              classes=classes)
+    return m.class_raster(coords, probs[keep], patch_size, downsample, shape, origin, classes=classes)
+
+
 def subtype_regions(class_map, tissue=None, connectivity=8, min_area=1, model=None):
     """The region table of every class of a label map -> ``{c: keep_amd.components.RegionTable}``: the connected regions of the pixels
     labelled c (inside ``tissue``, a ``TissueMask`` of the map's geometry, optional), scored on the class's own plane of the
