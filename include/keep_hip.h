@@ -528,6 +528,53 @@ int keep_probe_loss_grad(keep_handle* h, const float* features, int64_t N, int64
                          int64_t C, const float* class_weight, int64_t* grad, int64_t* gbias, int64_t* loss, int64_t* counts, int64_t* skipped,
                          float* probs_out, int32_t* label_out, float* best_out, float* margin_out, int groups, void* stream);
 
+/* ---- nearest neighbours ----------------------------------------------------------
+ * Replaces: the [N,M] keep_similarity matrix + torch.topk round trip on this engine, and the reference's
+ * arr.argsort()[-50:][::-1] over a host similarity row (training/path_training/zero_shot.py:168-171), which lists the HIGHER index
+ * first among equal scores; here the lower index comes first.  queries fp32 [Nq,D] and bank fp32 [M,D], row-major unit rows, both
+ * 16-byte aligned; 1 <= Nq, M <= 2^22 per call, D a multiple of 16 in 16 .. 1024, 1 <= k <= 64, 0 <= bank_base and bank_base + M <=
+ * 2^32 - 1.  Anything else is KEEP_EINVAL and nothing is launched.
+ *
+ * The order is total.  A neighbour is one 64-bit key, KEEP_TOPK_KEY(KEEP_TOPK_ORD(bits of score + 0.0f), g) with g the row's GLOBAL
+ * bank index (bank_base + its row in this call): a larger key is a larger score, and of equal scores the lower index.  0 is the empty
+ * slot, below the key of every finite score.  A list is k keys in descending order, its empty slots last; the top k of a union of
+ * candidates is the k largest keys of the union, so lists merge exactly across calls, chunks, files and devices.  The keys are
+ * part of the ABI.
+ * keep_topk: score = q . b as cluster_assign's k-ordered fp32 fma chain from 0 (v_mfma_f32_16x16x4_f32; the score of (query i, bank
+ * row r) is the `best` of keep_cluster_assign(queries, bank + r D, K = 1) bit for bit).  A row holding a non-finite value or an element
+ * with |x| > 1 is skipped: a skipped bank row is never a candidate, a skipped query row's list is left as it was (empty with merge =
+ * 0); *query_skipped / *bank_skipped (int64 on the device, may be null) are ADDED into, a bank row counted once per call.  keys:
+ * uint64 [Nq,k], 8-byte aligned.  merge = 0: the lists are written; merge = 1: the descending lists already there are candidates too
+ * (zeroed by the caller before the first call).  Offering the same global row twice across merged calls is the caller's error and
+ * is not detected: the row then appears twice.  self_first >= 0: query row i never takes global row self_first + i.  With fewer than
+ * k candidates the tail slots stay empty.  segments: 0 (chosen here), or 1 .. 1024 cuts of the bank run by different workgroups
+ * and merged by keys (any value gives the same words; for measurement); workspace segments ceil64(Nq) k 8 bytes of the handle's
+ * arena.  No host synchronisation.
+ * keep_topk_merge: out = the k largest keys of lists a and b of the same queries (out may be a).
+ * keep_topk_unpack: index_out int64 [Nq,k] (the global index, -1 for an empty slot), score_out fp32 [Nq,k] (exactly the fp32 in the
+ * key, 0 for an empty slot), count_out int32 [Nq] (the filled slots); each may be null, not all.
+ * keep_knn_vote: neighbour r = 0 .. k - 1 in list order votes for bank_labels[g_r] (int32 [n_bank]) when that lies in 0 .. C - 1
+ * (anything else, such as -1, does not vote) with weight 1 (KEEP_KNN_UNIFORM) or expf((s_r - s_0) / temperature) (KEEP_KNN_SOFTMAX;
+ * s_0 the list's best score, temperature > 0, the subtraction and the division single fp32 operations).  v_c = the fp32 sum of class
+ * c's weights in list order, probs_out fp32 [Nq,C] = v_c / (v_0 + v_1 + .. in class order), label_out int32 [Nq] = the smallest c
+ * with the largest v_c, margin_out fp32 [Nq] = the winner's probability minus the runner-up's.  A query without a voting neighbour
+ * (or whose votes sum to 0): label -1, a zero row, margin 0, one ADDED to *skipped (int64 on the device).  2 <= C <= 64; outputs may
+ * be null, not all.  A key whose index is >= n_bank is KEEP_EINVAL, found by one check launch and a 4-byte read-back (the one host
+ * synchronisation) before a label is read. */
+#define KEEP_TOPK_EMPTY 0ull
+#define KEEP_TOPK_ORD(u) ((uint32_t)(u) ^ ((((uint32_t)(u)) >> 31) ? 0xFFFFFFFFu : 0x80000000u))       /* u: the bits of score + 0.0f */
+#define KEEP_TOPK_KEY(ord, g) (((uint64_t)(uint32_t)(ord) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(g)))
+#define KEEP_TOPK_INDEX(key) (0xFFFFFFFFu - (uint32_t)(key))
+#define KEEP_TOPK_SCORE_BITS(ord) ((((uint32_t)(ord)) & 0x80000000u) ? ((uint32_t)(ord) ^ 0x80000000u) : ~(uint32_t)(ord))
+enum { KEEP_KNN_UNIFORM = 0, KEEP_KNN_SOFTMAX = 1 };
+int keep_topk(keep_handle* h, const float* queries, int64_t Nq, const float* bank, int64_t M, int64_t D, int k, int64_t bank_base,
+              int64_t self_first, int merge, uint64_t* keys, int64_t* query_skipped, int64_t* bank_skipped, int segments, void* stream);
+int keep_topk_merge(keep_handle* h, const uint64_t* a, const uint64_t* b, int64_t Nq, int k, uint64_t* out, void* stream);
+int keep_topk_unpack(keep_handle* h, const uint64_t* keys, int64_t Nq, int k, int64_t* index_out, float* score_out, int32_t* count_out,
+                     void* stream);
+int keep_knn_vote(keep_handle* h, const uint64_t* keys, int64_t Nq, int k, const int32_t* bank_labels, int64_t n_bank, int64_t C, int mode,
+                  float temperature, float* probs_out, int32_t* label_out, float* margin_out, int64_t* skipped, void* stream);
+
 /* Region outlines: the boundary rings of a label image, with holes, and an outline drawn into an image.
  * Replaces: the contour polygons with a hole list per contour that CLAM's segmentTissue hands back (cv2.findContours with
  * RETR_CCOMP; the step of README.md:74) and the polygon annotation a viewer takes a lesion of WSI_evaluation/segment_utils.py's

@@ -73,6 +73,10 @@ SIGNATURES = {
     "keep_cluster_seed_step": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
     "keep_probe_forward": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "keep_probe_loss_grad": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "keep_topk": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "keep_topk_merge": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "keep_topk_unpack": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "keep_knn_vote": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "keep_heat_mean":(_i32, [_vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "keep_heat_render": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "keep_heat_smooth": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp]),

@@ -411,6 +411,21 @@ void launch_probe(const float* x, int N, int D, const float* w, const float* bia
 // *bad = 1 for a label outside -1 .. C - 1 or a class weight (may be null) outside (0, 1]
 void launch_probe_check(const int32_t* labels, int N, int C, const float* class_weight, int* bad, hipStream_t s);
 
+// Nearest neighbours (neighbours.hip).  q: fp32 [Nq][D] and bank: fp32 [M][D] unit rows with the limits of the
+// clustering above; keys: uint64 [Nq][k] descending lists of KEEP_TOPK_KEY words, 1 <= k <= TOPK_MAX_K.
+constexpr int TOPK_MAX_K = 64;                          // a list is one key per lane of a wave
+constexpr int TOPK_MAX_SEGMENTS = 1024;
+int topk_segments(int Nq, int M, int cus);
+// S segments; ws: S ceil64(Nq) k keys when S > 1 (unused otherwise); g_base: global index of bank row 0; self_first < 0: no exclusion;
+// q_skipped / b_skipped may be null and are ADDED into
+void launch_topk(const float* q, int Nq, const float* bank, int M, int D, int k, unsigned g_base, long long self_first, int merge, uint64_t* keys,
+                 int64_t* q_skipped, int64_t* b_skipped, int S, uint64_t* ws, hipStream_t s);
+void launch_topk_merge(const uint64_t* a, const uint64_t* b, int Nq, int k, uint64_t* out, hipStream_t s);     // out may be a
+void launch_topk_unpack(const uint64_t* keys, int Nq, int k, int64_t* index, float* score, int32_t* count, hipStream_t s);   // outputs may be null
+void launch_knn_check(const uint64_t* keys, int Nq, int k, int64_t n_bank, int* bad, hipStream_t s);           // *bad = 1 for an index >= n_bank
+void launch_knn_vote(const uint64_t* keys, int Nq, int k, const int32_t* bank_labels, int C, int mode, float T, float* probs, int32_t* label,
+                     float* margin, int64_t* skipped, hipStream_t s);
+
 // Sorted score population and rank percentiles (rank.hip)
 constexpr int SORT_TILE = 4096;                         // keys per block; up to this many are sorted by one block in LDS
 constexpr int SORT_SCAN_CHUNK = 2048;                   // entries of the digit table per block of the scan

@@ -1,5 +1,5 @@
 // The slide-geometry entry points of include/keep_hip.h: patch grid, tissue mask, stain normalisation, tile quality, heatmap, sort / rank, region table, outlines, polygon
-// fill, segmentation evaluation, bootstrap resampling, the subtype map, tile clustering and the linear probe.  Host code only: each function validates its arguments, carves its workspace from the handle's
+// fill, segmentation evaluation, bootstrap resampling, the subtype map, tile clustering, the linear probe and nearest neighbours.  Host code only: each function validates its arguments, carves its workspace from the handle's
 // arena, calls the launch_* of its kernel file (region / tissue / stain / quality / heatmap / rank / components / outline / annotation / eval / bootstrap .hip) and
 // reports the launch.  Of the handle (handle.h) they use the device, the error text, the arena and the sticky error flag.
 #include "handle.h"
@@ -867,6 +867,101 @@ int keep_probe_loss_grad(keep_handle* h, const float* features, int64_t N, int64
     launch_probe(features, (int)N, (int)D, weight, bias, (int)C, groups, labels, class_weight, probs_out, label_out, best_out, margin_out, skipped, grad,
                  gbias, loss, counts, s);
     return check_launch(h, "probe_loss_grad");
+}
+
+// Nearest neighbours (neighbours.hip)
+static int topk_list_check(keep_handle* h, const char* who, int64_t Nq, int k) {
+    if (Nq < 1 || Nq > CLUSTER_MAX_ROWS) return h->fail(KEEP_EINVAL, "%s: %lld query rows (1 .. 2^22 per call)", who, (long long)Nq);
+    if (k < 1 || k > TOPK_MAX_K) return h->fail(KEEP_EINVAL, "%s: k = %d (1 .. %d)", who, k, TOPK_MAX_K);
+    return KEEP_OK;
+}
+
+int keep_topk(keep_handle* h, const float* queries, int64_t Nq, const float* bank, int64_t M, int64_t D, int k, int64_t bank_base,
+              int64_t self_first, int merge, uint64_t* keys, int64_t* query_skipped, int64_t* bank_skipped, int segments, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = topk_list_check(h, "topk", Nq, k)) return rc;
+    if (int rc = cluster_shape_check(h, "topk", M, D, 1)) return rc;
+    if (!queries || !bank || !keys) return h->fail(KEEP_EINVAL, "topk: null queries, bank or keys");
+    if (((uintptr_t)queries & 15) || ((uintptr_t)bank & 15)) return h->fail(KEEP_EINVAL, "topk: queries / bank not 16-byte aligned");
+    if (((uintptr_t)keys & 7) || ((uintptr_t)query_skipped & 7) || ((uintptr_t)bank_skipped & 7))
+        return h->fail(KEEP_EINVAL, "topk: keys or a counter is not 8-byte aligned");
+    if (bank_base < 0 || bank_base + M > (int64_t)0xFFFFFFFFll)
+        return h->fail(KEEP_EINVAL, "topk: bank_base %lld with %lld rows (0 <= bank_base, bank_base + M <= 2^32 - 1)", (long long)bank_base, (long long)M);
+    if (self_first > (int64_t)0xFFFFFFFFll) return h->fail(KEEP_EINVAL, "topk: self_first %lld (a global row index, or negative)", (long long)self_first);
+    if (merge != 0 && merge != 1) return h->fail(KEEP_EINVAL, "topk: merge %d (0 or 1)", merge);
+    if (segments < 0 || segments > TOPK_MAX_SEGMENTS) return h->fail(KEEP_EINVAL, "topk: segments %d (0 = chosen here, 1 .. %d)", segments, TOPK_MAX_SEGMENTS);
+    KEEP_ON_DEVICE(h);
+    int S = segments;
+    if (S == 0) {
+        int cus = 0;
+        HIPCHK(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+        S = topk_segments((int)Nq, (int)M, cus);
+    }
+    uint64_t* ws = nullptr;
+    if (S > 1) {
+        const size_t bytes = (size_t)S * (size_t)((Nq + 63) / 64 * 64) * (size_t)k * sizeof(uint64_t);
+        if (int rc = ensure_arena(h, align_up(bytes))) return rc;
+        ws = (uint64_t*)h->arena;
+    }
+    launch_topk(queries, (int)Nq, bank, (int)M, (int)D, k, (unsigned)bank_base, self_first < 0 ? -1 : (long long)self_first, merge, keys, query_skipped,
+                bank_skipped, S, ws, (hipStream_t)stream);
+    return check_launch(h, "topk");
+}
+
+int keep_topk_merge(keep_handle* h, const uint64_t* a, const uint64_t* b, int64_t Nq, int k, uint64_t* out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = topk_list_check(h, "topk_merge", Nq, k)) return rc;
+    if (!a || !b || !out) return h->fail(KEEP_EINVAL, "topk_merge: null a, b or out");
+    if (((uintptr_t)a & 7) || ((uintptr_t)b & 7) || ((uintptr_t)out & 7)) return h->fail(KEEP_EINVAL, "topk_merge: a list is not 8-byte aligned");
+    if (out == b && a != b) return h->fail(KEEP_EINVAL, "topk_merge: out may be a, not b");
+    KEEP_ON_DEVICE(h);
+    launch_topk_merge(a, b, (int)Nq, k, out, (hipStream_t)stream);
+    return check_launch(h, "topk_merge");
+}
+
+int keep_topk_unpack(keep_handle* h, const uint64_t* keys, int64_t Nq, int k, int64_t* index_out, float* score_out, int32_t* count_out,
+                     void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = topk_list_check(h, "topk_unpack", Nq, k)) return rc;
+    if (!keys || ((uintptr_t)keys & 7)) return h->fail(KEEP_EINVAL, "topk_unpack: keys is null or not 8-byte aligned");
+    if (!index_out && !score_out && !count_out) return h->fail(KEEP_EINVAL, "topk_unpack: no output (every pointer is null)");
+    if (((uintptr_t)index_out & 7) || ((uintptr_t)score_out & 3) || ((uintptr_t)count_out & 3))
+        return h->fail(KEEP_EINVAL, "topk_unpack: an output is not aligned to its element size");
+    KEEP_ON_DEVICE(h);
+    launch_topk_unpack(keys, (int)Nq, k, index_out, score_out, count_out, (hipStream_t)stream);
+    return check_launch(h, "topk_unpack");
+}
+
+int keep_knn_vote(keep_handle* h, const uint64_t* keys, int64_t Nq, int k, const int32_t* bank_labels, int64_t n_bank, int64_t C, int mode,
+                  float temperature, float* probs_out, int32_t* label_out, float* margin_out, int64_t* skipped, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = topk_list_check(h, "knn_vote", Nq, k)) return rc;
+    if (!keys || ((uintptr_t)keys & 7)) return h->fail(KEEP_EINVAL, "knn_vote: keys is null or not 8-byte aligned");
+    if (!bank_labels || ((uintptr_t)bank_labels & 3)) return h->fail(KEEP_EINVAL, "knn_vote: bank_labels is null or not 4-byte aligned");
+    if (n_bank < 1 || n_bank > (int64_t)0xFFFFFFFFll) return h->fail(KEEP_EINVAL, "knn_vote: n_bank %lld (1 .. 2^32 - 1)", (long long)n_bank);
+    if (C < 2 || C > PROBE_MAX_C) return h->fail(KEEP_EINVAL, "knn_vote: C = %lld (2 .. 64)", (long long)C);
+    if (mode != KEEP_KNN_UNIFORM && mode != KEEP_KNN_SOFTMAX) return h->fail(KEEP_EINVAL, "knn_vote: mode %d (0 uniform, 1 softmax)", mode);
+    if (mode == KEEP_KNN_SOFTMAX && !(temperature > 0.f && temperature <= 3.0e38f))
+        return h->fail(KEEP_EINVAL, "knn_vote: temperature %g (finite and > 0)", (double)temperature);
+    if (!probs_out && !label_out && !margin_out && !skipped) return h->fail(KEEP_EINVAL, "knn_vote: no output (every pointer is null)");
+    if (((uintptr_t)probs_out & 3) || ((uintptr_t)label_out & 3) || ((uintptr_t)margin_out & 3) || ((uintptr_t)skipped & 7))
+        return h->fail(KEEP_EINVAL, "knn_vote: an output is not aligned to its element size");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    // the flag is read back before a label is read (the one synchronisation of this call), as in keep_probe_loss_grad
+    int rc = ensure_arena(h, align_up(sizeof(int)));
+    if (rc) return rc;
+    int* bad = (int*)h->arena;
+    HIPCHK(h, hipMemsetAsync(bad, 0, sizeof(int), s));
+    launch_knn_check(keys, (int)Nq, k, n_bank, bad, s);
+    rc = check_launch(h, "knn_check");
+    if (rc) return rc;
+    int bad_h = 0;
+    HIPCHK(h, hipMemcpyAsync(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (bad_h) return h->fail(KEEP_EINVAL, "knn_vote: a key names bank row >= n_bank = %lld", (long long)n_bank);
+    launch_knn_vote(keys, (int)Nq, k, bank_labels, (int)C, mode, temperature, probs_out, label_out, margin_out, skipped, s);
+    return check_launch(h, "knn_vote");
 }
 
 // the image, mask and od table that the three fit passes of the stain normalisation share

@@ -27,6 +27,7 @@ from .morphometry import DEFAULT_MAX_PAIRS, RegionShape, check_shape_args
 from .outline import NCOLS as RING_COLS, RegionOutlines, check_draw_args, check_outline_args, check_ring_count, regions_labels, rgb_tensor
 from .region import (MASK_MODES, TILE, TissueMask, TissueSegmentation, check_downsample, check_grid_args, grid_shape, otsu_threshold, region_layout,
                      resize_tables, thumbnail_layout, tissue_params)
+from . import neighbours as _nb
 from . import probe as _probe
 from . import stain as _stain
 from .quality import NCOLS as QUALITY_COLS, MAX_CELLS as QUALITY_MAX_CELLS, QualityGate, TileQuality, check_gate, check_patch, check_rules
@@ -857,6 +858,125 @@ class SlideOps:
                 counts += torch.bincount(y[y >= 0].to(torch.int64), minlength=C_)[:C_]
         cw = _probe.check_class_weight(class_weight, C_, counts)
         return self._probe_fit(prepared, C_, D, l2, cw, gtol, max_iter, init, classes)
+
+    # ------------------------------------------------------------------ nearest neighbours
+    def _neighbours(self, keys, k: int, n_bank: int, query_skipped, bank_skipped):
+        """The ``Neighbours`` of device keys int64 ``[Nq, k]``: one unpack launch."""
+        Nq = keys.shape[0]
+        index = torch.empty((Nq, k), dtype=torch.int64, device=self._device)
+        score = torch.empty((Nq, k), dtype=torch.float32, device=self._device)
+        count = torch.empty(Nq, dtype=torch.int32, device=self._device)
+        self._call("topk_unpack", _ptr(keys), Nq, k, _ptr(index), _ptr(score), _ptr(count))
+        return _nb.Neighbours(keys, index, score, count, k, n_bank, query_skipped, bank_skipped, self)
+
+    def _topk_merged(self, a, b):
+        if a.keys.device != self._device or b.keys.device != self._device:
+            raise ValueError(f"the lists live on {a.keys.device} and {b.keys.device}, this engine on {self._device}")
+        self._ready_device()
+        out = torch.empty_like(a.keys)
+        self._call("topk_merge", _ptr(a.keys.contiguous()), _ptr(b.keys.contiguous()), a.keys.shape[0], a.k, _ptr(out))
+        return self._neighbours(out, a.k, max(a.n_bank, b.n_bank), a.query_skipped.clone(), a.bank_skipped + b.bank_skipped)
+
+    @torch.no_grad()
+    def topk(self, queries, bank, k: int, normalize=True, exclude_self=False, into=None, bank_base: int = 0, self_first=None, segments: int = 0):
+        """The k bank rows nearest to every query row by cosine, on the device -> ``keep_amd.neighbours.Neighbours``.
+        The ``[Nq, M]`` score matrix is never written: one fused launch scores tiles of the bank and keeps every query's k best keys.
+
+        ``queries`` fp32 ``[Nq, D]`` and ``bank`` fp32 ``[M, D]`` as the features of :meth:`cluster_assign` (``normalize=True`` makes unit
+        rows of both first); ``k`` in 1..64.  A score is :meth:`cluster_assign`'s fp32 fma chain, so its bits depend on the two rows
+        alone; of equal scores the lower bank row comes first.  A row with a non-finite value or an element beyond 1 in magnitude is
+        skipped: such a bank row is never returned, such a query's list stays as it was (empty without ``into``).  ``bank_base``: the
+        global index of ``bank[0]``; ``into``: an earlier ``Neighbours`` of the same queries against other bank rows, whose lists
+        are candidates too (it is not modified); the result does not depend on how a bank is cut into calls or on their order.
+        ``exclude_self=True`` (queries and bank are the same rows): no row takes itself; ``self_first``: the same for query row i
+        and global row ``self_first + i``.  ``segments``: 0, or 1..1024 cuts of the bank run side by side (the same words; for
+        measurement).  No host synchronisation."""
+        Nq, D = check_features(queries, "queries")
+        M, Db = check_features(bank, "bank")
+        if D != Db:
+            raise ValueError(f"the queries have width {D}, the bank {Db}")
+        k, segments = _nb.check_k(k), _nb.check_segments(segments)
+        bank_base = _nb.check_bank_range(bank_base, M)
+        if exclude_self:
+            if self_first is not None:
+                raise ValueError("exclude_self=True is self_first=bank_base: give one of the two")
+            if Nq != M:
+                raise ValueError(f"exclude_self=True takes queries and bank of the same rows, got {Nq} and {M}")
+            self_first = bank_base
+        sf = _nb.check_self_first(self_first)
+        if into is not None:
+            if not isinstance(into, _nb.Neighbours):
+                raise ValueError(f"into must be a Neighbours, got {type(into).__name__}")
+            if tuple(into.keys.shape) != (Nq, k):
+                raise ValueError(f"into holds lists {tuple(into.keys.shape)}, this call [{Nq}, {k}]")
+        q = self._cluster_features(queries, normalize)
+        b = q if bank is queries else self._cluster_features(bank, normalize)
+        if into is None:
+            keys = torch.empty((Nq, k), dtype=torch.int64, device=self._device)
+            qs, bs = (torch.zeros(1, dtype=torch.int64, device=self._device) for _ in range(2))
+            n_bank = bank_base + M
+        else:
+            if into.keys.device != self._device:
+                raise ValueError(f"into lives on {into.keys.device}, this engine on {self._device}")
+            keys, qs, bs = into.keys.clone(), into.query_skipped, into.bank_skipped.clone()
+            n_bank = max(into.n_bank, bank_base + M)
+        # the queries' skip count is that of the first call: the same rows are skipped in every one
+        self._call("topk", _ptr(q), Nq, _ptr(b), M, D, k, bank_base, sf, 0 if into is None else 1, _ptr(keys), _ptr(qs if into is None else None),
+                   _ptr(bs), segments)
+        return self._neighbours(keys, k, n_bank, qs, bs)
+
+    @torch.no_grad()
+    def topk_batches(self, queries, batches, k: int, normalize=True, self_first=None):
+        """:meth:`topk` against a bank that is never resident at once (a cohort's feature files) -> ``Neighbours`` over the
+        concatenation of the batches, equal to the resident call bit for bit.  ``batches``: an iterable of fp32 ``[m_i, D]``; batch i's
+        rows take the global indices that follow batch i - 1's.  ``self_first`` as in :meth:`topk`."""
+        Nq, D = check_features(queries, "queries")
+        k, sf = _nb.check_k(k), _nb.check_self_first(self_first)
+        q = self._cluster_features(queries, normalize)
+        keys = torch.zeros((Nq, k), dtype=torch.int64, device=self._device)
+        qs, bs = (torch.zeros(1, dtype=torch.int64, device=self._device) for _ in range(2))
+        base = 0
+        for x in batches:
+            M, Db = check_features(x, "a batch")
+            if Db != D:
+                raise ValueError(f"a batch has width {Db}, the queries {D}")
+            _nb.check_bank_range(base, M)
+            b = self._cluster_features(x, normalize)
+            self._call("topk", _ptr(q), Nq, _ptr(b), M, D, k, base, sf, 1, _ptr(keys), _ptr(qs if base == 0 else None), _ptr(bs), 0)
+            base += M
+        if base == 0:
+            raise ValueError("batches is empty")
+        return self._neighbours(keys, k, base, qs, bs)
+
+    @torch.no_grad()
+    def knn_vote(self, neighbours, bank_labels, n_classes: int, weights: str = "softmax", temperature: float = 0.07):
+        """The kNN classifier's vote on the device -> ``(labels, probs, margin, skipped)``: int32 ``[Nq]`` (the
+        smallest class with the largest vote; -1 for a query without a voting neighbour), fp32 ``[Nq, C]`` (the vote shares; a zero row
+        for such a query), fp32 ``[Nq]`` (the winner's share minus the runner-up's) and an int64 ``[1]`` count of such queries.
+
+        ``neighbours``: a ``Neighbours``; ``bank_labels``: integers ``[n]``, ``n >= neighbours.n_bank``, indexed by global bank row; a
+        label outside ``0 .. n_classes - 1`` (such as -1) does not vote.  ``weights="uniform"``: one vote each; ``"softmax"``:
+        ``exp((s_r - s_0) / temperature)`` with ``s_0`` the list's best score (DINO's kNN weights up to the common factor).  The votes
+        are added in list order in fp32, so the result is the same from run to run.  One 4-byte read-back (the check that every key
+        names a row of ``bank_labels``) is the only host synchronisation."""
+        if not isinstance(neighbours, _nb.Neighbours):
+            raise ValueError(f"neighbours must be a Neighbours, got {type(neighbours).__name__}")
+        C_, mode, t = _nb.check_vote_args(n_classes, weights, temperature)
+        n = len(bank_labels)
+        if n < neighbours.n_bank:
+            raise ValueError(f"bank_labels has {n} entries, the bank {neighbours.n_bank} rows")
+        self._ready_device()
+        if neighbours.keys.device != self._device:
+            raise ValueError(f"the lists live on {neighbours.keys.device}, this engine on {self._device}")
+        y = self._probe_labels(bank_labels, n)
+        Nq = neighbours.keys.shape[0]
+        labels = torch.empty(Nq, dtype=torch.int32, device=self._device)
+        probs = torch.empty((Nq, C_), dtype=torch.float32, device=self._device)
+        margin = torch.empty(Nq, dtype=torch.float32, device=self._device)
+        skipped = torch.zeros(1, dtype=torch.int64, device=self._device)
+        self._call("knn_vote", _ptr(neighbours.keys.contiguous()), Nq, neighbours.k, _ptr(y), n, C_, mode, t, _ptr(probs), _ptr(labels),
+                   _ptr(margin), _ptr(skipped))
+        return labels, probs, margin, skipped
 
     # ------------------------------------------------------------------ region table (DESIGN.md section 13)
     @torch.no_grad()

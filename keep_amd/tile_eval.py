@@ -131,6 +131,48 @@ def linear_probe(model, train_x, train_y, test_x, test_y, n_classes: int, l2: fl
     return out
 
 
+def knn_probe(model, train_x, train_y, test_x, test_y, n_classes: int, k: int = 20, weights: str = "softmax", temperature: float = 0.07,
+              n_boot: int = 1000, seed: int = 0, roc: bool = True) -> dict:
+    """The kNN-probe protocol on frozen features, :func:`linear_probe`'s non-parametric twin: every test
+    tile's ``k`` nearest labelled training tiles by cosine (``KEEPModel.topk``) vote for its class (``KEEPModel.knn_vote``: uniform
+    votes, or DINO's ``exp(s / temperature)`` weights) -> :func:`linear_probe`'s dict with ``neighbours`` (the ``Neighbours`` of the test
+    tiles in the kept training rows) in place of ``probe``; ``probs`` are the vote shares, and ``skipped`` counts the test tiles without
+    a label (the skip rule, or no voting neighbour).  Training rows labelled -1 are dropped from the bank before the search, so they
+    take no neighbour slot."""
+    from . import bootstrap
+    from .neighbours import check_k, check_vote_args
+    m = _engine(model)
+    C, _, _ = check_vote_args(n_classes, weights, temperature)
+    k = check_k(k)
+    m._ready_device()
+    ty = m._probe_labels(train_y, int(train_x.shape[0]))
+    if int(ty.max()) >= C or int(ty.min()) < -1:
+        raise ValueError(f"training labels must lie in -1..{C - 1}")
+    on = ty >= 0
+    if not bool(on.any()):
+        raise ValueError("no labelled training tile")
+    bank = m._on_device(train_x)[on].contiguous()
+    nb = m.topk(test_x, bank, k)
+    labels, probs, _, _ = m.knn_vote(nb, ty[on], C, weights, temperature)
+    truth = m._probe_labels(test_y, int(labels.shape[0]))
+    if int(truth.max()) >= C or int(truth.min()) < -1:
+        raise ValueError(f"test labels must lie in -1..{C - 1}")
+    keep = (labels >= 0) & (truth >= 0)
+    t, p = truth[keep].to(torch.int64), labels[keep].to(torch.int64)
+    if t.numel() == 0:
+        raise ValueError("no labelled test tile is kept")
+    conf = torch.bincount(t * C + p, minlength=C * C).reshape(C, C).cpu().numpy()
+    out = dict(neighbours=nb, labels=labels, probs=probs, confusion=conf, balanced_accuracy=float(bootstrap.balanced_accuracy(conf)),
+               weighted_f1=weighted_f1_from_confusion(conf), skipped=int((labels < 0).sum()), balanced_accuracy_ci=None,
+               weighted_f1_ci=None, ovr_roc=None)
+    if n_boot > 0 and C <= 16:
+        out["balanced_accuracy_ci"] = m.bootstrap_metric(t, p, C, "balanced_accuracy", n_boot, seed)
+        out["weighted_f1_ci"] = m.bootstrap_metric(t, p, C, "weighted_f1", n_boot, seed)
+    if n_boot > 0 and roc:
+        out["ovr_roc"] = m.bootstrap_ovr_roc(probs[keep], t, n_boot, seed)
+    return out
+
+
 def retrieval_ranks(model, image_embeddings: torch.Tensor, text_embeddings: torch.Tensor,
                     targets: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Position of each caption's target image in its descending similarity list (int32 [P] on the device)."""

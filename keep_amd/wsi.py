@@ -670,6 +670,58 @@ def probe_map(probe, tile_features, tile_coords, downsample, shape, patch_size=2
     return m.class_raster(coords, probs[keep], patch_size, downsample, shape, origin, classes=classes)
 
 
+def knn_map(train_features, train_labels, n_classes, tile_features, tile_coords, downsample, shape, patch_size=256, origin=(0, 0), k=20,
+            weights="softmax", temperature=0.07, vote=False, classes=None, model=None):
+    """The example-based morphology map: every tile's ``k`` nearest labelled training tiles vote for its class
+    (``KEEPModel.topk`` + ``knn_vote``) and the vote shares are rasterised in slide geometry -> ``keep_amd.classmap.ClassRaster``, as
+    :func:`probe_map` builds one.  ``train_labels``: integers, -1 for a training tile to leave out of the bank; ``vote=True`` rasterises
+    the predicted labels as one-hot rows instead.  Tiles without a label (a non-finite feature, or no voting neighbour) are in no
+    plane.  ``KEEPModel.class_map``, ``render_class_map`` and :func:`subtype_regions` take the raster from there."""
+    from .cluster import check_features
+    from .heatmap import check_raster_args
+    check_raster_args(patch_size, downsample, shape, origin)
+    f = tile_features.squeeze(0) if isinstance(tile_features, torch.Tensor) and tile_features.dim() == 3 else tile_features
+    N, _ = check_features(f)
+    coords = tile_coords if isinstance(tile_coords, torch.Tensor) else torch.as_tensor(np.asarray(tile_coords))
+    if tuple(coords.shape) != (N, 2):
+        raise ValueError(f"tile_coords must be [{N}, 2] beside {N} feature rows, got shape {tuple(coords.shape)}")
+    m = _engine(model, tile_features, train_features)
+    m._ready_device()
+    ty = m._probe_labels(train_labels, int(train_features.shape[0]))
+    on = ty >= 0
+    if not bool(on.any()):
+        raise ValueError("no labelled training tile")
+    nb = m.topk(f, m._on_device(train_features)[on].contiguous(), k)
+    labels, probs, _, _ = m.knn_vote(nb, ty[on], n_classes, weights, temperature)
+    keep = labels >= 0
+    coords = coords.to(m._device)[keep]
+    if vote:
+        return m.class_raster(coords, None, patch_size, downsample, shape, origin, labels=labels[keep], n_classes=int(probs.shape[1]),
+                              classes=classes)
+    return m.class_raster(coords, probs[keep], patch_size, downsample, shape, origin, classes=classes)
+
+
+def search_tiles(query_features, tile_features, k, tile_coords=None, exclude_self=False, model=None):
+    """Tile search: the ``k`` tiles most like every query by cosine -> ``(index int64 [Q, k], score fp32 [Q, k],
+    coords [Q, k, 2] or None)`` on the device, best first, of equal scores the lower tile first; -1 / 0 / (-1, -1) in an empty slot
+    (fewer than ``k`` tiles, or a query with a non-finite feature).  ``query_features``: prompt embeddings or tile features ``[Q, D]``;
+    ``tile_features`` ``[N, D]``: a slide's tiles; ``tile_coords`` ``[N, 2]``: gathered on the device into the third result.
+    ``exclude_self=True`` (the queries are the tiles themselves): no tile finds itself."""
+    qf = query_features.squeeze(0) if isinstance(query_features, torch.Tensor) and query_features.dim() == 3 else query_features
+    tf = tile_features.squeeze(0) if isinstance(tile_features, torch.Tensor) and tile_features.dim() == 3 else tile_features
+    m = _engine(model, tile_features, query_features)
+    if tile_coords is not None:
+        coords = tile_coords if isinstance(tile_coords, torch.Tensor) else torch.as_tensor(np.asarray(tile_coords))
+        if tuple(coords.shape) != (int(tf.shape[0]), 2):
+            raise ValueError(f"tile_coords must be [{int(tf.shape[0])}, 2] beside {int(tf.shape[0])} feature rows, got shape {tuple(coords.shape)}")
+    nb = m.topk(qf, tf, k, exclude_self=exclude_self)
+    if tile_coords is None:
+        return nb.index, nb.score, None
+    coords = coords.to(m._device)
+    found = coords[nb.index.clamp(min=0)]
+    return nb.index, nb.score, torch.where((nb.index >= 0)[..., None], found, torch.full_like(found, -1))
+
+
 def subtype_regions(class_map, tissue=None, connectivity=8, min_area=1, model=None):
     """The region table of every class of a label map -> ``{c: keep_amd.components.RegionTable}``: the connected regions of the pixels
     labelled c (inside ``tissue``, a ``TissueMask`` of the map's geometry, optional), scored on the class's own plane of the
