@@ -969,6 +969,50 @@ int keep_op_layernorm(keep_handle* h, const float* x, const float* add, const fl
 int keep_op_sgemm(keep_handle* h, const float* a, const float* b, const float* bias, int64_t M, int64_t N,
                   int64_t K, float scale, int act, float* out, void* stream);
 int keep_op_l2norm(keep_handle* h, float* x, int64_t rows, int64_t D, void* stream);
+/* The image tower in front of its first block (timm PatchEmbed + cls_token + pos_embed), as the engine runs it: im2col of the pixels into
+ *   the fp16 operand planes (and the CLS rows cls + pos[0] of the token stream), then the patch-embedding GEMM with the EPI_PATCH epilogue, which writes
+ *   patch p of image b to row b*(gh*gw+1)+1+p and adds pos[1+p]; the split-K scratch is attached, so the handle's options pick the GEMM route as they do
+ *   in the towers.  pixels: pix_dtype 0 fp32 / 1 fp16 / 2 bf16 [B,3,16 gh,16 gw], 3 uint8 [B,16 gh,16 gw,3] (normalised on the fly); w fp32 [D,768]
+ *   (the conv weight flattened), bias, cls fp32 [D], pos fp32 [gh*gw+1, D]; D % 128 == 0.  split 1: hi + lo planes and the 3-pass product; 0: the hi
+ *   plane and one pass.
+ *   resid fp32 [B*(gh*gw+1), D]: every byte is set to 0xFF (a NaN) before the launches, so a row nobody wrote shows up.  pat_hi, pat_lo fp32
+ *   [B*gh*gw, 768]: the two im2col planes read back SEPARATELY (fp16 values, exact in fp32); pat_lo may be NULL.  Every byte of the lo plane is set to
+ *   `sentinel` (0..255) before im2col runs, and with split 0 im2col is not given the plane (as in the engine): it then reads back as the sentinel. */
+int keep_op_patch_embed(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, int64_t gh, int64_t gw, int64_t D, const float* w,
+                        const float* bias, const float* cls, const float* pos, int split, int sentinel, float* resid, float* pat_hi,
+                        float* pat_lo, void* stream);
+/* The text tower in front of its first layer (HF BertEmbeddings: LayerNorm((word + token_type) + position)): ids, type_ids int64 [P,T]
+ *   (type_ids NULL: all 0), wemb fp32 [vocab,H], pemb fp32 [max_pos,H] (T <= max_pos), temb fp32 [type_vocab,H], gamma, beta fp32 [H]; H in {256, 768, 1024}.
+ *   resid fp32 [P*T, H]: the fp32 output; hi, lo fp32 [P*T, H]: the fp16 operand planes the kernel wrote in blk layout, read back separately (lo NULL: the
+ *   kernel is not given a lo plane).  *err_word (host): an error word of this call, zeroed before the launch -- bit 0: an id or type outside its table
+ *   (clamped into it); the handle's sticky error word is not touched. */
+int keep_op_bert_embed(keep_handle* h, const int64_t* ids, const int64_t* type_ids, const float* wemb, const float* pemb, const float* temb,
+                       const float* gamma, const float* beta, float eps, int64_t P, int64_t T, int64_t H, int64_t vocab, int64_t type_vocab,
+                       int64_t max_pos, float* resid, float* hi, float* lo, int* err_word, void* stream);
+/* keep_op_layernorm on rows that lie x_stride elements apart (x_stride >= D, a multiple of 4), as the image tower's final norm reads row 0 of every
+ *   tile out of the token stream: out fp32 [rows, D] dense = LayerNorm(x[r * x_stride .. + D]) */
+int keep_op_layernorm_rows(keep_handle* h, const float* x, int64_t x_stride, const float* gamma, const float* beta, int64_t rows, int64_t D,
+                           float eps, float* out, void* stream);
+/* keep_op_sgemm with explicit leading dimensions, as the BERT pooler reads row p*T of the token stream: row m of A at a + m*lda, row n of B at
+ *   b + n*ldb, row m of the output at out + m*ldo (lda, ldb >= K; ldo >= N; columns N..ldo of the output are not written).  lda % 4 != 0 or
+ *   ldb % 4 != 0: KEEP_EUNSUPPORTED. */
+int keep_op_sgemm_ld(keep_handle* h, const float* a, int64_t lda, const float* b, int64_t ldb, const float* bias, int64_t M, int64_t N, int64_t K,
+                     float scale, int act, float* out, int64_t ldo, void* stream);
+/* The kernels that move the CLS rows between the token stream (row stride `row_stride` rows: the tokens per tile) and the compact [rows, D] operands:
+ *   KEEP_ROWS_GATHER_F32   dst fp32 [rows, D]: row r <- row r*row_stride of src fp32 [rows*row_stride, D]
+ *   KEEP_ROWS_SCATTER_F32  row r*row_stride of dst fp32 [rows*row_stride, D] <- row r of src fp32 [rows, D]; the other rows of dst are the caller's
+ *   KEEP_ROWS_GATHER_BLK   src fp32 [rows*row_stride, D] is written as an fp16 plane in blk layout (D % 32 == 0), its rows r*row_stride are gathered into a
+ *                          compact blk plane, and that plane comes back as dst fp32 [rows, D] (fp16 values) */
+enum { KEEP_ROWS_GATHER_F32 = 0, KEEP_ROWS_SCATTER_F32 = 1, KEEP_ROWS_GATHER_BLK = 2 };
+int keep_op_rows(keep_handle* h, int kind, const float* src, int64_t row_stride, int64_t rows, int64_t D, float* dst, void* stream);
+/* The two kernels of the mean-input bias compensation (keep_calibrate_bias), one per call; K % 32 == 0:
+ *   KEEP_BIAS_COL_SUM    x fp32 [rows, K] is written as an fp16 hi plane in blk layout and its column sums are ADDED into col_sum fp32 [K] (the caller zeroes
+ *                        it; a second call continues the sum).  inv_rows, bias and out are not used.
+ *   KEEP_BIAS_MEAN_CORR  x is a GEMM weight fp32 [rows = N, K]: out[n] = bias[n] + inv_rows * sum_k w_lo[n][k] col_sum[k] on the lo plane of its blk-layout
+ *                        hi / lo split; col_sum fp32 [K] is read only; bias, out fp32 [N] */
+enum { KEEP_BIAS_COL_SUM = 0, KEEP_BIAS_MEAN_CORR = 1 };
+int keep_op_bias_corr(keep_handle* h, int step, const float* x, int64_t rows, int64_t K, float* col_sum, float inv_rows, const float* bias,
+                      float* out, void* stream);
 /* measurement aid: one wavefront spins for ~spin_us microseconds and writes {shader-clock cycles, 100 MHz reference ticks} to device_out2
  * (two int64 on the device): effective shader clock = cycles / ticks * 100 MHz.  Launched on a side stream next to a running workload it
  * reads the clock the part actually sustains under that load (bench.py records it; the MFMA peak is quoted at 2.4 GHz). */

@@ -122,6 +122,12 @@ SIGNATURES = {
     "keep_op_layernorm": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp]),
     "keep_op_sgemm": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _vp]),
     "keep_op_l2norm": (_i32, [_vp, _vp, _i64, _i64, _vp]),
+    "keep_op_patch_embed": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "keep_op_bert_embed": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, C.POINTER(_i32), _vp]),
+    "keep_op_layernorm_rows": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _f32, _vp, _vp]),
+    "keep_op_sgemm_ld": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _i64, _vp]),
+    "keep_op_rows": (_i32, [_vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "keep_op_bias_corr": (_i32, [_vp, _i32, _vp, _i64, _i64, _vp, _f32, _vp, _vp, _vp]),
     "keep_clock_probe": (_i32, [_vp, _i32, _vp, _vp]),
     "keep_mfma_probe": (_i32, [_vp, _vp, _vp, _i32, C.POINTER(C.c_double), _vp]),
     "keep_debug_read": (_i32, [_vp, _vp, _i64]),

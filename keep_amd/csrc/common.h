@@ -484,7 +484,7 @@ void launch_split_f16(const float* src, f16* hi, f16* lo, int64_t n, hipStream_t
 void launch_split_blockify(const float* src, f16* hi, f16* lo, int M, int K, hipStream_t s);
 // the same plus the MX-fp4 side planes of quant4.h (q: both planes, sc: scales); K % 32 == 0; lo may be null
 void launch_quant_blockify(const float* src, f16* hi, f16* lo, unsigned char* q, unsigned char* sc, int M, int K, hipStream_t s);
-// blk-layout fp16 hi (+lo) -> row-major fp32 [M][K]
+// blk-layout fp16 hi (+lo) -> row-major fp32 [M][K]; lo null: the hi plane's values as they are (the sign of a zero included)
 void launch_unblockify_f32(const f16* hi, const f16* lo, float* out, int M, int K, hipStream_t s);
 // stats2[0] = max |w| (read as float), stats2[1] = sum w^2 -- the load-time range check of the fp16 operand planes
 void launch_weight_stats(const float* w, int64_t n, float* stats2, hipStream_t s);

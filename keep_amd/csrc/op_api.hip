@@ -1,5 +1,5 @@
 // Single-operator entry points (keep_op_*) and hardware probes of libkeep_hip: the kernels of the towers, one at a time, on fp32 tensors of the
-// caller.  They are the test surface of the kernels (tests/test_ops_gpu.py, tests/test_small_m_gpu.py): each packs its operands the way the
+// caller.  They are the test surface of the kernels (tests/test_ops_gpu.py, tests/test_small_m_gpu.py, tests/test_front_ops_gpu.py): each packs its operands the way the
 // towers hold them (hi / lo planes, blk layout, MX-fp4 side planes), fills the launch parameters with the helpers the towers use (handle.h),
 // launches, and unpacks the result.  Temporaries are allocated per call; nothing here touches the arena.
 #include "handle.h"
@@ -349,6 +349,133 @@ int keep_op_sgemm(keep_handle* h, const float* a, const float* b, const float* b
     g.scale = scale; g.act = act;
     if (launch_sgemm_f32(g, (hipStream_t)stream)) return h->fail(KEEP_EUNSUPPORTED, "sgemm needs K%%16==0");
     return check_launch(h, "op_sgemm");
+}
+
+// ---- the towers' front ends, tails and row movers (tests/test_front_ops_gpu.py) ----
+
+int keep_op_patch_embed(keep_handle* h, const void* pixels, int pix_dtype, int64_t B, int64_t gh, int64_t gw, int64_t D, const float* w,
+                        const float* bias, const float* cls, const float* pos, int split, int sentinel, float* resid, float* pat_hi, float* pat_lo,
+                        void* stream) {
+    if (!h || !pixels || !w || !bias || !cls || !pos || !resid || !pat_hi) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
+    if (pix_dtype < PIX_F32 || pix_dtype > PIX_U8_HWC || (split != 0 && split != 1) || sentinel < 0 || sentinel > 255)
+        return h->fail(KEEP_EINVAL, "patch_embed: pixel dtype %d, split %d, sentinel %d", pix_dtype, split, sentinel);
+    if (B < 1 || gh < 1 || gw < 1 || gh > 1024 || gw > 1024 || B * gh * gw > (1 << 24)) return h->fail(KEEP_EINVAL, "patch_embed: B %lld, grid %lld x %lld", (long long)B, (long long)gh, (long long)gw);
+    if (D < 128 || D % 128 || D > (1 << 16)) return h->fail(KEEP_EUNSUPPORTED, "patch_embed needs D%%128==0");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t P = gh * gw, M = B * P, K = 768;
+    Tmp t;
+    const Planes A = alloc_planes(t, M, K, false), W = alloc_planes(t, D, K, false);
+    float* ws = t.get<float>(SKINNY_WS_BYTES / 4);
+    if (!t.ok) return h->fail(KEEP_ENOMEM, "temp alloc");
+    HIPCHK(h, hipMemsetAsync(A.lo, sentinel, blk_elems(M, K) * sizeof(f16), s));                  // what still holds the sentinel was not written
+    HIPCHK(h, hipMemsetAsync(resid, 0xFF, (size_t)B * (P + 1) * D * sizeof(float), s));           // a NaN pattern: a row nobody wrote shows up
+    launch_split_blockify(w, W.hi, W.lo, (int)D, (int)K, s);
+    // as vit_begin: im2col + the CLS rows, then the GEMM whose epilogue remaps the rows and adds the position table
+    launch_im2col(pixels, pix_dtype, (int)B, (int)gh, (int)gw, A.hi, split ? A.lo : nullptr, cls, pos, resid, (int)D, s);
+    GemmParams p = gemm_params(h, A.hi, A.lo, W.hi, W.lo, (int)M, (int)D, (int)K, split != 0, bias);
+    p.pos = pos; p.patches_per_img = (int)P;
+    p.resid = resid;
+    with_splitk(p, ws);
+    const int rc = launch_gemm_f16(p, EPI_PATCH, s);
+    launch_unblockify_f32(A.hi, nullptr, pat_hi, (int)M, (int)K, s);
+    if (pat_lo) launch_unblockify_f32(A.lo, nullptr, pat_lo, (int)M, (int)K, s);
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (rc < 0) return h->fail(KEEP_EUNSUPPORTED, "op_patch_embed: no kernel for this shape / mode");
+    return check_launch(h, "op_patch_embed");
+}
+
+int keep_op_bert_embed(keep_handle* h, const int64_t* ids, const int64_t* type_ids, const float* wemb, const float* pemb, const float* temb,
+                       const float* gamma, const float* beta, float eps, int64_t P, int64_t T, int64_t H, int64_t vocab, int64_t type_vocab,
+                       int64_t max_pos, float* resid, float* hi, float* lo, int* err_word, void* stream) {
+    if (!h || !ids || !wemb || !pemb || !temb || !gamma || !beta || !resid || !hi || !err_word) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
+    if (H != 256 && H != 768 && H != 1024) return h->fail(KEEP_EUNSUPPORTED, "bert_embed: width %lld", (long long)H);
+    if (P < 1 || T < 1 || T > max_pos || P * T > (1 << 24) || vocab < 1 || vocab > INT32_MAX || type_vocab < 1 || type_vocab > INT32_MAX)
+        return h->fail(KEEP_EINVAL, "bert_embed: P %lld, T %lld (position table %lld), vocab %lld, types %lld", (long long)P, (long long)T, (long long)max_pos, (long long)vocab, (long long)type_vocab);
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t M = P * T;
+    Tmp t;
+    const Planes X = alloc_planes(t, M, H, false);
+    int* err = t.get<int>(1);                            // an error word of this call: the handle's sticky one is left alone
+    if (!t.ok) return h->fail(KEEP_ENOMEM, "temp alloc");
+    HIPCHK(h, hipMemsetAsync(err, 0, sizeof(int), s));
+    launch_bert_embed_ln(ids, type_ids, wemb, pemb, temb, gamma, beta, eps, (int)P, (int)T, (int)H, (int)vocab, (int)type_vocab, resid, X.hi,
+                         lo ? X.lo : nullptr, err, s);
+    launch_unblockify_f32(X.hi, nullptr, hi, (int)M, (int)H, s);
+    if (lo) launch_unblockify_f32(X.lo, nullptr, lo, (int)M, (int)H, s);
+    HIPCHK(h, hipMemcpyAsync(err_word, err, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return check_launch(h, "op_bert_embed");
+}
+
+int keep_op_layernorm_rows(keep_handle* h, const float* x, int64_t x_stride, const float* gamma, const float* beta, int64_t rows, int64_t D,
+                           float eps, float* out, void* stream) {
+    if (!h || !x || !gamma || !beta || !out || rows < 1 || rows > INT32_MAX) return h ? h->fail(KEEP_EINVAL, "bad layernorm arguments") : KEEP_EINVAL;
+    if (x_stride < D || x_stride % 4) return h->fail(KEEP_EINVAL, "layernorm_rows: row stride %lld (>= D, a multiple of 4)", (long long)x_stride);
+    KEEP_ON_DEVICE(h);
+    LnParams p = ln_params(h, x, x_stride, (int)rows, (int)D, eps);      // as vit_end: row r of the output is row r * x_stride / D of the token stream
+    p.gamma = gamma; p.beta = beta;
+    p.out_f32 = out; p.out_f32_stride = D;
+    if (launch_layernorm(p, (hipStream_t)stream)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %lld", (long long)D);
+    return check_launch(h, "op_layernorm_rows");
+}
+
+int keep_op_sgemm_ld(keep_handle* h, const float* a, int64_t lda, const float* b, int64_t ldb, const float* bias, int64_t M, int64_t N, int64_t K,
+                     float scale, int act, float* out, int64_t ldo, void* stream) {
+    if (!h || !a || !b || !out) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
+    if (M < 1 || N < 1 || K < 1 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX || lda < K || ldb < K || ldo < N)
+        return h->fail(KEEP_EINVAL, "sgemm_ld: M %lld, N %lld, K %lld, lda %lld, ldb %lld, ldo %lld", (long long)M, (long long)N, (long long)K, (long long)lda, (long long)ldb, (long long)ldo);
+    KEEP_ON_DEVICE(h);
+    SgemmParams g{};
+    g.tune = &h->tune;
+    g.a = a; g.lda = lda; g.b = b; g.ldb = ldb; g.out = out; g.ldo = ldo; g.bias = bias; g.M = (int)M; g.N = (int)N; g.K = (int)K;
+    g.scale = scale; g.act = act;
+    if (launch_sgemm_f32(g, (hipStream_t)stream)) return h->fail(KEEP_EUNSUPPORTED, "sgemm needs K%%16==0, lda%%4==0 and ldb%%4==0");
+    return check_launch(h, "op_sgemm_ld");
+}
+
+int keep_op_rows(keep_handle* h, int kind, const float* src, int64_t row_stride, int64_t rows, int64_t D, float* dst, void* stream) {
+    if (!h || !src || !dst) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
+    if (kind < KEEP_ROWS_GATHER_F32 || kind > KEEP_ROWS_GATHER_BLK) return h->fail(KEEP_EINVAL, "rows: kind %d", kind);
+    if (rows < 1 || row_stride < 1 || D < 1 || D > (1 << 20) || rows * row_stride > (1 << 24)) return h->fail(KEEP_EINVAL, "rows: rows %lld, row stride %lld, D %lld", (long long)rows, (long long)row_stride, (long long)D);
+    if (kind == KEEP_ROWS_GATHER_BLK && D % 32) return h->fail(KEEP_EUNSUPPORTED, "rows: the blk layout needs D%%32==0");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (kind == KEEP_ROWS_GATHER_F32) {
+        launch_gather_rows_f32(src, row_stride * D, dst, (int)rows, (int)D, s);             // as vit_layer: the stride in elements, ntok * D
+    } else if (kind == KEEP_ROWS_SCATTER_F32) {
+        launch_scatter_rows_f32(src, dst, row_stride * D, (int)rows, (int)D, s);
+    } else {
+        const int64_t src_rows = rows * row_stride;
+        Tmp t;
+        f16* s_hi = t.get<f16>(blk_elems(src_rows, D)); f16* d_hi = t.get<f16>(blk_elems(rows, D));
+        if (!t.ok) return h->fail(KEEP_ENOMEM, "temp alloc");
+        HIPCHK(h, hipMemsetAsync(d_hi, 0, blk_elems(rows, D) * sizeof(f16), s));
+        launch_split_blockify(src, s_hi, nullptr, (int)src_rows, (int)D, s);
+        launch_gather_rows_blk(s_hi, (int)row_stride, d_hi, (int)rows, (int)D, s);
+        launch_unblockify_f32(d_hi, nullptr, dst, (int)rows, (int)D, s);
+        HIPCHK(h, hipStreamSynchronize(s));
+    }
+    return check_launch(h, "op_rows");
+}
+
+int keep_op_bias_corr(keep_handle* h, int step, const float* x, int64_t rows, int64_t K, float* col_sum, float inv_rows, const float* bias,
+                      float* out, void* stream) {
+    if (!h || !x || !col_sum) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
+    if (step != KEEP_BIAS_COL_SUM && step != KEEP_BIAS_MEAN_CORR) return h->fail(KEEP_EINVAL, "bias_corr: step %d", step);
+    if (step == KEEP_BIAS_MEAN_CORR && (!bias || !out)) return h->fail(KEEP_EINVAL, "bias_corr: missing bias / out");
+    if (rows < 1 || rows > (1 << 24) || K < 32 || K % 32 || K > (1 << 20)) return h->fail(KEEP_EUNSUPPORTED, "bias_corr needs K%%32==0");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    Tmp t;
+    const Planes X = alloc_planes(t, rows, K, false);
+    if (!t.ok) return h->fail(KEEP_ENOMEM, "temp alloc");
+    launch_split_blockify(x, X.hi, X.lo, (int)rows, (int)K, s);
+    if (step == KEEP_BIAS_COL_SUM) launch_blk_col_sum(X.hi, (int)rows, (int)K, col_sum, s);            // adds: what the site's input summed to so far stays
+    else launch_bias_mean_corr(X.lo, col_sum, inv_rows, bias, out, (int)rows, (int)K, s);              // x is a GEMM weight [N][K] here: its lo plane
+    HIPCHK(h, hipStreamSynchronize(s));
+    return check_launch(h, "op_bias_corr");
 }
 
 int keep_debug_read(keep_handle* h, void* host_dst, int64_t bytes) {

@@ -281,7 +281,7 @@ __global__ void unblockify_f32_kernel(const f16* __restrict__ hi, const f16* __r
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int m = (int)(i / K), k = (int)(i % K);
         const int64_t o = blk_off(m, k, KT);
-        out[i] = (float)hi[o] + (lo ? (float)lo[o] : 0.f);
+        out[i] = lo ? (float)hi[o] + (float)lo[o] : (float)hi[o];       // one plane alone: the value itself (-0 + 0.f would read back as +0)
     }
 }
 
