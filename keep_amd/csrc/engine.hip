@@ -1,5 +1,6 @@
 // Host side of libkeep_hip: workspace arena, graph replay, tower orchestration, options and the encoder's part of the extern "C"
-// boundary declared in include/keep_hip.h.  The handle itself is handle.h; weight ingestion is weights.hip; the single-operator
+// boundary declared in include/keep_hip.h.  The handle itself is handle.h, the decision what a block of the image tower runs under the
+// precision plan block_plan.h (vit_layer here only issues what it resolves); weight ingestion is weights.hip; the single-operator
 // entry points and probes are op_api.hip; the slide-geometry entry points (patch grid, tissue mask, heatmap, sort / rank, regions,
 // outlines, polygon fill, evaluation) are slide_api.hip.
 //
@@ -229,57 +230,91 @@ int vit_begin(keep_handle* h, VitLane& L) {
     return KEEP_OK;
 }
 
-int vit_layer(keep_handle* h, VitLane& L, int i) {
+// mean-input compensation: a PLAIN launch of site k of block i uses the bias with W_lo a_mean folded in; while calibrating, every site's input is summed
+const float* site_bias(const keep_handle* h, int i, int site, const float* orig, bool plain) {
+    return (plain && h->bias_ready && h->bias_correction && i < (int)h->cal.size() && h->cal[i].bias[site]) ? (const float*)h->cal[i].bias[site] : orig;
+}
+void capture(keep_handle* h, int i, int site, const f16* a_hi, int rows, int K, hipStream_t s) {
+    if (!h->capture || i >= (int)h->cal.size() || !h->cal[i].sum[site]) return;
+    launch_blk_col_sum(a_hi, rows, K, h->cal[i].sum[site], s);
+    h->cal[i].rows[site] += rows;
+}
+
+// The rows a block's per-token operators (proj, LayerNorm-2, fc1, fc2) run on: every token row of the lane, or the compact CLS rows (one per tile)
+struct RowSet { int M; float* resid; const f16 *att_hi, *att_lo; f16 *xn_hi, *xn_lo, *mlp_hi, *mlp_lo; };
+RowSet all_rows(const VitLane& L) { const VitWs& w = L.ws; return {L.Bc * L.ntok, w.resid, w.att_hi, w.att_lo, w.xn_hi, w.xn_lo, w.mlp_hi, w.mlp_lo}; }
+RowSet cls_rows(const VitLane& L) { const VitWs& w = L.ws; return {L.Bc, w.c_resid, w.c_att_hi, w.c_att_lo, w.c_xn_hi, w.c_xn_lo, w.c_mlp_hi, w.c_mlp_lo}; }
+// every site of the CLS-row chain: a split product with the checkpoint's own bias; its LayerNorm-2 writes hi + lo
+constexpr SiteStep kClsSite{true, 0, false, T_VIT_TAIL};
+constexpr LnStep kClsLn{true, false, false};
+
+// the CLS rows of the token stream's residual -> compact rows, and back
+void gather_cls_resid(keep_handle* h, VitLane& L) {
+    Scope sc(h, T_VIT_TAIL, L.s);
+    launch_gather_rows_f32(L.ws.resid, (int64_t)L.ntok * h->vit_D, L.ws.c_resid, L.Bc, h->vit_D, L.s);
+}
+void scatter_cls_resid(keep_handle* h, VitLane& L) {
+    Scope sc(h, T_VIT_TAIL, L.s);
+    launch_scatter_rows_f32(L.ws.c_resid, L.ws.resid, (int64_t)L.ntok * h->vit_D, L.Bc, h->vit_D, L.s);
+}
+
+// a LayerNorm of a block over `rows` rows of x: the hi plane of its output always, the other planes as `w` says
+LnParams block_ln(const keep_handle* h, const VitWs& ws, const float* x, int rows, f16* out_hi, f16* out_lo, const LnStep& w, const float* gamma, const float* beta) {
+    LnParams ln = ln_params(h, x, h->vit_D, rows, h->vit_D, 1e-6f);
+    ln.out_hi = out_hi; ln.out_lo = w.lo ? out_lo : nullptr; ln.out_kt = h->vit_D / 32;
+    ln.out_q = w.fp4 ? ws.xn_q : nullptr; ln.out_sc = w.fp4 ? ws.xn_sc : nullptr; ln.out_q_hi_only = w.fp4_hi_only;
+    ln.gamma = gamma; ln.beta = beta;
+    return ln;
+}
+// proj / fc1 / fc2 of block i on the rows `r`, run as `st` says
+GemmParams proj_gemm(const keep_handle* h, int i, const RowSet& r, const SiteStep& st) {
+    const VitBlock& b = h->vblocks[i];
+    GemmParams p = gemm_params(h, r.att_hi, r.att_lo, b.proj, r.M, st.split, site_bias(h, i, 1, b.proj_b, st.corrected_bias));
+    p.ls = b.ls1; p.resid = r.resid;
+    return p;
+}
+GemmParams fc1_gemm(const keep_handle* h, int i, const VitWs& ws, const RowSet& r, const SiteStep& st) {
+    const VitBlock& b = h->vblocks[i];
+    GemmParams p = gemm_params(h, r.xn_hi, r.xn_lo, b.fc1, r.M, st.split, site_bias(h, i, 2, b.fc1_b, st.corrected_bias));
+    p.out_hi = r.mlp_hi; p.out_lo = st.split ? r.mlp_lo : nullptr; p.out_kt = h->vit_F / 32;
+    if (st.comp) {
+        p.comp = st.comp; p.a_q = ws.xn_q; p.a_sc = ws.xn_sc; p.w_q = b.fc1->q; p.w_sc = b.fc1->sc;
+        p.out_q = ws.mlp_q; p.out_sc = ws.mlp_sc;
+    }
+    return p;
+}
+GemmParams fc2_gemm(const keep_handle* h, int i, const VitWs& ws, const RowSet& r, const SiteStep& st) {
+    const VitBlock& b = h->vblocks[i];
+    GemmParams p = gemm_params(h, r.mlp_hi, r.mlp_lo, b.fc2, r.M, st.split, site_bias(h, i, 3, b.fc2_b, st.corrected_bias));
+    p.ls = b.ls2; p.resid = r.resid;
+    if (st.comp) { p.comp = st.comp; p.a_q = ws.mlp_q; p.a_sc = ws.mlp_sc; p.w_q = b.fc2->q; p.w_sc = b.fc2->sc; }
+    return p;
+}
+
+// LayerNorm-1 (unless the previous block's fc2 wrote it), qkv, attention, and what taps the attention: the CLS attention map and the rollout step
+int vit_attn_side(keep_handle* h, VitLane& L, int i, const BlockSteps& st) {
     const int D = h->vit_D, Bc = L.Bc, ntok = L.ntok, M = Bc * ntok;
     hipStream_t s = L.s; VitWs& ws = L.ws;
     const VitBlock& b = h->vblocks[i];
-    // mean-input compensation: a PLAIN launch of site k uses the bias with W_lo a_mean folded in; while calibrating, every site's input is summed
-    auto site_bias = [&](int site, const float* orig, bool plain) {
-        return (plain && h->bias_ready && h->bias_correction && i < (int)h->cal.size() && h->cal[i].bias[site]) ? (const float*)h->cal[i].bias[site] : orig;
-    };
-    auto capture = [&](int site, const f16* a_hi, int rows, int K) {
-        if (!h->capture || i >= (int)h->cal.size() || !h->cal[i].sum[site]) return;
-        launch_blk_col_sum(a_hi, rows, K, h->cal[i].sum[site], s);
-        h->cal[i].rows[site] += rows;
-    };
-    // Last block: everything after the attention is per-token and only the CLS token is pooled
-    // (global_pool='token'), so its queries / proj / MLP are evaluated for the B CLS rows only.
-    // Exact (same arithmetic on the rows that matter); the skipped FLOPs still count as algorithmic work.
-    const bool cls_only = (i == h->vit_depth - 1) && h->cls_tail;
-    const bool sp = h->vit_attn_split(i, Bc);                          // qkv / attention / proj as split products
-    const int mlp = h->vit_mlp_mode(i, cls_only ? 0 : Bc);             // fc1 / fc2: 0 plain, 1 split, 2 compensated (both MX-fp4 terms), 3 compensated (W_lo term only)
-    const bool mlp_lo = mlp == KEEP_MLP_SPLIT, mlp_q = mlp == KEEP_MLP_COMP || mlp == KEEP_MLP_COMP_W;
-    const int mlp_comp = mlp == KEEP_MLP_COMP_W ? 1 : 2;               // GemmParams.comp of the block's fc1 / fc2
-    const bool mlp_cls = mlp == KEEP_MLP_CLS;                          // every row plain, then the CLS rows again as split products (below)
-    const bool mlp_plain = mlp == KEEP_MLP_PLAIN || mlp_cls;
-    // KEEP_ATTN_PROJ_CLS: every row plain; the attention kernel also writes the CLS rows' output hi + lo (compact), and their proj runs again as a split product
-    const bool proj_cls = !sp && !cls_only && (h->plan_attn(i) == KEEP_ATTN_PROJ_CLS || h->plan_attn(i) == KEEP_ATTN_COMPQKV_PROJ_CLS) && i >= h->strict_blocks;
-    // qkv of a split-attention block in the compensated mode: fp16 pass + MX-fp4 correction terms instead of three fp16 passes (lanes
-    // large enough for the 256x256 kernel; LayerNorm-1 then writes the fp4 planes of its output instead of the lo plane)
-    const bool qkv_q = h->vit_qkv_comp(i, Bc) && b.qkv->q && ws.xn_q && !L.xn_ready;
-    LnParams ln = ln_params(h, ws.resid, D, M, D, 1e-6f);
-    ln.out_hi = ws.xn_hi; ln.out_lo = (sp && !qkv_q) ? ws.xn_lo : nullptr; ln.out_kt = D / 32;
-    ln.out_q = qkv_q ? ws.xn_q : nullptr; ln.out_sc = qkv_q ? ws.xn_sc : nullptr;
+    const bool sp = st.attn_split;
     if (!L.xn_ready) {
         Scope sc(h, T_VIT_LN, s);
-        ln.gamma = b.n1w; ln.beta = b.n1b;
-        if (launch_layernorm(ln, s)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %d", D);
+        if (launch_layernorm(block_ln(h, ws, ws.resid, M, ws.xn_hi, ws.xn_lo, st.ln1, b.n1w, b.n1b), s)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %d", D);
     }
     L.xn_ready = false;
     {
-        const int tag = (sp || qkv_q) ? T_VIT_QKV_X : T_VIT_QKV;
-        Scope sc(h, tag, s);
-        capture(0, ws.xn_hi, M, D);
-        GemmParams p = gemm_params(h, ws.xn_hi, ws.xn_lo, b.qkv, M, sp && !qkv_q, site_bias(0, b.qkv_b, !sp && !qkv_q));
+        Scope sc(h, st.qkv.tag, s);
+        capture(h, i, 0, ws.xn_hi, M, D, s);
+        GemmParams p = gemm_params(h, ws.xn_hi, ws.xn_lo, b.qkv, M, st.qkv.split, site_bias(h, i, 0, b.qkv_b, st.qkv.corrected_bias));
         p.out_hi = ws.qkv_hi; p.out_lo = sp ? ws.qkv_lo : nullptr;
-        if (qkv_q) { p.comp = 2; p.a_q = ws.xn_q; p.a_sc = ws.xn_sc; p.w_q = b.qkv->q; p.w_sc = b.qkv->sc; }
-        if (run_gemm(h, tag, p, EPI_F16, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "qkv GEMM launch failed");
+        if (st.qkv.comp) { p.comp = st.qkv.comp; p.a_q = ws.xn_q; p.a_sc = ws.xn_sc; p.w_q = b.qkv->q; p.w_sc = b.qkv->sc; }
+        if (run_gemm(h, st.qkv.tag, p, EPI_F16, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "qkv GEMM launch failed");
     }
     {
-        Scope sc(h, sp ? T_VIT_ATTN_X : T_VIT_ATTN, s);
+        Scope sc(h, st.attn_tag, s);
         AttnParams a = attn_params(h, ws.qkv_hi, ws.qkv_lo, ws.att_hi, sp ? ws.att_lo : nullptr, Bc, ntok, h->vit_heads, sp, D / 32);
-        a.q_rows = cls_only ? 1 : 0;
-        if (proj_cls) { a.cls_hi = ws.c_att_hi; a.cls_lo = ws.c_att_lo; }
+        a.q_rows = st.cls_only ? 1 : 0;
+        if (st.cls_proj) { a.cls_hi = ws.c_att_hi; a.cls_lo = ws.c_att_lo; }
         a.part_ws = ws.part; a.part_bytes = ws.part_bytes;
         // beyond 512 tokens (grids past 22 x 22 patches) the key-blocked kernel; up to 512 the whole-sequence kernels of the 224 path
         if ((ntok > 512 ? launch_attention_long(a, s) : launch_attention(a, s))) return h->fail(KEEP_EUNSUPPORTED, "attention launch failed (%d tokens)", ntok);
@@ -294,112 +329,102 @@ int vit_layer(keep_handle* h, VitLane& L, int i) {
             return h->fail(KEEP_EUNSUPPORTED, "attention rollout launch failed (%d tokens, at most %d)", ntok, ROLLOUT_MAX_TOKENS);
         if (!first && !last) L.roll_cur ^= 1;
     }
-    const int Mr = cls_only ? Bc : M;
-    float* resid = cls_only ? ws.c_resid : ws.resid;
-    const f16 *att_hi = ws.att_hi, *att_lo = ws.att_lo;
-    f16 *xn_hi = ws.xn_hi, *xn_lo = ws.xn_lo, *mlp_hi = ws.mlp_hi, *mlp_lo_p = ws.mlp_lo;
-    if (cls_only) {
+    return KEEP_OK;
+}
+
+// proj + LayerScale + residual on the rows `r`, offered their LayerNorm-2 (`ln`); in front of it the gathers into the compact rows.
+// -> the GEMM_DID_* flags of the launch, or < 0
+int vit_proj(keep_handle* h, VitLane& L, int i, const BlockSteps& st, const RowSet& r, const LnParams& ln) {
+    hipStream_t s = L.s; VitWs& ws = L.ws;
+    if (st.cls_only) {
         Scope sc(h, T_VIT_HEAD, s);
-        launch_gather_rows_f32(ws.resid, (int64_t)ntok * D, ws.c_resid, Bc, D, s);
-        launch_gather_rows_blk(ws.att_hi, ntok, ws.c_att_hi, Bc, D, s);
-        if (sp) launch_gather_rows_blk(ws.att_lo, ntok, ws.c_att_lo, Bc, D, s);
-        att_hi = ws.c_att_hi; att_lo = ws.c_att_lo; xn_hi = ws.c_xn_hi; xn_lo = ws.c_xn_lo; mlp_hi = ws.c_mlp_hi; mlp_lo_p = ws.c_mlp_lo;
+        launch_gather_rows_f32(ws.resid, (int64_t)L.ntok * h->vit_D, ws.c_resid, L.Bc, h->vit_D, s);
+        launch_gather_rows_blk(ws.att_hi, L.ntok, ws.c_att_hi, L.Bc, h->vit_D, s);
+        if (st.attn_split) launch_gather_rows_blk(ws.att_lo, L.ntok, ws.c_att_lo, L.Bc, h->vit_D, s);
         L.cls_compact = true;
     }
-    ln.x = resid; ln.rows = Mr; ln.out_hi = xn_hi; ln.out_lo = mlp_lo ? xn_lo : nullptr;
-    ln.out_q = mlp_q ? ws.xn_q : nullptr; ln.out_sc = mlp_q ? ws.xn_sc : nullptr; ln.out_q_hi_only = mlp == KEEP_MLP_COMP_W;
-    ln.gamma = b.n2w; ln.beta = b.n2b;
-    if (proj_cls && !L.c_resid_live) {      // the CLS rows' residual as it enters proj (the plain proj below updates these rows too; the split result replaces that)
-        Scope sc(h, T_VIT_TAIL, s);
-        launch_gather_rows_f32(ws.resid, (int64_t)ntok * D, ws.c_resid, Bc, D, s);
-    }
-    int did = 0;
-    {
-        const int tag = cls_only ? T_VIT_TAIL : sp ? T_VIT_PROJ_X : T_VIT_PROJ;
-        Scope sc(h, tag, s);
-        capture(1, att_hi, Mr, D);
-        GemmParams p = gemm_params(h, att_hi, att_lo, b.proj, Mr, sp, site_bias(1, b.proj_b, !sp));
-        p.ls = b.ls1; p.resid = resid; p.impl_hint = h->proj_impl;
-        if (!mlp_q) offer_ln(p, ln);                 // the fused LayerNorm of the small-M path does not write fp4 planes
-        did = run_gemm(h, tag, p, EPI_RESID_LS, s, ws.splitk);
-        if (did < 0) return h->fail(KEEP_EUNSUPPORTED, "proj GEMM launch failed");
-    }
-    // The CLS-row chain of this block (KEEP_ATTN_PROJ_CLS and / or KEEP_MLP_CLS) on the compact [Bc, D] rows, in the lane's own stream: issued here, between the
-    // plain proj and LayerNorm-2, and scattered behind the plain fc2 (whose rows it replaces).  The small kernels then sit between the lane's two light kernels
-    // instead of between two persistent GEMMs: +1.5 % against the whole chain behind fc2.  On a side stream of its own the chain cost 11 %: a cross-queue
-    // dependency is a barrier packet the next persistent GEMM sits behind (both measured in round 6: tools/experiments/README.md).
-    if (mlp_cls && !proj_cls) { // the CLS rows' residual as it enters the MLP, i.e. BEHIND this block's proj (a live compact copy is the residual in front of it): always gathered
-        Scope sc(h, T_VIT_TAIL, s);
-        launch_gather_rows_f32(ws.resid, (int64_t)ntok * D, ws.c_resid, Bc, D, s);
-    }
+    if (st.gather_before_proj) gather_cls_resid(h, L);
+    Scope sc(h, st.proj.tag, s);
+    capture(h, i, 1, r.att_hi, r.M, h->vit_D, s);
+    GemmParams p = proj_gemm(h, i, r, st.proj);
+    p.impl_hint = h->proj_impl;
+    if (st.ln2_to_proj) offer_ln(p, ln);
+    const int did = run_gemm(h, st.proj.tag, p, EPI_RESID_LS, s, ws.splitk);
+    return did < 0 ? h->fail(KEEP_EUNSUPPORTED, "proj GEMM launch failed") : did;
+}
+
+// The CLS-row chain of this block (KEEP_ATTN_PROJ_CLS and / or KEEP_MLP_CLS) on the compact [Bc, D] rows, in the lane's own stream: issued between the
+// plain proj and LayerNorm-2, and scattered behind the plain fc2 (whose rows it replaces).  The small kernels then sit between the lane's two light kernels
+// instead of between two persistent GEMMs: +1.5 % against the whole chain behind fc2.  On a side stream of its own the chain cost 11 %: a cross-queue
+// dependency is a barrier packet the next persistent GEMM sits behind (both measured in round 6: tools/experiments/README.md).
+int vit_cls_chain(keep_handle* h, VitLane& L, int i, const BlockSteps& st) {
+    hipStream_t s = L.s; VitWs& ws = L.ws;
+    const VitBlock& b = h->vblocks[i];
+    const RowSet c = cls_rows(L);
+    if (st.gather_before_mlp) gather_cls_resid(h, L);
     bool cls_ln_done = false;   // LayerNorm-2 of the compact CLS rows already written (hi + lo) by the CLS-row proj's epilogue
-    LnParams cl = ln_params(h, ws.c_resid, D, Bc, D, 1e-6f);      // LayerNorm-2 of the compact CLS rows (KEEP_MLP_CLS)
-    cl.gamma = b.n2w; cl.beta = b.n2b; cl.out_hi = ws.c_xn_hi; cl.out_lo = ws.c_xn_lo; cl.out_kt = D / 32;
-    if (proj_cls) {
+    const LnParams cl = block_ln(h, ws, c.resid, c.M, c.xn_hi, c.xn_lo, kClsLn, b.n2w, b.n2b);      // LayerNorm-2 of the compact CLS rows (KEEP_MLP_CLS)
+    if (st.cls_proj) {
         // [Bc, D] x W_proj^T as a split product on the small-M kernels: the CLS rows' attention output from the fp32 accumulators (hi + lo) against W hi + lo,
         // + LayerScale + the residual.  With KEEP_MLP_CLS in the same block the chain continues on the compact rows (its LayerNorm-2 is fused into this GEMM's reduce)
         Scope sc(h, T_VIT_TAIL, s);
-        GemmParams r = gemm_params(h, ws.c_att_hi, ws.c_att_lo, b.proj, Bc, true, b.proj_b);
-        r.ls = b.ls1; r.resid = ws.c_resid;
-        if (mlp_cls) offer_ln(r, cl);
+        GemmParams r = proj_gemm(h, i, c, kClsSite);
+        if (st.cls_proj_fuses_ln2) offer_ln(r, cl);
         const int rc = run_gemm(h, T_VIT_TAIL, r, EPI_RESID_LS, s, ws.splitk);
         if (rc < 0) return h->fail(KEEP_EUNSUPPORTED, "CLS-row proj GEMM launch failed");
-        cls_ln_done = mlp_cls && (rc & GEMM_DID_LN);
+        cls_ln_done = st.cls_proj_fuses_ln2 && (rc & GEMM_DID_LN);
     }
-    if (mlp_cls) {
+    if (st.cls_mlp) {
         // LayerNorm-2 -> fc1 + GELU -> fc2 + LayerScale + residual as split products on the compact rows.  0.5 % of the rows; the feature is pooled from them.
         Scope sc(h, T_VIT_TAIL, s);
-        if (!cls_ln_done && launch_layernorm(cl, s)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %d", D);
-        GemmParams p = gemm_params(h, ws.c_xn_hi, ws.c_xn_lo, b.fc1, Bc, true, b.fc1_b);
-        p.out_hi = ws.c_mlp_hi; p.out_lo = ws.c_mlp_lo; p.out_kt = h->vit_F / 32;
-        if (run_gemm(h, T_VIT_TAIL, p, EPI_GELU_F16, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "CLS-row fc1 GEMM launch failed");
-        GemmParams r = gemm_params(h, ws.c_mlp_hi, ws.c_mlp_lo, b.fc2, Bc, true, b.fc2_b);
-        r.ls = b.ls2; r.resid = ws.c_resid;
-        if (run_gemm(h, T_VIT_TAIL, r, EPI_RESID_LS, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "CLS-row fc2 GEMM launch failed");
-    } else if (proj_cls) {      // no CLS-row MLP behind it: the rows go back before LayerNorm-2 reads them
-        Scope sc(h, T_VIT_TAIL, s);
-        launch_scatter_rows_f32(ws.c_resid, ws.resid, (int64_t)ntok * D, Bc, D, s);
+        if (!cls_ln_done && launch_layernorm(cl, s)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %d", h->vit_D);
+        if (run_gemm(h, T_VIT_TAIL, fc1_gemm(h, i, ws, c, kClsSite), EPI_GELU_F16, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "CLS-row fc1 GEMM launch failed");
+        if (run_gemm(h, T_VIT_TAIL, fc2_gemm(h, i, ws, c, kClsSite), EPI_RESID_LS, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "CLS-row fc2 GEMM launch failed");
     }
-    if (!(did & GEMM_DID_LN)) {
-        Scope sc(h, T_VIT_LN, s);
-        if (launch_layernorm(ln, s)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %d", D);
+    if (st.scatter_after_proj) scatter_cls_resid(h, L);
+    return KEEP_OK;
+}
+
+// fc1 + GELU and fc2 + LayerScale + residual on the rows `r`; fc2 is offered the next block's LayerNorm-1, and the CLS-row chain's rows go back behind it
+int vit_mlp(keep_handle* h, VitLane& L, int i, const BlockSteps& st, const RowSet& r) {
+    hipStream_t s = L.s; VitWs& ws = L.ws;
+    {
+        Scope sc(h, st.fc1.tag, s);
+        capture(h, i, 2, r.xn_hi, r.M, h->vit_D, s);
+        if (run_gemm(h, st.fc1.tag, fc1_gemm(h, i, ws, r, st.fc1), EPI_GELU_F16, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "fc1 GEMM launch failed");
     }
     {
-        const int tag = cls_only ? T_VIT_TAIL : !mlp_plain ? T_VIT_FC1_X : T_VIT_FC1;
-        Scope sc(h, tag, s);
-        capture(2, xn_hi, Mr, D);
-        GemmParams p = gemm_params(h, xn_hi, xn_lo, b.fc1, Mr, mlp_lo, site_bias(2, b.fc1_b, mlp_plain));
-        p.out_hi = mlp_hi; p.out_lo = mlp_lo ? mlp_lo_p : nullptr; p.out_kt = h->vit_F / 32;
-        if (mlp_q) {
-            p.comp = mlp_comp; p.a_q = ws.xn_q; p.a_sc = ws.xn_sc; p.w_q = b.fc1->q; p.w_sc = b.fc1->sc;
-            p.out_q = ws.mlp_q; p.out_sc = ws.mlp_sc;
-        }
-        if (run_gemm(h, tag, p, EPI_GELU_F16, s, ws.splitk) < 0) return h->fail(KEEP_EUNSUPPORTED, "fc1 GEMM launch failed");
-    }
-    {
-        const int tag = cls_only ? T_VIT_TAIL : !mlp_plain ? T_VIT_FC2_X : T_VIT_FC2;
-        Scope sc(h, tag, s);
-        capture(3, mlp_hi, Mr, h->vit_F);
-        GemmParams p = gemm_params(h, mlp_hi, mlp_lo_p, b.fc2, Mr, mlp_lo, site_bias(3, b.fc2_b, mlp_plain));
-        p.ls = b.ls2; p.resid = resid;
-        if (mlp_q) { p.comp = mlp_comp; p.a_q = ws.mlp_q; p.a_sc = ws.mlp_sc; p.w_q = b.fc2->q; p.w_sc = b.fc2->sc; }
-        if (i + 1 < h->vit_depth && !cls_only && !mlp_cls) {        // next block's LayerNorm-1 reads exactly the rows written here (not when CLS rows are still to be replaced)
+        Scope sc(h, st.fc2.tag, s);
+        capture(h, i, 3, r.mlp_hi, r.M, h->vit_F, s);
+        GemmParams p = fc2_gemm(h, i, ws, r, st.fc2);
+        if (st.next_ln1_to_fc2) {
             const VitBlock& nb = h->vblocks[i + 1];
-            ln.x = ws.resid; ln.rows = M; ln.out_hi = ws.xn_hi; ln.out_lo = h->vit_attn_split(i + 1, Bc) ? ws.xn_lo : nullptr;
-            ln.out_q = nullptr; ln.out_sc = nullptr; ln.out_q_hi_only = 0;
-            ln.gamma = nb.n1w; ln.beta = nb.n1b;
-            offer_ln(p, ln);
+            offer_ln(p, block_ln(h, ws, ws.resid, L.Bc * L.ntok, ws.xn_hi, ws.xn_lo, LnStep{st.next_ln1_lo, false, false}, nb.n1w, nb.n1b));
         }
-        const int rc = run_gemm(h, tag, p, EPI_RESID_LS, s, ws.splitk);
+        const int rc = run_gemm(h, st.fc2.tag, p, EPI_RESID_LS, s, ws.splitk);
         if (rc < 0) return h->fail(KEEP_EUNSUPPORTED, "fc2 GEMM launch failed");
         L.xn_ready = (rc & GEMM_DID_LN) != 0;
     }
-    if (mlp_cls) {              // the chain's rows replace what the plain fc2 wrote
-        Scope sc(h, T_VIT_TAIL, s);
-        launch_scatter_rows_f32(ws.c_resid, ws.resid, (int64_t)ntok * D, Bc, D, s);
-    }
-    L.c_resid_live = mlp_cls;   // (any other block's proj / fc2 moved the CLS rows of the token stream on without the compact copy)
+    if (st.scatter_after_fc2) scatter_cls_resid(h, L);
+    L.c_resid_live = st.c_resid_live_after;
     return KEEP_OK;
+}
+
+// One block of one lane: what it does is resolved once (block_plan.h); the rest issues launches
+int vit_layer(keep_handle* h, VitLane& L, int i) {
+    const VitBlock& b = h->vblocks[i];
+    const BlockSteps st = resolve_block(*h, i, L.Bc, L.xn_ready, b.qkv->q && L.ws.xn_q, L.c_resid_live);
+    if (int rc = vit_attn_side(h, L, i, st)) return rc;
+    const RowSet r = st.cls_only ? cls_rows(L) : all_rows(L);
+    const LnParams ln2 = block_ln(h, L.ws, r.resid, r.M, r.xn_hi, r.xn_lo, st.ln2, b.n2w, b.n2b);
+    const int did = vit_proj(h, L, i, st, r, ln2);
+    if (did < 0) return did;
+    if (int rc = vit_cls_chain(h, L, i, st)) return rc;
+    if (!(did & GEMM_DID_LN)) {
+        Scope sc(h, T_VIT_LN, L.s);
+        if (launch_layernorm(ln2, L.s)) return h->fail(KEEP_EUNSUPPORTED, "layernorm width %d", h->vit_D);
+    }
+    return vit_mlp(h, L, i, st, r);
 }
 
 int vit_end(keep_handle* h, VitLane& L) {

@@ -1,9 +1,10 @@
 // The engine handle: what keep_create returns and every extern "C" entry point receives.  engine.hip owns it (arena, towers,
 // graphs, options, profile); weights.hip fills its weight store and block tables; op_api.hip borrows its device and kernel
-// selection; slide_api.hip uses its device, error text, arena and error flag.
+// selection; slide_api.hip uses its device, error text, arena and error flag.  The image tower's precision plan, what it means for a
+// block (resolve_block) and the profile tags are block_plan.h, which has no HIP in it.
 #pragma once
 #include "common.h"
-#include "../../include/keep_hip.h"
+#include "block_plan.h"
 
 #include <cstdarg>
 #include <cstdio>
@@ -41,15 +42,6 @@ struct WTensor {
     float prescale = 1.f;     // the planes hold prescale * W (a power of two; proj / fc2 of the image tower only): folded back through LayerScale and bias at finalize
 };
 
-enum Tag {
-    T_VIT_IM2COL, T_VIT_PATCH, T_VIT_LN, T_VIT_QKV, T_VIT_ATTN, T_VIT_PROJ, T_VIT_FC1, T_VIT_FC2, T_VIT_HEAD,
-    T_TXT_EMBED, T_TXT_LN, T_TXT_QKV, T_TXT_ATTN, T_TXT_OUT, T_TXT_FFN1, T_TXT_FFN2, T_TXT_POOL, T_SIM,
-    // image-tower launches that are NOT the plain single-pass kernel of their operator: split products / compensated (MX-fp4) products of the
-    // blocks the precision setting names ("x" = extra passes), and the CLS-rows-only operators of the last block ("tail": small-M kernels).
-    // The plain tags above then time one kernel instantiation each (bench.py's roofline block needs a per-kernel figure).
-    T_VIT_QKV_X, T_VIT_ATTN_X, T_VIT_PROJ_X, T_VIT_FC1_X, T_VIT_FC2_X, T_VIT_TAIL, T_COUNT
-};
-
 struct VitBlock {
     const float *n1w, *n1b, *n2w, *n2b, *qkv_b, *proj_b, *fc1_b, *fc2_b, *ls1, *ls2;
     const WTensor *qkv, *proj, *fc1, *fc2;
@@ -61,7 +53,7 @@ struct BertLayer {
     const WTensor *o, *i, *d;
 };
 
-struct keep_handle {
+struct keep_handle : PrecisionPlan {      // (the precision plan of the image tower and its queries: block_plan.h)
     int device = 0;
     std::string err;
     std::string load_warnings;   // '\n'-separated notes of keep_load_tensor calls (a weight the fp16 planes resolve poorly); read and cleared by keep_load_warnings
@@ -69,7 +61,7 @@ struct keep_handle {
     bool finalized = false;
 
     // dims (filled at finalize)
-    int vit_depth = 0, vit_D = 0, vit_heads = 0, vit_F = 0, proj_dim = 0;
+    int vit_D = 0, vit_heads = 0, vit_F = 0, proj_dim = 0;
     int bert_layers = 0, bert_H = 0, bert_heads = 0, bert_F = 0, bert_vocab = 0, bert_maxpos = 0, bert_types = 0;
     std::vector<VitBlock> vblocks;
     std::vector<BertLayer> blayers;
@@ -77,54 +69,13 @@ struct keep_handle {
 
     // options
     KeepTune tune;               // kernel selection (travels in the launch parameter blocks; nothing is process-wide)
-    int precision = KEEP_PREC_COMP;
-    int strict_blocks = 0;       // first n blocks / layers as full hi/lo split products (any mode)
-    // The prefix shorthands (state of the last keep_set_option; they only take effect once one of them is set -- see plan_default below)
-    int comp_full_blocks = 1;    // KEEP_PREC_COMP: first n ViT blocks run qkv / attention / proj as split products as well
-    int comp_mlp_blocks = 8;     // KEEP_PREC_COMP: first n ViT blocks run fc1 / fc2 as compensated (fp16 + MX-fp4) products
     int fused_screening = 1;     // keep_prompt_scores: 1 fused compensated GEMM (default) | 2 fused 3-pass split GEMM | 0 logits through HBM (any C)
-    int comp_min_tiles = 32;     // lanes with fewer tiles take the split product where a compensated one is asked for (small-M kernels)
-    int comp_qkv = 0;            // 1: KEEP_PREC_COMP, blocks < comp_full_blocks: the qkv GEMM as a compensated product (x1.5) instead of a split one (x3);
-                                 // q / k / v still stored as hi + lo planes, attention still a split product.  Measured (round 3): +0.9 % at equal settings,
-                                 // but block 0's qkv is where the error budget is tightest (the 3 % of the rounding variance the fp4 terms leave is
-                                 // amplified by all 24 blocks): calibrate() then needs 10 compensated MLP blocks instead of 6 -- a net loss.  Off.
-    int comp_qkv_from = 1 << 20; // the same for the split-attention blocks with index >= this only (block 0 keeps its three-pass qkv)
-    // The per-block plan of KEEP_PREC_COMP (keep_set_block_precision; the four options above are prefix shorthands that rewrite it):
-    //   attn_mode[i]  attention side of block i: KEEP_ATTN_PLAIN | KEEP_ATTN_SPLIT (qkv, q/k/v storage, attention, proj as split products) |
-    //                 KEEP_ATTN_SPLIT_COMPQKV (the same with the qkv GEMM as a compensated product) | KEEP_ATTN_COMPQKV (compensated qkv only) |
-    //                 KEEP_ATTN_PROJ_CLS (plain for every row + the CLS rows' proj again as a split product on their fp32-grade attention output) |
-    //                 KEEP_ATTN_COMPQKV_PROJ_CLS (both of the last two)
-    //   mlp_mode[i]   fc1 / fc2 of block i: KEEP_MLP_PLAIN | KEEP_MLP_SPLIT | KEEP_MLP_COMP (both MX-fp4 correction terms) | KEEP_MLP_COMP_W (the W_lo term only) |
-    //                 KEEP_MLP_CLS (plain for every row + the CLS rows again as split products)
-    // Which block gets what is a measured, per-checkpoint decision (tools/precision_budget.py, KEEPModel.calibrate).
-    static constexpr int MAX_BLOCKS = 64;
-    unsigned char attn_mode[MAX_BLOCKS] = {}, mlp_mode[MAX_BLOCKS] = {};
-    bool plan_custom = false;    // keep_set_block_precision was called since the last prefix option
-    void plan_from_prefix() {
-        for (int i = 0; i < MAX_BLOCKS; ++i) {
-            attn_mode[i] = i < comp_full_blocks ? ((comp_qkv || i >= comp_qkv_from) ? KEEP_ATTN_SPLIT_COMPQKV : KEEP_ATTN_SPLIT) : KEEP_ATTN_PLAIN;
-            mlp_mode[i] = i < comp_mlp_blocks ? KEEP_MLP_COMP : KEEP_MLP_PLAIN;
-        }
-        plan_custom = false;
-    }
-    // The plan a handle starts with (no calibration has seen the weights yet): block 0's attention side as split products with a compensated qkv
-    // and its MLP compensated -- the first block's rounding errors, in EVERY row, are amplified by all the attention layers that follow: 45-48 % of the
-    // all-fp16 error variance on the synthetic checkpoints --, every other block plain with the CLS rows' MLP redone as split products (the pooled
-    // feature is a CLS row).  profiles/r05_precision_budget.md: cosine rms 8.5e-6 on the bench weights, a quarter of what the 1e-4 tolerance allows a
-    // 100 000-tile slide, 3 % slower than what KEEPModel.calibrate picks for them.
-    void plan_default() {
-        for (int i = 0; i < MAX_BLOCKS; ++i) { attn_mode[i] = KEEP_ATTN_PLAIN; mlp_mode[i] = KEEP_MLP_CLS; }
-        attn_mode[0] = KEEP_ATTN_SPLIT_COMPQKV; mlp_mode[0] = KEEP_MLP_COMP;
-        plan_custom = false;
-    }
-    keep_handle() { plan_default(); }
     // keep_classify: tiles whose top-2 cosine margin is below this are re-encoded in KEEP_PREC_STRICT before their label is taken.
     // Default = 2 x the north-star tolerance (both cosines of a pair can move by 1e-4 in opposite directions) + 25 %.
     float label_margin = 2.5e-4f;
     char* cls_buf = nullptr; size_t cls_bytes = 0;     // keep_classify scratch (features, similarity, flags, staged tiles): outside the arena, which the encodes carve
     int max_tiles = 256;
     int max_prompts = 64;
-    int cls_tail = 1;            // last ViT block: proj / MLP on the CLS rows only (exact; 0 = evaluate every token)
     // Mean-input compensation of the weight-rounding error (keep_calibrate_bias).  A plain fp16 GEMM computes A_hi W_hi^T: the W_lo A_hi term it drops has
     // a part that is the SAME for every row -- W_lo a_mean, a_mean = the mean input row of that GEMM (GELU outputs are positive, LayerNorm outputs carry their
     // bias, attention outputs are averages) -- which no amount of averaging over tiles removes.  It is a constant vector per GEMM: folded into the bias the plain
@@ -196,44 +147,6 @@ struct keep_handle {
         err = buf;
         return code;
     }
-    // Where the 11 bits of an fp16 operand are not enough (tools/precision_study.py: block 0 alone is 41 % of the cosine error
-    // variance, blocks 0-1 52 %, and outside them the MLP GEMMs carry > 80 %):
-    //   attention side (qkv, q/k/v storage, softmax probabilities, proj) of block i: split product or plain
-    //   MLP (fc1, fc2) of block i: 0 plain | 1 split (three fp16 passes) | 2 compensated (fp16 pass + two MX-fp4 correction terms)
-    int plan_attn(int i) const { return (precision == KEEP_PREC_COMP && i >= 0 && i < MAX_BLOCKS) ? attn_mode[i] : KEEP_ATTN_PLAIN; }
-    // lanes too small for the 256x256 kernel take split products wherever a compensated one is asked for (they run on the small-M / K-sliced kernels)
-    bool vit_attn_split(int i, int lane_tiles = 1 << 20) const {
-        if (precision == KEEP_PREC_STRICT || i < strict_blocks) return true;
-        const int a = plan_attn(i);
-        return a == KEEP_ATTN_SPLIT || a == KEEP_ATTN_SPLIT_COMPQKV || ((a == KEEP_ATTN_COMPQKV || a == KEEP_ATTN_COMPQKV_PROJ_CLS) && !(lane_tiles >= comp_min_tiles && vit_has_q));
-    }
-    bool vit_qkv_comp(int i, int lane_tiles) const {
-        if (precision != KEEP_PREC_COMP || i < strict_blocks || !(lane_tiles >= comp_min_tiles && vit_has_q)) return false;
-        const int a = plan_attn(i);
-        return a == KEEP_ATTN_SPLIT_COMPQKV || a == KEEP_ATTN_COMPQKV || a == KEEP_ATTN_COMPQKV_PROJ_CLS;
-    }
-    // fc1 / fc2 of block i: 0 plain | 1 split (three fp16 passes) | 2 compensated (both MX-fp4 terms) | 3 compensated, W_lo term only | 4 plain + CLS rows split
-    // (lane_tiles == 0: the last block's CLS-rows-only tail, which is the "CLS rows as split products" half on its own)
-    int vit_mlp_mode(int i, int lane_tiles) const {
-        if (precision == KEEP_PREC_STRICT || i < strict_blocks) return KEEP_MLP_SPLIT;
-        if (precision != KEEP_PREC_COMP || i < 0 || i >= MAX_BLOCKS) return KEEP_MLP_PLAIN;
-        const int m = mlp_mode[i];
-        if (m == KEEP_MLP_COMP || m == KEEP_MLP_COMP_W) return (lane_tiles >= comp_min_tiles && vit_has_q) ? m : KEEP_MLP_SPLIT;
-        if (m == KEEP_MLP_CLS) return lane_tiles == 0 ? KEEP_MLP_SPLIT : KEEP_MLP_CLS;
-        return m;
-    }
-    // the text tower is 1 % of a slide's work: in the compensated mode it simply runs split products throughout, at every length BertModel accepts
-    // (T <= 512 = max_position_embeddings; above 256 keys the split attention runs as two key windows of <= 256, merged like an online softmax)
-    bool txt_split(int l, int T) const { (void)T; return precision == KEEP_PREC_STRICT || l < strict_blocks || precision == KEEP_PREC_COMP; }
-    bool any_split() const { return precision != KEEP_PREC_FP16 || strict_blocks > 0; }
-    bool vit_has_q = false;      // every fc1 / fc2 weight has its fp4 side planes (dims % 128 == 0)
-    bool any_comp() const {
-        if (precision != KEEP_PREC_COMP || !vit_has_q) return false;
-        for (int i = 0; i < MAX_BLOCKS && i < (vit_depth ? vit_depth : MAX_BLOCKS); ++i)
-            if (mlp_mode[i] == KEEP_MLP_COMP || mlp_mode[i] == KEEP_MLP_COMP_W || attn_mode[i] == KEEP_ATTN_SPLIT_COMPQKV || attn_mode[i] == KEEP_ATTN_COMPQKV || attn_mode[i] == KEEP_ATTN_COMPQKV_PROJ_CLS) return true;
-        return false;
-    }
-
     bool prof_on(int tag) const { return prof_mode == 2 || (prof_mode == 1 && ((prof_mask >> tag) & 1ull)); }
     void prof_add_flops(int tag, double f) { if (prof_on(tag)) prof_flops[tag] += f; }
     void prof_begin(int tag, hipStream_t s) {

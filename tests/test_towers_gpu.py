@@ -896,6 +896,84 @@ def test_per_block_plan_is_what_the_prefix_options_stand_for():
         m.set_plan([(0, 7)])
 
 
+VIT_TAGS = ["vit.im2col", "vit.patch", "vit.ln", "vit.qkv", "vit.attn", "vit.proj", "vit.fc1", "vit.fc2", "vit.head",
+            "vit.qkv.x", "vit.attn.x", "vit.proj.x", "vit.fc1.x", "vit.fc2.x", "vit.tail"]
+
+
+def _counts(ln, qkv, attn, proj, fc, qkv_x, attn_x, proj_x, fc_x, tail, lanes):
+    """Launch brackets per tag of one call at depth 3: every lane runs one im2col, one patch embed and two vit.head brackets (the last block's gather
+    onto the compact CLS rows, and the final LayerNorm + head); fc1 and fc2 always share a treatment."""
+    one = dict(zip(VIT_TAGS, [1, 1, ln, qkv, attn, proj, fc, fc, 2, qkv_x, attn_x, proj_x, fc_x, fc_x, tail]))
+    return {k: v * lanes for k, v in one.items()}
+
+
+# 64 tiles = two lanes of 32 (= comp_min_tiles: the compensated kernels run where asked for), 6304 token rows each: the persistent kernels, which fuse
+# no LayerNorm.  Derived by hand from the schedule.  In every plan:
+#   vit.ln 5 = LayerNorm-1 of the three blocks + LayerNorm-2 of blocks 0 and 1; the last block's proj runs on the 32 compact CLS rows (cls_tail), on the
+#            small-M path, which takes the LayerNorm-2 it is offered
+#   the last block's proj / fc1 / fc2 are three vit.tail brackets whatever the plan (its qkv and attention keep their tags), so the other tags of
+#            proj / fc1 / fc2 count blocks 0 and 1 only
+PLAN_COUNTS_64 = {
+    "plain":     ([(0, 0)] * 3, _counts(5, 3, 3, 2, 2, 0, 0, 0, 0, 3, lanes=2)),
+    "split":     ([(1, 1)] * 3, _counts(5, 0, 0, 0, 0, 3, 3, 2, 2, 3, lanes=2)),
+    # split attention side with a compensated qkv (still .x), compensated MLP: the same brackets as "split" (the tail takes split products for compensated ones)
+    "2,2":       ([(2, 2)] * 3, _counts(5, 0, 0, 0, 0, 3, 3, 2, 2, 3, lanes=2)),
+    # compensated qkv only on a lane this large: attention and proj stay plain
+    "3,3":       ([(3, 3)] * 3, _counts(5, 0, 3, 2, 0, 3, 0, 0, 2, 3, lanes=2)),
+    # CLS-row MLP in blocks 0 and 1: gather behind proj, the chain, scatter behind fc2 = 3 tail brackets each; the last block's tail IS that chain: its usual 3
+    "0,4":       ([(0, 4)] * 3, _counts(5, 3, 3, 2, 2, 0, 0, 0, 0, 3 + 2 * 3, lanes=2)),
+    # CLS-row proj in blocks 0 and 1: gather in front of proj, the split proj, scatter behind it = 3 each
+    "4,0":       ([(4, 0)] * 3, _counts(5, 3, 3, 2, 2, 0, 0, 0, 0, 3 + 2 * 3, lanes=2)),
+    # both: block 0 gather, CLS-row proj, CLS-row MLP, scatter behind fc2 = 4; block 1 finds the compact rows live (no gather) = 3
+    "4,4":       ([(4, 4)] * 3, _counts(5, 3, 3, 2, 2, 0, 0, 0, 0, 3 + 4 + 3, lanes=2)),
+    "5,4":       ([(5, 4)] * 3, _counts(5, 0, 3, 2, 2, 3, 0, 0, 0, 3 + 4 + 3, lanes=2)),       # the same with every qkv compensated
+    # what a handle starts with: block 0 as "2,2", blocks 1 and 2 as "0,4" (block 1: 3 tail brackets, block 2: its tail)
+    "default":   (None, _counts(5, 2, 2, 1, 1, 1, 1, 1, 1, 3 + 3, lanes=2)),
+}
+# 3 tiles = one lane of 591 token rows: below comp_min_tiles (split products for compensated ones) and on the K-sliced kernels, whose reduce takes the
+# LayerNorm it is offered (vit.ln counts what is left; the next block then finds its LayerNorm-1 done).  Which launches fuse is the kernels' choice, so
+# this table is not derived: it was read off this same test run on the commit before the block plan was split from the launches.
+# (vit.ln 1: only block 0's LayerNorm-1 runs on its own; 3: a block with a CLS-row MLP does not offer the next LayerNorm-1.  On this lane "3,3" and "5,4"
+# run a split attention side, so "5,4" has no CLS-row proj: 3 tail brackets per block.)
+PLAN_COUNTS_3 = {
+    "plain":     _counts(1, 3, 3, 2, 2, 0, 0, 0, 0, 3, lanes=1),
+    "split":     _counts(1, 0, 0, 0, 0, 3, 3, 2, 2, 3, lanes=1),
+    "2,2":       _counts(1, 0, 0, 0, 0, 3, 3, 2, 2, 3, lanes=1),
+    "3,3":       _counts(1, 0, 0, 0, 0, 3, 3, 2, 2, 3, lanes=1),
+    "0,4":       _counts(3, 3, 3, 2, 2, 0, 0, 0, 0, 9, lanes=1),
+    "4,0":       _counts(1, 3, 3, 2, 2, 0, 0, 0, 0, 9, lanes=1),
+    "4,4":       _counts(3, 3, 3, 2, 2, 0, 0, 0, 0, 10, lanes=1),
+    "5,4":       _counts(3, 0, 0, 0, 2, 3, 3, 2, 0, 9, lanes=1),
+    "default":   _counts(2, 2, 2, 1, 1, 1, 1, 1, 1, 6, lanes=1),
+}
+
+
+def test_launch_schedule_of_every_plan_is_pinned():
+    """What a block issues under each kind of plan, pinned by the launch brackets per profile tag (profile_read(tag)[1]) of one encode_image call: on
+    two bench-sized lanes and on one small lane.  Profiling runs every call unreplayed, launch by launch."""
+    shape = small_shape(3, 2)
+    sd = synth_state_dict(shape, seed=8, text=False)
+    m = KEEPModel(shape, precision="comp", towers=("image",))
+    m.auto_calibrate = False
+    m.load_state_dict(sd, strict=True)
+    m.to("cuda:0")
+    m.profile_enable()
+    x = synth_tiles(64, seed=31).cuda()
+    got = {}
+    for name, (plan, _) in sorted(PLAN_COUNTS_64.items(), key=lambda kv: kv[0] != "default"):       # the handle's own plan first, before any is set
+        if plan is not None:
+            m.set_plan(plan)
+        for n in (64, 3):
+            m.profile_reset()
+            m.encode_image(x[:n])
+            got[name, n] = {t: m.profile_read(t)[1] for t in VIT_TAGS}
+            print(f"[launch counts] {name!r} {n} tiles: {got[name, n]}")
+    m.profile_disable()
+    for name, (_, want) in PLAN_COUNTS_64.items():
+        assert got[name, 64] == want, (name, 64)
+        assert got[name, 3] == PLAN_COUNTS_3[name], (name, 3)
+
+
 def test_mean_input_bias_compensation():
     """keep_calibrate_bias: the row-independent part of the dropped W_lo A_hi term (W_lo @ mean input row) folded into the bias of the plain fp16
     launches.  Full depth, bench weights, everything plain: with the compensation the cosine errors against the split-product mode are smaller than
