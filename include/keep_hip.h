@@ -528,6 +528,50 @@ int keep_probe_loss_grad(keep_handle* h, const float* features, int64_t N, int64
                          int64_t C, const float* class_weight, int64_t* grad, int64_t* gbias, int64_t* loss, int64_t* counts, int64_t* skipped,
                          float* probs_out, int32_t* label_out, float* best_out, float* margin_out, int groups, void* stream);
 
+/* ---- attention MIL ---------------------------------------------------------------
+ * Replaces: nothing in the reference, which has no slide-level supervised protocol; on this engine a torch loop of x @ V.T, tanh, a
+ * segment softmax, index_add_ and R.T @ x, whose float sums depend on the order the library picks.  Attention-based multiple-instance
+ * learning (Ilse, Tomczak and Welling 2018): features fp32 [N,D] row-major unit rows in S bags of contiguous rows; V fp32 [L,D], bv and
+ * w fp32 [L]; features and V 16-byte aligned; 1 <= N <= 2^22 and 1 <= S <= 2^16 per call, D a multiple of 16 in 16 .. 1024, L a
+ * multiple of 16 in 16 .. 128.  chunks int32 [n_chunks,3] on the device: (bag, first row, rows), every bag cut from its own first
+ * row into runs of at most KEEP_MIL_CHUNK rows (an empty bag has none).  THE WORDS DEPEND ON KEEP_MIL_CHUNK: it is part of the
+ * contract.  A chunk outside [0,S) x [0,N) or with rows outside 1 .. KEEP_MIL_CHUNK is KEEP_EINVAL, found by one check launch and a
+ * 4-byte read-back (the one host synchronisation of each call) before the table is an index.  Anything else above is KEEP_EINVAL
+ * too and nothing is launched.  workspace: device memory of at least keep_mil_workspace_bytes(N, D, S) bytes, 256-byte aligned, the
+ * caller's; keep_mil_backward reads what keep_mil_forward left in it for the same features and table.
+ *
+ * keep_mil_forward: h_i = tanhf(V x_i + bv) (a k-ordered fp32 fma chain on v_mfma_f32_16x16x4_f32, the bias after it), s_i = w . h_i in
+ * one fixed order; a row's s and h depend on that row alone.  Per bag: m_b = max s, e_i = expf(s_i - m_b), Z_b = sum llrint(e_i 2^40),
+ * P_b[d] = sum llrint(fp32(e_i x_id) 2^40) (integers: any order), attn_out[i] = e_i / fp32(Z_b 2^-40), pooled_out[b,d] =
+ * fp32(P_b[d] / Z_b).  A row holding a non-finite value or an element with |x| > 1 (or whose score is not finite) is skipped:
+ * scores_out -inf, attention 0, in no sum, one added to *skipped_rows.  A bag without a kept row: a zero pooled row, kept_rows_out
+ * 0, head label -1, one added to *skipped_bags.  scores_out / attn_out fp32 [N], pooled_out fp32 [S,D], kept_rows_out int32 [S]:
+ * required.  hidden_out fp32 [N,L] (the backward needs it) and head_labels_out int32 [S] (labels[b], or 0 without labels, for a bag
+ * with a kept row, else -1: the labels of the head, keep_probe_loss_grad on pooled_out) may be null; labels int32 [S] may be null.
+ * skipped_rows / skipped_bags: int64 on the device, ADDED into.
+ * keep_mil_backward: after the head.  probs fp32 [S,C] and head_labels as the head saw them, Wc fp32 [C,D], class_weight fp32 [C] or
+ * null, 2 <= C <= 64.  r_bc = cw[y_b] (p_bc - [c = y_b]) as the probe forms it, dz_b = sum_c r_bc Wc[c,:] (c ascending, fma), u_b =
+ * dz_b . z_b, da_i = dz_b . x_i, ds_i = a_i (da_i - u_b), each in one fixed order; R_il = fp32(ds_i w_l) fp32(1 - fp32(h_il^2)).  Per
+ * chunk gV[l,d] += llrint(acc 2^36), acc the fp32 MFMA chain of R_il x_id over the chunk's rows in row order (one rounding per
+ * chunk and word); gbv[l] += llrint(R_il 2^36) and gw[l] += llrint(fp32(ds_i h_il) 2^36) per term.  gV int64 [L,D], gbv / gw int64
+ * [L], 8-byte aligned, all required: the call ALWAYS ADDS, the caller zeroes.  A bag with head label -1 adds nothing.  A bag's
+ * contribution to every word depends on that bag alone: the same words for every split of the bags over calls and every order.
+ * A bag adds at most G = 4 max(1, max|w|) max_c |Wc_c|_1 to a word: the caller holds G <= 2^10 and the bags added into one set of
+ * accumulators <= 2^16, which keeps |word| <= 2^62.  ds_out fp32 [N] (may be null): the rows' ds_i, 0 for a row in no sum. */
+#ifndef KEEP_MIL_CHUNK
+#define KEEP_MIL_CHUNK 512
+#endif
+int keep_mil_chunk(void);
+int keep_mil_workspace_bytes(keep_handle* h, int64_t N, int64_t D, int64_t S, int64_t* bytes);
+int keep_mil_forward(keep_handle* h, const float* features, int64_t N, int64_t D, const int32_t* chunks, int64_t n_chunks, int64_t S,
+                     const int32_t* labels, const float* V, const float* bv, const float* w, int64_t L, float* scores_out, float* attn_out,
+                     float* pooled_out, int32_t* kept_rows_out, float* hidden_out, int32_t* head_labels_out, int64_t* skipped_rows,
+                     int64_t* skipped_bags, void* workspace, int64_t workspace_bytes, void* stream);
+int keep_mil_backward(keep_handle* h, const float* features, int64_t N, int64_t D, const int32_t* chunks, int64_t n_chunks, int64_t S,
+                      const int32_t* head_labels, const float* probs, const float* Wc, int64_t C, const float* class_weight, const float* w,
+                      int64_t L, const float* scores, const float* attn, const float* pooled, const float* hidden, int64_t* gV, int64_t* gbv,
+                      int64_t* gw, float* ds_out, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- nearest neighbours ----------------------------------------------------------
  * Replaces: the [N,M] keep_similarity matrix + torch.topk round trip on this engine, and the reference's
  * arr.argsort()[-50:][::-1] over a host similarity row (training/path_training/zero_shot.py:168-171), which lists the HIGHER index

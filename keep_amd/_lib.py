@@ -73,6 +73,11 @@ SIGNATURES = {
     "keep_cluster_seed_step": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
     "keep_probe_forward": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "keep_probe_loss_grad": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "keep_mil_chunk": (_i32, []),
+    "keep_mil_workspace_bytes": (_i32, [_vp, _i64, _i64, _i64, C.POINTER(_i64)]),
+    "keep_mil_forward": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "keep_mil_backward": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _i64, _vp]),
     "keep_topk": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),
     "keep_topk_merge": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "keep_topk_unpack": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),

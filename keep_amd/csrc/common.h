@@ -411,6 +411,25 @@ void launch_probe(const float* x, int N, int D, const float* w, const float* bia
 // *bad = 1 for a label outside -1 .. C - 1 or a class weight (may be null) outside (0, 1]
 void launch_probe_check(const int32_t* labels, int N, int C, const float* class_weight, int* bad, hipStream_t s);
 
+// Attention MIL (mil.hip).  x: fp32 [N][D] unit rows with the limits of the clustering above; chunks: int32
+// [n_chunks][3] of (bag, first row, rows <= KEEP_MIL_CHUNK), checked by launch_mil_check before any other launch reads it.
+constexpr int MIL_MAX_L = 128;                          // hidden units: a multiple of 16 in 16 .. 128
+constexpr int64_t MIL_MAX_BAGS = (int64_t)1 << 16;      // per call, and in all into one set of accumulators
+// *bad = 1 for a chunk outside [0, S) x [0, N) or with rows outside 1 .. KEEP_MIL_CHUNK
+void launch_mil_check(const int32_t* chunks, int n_chunks, int N, int S, int* bad, hipStream_t s);
+// s_out fp32 [N] (-inf for a skipped row), h_out fp32 [N][L] or null; skipped_rows is ADDED into
+void launch_mil_scores(const float* x, int N, int D, const float* V, const float* bv, const float* w, int L, float* s_out, float* h_out,
+                       int64_t* skipped_rows, hipStream_t s);
+// mkey int32 [S], Z int64 [S], P int64 [S][D]: workspace, set here.  a_out fp32 [N], z_out fp32 [S][D], kept_rows int32 [S]; y and
+// head_labels (int32 [S]) may be null; skipped_bags is ADDED into
+void launch_mil_pool(const float* x, int N, int D, const float* s_in, const int32_t* chunks, int n_chunks, int S, const int32_t* y, int* mkey,
+                     int64_t* Z, int64_t* P, float* a_out, float* z_out, int32_t* kept_rows, int32_t* head_labels, int64_t* skipped_bags,
+                     hipStream_t s);
+// dz fp32 [S][D], u fp32 [S], ds fp32 [N]: workspace; cw may be null; gV int64 [L][D], gbv and gw int64 [L] are ADDED into
+void launch_mil_backward(const float* x, int D, const int32_t* chunks, int n_chunks, int S, const int32_t* head_labels, const float* probs,
+                         const float* Wc, int C, const float* cw, const float* w, int L, const float* s_in, const float* a, const float* z,
+                         const float* hbuf, float* dz, float* u, float* ds, int64_t* gV, int64_t* gbv, int64_t* gw, hipStream_t s);
+
 // Nearest neighbours (neighbours.hip).  q: fp32 [Nq][D] and bank: fp32 [M][D] unit rows with the limits of the
 // clustering above; keys: uint64 [Nq][k] descending lists of KEEP_TOPK_KEY words, 1 <= k <= TOPK_MAX_K.
 constexpr int TOPK_MAX_K = 64;                          // a list is one key per lane of a wave

@@ -1,5 +1,5 @@
 // The slide-geometry entry points of include/keep_hip.h: patch grid, tissue mask, stain normalisation, tile quality, heatmap, sort / rank, region table, outlines, polygon
-// fill, segmentation evaluation, bootstrap resampling, the subtype map, tile clustering, the linear probe and nearest neighbours.  Host code only: each function validates its arguments, carves its workspace from the handle's
+// fill, segmentation evaluation, bootstrap resampling, the subtype map, tile clustering, the linear probe, attention MIL and nearest neighbours.  Host code only: each function validates its arguments, carves its workspace from the handle's
 // arena, calls the launch_* of its kernel file (region / tissue / stain / quality / heatmap / rank / components / outline / annotation / eval / bootstrap .hip) and
 // reports the launch.  Of the handle (handle.h) they use the device, the error text, the arena and the sticky error flag.
 #include "handle.h"
@@ -867,6 +867,110 @@ int keep_probe_loss_grad(keep_handle* h, const float* features, int64_t N, int64
     launch_probe(features, (int)N, (int)D, weight, bias, (int)C, groups, labels, class_weight, probs_out, label_out, best_out, margin_out, skipped, grad,
                  gbias, loss, counts, s);
     return check_launch(h, "probe_loss_grad");
+}
+
+// Attention MIL (mil.hip).  The workspace: [flag][mkey S][Z S][P S D][dz S D][u S][ds N], each 256-byte aligned.
+struct MilWorkspace {
+    size_t o_mkey, o_Z, o_P, o_dz, o_u, o_ds, total;
+    MilWorkspace(int64_t N, int64_t D, int64_t S) {
+        o_mkey = align_up(sizeof(int));
+        o_Z = o_mkey + align_up((size_t)S * 4);
+        o_P = o_Z + align_up((size_t)S * 8);
+        o_dz = o_P + align_up((size_t)S * D * 8);
+        o_u = o_dz + align_up((size_t)S * D * 4);
+        o_ds = o_u + align_up((size_t)S * 4);
+        total = o_ds + align_up((size_t)N * 4);
+    }
+};
+
+static int mil_args_check(keep_handle* h, const char* who, const float* features, int64_t N, int64_t D, const int32_t* chunks, int64_t n_chunks,
+                          int64_t S, int64_t L, const void* workspace, int64_t workspace_bytes) {
+    if (int rc = cluster_shape_check(h, who, N, D, 1)) return rc;
+    if (S < 1 || S > MIL_MAX_BAGS) return h->fail(KEEP_EINVAL, "%s: %lld bags (1 .. 2^16 per call)", who, (long long)S);
+    if (L < 16 || L > MIL_MAX_L || L % 16) return h->fail(KEEP_EINVAL, "%s: L = %lld (a multiple of 16, 16 .. 128)", who, (long long)L);
+    if (n_chunks < 0 || n_chunks > N) return h->fail(KEEP_EINVAL, "%s: %lld chunks for %lld rows", who, (long long)n_chunks, (long long)N);
+    if (!features || ((uintptr_t)features & 15)) return h->fail(KEEP_EINVAL, "%s: features null or not 16-byte aligned", who);
+    if (n_chunks > 0 && (!chunks || ((uintptr_t)chunks & 3))) return h->fail(KEEP_EINVAL, "%s: the chunk table is null or not 4-byte aligned", who);
+    if (!workspace || ((uintptr_t)workspace & 255) || workspace_bytes < (int64_t)MilWorkspace(N, D, S).total)
+        return h->fail(KEEP_EINVAL, "%s: workspace null, not 256-byte aligned or of %lld bytes, %lld needed (keep_mil_workspace_bytes)", who,
+                       (long long)workspace_bytes, (long long)MilWorkspace(N, D, S).total);
+    return KEEP_OK;
+}
+
+// the chunk table is read back as one flag before it is an index (the one synchronisation of the call), as in keep_probe_loss_grad
+static int mil_chunks_check(keep_handle* h, const char* who, const int32_t* chunks, int64_t n_chunks, int64_t N, int64_t S, char* ws, hipStream_t s) {
+    if (n_chunks == 0) return KEEP_OK;
+    int* bad = (int*)ws;
+    HIPCHK(h, hipMemsetAsync(bad, 0, sizeof(int), s));
+    launch_mil_check(chunks, (int)n_chunks, (int)N, (int)S, bad, s);
+    if (int rc = check_launch(h, "mil_check")) return rc;
+    int bad_h = 0;
+    HIPCHK(h, hipMemcpyAsync(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (bad_h) return h->fail(KEEP_EINVAL, "%s: a chunk leaves [0, %lld) bags or [0, %lld) rows, or has rows outside 1 .. %d", who, (long long)S,
+                              (long long)N, KEEP_MIL_CHUNK);
+    return KEEP_OK;
+}
+
+int keep_mil_chunk(void) { return KEEP_MIL_CHUNK; }
+
+int keep_mil_workspace_bytes(keep_handle* h, int64_t N, int64_t D, int64_t S, int64_t* bytes) {
+    if (!h) return KEEP_EINVAL;
+    if (!bytes) return h->fail(KEEP_EINVAL, "mil_workspace_bytes: null pointer");
+    if (int rc = cluster_shape_check(h, "mil_workspace_bytes", N, D, 1)) return rc;
+    if (S < 1 || S > MIL_MAX_BAGS) return h->fail(KEEP_EINVAL, "mil_workspace_bytes: %lld bags (1 .. 2^16 per call)", (long long)S);
+    *bytes = (int64_t)MilWorkspace(N, D, S).total;
+    return KEEP_OK;
+}
+
+int keep_mil_forward(keep_handle* h, const float* features, int64_t N, int64_t D, const int32_t* chunks, int64_t n_chunks, int64_t S,
+                     const int32_t* labels, const float* V, const float* bv, const float* w, int64_t L, float* scores_out, float* attn_out,
+                     float* pooled_out, int32_t* kept_rows_out, float* hidden_out, int32_t* head_labels_out, int64_t* skipped_rows,
+                     int64_t* skipped_bags, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = mil_args_check(h, "mil_forward", features, N, D, chunks, n_chunks, S, L, workspace, workspace_bytes)) return rc;
+    if (!V || !bv || !w || ((uintptr_t)V & 15) || ((uintptr_t)bv & 3) || ((uintptr_t)w & 3))
+        return h->fail(KEEP_EINVAL, "mil_forward: null V, bv or w, or V not 16-byte aligned");
+    if (!scores_out || !attn_out || !pooled_out || !kept_rows_out || !skipped_rows || !skipped_bags)
+        return h->fail(KEEP_EINVAL, "mil_forward: null scores_out, attn_out, pooled_out, kept_rows_out, skipped_rows or skipped_bags");
+    if (((uintptr_t)scores_out & 3) || ((uintptr_t)attn_out & 3) || ((uintptr_t)pooled_out & 3) || ((uintptr_t)kept_rows_out & 3) ||
+        ((uintptr_t)hidden_out & 3) || ((uintptr_t)head_labels_out & 3) || ((uintptr_t)labels & 3) || ((uintptr_t)skipped_rows & 7) ||
+        ((uintptr_t)skipped_bags & 7))
+        return h->fail(KEEP_EINVAL, "mil_forward: labels or an output is not aligned to its element size");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const MilWorkspace m(N, D, S);
+    if (int rc = mil_chunks_check(h, "mil_forward", chunks, n_chunks, N, S, ws, s)) return rc;
+    launch_mil_scores(features, (int)N, (int)D, V, bv, w, (int)L, scores_out, hidden_out, skipped_rows, s);
+    if (int rc = check_launch(h, "mil_scores")) return rc;
+    launch_mil_pool(features, (int)N, (int)D, scores_out, chunks, (int)n_chunks, (int)S, labels, (int*)(ws + m.o_mkey), (int64_t*)(ws + m.o_Z),
+                    (int64_t*)(ws + m.o_P), attn_out, pooled_out, kept_rows_out, head_labels_out, skipped_bags, s);
+    return check_launch(h, "mil_pool");
+}
+
+int keep_mil_backward(keep_handle* h, const float* features, int64_t N, int64_t D, const int32_t* chunks, int64_t n_chunks, int64_t S,
+                      const int32_t* head_labels, const float* probs, const float* Wc, int64_t C, const float* class_weight, const float* w,
+                      int64_t L, const float* scores, const float* attn, const float* pooled, const float* hidden, int64_t* gV, int64_t* gbv,
+                      int64_t* gw, float* ds_out, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = mil_args_check(h, "mil_backward", features, N, D, chunks, n_chunks, S, L, workspace, workspace_bytes)) return rc;
+    if (C < 2 || C > PROBE_MAX_C) return h->fail(KEEP_EINVAL, "mil_backward: C = %lld (2 .. 64)", (long long)C);
+    if (!head_labels || !probs || !Wc || !w || !scores || !attn || !pooled || !hidden)
+        return h->fail(KEEP_EINVAL, "mil_backward: null head_labels, probs, Wc, w, scores, attn, pooled or hidden");
+    if (!gV || !gbv || !gw) return h->fail(KEEP_EINVAL, "mil_backward: null gV, gbv or gw");
+    if (((uintptr_t)gV & 7) || ((uintptr_t)gbv & 7) || ((uintptr_t)gw & 7)) return h->fail(KEEP_EINVAL, "mil_backward: an accumulator is not 8-byte aligned");
+    if (((uintptr_t)head_labels & 3) || ((uintptr_t)probs & 3) || ((uintptr_t)Wc & 3) || ((uintptr_t)class_weight & 3) || ((uintptr_t)w & 3) ||
+        ((uintptr_t)scores & 3) || ((uintptr_t)attn & 3) || ((uintptr_t)pooled & 3) || ((uintptr_t)hidden & 3) || ((uintptr_t)ds_out & 3))
+        return h->fail(KEEP_EINVAL, "mil_backward: an input or ds_out is not 4-byte aligned");
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const MilWorkspace m(N, D, S);
+    if (int rc = mil_chunks_check(h, "mil_backward", chunks, n_chunks, N, S, ws, s)) return rc;
+    launch_mil_backward(features, (int)D, chunks, (int)n_chunks, (int)S, head_labels, probs, Wc, (int)C, class_weight, w, (int)L, scores, attn, pooled,
+                        hidden, (float*)(ws + m.o_dz), (float*)(ws + m.o_u), ds_out ? ds_out : (float*)(ws + m.o_ds), gV, gbv, gw, s);
+    return check_launch(h, "mil_backward");
 }
 
 // Nearest neighbours (neighbours.hip)

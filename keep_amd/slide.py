@@ -1,5 +1,5 @@
 """The slide-analysis methods of ``KEEPModel``: patch grid and tiles of a region, tissue mask, heatmap raster, percentiles and
-smoothing, region table, outlines, region shape, polygon fill, segmentation evaluation, the subtype map, bootstrap resampling and the linear probe (DESIGN.md sections 10-27).  Thin wrappers of the
+smoothing, region table, outlines, region shape, polygon fill, segmentation evaluation, the subtype map, bootstrap resampling, the linear probe and attention MIL (DESIGN.md sections 10-29).  Thin wrappers of the
 entry points in csrc/slide_api.hip; the argument checks and the numpy references live in the feature modules imported below."""
 from __future__ import annotations
 
@@ -27,6 +27,7 @@ from .morphometry import DEFAULT_MAX_PAIRS, RegionShape, check_shape_args
 from .outline import NCOLS as RING_COLS, RegionOutlines, check_draw_args, check_outline_args, check_ring_count, regions_labels, rgb_tensor
 from .region import (MASK_MODES, TILE, TissueMask, TissueSegmentation, check_downsample, check_grid_args, grid_shape, otsu_threshold, region_layout,
                      resize_tables, thumbnail_layout, tissue_params)
+from . import mil as _mil
 from . import neighbours as _nb
 from . import probe as _probe
 from . import stain as _stain
@@ -858,6 +859,214 @@ class SlideOps:
                 counts += torch.bincount(y[y >= 0].to(torch.int64), minlength=C_)[:C_]
         cw = _probe.check_class_weight(class_weight, C_, counts)
         return self._probe_fit(prepared, C_, D, l2, cw, gtol, max_iter, init, classes)
+
+    # ------------------------------------------------------------------ attention MIL
+    def _mil_bags(self, features, offsets, normalize: bool = True):
+        """Checked features and offsets -> (device features, int64 host offsets, device chunk table int32 [n, 3], workspace)."""
+        N, D = check_features(features)
+        o = _mil.check_offsets(offsets, N)
+        self._ready_device()
+        x = self._cluster_features(features, normalize)
+        lib = _lib.load()
+        table = _mil.chunk_table(o, int(lib.keep_mil_chunk()))
+        chunks = torch.from_numpy(np.ascontiguousarray(table)).to(self._device)
+        need = C.c_int64(0)
+        _lib.check(self._handle, lib.keep_mil_workspace_bytes(self._handle, N, D, len(o) - 1, C.byref(need)), "mil_workspace_bytes")
+        ws = torch.empty(int(need.value), dtype=torch.uint8, device=self._device)
+        return x, o, chunks, ws
+
+    def _mil_params(self, params, D: int, values: bool = True):
+        if isinstance(params, _mil.AttentionMIL):
+            params = params.params
+        L, C_, _ = _mil.check_params(params, D, values)
+        return L, C_, tuple(self._on_device(a) for a in params)
+
+    def _mil_forward(self, bags, y, dev_params, L: int, hidden: bool, skipped_rows, skipped_bags) -> dict:
+        x, o, chunks, ws = bags
+        N, D, S = x.shape[0], x.shape[1], len(o) - 1
+        V, bv, w = dev_params[:3]
+        dev = self._device
+        out = dict(scores=torch.empty(N, dtype=torch.float32, device=dev), attention=torch.empty(N, dtype=torch.float32, device=dev),
+                   pooled=torch.empty((S, D), dtype=torch.float32, device=dev), kept_rows=torch.empty(S, dtype=torch.int32, device=dev),
+                   hidden=torch.empty((N, L), dtype=torch.float32, device=dev) if hidden else None,
+                   head_labels=torch.empty(S, dtype=torch.int32, device=dev))
+        self._call("mil_forward", _ptr(x), N, D, _ptr(chunks), chunks.shape[0], S, _ptr(y), _ptr(V), _ptr(bv), _ptr(w), L, _ptr(out["scores"]),
+                   _ptr(out["attention"]), _ptr(out["pooled"]), _ptr(out["kept_rows"]), _ptr(out["hidden"]), _ptr(out["head_labels"]),
+                   _ptr(skipped_rows), _ptr(skipped_bags), _ptr(ws), ws.numel())
+        return out
+
+    @torch.no_grad()
+    def mil_forward(self, features, offsets, params, labels=None, normalize=True, hidden=False) -> dict:
+        """The attention pooling on the device -> a dict with ``scores`` fp32 ``[N]`` (``s_i``; -inf for a skipped
+        row), ``attention`` fp32 ``[N]`` (the softmax of the scores over each bag; 0 for a skipped row), ``pooled`` fp32 ``[S, D]``
+        (``z_b``; a zero row for a bag without a kept row), ``kept_rows`` int32 ``[S]``, ``head_labels`` int32 ``[S]`` (``labels[b]``, 0 without
+        labels, or -1 for a bag without a kept row), ``hidden`` fp32 ``[N, L]`` (``tanh(V x + bv)``, with ``hidden=True``) and ``skipped``
+        int64 ``[2]`` (rows, bags).  ``features`` fp32 ``[N, D]`` as in :meth:`cluster_assign`; ``offsets`` integers ``[S + 1]`` (bag b is the
+        rows ``offsets[b] .. offsets[b + 1]``); ``params``: ``(V, bv, w, Wc, bc)`` or an ``AttentionMIL`` (the head is not used here).  A
+        row's score and a bag's pooled row depend on that row and that bag alone."""
+        bags = self._mil_bags(features, offsets, normalize)
+        L, _, dp = self._mil_params(params, bags[0].shape[1], values=False)
+        y = None if labels is None else self._probe_labels(labels, len(bags[1]) - 1)
+        skipped = torch.zeros(2, dtype=torch.int64, device=self._device)
+        out = self._mil_forward(bags, y, dp, L, hidden, skipped[0:1], skipped[1:2])
+        out["skipped"] = skipped
+        return out
+
+    def _mil_eval(self, bags, y, dp, L: int, C_: int, cwd, sums, forward: bool = False, ds=None):
+        """One loss + gradient evaluation of prepared bags into ``sums``: the pooling, the head (the probe's own launch on the pooled
+        rows) and the backward -> ``(forward outputs, head probabilities, head labels)``."""
+        x, o, chunks, ws = bags
+        N, D, S = x.shape[0], x.shape[1], len(o) - 1
+        sums.claim(S)
+        f = self._mil_forward(bags, y, dp, L, True, sums.skipped_rows, sums.skipped_bags)
+        V, bv, w, Wc, bc = dp
+        h = sums.head
+        probs = torch.empty((S, C_), dtype=torch.float32, device=self._device)
+        plab = torch.empty(S, dtype=torch.int32, device=self._device) if forward else None
+        self._call("probe_loss_grad", _ptr(f["pooled"]), S, D, _ptr(f["head_labels"]), _ptr(Wc), _ptr(bc), C_, _ptr(cwd), _ptr(h.grad), _ptr(h.gbias),
+                   _ptr(h.loss), _ptr(h.counts), _ptr(h.skipped), _ptr(probs), _ptr(plab), _ptr(None), _ptr(None), 0)
+        self._call("mil_backward", _ptr(x), N, D, _ptr(chunks), chunks.shape[0], S, _ptr(f["head_labels"]), _ptr(probs), _ptr(Wc), C_, _ptr(cwd),
+                   _ptr(w), L, _ptr(f["scores"]), _ptr(f["attention"]), _ptr(f["pooled"]), _ptr(f["hidden"]), _ptr(sums.gV), _ptr(sums.gbv),
+                   _ptr(sums.gw), _ptr(ds), _ptr(ws), ws.numel())
+        return f, probs, plab
+
+    @staticmethod
+    def _mil_mask(f: dict, labels, probs):
+        """A bag without a kept row: label -1 and a zero row of probabilities, whatever the head made of its zero pooled row."""
+        gone = f["kept_rows"] == 0
+        return labels.masked_fill(gone, -1), probs.masked_fill(gone[:, None], 0.0)
+
+    @torch.no_grad()
+    def mil_loss_grad(self, features, offsets, labels, params, sums, class_weight=None, normalize=True, forward=False, detail=False):
+        """One loss + gradient evaluation of the attention MIL model on the device, added into ``sums`` (a
+        ``keep_amd.mil.MilSums`` of the same L, C and D).  ``features`` / ``offsets`` / ``params`` as in :meth:`mil_forward`; ``labels``:
+        integers ``[S]``, -1 for a bag to leave out; ``class_weight``: None or fp32 ``[C]`` in (0, 1].  The words are integers and a bag's
+        contribution to each depends on that bag alone: the same words for every split of the bags over calls, in any order;
+        ``keep_amd.mil.objective_from_words`` turns them into the objective and its gradient.  ``forward=True`` returns
+        ``(labels, probs, attention)`` as :meth:`mil_predict` would, otherwise None; ``detail=True`` returns every intermediate instead:
+        the dict of :meth:`mil_forward` (with ``hidden``) plus ``probs`` fp32 ``[S, C]`` as the head wrote them and ``ds`` fp32 ``[N]``, the
+        derivative of the unnormalised loss by each row's score."""
+        bags = self._mil_bags(features, offsets, normalize)
+        D, S = bags[0].shape[1], len(bags[1]) - 1
+        L, C_, dp = self._mil_params(params, D)
+        if not isinstance(sums, _mil.MilSums):
+            raise ValueError(f"sums must be a MilSums, got {type(sums).__name__}")
+        sums.check(L, C_, D)
+        if sums.buf.device != self._device:
+            raise ValueError(f"the accumulators live on {sums.buf.device}, this engine on {self._device}")
+        cw = None
+        if class_weight is not None:
+            cw = class_weight if isinstance(class_weight, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(class_weight))
+            if tuple(cw.shape) != (C_,) or cw.dtype != torch.float32:
+                raise ValueError(f"class_weight must be float32 [{C_}], got {cw.dtype} {tuple(cw.shape)}")
+            cw = self._on_device(cw)
+        y = self._probe_labels(labels, S)
+        ds = torch.empty(bags[0].shape[0], dtype=torch.float32, device=self._device) if detail else None
+        f, probs, plab = self._mil_eval(bags, y, dp, L, C_, cw, sums, forward, ds)
+        if detail:
+            return dict(f, probs=probs, ds=ds)
+        return (*self._mil_mask(f, plab, probs), f["attention"]) if forward else None
+
+    @torch.no_grad()
+    def mil_predict(self, mil, features, offsets, normalize=True):
+        """The attention MIL forward on the device -> ``(labels, probs, attention, skipped)``: int32 ``[S]`` (the
+        first maximum of the bag's logits; -1 for a bag without a kept row), fp32 ``[S, C]`` (a zero row for such a bag), fp32 ``[N]`` (the
+        tiles' attention within their bag; 0 for a skipped tile) and int64 ``[2]`` (skipped rows, skipped bags).  ``mil``: an
+        ``AttentionMIL`` or ``(V, bv, w, Wc, bc)``."""
+        bags = self._mil_bags(features, offsets, normalize)
+        D, S = bags[0].shape[1], len(bags[1]) - 1
+        L, C_, dp = self._mil_params(mil, D, values=False)
+        skipped = torch.zeros(2, dtype=torch.int64, device=self._device)
+        f = self._mil_forward(bags, None, dp, L, False, skipped[0:1], skipped[1:2])
+        labels = torch.empty(S, dtype=torch.int32, device=self._device)
+        probs = torch.empty((S, C_), dtype=torch.float32, device=self._device)
+        self._call("probe_forward", _ptr(f["pooled"]), S, D, _ptr(dp[3]), _ptr(dp[4]), C_, _ptr(probs), _ptr(labels), _ptr(None), _ptr(None), _ptr(None), 0)
+        return (*self._mil_mask(f, labels, probs), f["attention"], skipped)
+
+    def _mil_fit(self, batches, L: int, C_: int, D: int, l2: float, cw: np.ndarray, lr: float, n_steps: int, seed: int, init, classes):
+        """Adam on the host over ``batches()`` (an iterable of prepared ``(bags, labels)`` pairs, the same bags every time it is called).
+        Every evaluation streams all batches into one ``MilSums`` and reads it back once."""
+        dev = self._device
+        sums = _mil.MilSums(L, C_, D, dev)
+        cwd = torch.from_numpy(cw).to(dev)
+        last = {}
+
+        def fun(theta):
+            p64 = _mil.unpack(theta, L, C_, D)
+            p32 = tuple(np.ascontiguousarray(a, np.float32) for a in p64)
+            _mil.check_params(p32, D)
+            dp = tuple(torch.from_numpy(a).to(dev) for a in p32)
+            sums.zero_()
+            for bags, y in batches():
+                self._mil_eval(bags, y, dp, L, C_, cwd, sums)
+            if sums.bags == 0:
+                raise ValueError("batches() returned no bags")
+            words = sums.host()                                          # the evaluation's one read of the sums
+            f, g = _mil.objective_from_words(words, cw, p64, l2)
+            last.update(words=words, params=dp)
+            return f, _mil.pack(g)
+
+        theta0 = _mil.pack(_mil.init_params(seed, L, C_, D) if init is None else init)
+        if theta0.shape != (sum(_mil.sizes(L, C_, D)),):
+            raise ValueError(f"init must be (V [{L}, {D}], bv [{L}], w [{L}], Wc [{C_}, {D}], bc [{C_}])")
+        res = _mil.adam(fun, theta0, lr, n_steps)
+        words = last["words"]
+        return _mil.AttentionMIL(*last["params"], l2, cw, classes, lr, n_steps, seed, res.history, float(res.f), float(np.abs(res.g).max()),
+                                 torch.from_numpy(words["head"]["counts"].copy()).to(dev), words["skipped_rows"], words["skipped_bags"])
+
+    @torch.no_grad()
+    def mil_fit(self, features, offsets, labels, n_classes: int, hidden: int = 64, l2: float = 1e-4, class_weight=None, lr: float = 0.01,
+                n_steps: int = 300, seed: int = 0, init=None, classes=None):
+        """Fit attention-based multiple-instance learning on frozen features -> ``keep_amd.mil.AttentionMIL``.
+
+        ``features``: fp32 ``[N, D]`` (made unit rows first); ``offsets``: integers ``[S + 1]``; ``labels``: integers ``[S]``, -1 for a slide
+        to leave out; ``n_classes`` in 2..64; ``hidden``: a multiple of 16 in 16..128; ``class_weight``: None, ``"balanced"`` (over the
+        labelled bags) or ``[C]`` positive numbers.  The parameters live on the host in float64 and full-batch Adam (``lr``, ``n_steps``)
+        runs there from initial values drawn by a counter-based generator of ``seed`` (or from ``init``, an ``AttentionMIL`` or the five
+        arrays); every evaluation is one pass on the device and one read of the integer sums.  Two fits give the same bits, and
+        :meth:`mil_fit_batches` over any split of the same bags gives them too."""
+        C_, L = _probe.check_n_classes(n_classes), _mil.check_hidden(hidden)
+        l2, _, _ = _probe.check_fit(l2, 1.0, 0)
+        lr, n_steps = _mil.check_adam(lr, n_steps)
+        classes = check_class_names(classes, C_)
+        bags = self._mil_bags(features, offsets, True)
+        y = self._probe_labels(labels, len(bags[1]) - 1)
+        counts = torch.bincount(y[y >= 0].to(torch.int64), minlength=C_)[:C_] if isinstance(class_weight, str) else None
+        cw = _probe.check_class_weight(class_weight, C_, counts)
+        init = init.params if isinstance(init, _mil.AttentionMIL) else init
+        return self._mil_fit(lambda: ((bags, y),), L, C_, bags[0].shape[1], l2, cw, lr, n_steps, seed, init, classes)
+
+    @torch.no_grad()
+    def mil_fit_batches(self, batches, n_classes: int, dim: int, hidden: int = 64, l2: float = 1e-4, class_weight=None, lr: float = 0.01,
+                        n_steps: int = 300, seed: int = 0, init=None, classes=None):
+        """:meth:`mil_fit` for a cohort that is never resident at once (feature files) -> ``AttentionMIL`` over all the bags.
+        ``batches``: a callable returning an iterable of ``(features fp32 [n_i, dim], offsets [s_i + 1], labels [s_i])`` triples (whole
+        bags: a bag is never split over batches), called once per evaluation (and once more for ``class_weight="balanced"``) and
+        returning the same bags each time, in any order.  The sums are integers and a bag's contribution depends on that bag alone, so
+        the result equals ``mil_fit`` on the concatenation bit for bit."""
+        C_, D, L = _probe.check_n_classes(n_classes), check_dim(dim), _mil.check_hidden(hidden)
+        l2, _, _ = _probe.check_fit(l2, 1.0, 0)
+        lr, n_steps = _mil.check_adam(lr, n_steps)
+        classes = check_class_names(classes, C_)
+        if not callable(batches):
+            raise ValueError(f"batches must be a callable returning (features, offsets, labels) triples, got {type(batches).__name__}")
+        self._ready_device()
+
+        def prepared():
+            for x, o, y in batches():
+                if check_features(x)[1] != D:
+                    raise ValueError(f"a batch has width {x.shape[1]}, dim is {D}")
+                bags = self._mil_bags(x, o, True)
+                yield bags, self._probe_labels(y, len(bags[1]) - 1)
+        counts = None
+        if isinstance(class_weight, str):
+            counts = torch.zeros(C_, dtype=torch.int64, device=self._device)
+            for _, _, y in batches():
+                y = self._probe_labels(y, len(y))
+                counts += torch.bincount(y[y >= 0].to(torch.int64), minlength=C_)[:C_]
+        cw = _probe.check_class_weight(class_weight, C_, counts)
+        init = init.params if isinstance(init, _mil.AttentionMIL) else init
+        return self._mil_fit(prepared, L, C_, D, l2, cw, lr, n_steps, seed, init, classes)
 
     # ------------------------------------------------------------------ nearest neighbours (DESIGN.md section 28)
     def _neighbours(self, keys, k: int, n_bank: int, query_skipped, bank_skipped):

@@ -131,6 +131,39 @@ def linear_probe(model, train_x, train_y, test_x, test_y, n_classes: int, l2: fl
     return out
 
 
+def attention_mil(model, train_bags, train_labels, test_bags, test_labels, n_classes: int, hidden: int = 64, l2: float = 1e-4,
+                  class_weight=None, lr: float = 0.01, n_steps: int = 300, fit_seed: int = 0, n_boot: int = 1000, seed: int = 0,
+                  roc: bool = True) -> dict:
+    """The slide-level supervised protocol on frozen features, attention-based multiple-instance learning:
+    ``KEEPModel.mil_fit`` on the training slides, then ``mil_predict`` on the test slides -> :func:`linear_probe`'s dict with ``mil`` (the
+    ``keep_amd.mil.AttentionMIL``) in place of ``probe`` and ``attention`` (fp32 ``[N_test]``: the test tiles' weights within their slide)
+    beside it.  ``train_bags`` / ``test_bags``: ``(features fp32 [N, D], offsets [S + 1])`` pairs, ``*_labels``: integers ``[S]``, -1 for a
+    slide to leave out.  ``skipped`` counts the test slides without a kept tile; they are in no metric."""
+    from . import bootstrap
+    m = _engine(model)
+    mil = m.mil_fit(train_bags[0], train_bags[1], train_labels, n_classes, hidden=hidden, l2=l2, class_weight=class_weight, lr=lr, n_steps=n_steps,
+                    seed=fit_seed)
+    C = mil.n_classes
+    labels, probs, attention, _ = m.mil_predict(mil, test_bags[0], test_bags[1])
+    truth = m._probe_labels(test_labels, int(labels.shape[0]))
+    if int(truth.max()) >= C or int(truth.min()) < -1:
+        raise ValueError(f"test labels must lie in -1..{C - 1}")
+    keep = (labels >= 0) & (truth >= 0)
+    t, p = truth[keep].to(torch.int64), labels[keep].to(torch.int64)
+    if t.numel() == 0:
+        raise ValueError("no labelled test slide is kept")
+    conf = torch.bincount(t * C + p, minlength=C * C).reshape(C, C).cpu().numpy()
+    out = dict(mil=mil, labels=labels, probs=probs, attention=attention, confusion=conf, balanced_accuracy=float(bootstrap.balanced_accuracy(conf)),
+               weighted_f1=weighted_f1_from_confusion(conf), skipped=int((labels < 0).sum()), balanced_accuracy_ci=None,
+               weighted_f1_ci=None, ovr_roc=None)
+    if n_boot > 0 and C <= 16:
+        out["balanced_accuracy_ci"] = m.bootstrap_metric(t, p, C, "balanced_accuracy", n_boot, seed)
+        out["weighted_f1_ci"] = m.bootstrap_metric(t, p, C, "weighted_f1", n_boot, seed)
+    if n_boot > 0 and roc:
+        out["ovr_roc"] = m.bootstrap_ovr_roc(probs[keep], t, n_boot, seed)
+    return out
+
+
 def knn_probe(model, train_x, train_y, test_x, test_y, n_classes: int, k: int = 20, weights: str = "softmax", temperature: float = 0.07,
               n_boot: int = 1000, seed: int = 0, roc: bool = True) -> dict:
     """The kNN-probe protocol on frozen features, :func:`linear_probe`'s non-parametric twin: every test

@@ -670,6 +670,28 @@ def probe_map(probe, tile_features, tile_coords, downsample, shape, patch_size=2
     return m.class_raster(coords, probs[keep], patch_size, downsample, shape, origin, classes=classes)
 
 
+def mil_attention_map(mil, tile_features, tile_coords, downsample, shape, patch_size=256, origin=(0, 0), model=None):
+    """The learned attention of one slide as a heatmap: the slide's tiles are one bag, every tile's attention is
+    divided by the bag's largest and rasterised by ``KEEPModel.tile_raster`` -> ``keep_amd.heatmap.TileRaster`` for ``render_heatmap``,
+    ``smooth_raster`` and ``mask_regions``.  ``mil``: a ``keep_amd.mil.AttentionMIL`` (of ``KEEPModel.mil_fit``) or ``(V, bv, w, Wc, bc)``.
+    Skipped tiles (a non-finite feature) are not rasterised."""
+    from .cluster import check_features
+    from .heatmap import check_raster_args
+    check_raster_args(patch_size, downsample, shape, origin)
+    f = tile_features.squeeze(0) if isinstance(tile_features, torch.Tensor) and tile_features.dim() == 3 else tile_features
+    N, _ = check_features(f)
+    coords = tile_coords if isinstance(tile_coords, torch.Tensor) else torch.as_tensor(np.asarray(tile_coords))
+    if tuple(coords.shape) != (N, 2):
+        raise ValueError(f"tile_coords must be [{N}, 2] beside {N} feature rows, got shape {tuple(coords.shape)}")
+    m = _engine(model, tile_features)
+    out = m.mil_forward(f, np.array([0, N], np.int64), mil)
+    keep = out["scores"] > float("-inf")
+    a = out["attention"][keep]
+    if a.numel() == 0:
+        raise ValueError("every tile of the slide is skipped: there is no attention to draw")
+    return m.tile_raster(coords.to(m._device)[keep], a / a.max(), patch_size, downsample, shape, origin)
+
+
 def knn_map(train_features, train_labels, n_classes, tile_features, tile_coords, downsample, shape, patch_size=256, origin=(0, 0), k=20,
             weights="softmax", temperature=0.07, vote=False, classes=None, model=None):
     """The example-based morphology map: every tile's ``k`` nearest labelled training tiles vote for its class
