@@ -12,6 +12,14 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define KEEP_WAVE 64
 
+// MFMA shape of the plain (not fp4-compensated) K loops of gemm_f16_v2.hip, and of the ceiling probe (keep_mfma_probe): 32 = v_mfma_f32_32x32x16_f16, 16 = v_mfma_f32_16x16x32_f16.  Same cycles per FLOP, same 12 ds_read_b128 per K tile
+// and wave; under load the chip holds a higher clock on the 16 shape (profiles/mfma_shape_ladder.txt, profiles/ab_mfma_shape.txt).  A build-time property
+// (KEEP_BUILD_DEFINES=-DKEEP_MFMA_SHAPE=32 for the other arm of an A/B); the compensated kernels stay on 32x32x16, whose accumulator layout their MX-fp4 phase shares.
+#ifndef KEEP_MFMA_SHAPE
+#define KEEP_MFMA_SHAPE 16
+#endif
+static_assert(KEEP_MFMA_SHAPE == 16 || KEEP_MFMA_SHAPE == 32, "KEEP_MFMA_SHAPE: 16 (16x16x32) or 32 (32x32x16)");
+
 // fp16 has 65504 as its largest finite value: saturate instead of producing inf
 // (ViT residual streams can carry outlier channels; the stream itself stays fp32).
 // hi/lo split used by the "strict" (3-pass) precision mode: x ~= hi + lo with

@@ -82,7 +82,8 @@ extern "C" {
 int keep_op_linear(keep_handle* h, const float* a, const float* w, const float* bias, const float* ls, const float* resid,
                    int64_t M, int64_t N, int64_t K, int epi, int split, float* out, void* stream) {
     if (!h || !a || !w || !bias || !out) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
-    if (M < 1 || N % 128 || N < 128 || K < 64 || K % 32) return h->fail(KEEP_EUNSUPPORTED, "linear needs N%%128==0 and K%%32==0");
+    // K = 32 is a single K step: the LDS-DMA kernels take it, the small-M split-K kernels need two -- so only on a handle that has them switched off
+    if (M < 1 || N % 128 || N < 128 || K < 32 || (K < 64 && h->tune.gemm_skinny_m > 0) || K % 32) return h->fail(KEEP_EUNSUPPORTED, "linear needs N%%128==0 and K%%32==0");
     if (epi != EPI_F16 && epi != EPI_GELU_F16 && epi != EPI_RESID_LS && epi != EPI_RESID_F32) return h->fail(KEEP_EINVAL, "epilogue %d", epi);
     if ((epi == EPI_RESID_LS && (!ls || !resid)) || (epi == EPI_RESID_F32 && !resid)) return h->fail(KEEP_EINVAL, "missing ls/resid");
     const bool comp = split == 2 || split == 3;          // 3: the W_lo term only (K >= 512)
@@ -110,6 +111,7 @@ int keep_op_linear(keep_handle* h, const float* a, const float* w, const float* 
     } else if (epi == EPI_RESID_LS) {
         HIPCHK(h, hipMemcpyAsync(out, resid, M * N * sizeof(float), hipMemcpyDeviceToDevice, s));
         p.resid = out;
+        p.impl_hint = h->proj_impl;      // as the image tower's proj: option proj_impl picks the 256 x 128 kernel where the launcher admits it
         launch_rc = launch_gemm_f16(p, epi, s);
     } else {
         p.resid = const_cast<float*>(resid); p.out_f32 = out;
@@ -299,12 +301,16 @@ int keep_op_attention_rollout_step(keep_handle* h, const float* qkv, int64_t B, 
     return check_launch(h, "op_attention_rollout_step");
 }
 
-// Matrix-pipe ceiling probe (keep_mfma_probe): no memory traffic inside the loop; every wave holds 2 A and 4 B fragments of the caller's data in registers and
-// issues 8 independent v_mfma_f32_32x32x16_f16 per iteration (all (i, j) pairs: the pipe's inputs change with every instruction); one 8-wave workgroup per CU,
-// two waves per SIMD, as the GEMM kernels run.
+// Matrix-pipe ceiling probe (keep_mfma_probe): no memory traffic inside the loop; every wave holds fragments of the caller's data in registers and issues
+// independent MFMAs on a 128 x 64 output tile (the pipe's inputs change with every instruction); one 8-wave workgroup per CU, two waves per SIMD, as the GEMM
+// kernels run -- and on the MFMA shape their plain K loops are built with (KEEP_MFMA_SHAPE), so the ceiling is the ceiling of the loop in use.
+//   32: 2 A x 4 B fragments, 8 v_mfma_f32_32x32x16_f16 per iteration (all (i, j) pairs)
+//   16: 8 A x 4 B fragments (6 of the thread's own, 6 of the thread one wave on), 16 v_mfma_f32_16x16x32_f16 per iteration: the same FLOPs per iteration
 __global__ __launch_bounds__(512, 2) void mfma_probe_kernel(const f16x8* __restrict__ src, float* __restrict__ sink, int iters) {
-    f16x8 a[2], b[4];
     const int t = blockIdx.x * 512 + threadIdx.x;
+    float v = 0.f;
+#if KEEP_MFMA_SHAPE == 32
+    f16x8 a[2], b[4];
 #pragma unroll
     for (int i = 0; i < 2; ++i) a[i] = src[(size_t)t * 6 + i];
 #pragma unroll
@@ -320,11 +326,36 @@ __global__ __launch_bounds__(512, 2) void mfma_probe_kernel(const f16x8* __restr
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i * 4 + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], acc[i * 4 + j], 0, 0, 0);
     }
-    float v = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) v += acc[i][r];
+#else
+    f16x8 a[8], b[4];
+    const int t2 = (t + 64) % ((int)gridDim.x * 512);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) a[i] = src[(size_t)t * 6 + i];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) a[6 + i] = src[(size_t)t2 * 6 + i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) b[i] = src[(size_t)t2 * 6 + 2 + i];
+    f32x4 acc[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[i][r] = 0.f;
+    // two iterations per trip: all 8 A fragments against all of B = 32 MFMAs, the FLOPs of 16 of the 32 shape (an odd count runs one iteration more)
+    for (int it = 0; it < iters; it += 2) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[j], a[i], acc[i * 4 + j], 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < 32; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v += acc[i][r];
+#endif
     sink[t] = v;
 }
 
