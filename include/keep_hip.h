@@ -619,6 +619,52 @@ int keep_topk_unpack(keep_handle* h, const uint64_t* keys, int64_t Nq, int k, in
 int keep_knn_vote(keep_handle* h, const uint64_t* keys, int64_t Nq, int k, const int32_t* bank_labels, int64_t n_bank, int64_t C, int mode,
                   float temperature, float* probs_out, int32_t* label_out, float* margin_out, int64_t* skipped, void* stream);
 
+/* ---- feature PCA ------------------------------------------------------------------
+ * Replaces: nothing in the reference, which never looks at the feature space itself; on this engine xc = x - x.mean(0); xc.T @ xc in
+ * torch, which reads the features twice, materialises xc, sums in an order the library picks and loses the small eigenvalues to the
+ * features' common mean.  features fp32 [N,D] row-major unit rows, 16-byte aligned; 1 <= N <= 2^22 per call, D a multiple of 16 in
+ * 16 .. 1024; at most 2^24 rows may be added into one set of accumulators.  Anything else is KEEP_EINVAL and nothing is launched.  A
+ * row holding a non-finite value or an element with |x| > 1 is skipped exactly as in keep_cluster_assign: in no sum, one added to
+ * *skipped.  No host synchronisation.
+ *
+ * keep_pca_moments: sum int64 [D] += llrint(x_d 2^30) per kept row and column (every term rounded before it is added: the fixed
+ * point of keep_cluster_assign's sums), count int64 [1] += the kept rows.  gram int64 [D,D] (may be NULL: sum and count alone): the
+ * rows of the call are cut from its row 0 into chunks of KEEP_PCA_CHUNK rows; per chunk and word acc = the fp32
+ * v_mfma_f32_16x16x4_f32 chain of a_id a_ie over the chunk's rows in row order, a_i = fp32(x_i - centre) (one fp32 subtraction per
+ * element; a skipped row is a zero row; the tail padded with zero rows to a multiple of 4), and gram[d,e] += llrint(acc 2^32): one
+ * rounding per chunk and word, one no-return 64-bit atomic.  centre: fp32 [D], 16-byte aligned, |c_d| <= 1 (THE CALLER'S
+ * precondition, not checked on the device), or NULL for zero.  Only the 16 x 16 tiles with tile row <= tile column are written,
+ * the diagonal tiles in full (and symmetric bit for bit); the words below are never touched.  |a| <= 2, so |acc| <= 4 x 512 =
+ * 2^11, a chunk adds at most 2^43 to a word and the 2^15 chunks of 2^24 rows at most 2^58.  sum, count, gram, skipped: int64, 8-byte
+ * aligned, on the device; sum and count are required, skipped may be NULL.  The call ALWAYS ADDS: the caller zeroes.
+ * THE WORDS OF gram DEPEND ON KEEP_PCA_CHUNK and on where the chunk boundaries fall: both are part of the contract.  They do not
+ * depend on the grid, on how many chunks a workgroup walks, on the order of the calls or on a split of the rows over calls at
+ * multiples of the chunk; sum and count do not depend on the split at all.  groups: 0 (chosen here) or 1 .. 64 chunks walked by
+ * a workgroup before it issues its atomics, the per-chunk rounded integers summed in registers: any value gives the same words
+ * (for measurement, tools/pca_bench.py).  Workspace (one byte per row) comes from the handle's arena.
+ * keep_pca_project: out fp32 [N,k], out[i,j] = fp32(fp32(chain_j(x_i) + bias[j]) * scale[j]) with chain_j the k-ordered fp32 fma chain
+ * of x_i . w_j in keep_cluster_assign's operand flow; components fp32 [k,D], 16-byte aligned, 1 <= k <= 64; bias / scale fp32 [k] or
+ * NULL, and a step whose vector is NULL is not made: with both NULL out[:,j] is the `best` of keep_cluster_assign(features, w_j,
+ * K = 1) bit for bit.  A row's scores depend on that row alone.  A skipped row: a zero row of out, kept_out[i] = 0 (uint8 [N], may be
+ * NULL; 1 for the other rows), one added to *skipped (may be NULL).
+ * keep_class_render_rgb: three planes of a class raster (acc int64 [C,H,W] as keep_heat_accumulate_classes leaves it) as one
+ * colour picture.  planes: three ints ON THE HOST in 0 .. C - 1, for red, green and blue.  With S, c the fields of a plane's word a
+ * pixel is shown iff c > 0 and the mask (uint8 [H,W] or NULL) is set; its channel is v = min(255, (2 255 S + 65535 c) / (2 65535 c))
+ * (the colour index keep_heat_render gives the window [0, 65535]) and out = (alpha v + (256 - alpha) under + 128) >> 8; other pixels
+ * pass `under` through.  thumb / row stride / pixel stride / background_rgb as keep_heat_render; 0 <= alpha <= 256.  out: uint8
+ * [H,W,3] contiguous. */
+#ifndef KEEP_PCA_CHUNK
+#define KEEP_PCA_CHUNK 512
+#endif
+int keep_pca_chunk(void);
+int keep_pca_moments(keep_handle* h, const float* features, int64_t N, int64_t D, const float* centre, int64_t* sum, int64_t* count,
+                     int64_t* gram, int64_t* skipped, int groups, void* stream);
+int keep_pca_project(keep_handle* h, const float* features, int64_t N, int64_t D, const float* components, int64_t k, const float* bias,
+                     const float* scale, float* out, unsigned char* kept_out, int64_t* skipped, void* stream);
+int keep_class_render_rgb(keep_handle* h, const int64_t* acc, int64_t C, int64_t H, int64_t W, const int* planes, const unsigned char* thumb,
+                          int64_t row_stride_bytes, int pix_stride, int background_rgb, const unsigned char* mask, int alpha,
+                          unsigned char* out, void* stream);
+
 /* Region outlines: the boundary rings of a label image, with holes, and an outline drawn into an image.
  * Replaces: the contour polygons with a hole list per contour that CLAM's segmentTissue hands back (cv2.findContours with
  * RETR_CCOMP; the step of README.md:74) and the polygon annotation a viewer takes a lesion of WSI_evaluation/segment_utils.py's

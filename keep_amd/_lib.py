@@ -82,6 +82,10 @@ SIGNATURES = {
     "keep_topk_merge": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "keep_topk_unpack": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "keep_knn_vote": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "keep_pca_chunk": (_i32, []),
+    "keep_pca_moments": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "keep_pca_project": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "keep_class_render_rgb": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
     "keep_heat_mean":(_i32, [_vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "keep_heat_render": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "keep_heat_smooth": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp]),

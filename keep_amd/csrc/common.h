@@ -438,6 +438,20 @@ void launch_mil_backward(const float* x, int D, const int32_t* chunks, int n_chu
                          const float* Wc, int C, const float* cw, const float* w, int L, const float* s_in, const float* a, const float* z,
                          const float* hbuf, float* dz, float* u, float* ds, int64_t* gV, int64_t* gbv, int64_t* gw, hipStream_t s);
 
+// Feature PCA (pca.hip).  x: fp32 [N][D] unit rows with the limits of the clustering above.
+constexpr int PCA_MAX_K = 64;
+constexpr int PCA_MAX_GROUPS = 64;                      // chunks a workgroup of the Gram kernel walks
+// sum int64 [D], count int64 [1], gram int64 [D][D] (null: sum and count alone), skipped (may be null) are ADDED into; centre fp32 [D] or
+// null; kept_ws: N bytes of workspace (the rows' flags); groups: 0 (chosen there) or the chunks per workgroup
+void launch_pca_moments(const float* x, int N, int D, const float* centre, int64_t* sum, int64_t* count, int64_t* gram, int64_t* skipped,
+                        unsigned char* kept_ws, int groups, hipStream_t s);
+// w fp32 [K][D]; bias / scale fp32 [K] or null; out fp32 [N][K]; kept_out uint8 [N] and skipped (ADDED into) may be null
+void launch_pca_project(const float* x, int N, int D, const float* w, int K, const float* bias, const float* scale, float* out,
+                        unsigned char* kept_out, int64_t* skipped, hipStream_t s);
+// acc: the class raster [C][h][w]; planes: three plane indices on the host; thumb / mask may be null
+void launch_class_render_rgb(const int64_t* acc, int h, int w, const int* planes, const unsigned char* thumb, int64_t row_stride, int ps,
+                             unsigned bg, const unsigned char* mask, int alpha, unsigned char* out, hipStream_t s);
+
 // Nearest neighbours (neighbours.hip).  q: fp32 [Nq][D] and bank: fp32 [M][D] unit rows with the limits of the
 // clustering above; keys: uint64 [Nq][k] descending lists of KEEP_TOPK_KEY words, 1 <= k <= TOPK_MAX_K.
 constexpr int TOPK_MAX_K = 64;                          // a list is one key per lane of a wave

@@ -1197,3 +1197,64 @@ int keep_pen_mask(keep_handle* h, const unsigned char* thumb, int64_t H, int64_t
 }
 
 }  // extern "C"
+
+// Feature PCA (pca.hip)
+extern "C" {
+
+int keep_pca_chunk(void) { return KEEP_PCA_CHUNK; }
+
+int keep_pca_moments(keep_handle* h, const float* features, int64_t N, int64_t D, const float* centre, int64_t* sum, int64_t* count,
+                     int64_t* gram, int64_t* skipped, int groups, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = cluster_shape_check(h, "pca_moments", N, D, 1)) return rc;
+    if (!features || ((uintptr_t)features & 15)) return h->fail(KEEP_EINVAL, "pca_moments: features null or not 16-byte aligned");
+    if ((uintptr_t)centre & 15) return h->fail(KEEP_EINVAL, "pca_moments: centre is not 16-byte aligned");
+    if (!sum || !count) return h->fail(KEEP_EINVAL, "pca_moments: null sum or count");
+    if (((uintptr_t)sum & 7) || ((uintptr_t)count & 7) || ((uintptr_t)gram & 7) || ((uintptr_t)skipped & 7))
+        return h->fail(KEEP_EINVAL, "pca_moments: an accumulator is not 8-byte aligned");
+    if (groups < 0 || groups > PCA_MAX_GROUPS) return h->fail(KEEP_EINVAL, "pca_moments: groups %d (0 = chosen here, 1 .. %d)", groups, PCA_MAX_GROUPS);
+    KEEP_ON_DEVICE(h);
+    if (int rc = ensure_arena(h, align_up((size_t)N))) return rc;
+    launch_pca_moments(features, (int)N, (int)D, centre, sum, count, gram, skipped, (unsigned char*)h->arena, groups, (hipStream_t)stream);
+    return check_launch(h, "pca_moments");
+}
+
+int keep_pca_project(keep_handle* h, const float* features, int64_t N, int64_t D, const float* components, int64_t k, const float* bias,
+                     const float* scale, float* out, unsigned char* kept_out, int64_t* skipped, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = cluster_shape_check(h, "pca_project", N, D, 1)) return rc;
+    if (k < 1 || k > PCA_MAX_K) return h->fail(KEEP_EINVAL, "pca_project: k = %lld (1 .. 64)", (long long)k);
+    if (!features || !components || !out) return h->fail(KEEP_EINVAL, "pca_project: null features, components or output");
+    if (((uintptr_t)features & 15) || ((uintptr_t)components & 15)) return h->fail(KEEP_EINVAL, "pca_project: features / components not 16-byte aligned");
+    if (((uintptr_t)bias & 3) || ((uintptr_t)scale & 3) || ((uintptr_t)out & 3) || ((uintptr_t)skipped & 7))
+        return h->fail(KEEP_EINVAL, "pca_project: bias, scale or an output is not aligned to its element size");
+    KEEP_ON_DEVICE(h);
+    launch_pca_project(features, (int)N, (int)D, components, (int)k, bias, scale, out, kept_out, skipped, (hipStream_t)stream);
+    return check_launch(h, "pca_project");
+}
+
+int keep_class_render_rgb(keep_handle* h, const int64_t* acc, int64_t C, int64_t H, int64_t W, const int* planes, const unsigned char* thumb,
+                          int64_t row_stride_bytes, int pix_stride, int background_rgb, const unsigned char* mask, int alpha,
+                          unsigned char* out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (!acc || ((uintptr_t)acc & 7)) return h->fail(KEEP_EINVAL, "class_render_rgb: acc is null or not 8-byte aligned");
+    if (!planes || !out) return h->fail(KEEP_EINVAL, "class_render_rgb: null planes or output");
+    if (C < 1 || C > CLASS_MAX) return h->fail(KEEP_EINVAL, "class_render_rgb: %lld classes (1 .. 64)", (long long)C);
+    if (!pixels_ok(H, W, HEAT_MAX_PIXELS) || C * H * W > HEAT_MAX_PIXELS)
+        return h->fail(KEEP_EINVAL, "class_render_rgb: %lld planes of %lldx%lld pixels (1 <= C H W <= 2^30)", (long long)C, (long long)H, (long long)W);
+    for (int i = 0; i < 3; ++i)
+        if (planes[i] < 0 || planes[i] >= C) return h->fail(KEEP_EINVAL, "class_render_rgb: plane %d outside 0 .. %lld", planes[i], (long long)(C - 1));
+    if (thumb) {
+        if (int rc = pix_stride_check(h, "class_render_rgb", pix_stride)) return rc;
+        if (int rc = row_stride_check(h, "class_render_rgb", W, row_stride_bytes, pix_stride)) return rc;
+    } else if (background_rgb < 0 || background_rgb > 0xFFFFFF) {
+        return h->fail(KEEP_EINVAL, "class_render_rgb: background 0x%x outside [0, 0xFFFFFF]", background_rgb);
+    }
+    if (alpha < 0 || alpha > 256) return h->fail(KEEP_EINVAL, "class_render_rgb: alpha %d outside [0, 256]", alpha);
+    KEEP_ON_DEVICE(h);
+    launch_class_render_rgb(acc, (int)H, (int)W, planes, thumb, row_stride_bytes, pix_stride, (unsigned)background_rgb, mask, alpha, out,
+                            (hipStream_t)stream);
+    return check_launch(h, "class_render_rgb");
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 """The slide-analysis methods of ``KEEPModel``: patch grid and tiles of a region, tissue mask, heatmap raster, percentiles and
-smoothing, region table, outlines, region shape, polygon fill, segmentation evaluation, the subtype map, bootstrap resampling, the linear probe and attention MIL (DESIGN.md sections 10-29).  Thin wrappers of the
+smoothing, region table, outlines, region shape, polygon fill, segmentation evaluation, the subtype map, bootstrap resampling, the linear probe, attention MIL and feature PCA (DESIGN.md sections 10-30).  Thin wrappers of the
 entry points in csrc/slide_api.hip; the argument checks and the numpy references live in the feature modules imported below."""
 from __future__ import annotations
 
@@ -29,6 +29,7 @@ from .region import (MASK_MODES, TILE, TissueMask, TissueSegmentation, check_dow
                      resize_tables, thumbnail_layout, tissue_params)
 from . import mil as _mil
 from . import neighbours as _nb
+from . import pca as _pca
 from . import probe as _probe
 from . import stain as _stain
 from .quality import NCOLS as QUALITY_COLS, MAX_CELLS as QUALITY_MAX_CELLS, QualityGate, TileQuality, check_gate, check_patch, check_rules
@@ -1067,6 +1068,151 @@ class SlideOps:
         cw = _probe.check_class_weight(class_weight, C_, counts)
         init = init.params if isinstance(init, _mil.AttentionMIL) else init
         return self._mil_fit(prepared, L, C_, D, l2, cw, lr, n_steps, seed, init, classes)
+
+    # ------------------------------------------------------------------ feature PCA
+    def _pca_moments(self, x: torch.Tensor, sums, gram: bool = True, groups: int = 0) -> None:
+        self._call("pca_moments", _ptr(x), x.shape[0], x.shape[1], _ptr(sums.centre_dev), _ptr(sums.sum), _ptr(sums.count),
+                   _ptr(sums.gram if gram else None), _ptr(sums.skipped), groups)
+
+    @torch.no_grad()
+    def pca_moments(self, features, sums, normalize=True, groups=0):
+        """The integer moments of the tiles' features, added into ``sums`` (a ``keep_amd.pca.PcaSums``) in one call (DESIGN.md section
+        30) -> ``sums``.  ``features``: fp32 ``[N, D]``, ``1 <= N <= 2^22``, D a multiple of 16 up to 1024; ``normalize`` as in
+        :meth:`cluster_assign`.  ``sums.sum`` and ``sums.count`` are the same words for every order and split of the rows; the words of
+        ``sums.gram`` (about ``sums.centre``) depend on where the chunks of ``keep_pca_chunk()`` rows fall, counted from row 0 of every
+        call, and on nothing else: not on ``groups`` (the chunks a workgroup walks before its atomics; for measurement), the order
+        of the calls or a split at multiples of the chunk.  A tile with a non-finite value or an element beyond 1 in magnitude is
+        in no sum and counted in ``sums.skipped``.  No host synchronisation."""
+        N, D = check_features(features)
+        if not isinstance(sums, _pca.PcaSums):
+            raise ValueError(f"sums must be a PcaSums, got {type(sums).__name__}")
+        sums.check(D)
+        groups = _pca.check_groups(groups)
+        x = self._cluster_features(features, normalize)
+        if sums.buf.device != self._device:
+            raise ValueError(f"the accumulators live on {sums.buf.device}, this engine on {self._device}")
+        sums.claim(N)
+        self._pca_moments(x, sums, True, groups)
+        return sums
+
+    def _pca_fit(self, batches, k: int, D: int, two_pass: bool):
+        """``batches()``: an iterable of prepared device tensors, the same rows in the same order every time it is called."""
+        chunk = _lib.load().keep_pca_chunk()
+
+        def one_pass(sums, gram):
+            prev = None
+            for i, x in enumerate(batches()):
+                if prev is not None:
+                    _pca.check_batch_rows(prev, i - 1, chunk)
+                prev = int(x.shape[0])
+                sums.claim(prev)
+                self._pca_moments(x, sums, gram)
+            if prev is None:
+                raise ValueError("batches() returned no batch (at least one is needed)")
+
+        centre = None
+        if two_pass:
+            first = _pca.PcaSums(D, None, self._device)
+            one_pass(first, False)
+            tail = first.buf.cpu().numpy()                               # the fit's first host synchronisation
+            _pca.check_kept_rows(int(tail[-2]))
+            centre = _pca.centre_from_sums(tail[:D], int(tail[-2]))
+        sums = _pca.PcaSums(D, centre, self._device)
+        one_pass(sums, True)
+        words = torch.cat([sums.sum, sums.gram_full().reshape(-1), sums.count, sums.skipped]).cpu().numpy()
+        return _pca.pca_from_sums(words[:D], words[D:D + D * D].reshape(D, D), int(words[-2]), int(words[-1]), k, centre)
+
+    @torch.no_grad()
+    def pca_fit(self, features, k: int, two_pass=True, normalize=True):
+        """The principal components of the tiles' features -> ``keep_amd.pca.FeaturePCA``.
+
+        ``features``: fp32 ``[N, D]`` as in :meth:`pca_moments`; ``k`` in 1..64.  With ``two_pass`` the first pass over the features takes
+        the integer sum and count alone, the second the Gram about ``fp32(mean)``, so that the shifted-data formula ``(G - n (mu - c)(mu
+        - c)^T) / (n - 1)`` cancels nothing; ``two_pass=False`` is one pass about a zero centre, which loses the small eigenvalues to the
+        features' common mean.  The D x D ``eigh`` runs on the host in float64.  Integer moments: two runs give the same bits, and
+        :meth:`pca_fit_batches` over a split at multiples of ``keep_pca_chunk()`` gives them too.  Fewer than two kept tiles is an
+        error."""
+        N, D = check_features(features)
+        k = _pca.check_k(k, D)
+        x = self._cluster_features(features, normalize)
+        return self._pca_fit(lambda: (x,), k, D, bool(two_pass))
+
+    @torch.no_grad()
+    def pca_fit_batches(self, batches, k: int, dim: int, two_pass=True):
+        """:meth:`pca_fit` for features that are never resident at once -> ``FeaturePCA`` over the concatenation of the batches.
+        ``batches``: a callable returning a fresh iterable of fp32 ``[n_i, dim]`` tensors (made unit rows here), called twice under
+        ``two_pass`` and returning the same rows in the same order each time.  Every batch except the last must hold a multiple of
+        ``keep_pca_chunk()`` rows (a ``ValueError`` otherwise): the chunk boundaries then fall where they fall in the concatenation
+        and the result equals ``pca_fit`` on it bit for bit."""
+        D = check_dim(dim)
+        k = _pca.check_k(k, D)
+        if not callable(batches):
+            raise ValueError(f"batches must be a callable returning the feature tensors, got {type(batches).__name__}")
+        self._ready_device()
+
+        def prepared():
+            for x in batches():
+                if check_features(x)[1] != D:
+                    raise ValueError(f"a batch has width {x.shape[1]}, dim is {D}")
+                yield self._cluster_features(x, True)
+        return self._pca_fit(prepared, k, D, bool(two_pass))
+
+    @torch.no_grad()
+    def pca_transform(self, pca, features, k=None, whiten=False, normalize=True):
+        """The tiles' scores on the first ``k`` components of a ``FeaturePCA`` -> ``(scores fp32 [N, k], kept bool
+        [N])`` on the device.  ``scores[i, j] = fp32(chain_j(x_i) + bias[j])`` with ``chain_j`` the fp32 fma chain of :meth:`cluster_assign`
+        on component j and ``bias[j] = fp32(-(mean . w_j))``; ``whiten`` multiplies by ``fp32(1 / sqrt(lambda_j))``.  A tile's scores
+        depend on that tile alone; a skipped tile gives a zero row and ``kept = False``.  No host synchronisation."""
+        if not isinstance(pca, _pca.FeaturePCA):
+            raise ValueError(f"pca must be a FeaturePCA, got {type(pca).__name__}")
+        N, D = check_features(features)
+        if D != pca.dim:
+            raise ValueError(f"the features have width {D}, the PCA {pca.dim}")
+        k = pca.k if k is None else _pca.check_k(k, pca.k)
+        x = self._cluster_features(features, normalize)
+        w = self._on_device(np.ascontiguousarray(pca.components[:k], np.float32))
+        bias = self._on_device(pca.bias(k))
+        scale = self._on_device(pca.whiten_scale(k)) if whiten else None
+        return self._pca_project(x, w, bias, scale)
+
+    def _pca_project(self, x, w, bias, scale):
+        N, k = x.shape[0], w.shape[0]
+        out = torch.empty((N, k), dtype=torch.float32, device=self._device)
+        kept = torch.empty(N, dtype=torch.uint8, device=self._device)
+        self._call("pca_project", _ptr(x), N, x.shape[1], _ptr(w), k, _ptr(bias), _ptr(scale), _ptr(out), _ptr(kept), _ptr(None))
+        return out, kept.view(torch.bool)
+
+    @torch.no_grad()
+    def render_rgb_map(self, class_raster, thumbnail=None, planes=(0, 1, 2), alpha: float = 0.6, tissue=None,
+                       background=(255, 255, 255)) -> torch.Tensor:
+        """Three planes of a ``ClassRaster`` as one colour picture over the thumbnail -> uint8 [h,w,3] on the
+        device: red, green and blue are the exact means of ``planes`` (0..1 mapped to 0..255 by :meth:`render_heatmap`'s integer
+        division), blended with ``round(256 alpha)``; pixels no tile covers or outside ``tissue`` keep the thumbnail or
+        ``background``.  ``thumbnail`` as in :meth:`render_heatmap`.  Equal to ``keep_amd.pca.render_rgb_numpy`` bit for bit."""
+        if not isinstance(class_raster, ClassRaster):
+            raise ValueError(f"class_raster must be a ClassRaster, got {type(class_raster).__name__}")
+        a, _, _, _, bg = render_args(alpha, (0.0, 1.0), 0.0, background)
+        C_, (h, w) = class_raster.n_classes, class_raster.shape
+        p = _pca.check_planes(planes, C_)
+        x = None
+        if thumbnail is not None:
+            x = torch.from_numpy(thumbnail) if not isinstance(thumbnail, torch.Tensor) else thumbnail
+            if region_layout(x)[:2] != (h, w):
+                raise ValueError(f"thumbnail is {tuple(x.shape[:2])}, the raster {(h, w)}")
+        if tissue is not None:
+            _check_tissue(tissue, class_raster)
+        self._ready_device()
+        self._raster_here(class_raster)
+        ps, row = 3, 0
+        if x is not None:
+            if x.device != self._device:
+                x = x.to(self._device)
+            _, _, ps, row = region_layout(x)
+        md = None if tissue is None else self._on_device(tissue.mask)
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=self._device)
+        self._call("class_render_rgb", _ptr(class_raster.acc), C_, h, w, (C.c_int * 3)(*p), _ptr(x), row, ps, bg[0] | bg[1] << 8 | bg[2] << 16,
+                   _ptr(md), a, _ptr(out))
+        return out
 
     # ------------------------------------------------------------------ nearest neighbours (DESIGN.md section 28)
     def _neighbours(self, keys, k: int, n_bank: int, query_skipped, bank_skipped):

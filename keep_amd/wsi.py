@@ -643,6 +643,54 @@ def cluster_map(tile_features, tile_coords, k_or_centroids, downsample, shape, p
     return raster, res
 
 
+def pca_map(tile_features, tile_coords, k_or_pca, downsample, shape, patch_size=256, origin=(0, 0), components=(0, 1, 2), scale="rank",
+            model=None):
+    """The PCA colour map of a slide: three principal components of the tiles' features as the three planes of a
+    raster -> ``(keep_amd.classmap.ClassRaster, keep_amd.pca.FeaturePCA)``.  ``k_or_pca``: an integer k, which fits
+    ``KEEPModel.pca_fit(tile_features, k)`` on the slide's own tiles, or a ``FeaturePCA`` (of an earlier fit), which only projects: two
+    slides then share one colour space.  ``components``: the three components shown as red, green and blue.  ``scale``: ``"rank"`` maps
+    every component to its percentile among the slide's tiles (``KEEPModel.percentiles``); a ``(lo, hi)`` pair of length-3 sequences clips
+    linearly, ``(score - lo) / (hi - lo)`` into [0, 1].  Skipped tiles (a non-finite feature) are in no plane.
+    ``KEEPModel.render_rgb_map`` paints the raster."""
+    from .cluster import check_features
+    from .heatmap import check_raster_args
+    from .pca import FeaturePCA, check_k
+    check_raster_args(patch_size, downsample, shape, origin)
+    f = tile_features.squeeze(0) if isinstance(tile_features, torch.Tensor) and tile_features.dim() == 3 else tile_features
+    N, D = check_features(f)
+    coords = tile_coords if isinstance(tile_coords, torch.Tensor) else torch.as_tensor(np.asarray(tile_coords))
+    if tuple(coords.shape) != (N, 2):
+        raise ValueError(f"tile_coords must be [{N}, 2] beside {N} feature rows, got shape {tuple(coords.shape)}")
+    given = isinstance(k_or_pca, FeaturePCA)
+    K = k_or_pca.k if given else check_k(k_or_pca, D)
+    comp = tuple(int(c) for c in components)
+    if len(comp) != 3 or any(c < 0 or c >= K for c in comp):
+        raise ValueError(f"components must be three component indices in 0..{K - 1}, got {components!r}")
+    linear = None
+    if not isinstance(scale, str):
+        if len(scale) != 2 or len(scale[0]) != 3 or len(scale[1]) != 3:
+            raise ValueError(f'scale must be "rank" or a (lo, hi) pair of length-3 sequences, got {scale!r}')
+        linear = (np.asarray(scale[0], np.float32), np.asarray(scale[1], np.float32))
+        if not bool((linear[1] > linear[0]).all()):
+            raise ValueError(f"scale needs lo < hi for every component, got {scale!r}")
+    elif scale != "rank":
+        raise ValueError(f'scale must be "rank" or a (lo, hi) pair of length-3 sequences, got {scale!r}')
+    m = _engine(model, tile_features)
+    pca = k_or_pca if given else m.pca_fit(f, K)
+    scores, kept = m.pca_transform(pca, f, K)
+    nan = torch.full((), float("nan"), dtype=torch.float32, device=m._device)
+    values = torch.empty((N, 3), dtype=torch.float32, device=m._device)
+    for ch, c in enumerate(comp):
+        s = torch.where(kept, scores[:, c], nan)                        # a skipped tile is no part of the population
+        if linear is None:
+            values[:, ch] = m.percentiles(s)
+        else:
+            lo, hi = float(linear[0][ch]), float(linear[1][ch])
+            values[:, ch] = torch.where(kept, ((s - lo) / (hi - lo)).clamp(0.0, 1.0), nan)
+    raster = m.class_raster(coords.to(m._device), values, patch_size, downsample, shape, origin, classes=[f"PC{c + 1}" for c in comp])
+    return raster, pca
+
+
 def probe_map(probe, tile_features, tile_coords, downsample, shape, patch_size=256, origin=(0, 0), vote=False, classes=None, model=None):
     """The supervised morphology map: a fitted linear probe's probabilities of every tile rasterised in slide
     geometry -> ``keep_amd.classmap.ClassRaster``.  ``probe``: a ``keep_amd.probe.LinearProbe`` (of ``KEEPModel.probe_fit``) or a
