@@ -1116,6 +1116,11 @@ int keep_mfma_probe(keep_handle* h, const void* operands_f16, float* sink, int i
 /* diagnostics: with option "gemm_dbg"=1 every GEMM launch records, per workgroup, four shader-clock
  * stamps [start, first K tile landed, main loop end, end]; this copies them to host memory. */
 int keep_debug_read(keep_handle* h, void* host_dst, int64_t bytes);
+/* test hook: fills the handle's scratch memory -- the whole workspace arena (keep_workspace_bytes) and keep_classify's buffer -- with the 32-bit `word`
+ * on `stream`, and writes the number of bytes filled to *bytes_out (0, and still KEEP_OK, on a handle that has carved nothing yet).  It allocates and
+ * frees nothing.  No entry point may read a workspace byte it has not written in the same call, so a result must not depend on `word`
+ * (tests/test_workspace_poison_gpu.py); production code has no use for it. */
+int keep_debug_fill_workspace(keep_handle* h, uint32_t word, int64_t* bytes_out, void* stream);
 
 #ifdef __cplusplus
 }

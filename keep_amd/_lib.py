@@ -140,6 +140,7 @@ SIGNATURES = {
     "keep_clock_probe": (_i32, [_vp, _i32, _vp, _vp]),
     "keep_mfma_probe": (_i32, [_vp, _vp, _vp, _i32, C.POINTER(C.c_double), _vp]),
     "keep_debug_read": (_i32, [_vp, _vp, _i64]),
+    "keep_debug_fill_workspace": (_i32, [_vp, C.c_uint32, C.POINTER(_i64), _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

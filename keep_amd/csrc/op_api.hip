@@ -517,6 +517,17 @@ int keep_debug_read(keep_handle* h, void* host_dst, int64_t bytes) {
     return KEEP_OK;
 }
 
+int keep_debug_fill_workspace(keep_handle* h, uint32_t word, int64_t* bytes_out, void* stream) {
+    if (!h || !bytes_out) return h ? h->fail(KEEP_EINVAL, "null pointer") : KEEP_EINVAL;
+    KEEP_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t na = h->arena ? h->arena_bytes / 4 : 0, nc = h->cls_buf ? h->cls_bytes / 4 : 0;     // whole words: both sizes are multiples of 256
+    if (na) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->arena, (int)word, na, s));
+    if (nc) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->cls_buf, (int)word, nc, s));
+    *bytes_out = (int64_t)(na + nc) * 4;
+    return KEEP_OK;
+}
+
 int keep_mfma_probe(keep_handle* h, const void* operands_f16, float* sink, int iters, double* flops_out, void* stream) {
     if (!h || !operands_f16 || !sink || iters < 1 || iters > (1 << 24)) return h ? h->fail(KEEP_EINVAL, "bad mfma_probe arguments") : KEEP_EINVAL;
     KEEP_ON_DEVICE(h);
