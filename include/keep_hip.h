@@ -665,6 +665,40 @@ int keep_class_render_rgb(keep_handle* h, const int64_t* acc, int64_t C, int64_t
                           int64_t row_stride_bytes, int pix_stride, int background_rgb, const unsigned char* mask, int alpha,
                           unsigned char* out, void* stream);
 
+/* ---- exact t-SNE of tile features --------------------------------------------------
+ * Replaces: nothing in the reference; on this engine a trip to scikit-learn or openTSNE on the host.  Every buffer is the caller's: no
+ * workspace comes from the handle.  1 <= N <= 2^20 rows; anything else named below is KEEP_EINVAL and nothing is launched.  No host
+ * synchronisation.
+ *
+ * keep_tsne_affinities: neighbour lists (index int64 [N,k], score fp32 [N,k], count int32 [N] as keep_topk_unpack leaves them, 1 <= k <=
+ * 64) -> p_out fp32 [N,k], the conditional probabilities p_{j|i} at `perplexity` (finite, > 1).  Slot j of a row is filled iff j <
+ * count and index >= 0; d_j = max(0, 2 - 2 s_j) over the filled slots, shifted by the row's minimum; beta by 64 bisection steps on the
+ * entropy of p_j ~ exp(-beta d_j), all of them taken; p_out is 0 in an empty slot and a row with fewer than two filled slots is a zero
+ * row.  A row's bits depend on that row alone.
+ * keep_tsne_repulsion: y fp32 [N,2] (8-byte aligned) -> partials fp32 [n_seg, N, 4] (16-byte aligned), n_seg = ceil(N /
+ * KEEP_TSNE_SEGMENT): for row i and segment s the sums over j in the segment, j != i, ascending, of w^2 (y_i - y_j) (words 0 and 1)
+ * and of w (word 2), w = rcp(1 + |y_i - y_j|^2) in fp32 with the hardware reciprocal; word 3 is 0.  Every word is written.  THE WORDS
+ * DEPEND ON KEEP_TSNE_SEGMENT and on nothing else about the launch or N.
+ * keep_tsne_step: the rest of an iteration at y, two launches.  Adds a row's partials in segment order into rz fp32 [N,4] (scratch,
+ * 16-byte aligned; every word written) and sums[0] += llrint(Z_i 2^22) per row; then per row the attractive force A = sum val w (y_i -
+ * y_j) over its CSR entries (row_ptr int32 [N+1], col int32 [nnz], val fp32 [nnz]; an entry whose column lies outside 0 .. N - 1 is no
+ * edge) in stored order and g = 4 (exaggeration A - R / Z), Z = fp32(sums[0] 2^-22); grad_out fp32 [N,2] (may be NULL) takes g.  With
+ * update / gains / y_out (fp32 [N,2] each; all three or none; y_out must not be y): gain += 0.2 where g and update differ in sign, x 0.8
+ * otherwise, floor 0.01; update = momentum update - lr gain g; y_out = y + update.  stats != 0: sums[1] += llrint(2^40 row sum of val
+ * (log val + log Z - log w)) and sums[2] += llrint(2^50 |g_i|^2) per row.  sums: int64 [3], 8-byte aligned, ALWAYS ADDED into: the
+ * caller zeroes; integer adds of terms rounded before they are added, so the words do not depend on the order.  0 <= exaggeration <= 32
+ * keeps sums[2] inside 63 bits. */
+#ifndef KEEP_TSNE_SEGMENT
+#define KEEP_TSNE_SEGMENT 2048
+#endif
+int keep_tsne_segment(void);
+int keep_tsne_affinities(keep_handle* h, const int64_t* index, const float* score, const int32_t* count, int64_t N, int k, float perplexity,
+                         float* p_out, void* stream);
+int keep_tsne_repulsion(keep_handle* h, const float* y, int64_t N, float* partials, void* stream);
+int keep_tsne_step(keep_handle* h, const float* y, int64_t N, const float* partials, const int32_t* row_ptr, const int32_t* col,
+                   const float* val, int64_t nnz, float exaggeration, float momentum, float lr, int stats, int64_t* sums, float* rz,
+                   float* grad_out, float* update, float* gains, float* y_out, void* stream);
+
 /* Region outlines: the boundary rings of a label image, with holes, and an outline drawn into an image.
  * Replaces: the contour polygons with a hole list per contour that CLAM's segmentTissue hands back (cv2.findContours with
  * RETR_CCOMP; the step of README.md:74) and the polygon annotation a viewer takes a lesion of WSI_evaluation/segment_utils.py's

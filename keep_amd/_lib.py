@@ -86,6 +86,10 @@ SIGNATURES = {
     "keep_pca_moments": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "keep_pca_project": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "keep_class_render_rgb": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "keep_tsne_segment": (_i32, []),
+    "keep_tsne_affinities": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp]),
+    "keep_tsne_repulsion": (_i32, [_vp, _vp, _i64, _vp, _vp]),
+    "keep_tsne_step": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "keep_heat_mean":(_i32, [_vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "keep_heat_render": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "keep_heat_smooth": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp]),

@@ -452,6 +452,19 @@ void launch_pca_project(const float* x, int N, int D, const float* w, int K, con
 void launch_class_render_rgb(const int64_t* acc, int h, int w, const int* planes, const unsigned char* thumb, int64_t row_stride, int ps,
                              unsigned bg, const unsigned char* mask, int alpha, unsigned char* out, hipStream_t s);
 
+// Exact t-SNE (tsne.hip).  Every buffer is the caller's; y: fp32 [N][2], N <= TSNE_MAX_ROWS.
+constexpr int TSNE_MAX_ROWS = 1 << 20;
+constexpr float TSNE_MAX_EXAGGERATION = 32.f;           // keeps the squared gradient norm's word inside 63 bits
+// index int64 [N][k], score fp32 [N][k], count int32 [N] (the lists of topk_unpack) -> p_out fp32 [N][k]
+void launch_tsne_affinities(const int64_t* index, const float* score, const int32_t* count, int N, int k, float perplexity, float* p_out,
+                            hipStream_t s);
+// partials fp32 [ceil(N / KEEP_TSNE_SEGMENT)][N][4]
+void launch_tsne_repulsion(const float* y, int N, float* partials, hipStream_t s);
+// sums int64 [3] is ADDED into; rz fp32 [N][4] scratch; grad_out may be null; update / gains / y_out all null or none
+void launch_tsne_step(const float* y, int N, const float* partials, const int32_t* row_ptr, const int32_t* col, const float* val, int nnz,
+                      float exaggeration, float momentum, float lr, int stats, int64_t* sums, float* rz, float* grad_out, float* update,
+                      float* gains, float* y_out, hipStream_t s);
+
 // Nearest neighbours (neighbours.hip).  q: fp32 [Nq][D] and bank: fp32 [M][D] unit rows with the limits of the
 // clustering above; keys: uint64 [Nq][k] descending lists of KEEP_TOPK_KEY words, 1 <= k <= TOPK_MAX_K.
 constexpr int TOPK_MAX_K = 64;                          // a list is one key per lane of a wave

@@ -1258,3 +1258,65 @@ int keep_class_render_rgb(keep_handle* h, const int64_t* acc, int64_t C, int64_t
 }
 
 }  // extern "C"
+
+// Exact t-SNE (tsne.hip)
+extern "C" {
+
+int keep_tsne_segment(void) { return KEEP_TSNE_SEGMENT; }
+
+static int tsne_rows_check(keep_handle* h, const char* who, int64_t N) {
+    if (N < 1 || N > TSNE_MAX_ROWS) return h->fail(KEEP_EINVAL, "%s: %lld rows (1 .. 2^20)", who, (long long)N);
+    return KEEP_OK;
+}
+
+int keep_tsne_affinities(keep_handle* h, const int64_t* index, const float* score, const int32_t* count, int64_t N, int k, float perplexity,
+                         float* p_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = tsne_rows_check(h, "tsne_affinities", N)) return rc;
+    if (k < 1 || k > TOPK_MAX_K) return h->fail(KEEP_EINVAL, "tsne_affinities: k = %d (1 .. 64)", k);
+    if (!(perplexity > 1.f) || !std::isfinite(perplexity)) return h->fail(KEEP_EINVAL, "tsne_affinities: perplexity %g (finite, > 1)", (double)perplexity);
+    if (!index || !score || !count || !p_out) return h->fail(KEEP_EINVAL, "tsne_affinities: null index, score, count or output");
+    if (((uintptr_t)index & 7) || ((uintptr_t)score & 3) || ((uintptr_t)count & 3) || ((uintptr_t)p_out & 3))
+        return h->fail(KEEP_EINVAL, "tsne_affinities: a buffer is not aligned to its element size");
+    KEEP_ON_DEVICE(h);
+    launch_tsne_affinities(index, score, count, (int)N, k, perplexity, p_out, (hipStream_t)stream);
+    return check_launch(h, "tsne_affinities");
+}
+
+int keep_tsne_repulsion(keep_handle* h, const float* y, int64_t N, float* partials, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = tsne_rows_check(h, "tsne_repulsion", N)) return rc;
+    if (!y || ((uintptr_t)y & 7)) return h->fail(KEEP_EINVAL, "tsne_repulsion: y is null or not 8-byte aligned");
+    if (!partials || ((uintptr_t)partials & 15)) return h->fail(KEEP_EINVAL, "tsne_repulsion: partials is null or not 16-byte aligned");
+    KEEP_ON_DEVICE(h);
+    launch_tsne_repulsion(y, (int)N, partials, (hipStream_t)stream);
+    return check_launch(h, "tsne_repulsion");
+}
+
+int keep_tsne_step(keep_handle* h, const float* y, int64_t N, const float* partials, const int32_t* row_ptr, const int32_t* col,
+                   const float* val, int64_t nnz, float exaggeration, float momentum, float lr, int stats, int64_t* sums, float* rz,
+                   float* grad_out, float* update, float* gains, float* y_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = tsne_rows_check(h, "tsne_step", N)) return rc;
+    if (!y || ((uintptr_t)y & 7)) return h->fail(KEEP_EINVAL, "tsne_step: y is null or not 8-byte aligned");
+    if (!partials || ((uintptr_t)partials & 15) || !rz || ((uintptr_t)rz & 15))
+        return h->fail(KEEP_EINVAL, "tsne_step: partials or rz is null or not 16-byte aligned");
+    if (nnz < 0 || nnz > INT32_MAX) return h->fail(KEEP_EINVAL, "tsne_step: %lld graph entries (0 .. 2^31 - 1)", (long long)nnz);
+    if (!row_ptr || ((uintptr_t)row_ptr & 3) || (nnz && (!col || !val)) || ((uintptr_t)col & 3) || ((uintptr_t)val & 3))
+        return h->fail(KEEP_EINVAL, "tsne_step: a graph array is null or not 4-byte aligned");
+    if (!sums || ((uintptr_t)sums & 7)) return h->fail(KEEP_EINVAL, "tsne_step: sums is null or not 8-byte aligned");
+    if (!(exaggeration >= 0.f && exaggeration <= TSNE_MAX_EXAGGERATION))
+        return h->fail(KEEP_EINVAL, "tsne_step: exaggeration %g outside [0, 32]", (double)exaggeration);
+    if (!std::isfinite(momentum) || !std::isfinite(lr)) return h->fail(KEEP_EINVAL, "tsne_step: momentum or lr is not finite");
+    const int given = (update != nullptr) + (gains != nullptr) + (y_out != nullptr);
+    if (given != 0 && given != 3) return h->fail(KEEP_EINVAL, "tsne_step: update, gains and y_out go together (all or none)");
+    if (given && y_out == y) return h->fail(KEEP_EINVAL, "tsne_step: y_out must not be y (other rows still read it)");
+    if (((uintptr_t)grad_out & 3) || ((uintptr_t)update & 3) || ((uintptr_t)gains & 3) || ((uintptr_t)y_out & 7))
+        return h->fail(KEEP_EINVAL, "tsne_step: an output is not aligned");
+    KEEP_ON_DEVICE(h);
+    launch_tsne_step(y, (int)N, partials, row_ptr, col, val, (int)nnz, exaggeration, momentum, lr, stats ? 1 : 0, sums, rz, grad_out, update,
+                     gains, y_out, (hipStream_t)stream);
+    return check_launch(h, "tsne_step");
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 """The slide-analysis methods of ``KEEPModel``: patch grid and tiles of a region, tissue mask, heatmap raster, percentiles and
-smoothing, region table, outlines, region shape, polygon fill, segmentation evaluation, the subtype map, bootstrap resampling, the linear probe, attention MIL and feature PCA (DESIGN.md sections 10-30).  Thin wrappers of the
+smoothing, region table, outlines, region shape, polygon fill, segmentation evaluation, the subtype map, bootstrap resampling, the linear probe, attention MIL, feature PCA and the t-SNE tile embedding (DESIGN.md sections 10-32).  Thin wrappers of the
 entry points in csrc/slide_api.hip; the argument checks and the numpy references live in the feature modules imported below."""
 from __future__ import annotations
 
@@ -32,6 +32,7 @@ from . import neighbours as _nb
 from . import pca as _pca
 from . import probe as _probe
 from . import stain as _stain
+from . import tsne as _tsne
 from .quality import NCOLS as QUALITY_COLS, MAX_CELLS as QUALITY_MAX_CELLS, QualityGate, TileQuality, check_gate, check_patch, check_rules
 from .stain import StainFit, StainTarget, check_stain
 
@@ -1332,6 +1333,220 @@ class SlideOps:
         self._call("knn_vote", _ptr(neighbours.keys.contiguous()), Nq, neighbours.k, _ptr(y), n, C_, mode, t, _ptr(probs), _ptr(labels),
                    _ptr(margin), _ptr(skipped))
         return labels, probs, margin, skipped
+
+    # ------------------------------------------------------------------ t-SNE tile embedding
+    def _tsne_neighbours(self, neighbours):
+        if not isinstance(neighbours, _nb.Neighbours):
+            raise ValueError(f"neighbours must be a Neighbours, got {type(neighbours).__name__}")
+        self._ready_device()
+        if neighbours.keys.device != self._device:
+            raise ValueError(f"the lists live on {neighbours.keys.device}, this engine on {self._device}")
+
+    @torch.no_grad()
+    def tsne_affinities(self, neighbours, perplexity) -> torch.Tensor:
+        """The conditional probabilities ``p_{j|i}`` of neighbour lists at a perplexity -> fp32 ``[N, k]`` on the
+        device, 0 in an empty slot; a row with fewer than two neighbours is zero.  ``neighbours``: a ``Neighbours`` (:meth:`topk` with
+        ``exclude_self=True``); ``2 <= perplexity <= k / 2``.  One wave per row, 64 bisection steps, none skipped: a row's bits depend
+        on that row alone.  Held to ``keep_amd.tsne.conditional_numpy``; no host synchronisation."""
+        self._tsne_neighbours(neighbours)
+        perp, k = _tsne.check_perplexity(perplexity, neighbours.k)
+        N = _tsne.check_rows(neighbours.index.shape[0])
+        p = torch.empty((N, k), dtype=torch.float32, device=self._device)
+        self._call("tsne_affinities", _ptr(neighbours.index.contiguous()), _ptr(neighbours.score.contiguous()), _ptr(neighbours.count.contiguous()),
+                   N, k, perp, _ptr(p))
+        return p
+
+    @torch.no_grad()
+    def tsne_graph(self, neighbours, p):
+        """The joint graph of :meth:`tsne_affinities`' rows -> ``(keep_amd.tsne.TsneGraph, kept bool [N])`` on the
+        device.  A row is kept iff its list is not empty (the skip rule empties a skipped tile's list and never returns it as a
+        neighbour); the N' kept rows are renumbered in order.  Edges ``(i, j)`` and ``(j, i)`` carry ``fp32(p_{j|i} / (2 N'))``, are sorted by
+        ``row << 32 | col`` and equal keys are merged by one fp32 addition (at most two meet, so the sum has no order).  Torch plumbing,
+        once per fit; reads N' and the number of edges back (two host synchronisations)."""
+        self._tsne_neighbours(neighbours)
+        index = neighbours.index
+        N, k = index.shape
+        if tuple(p.shape) != (N, k) or p.dtype != torch.float32 or p.device != self._device:
+            raise ValueError(f"p must be fp32 [{N}, {k}] on {self._device}, got {p.dtype} {tuple(p.shape)} on {p.device}")
+        if neighbours.n_bank > N:
+            raise ValueError(f"the lists name bank rows up to {neighbours.n_bank - 1}, the graph has {N} rows: t-SNE takes the tiles' own neighbours")
+        kept = neighbours.count > 0
+        new = torch.cumsum(kept, 0) - 1
+        m = _tsne.check_rows(int(new[-1]) + 1, "kept tiles")
+        ok = (index >= 0) & (p > 0)
+        ok &= kept[index.clamp(min=0)]
+        rows = new[torch.arange(N, device=self._device)].unsqueeze(1).expand(N, k)[ok]
+        cols = new[index[ok]]
+        v = p[ok] / float(2 * m)
+        keys, order = torch.sort(torch.cat([(rows << 32) | cols, (cols << 32) | rows]))
+        v = torch.cat([v, v])[order]
+        first = torch.ones_like(keys, dtype=torch.bool)
+        first[1:] = keys[1:] != keys[:-1]
+        twin = torch.zeros_like(v)
+        twin[:-1] = torch.where(first[1:], torch.zeros_like(v[1:]), v[1:])        # the mirror edge of a mutual pair, next in key order
+        val = (v + twin)[first].contiguous()
+        keys = keys[first]
+        row_ptr = torch.zeros(m + 1, dtype=torch.int64, device=self._device)
+        row_ptr[1:] = torch.cumsum(torch.bincount(keys >> 32, minlength=m), 0)
+        graph = _tsne.TsneGraph(row_ptr.to(torch.int32), (keys & 0xFFFFFFFF).to(torch.int32).contiguous(), val, m)
+        return graph, kept
+
+    def _tsne_graph_here(self, graph, n: int) -> None:
+        if not isinstance(graph, _tsne.TsneGraph):
+            raise ValueError(f"graph must be a TsneGraph, got {type(graph).__name__}")
+        if graph.n != n:
+            raise ValueError(f"the graph has {graph.n} rows, the embedding {n}")
+        for a, dt in ((graph.row_ptr, torch.int32), (graph.col, torch.int32), (graph.val, torch.float32)):
+            if not isinstance(a, torch.Tensor) or a.dtype != dt or a.device != self._device or not a.is_contiguous():
+                raise ValueError(f"the graph's arrays must be contiguous int32 / int32 / fp32 tensors on {self._device} (tsne_graph makes them)")
+
+    @torch.no_grad()
+    def tsne_repulsion(self, y, out=None) -> torch.Tensor:
+        """The all-pairs repulsion of an embedding in partial sums -> fp32 ``[n_seg, N, 4]`` on the device: for
+        row i and segment s of ``keep_tsne_segment()`` columns the sums over the segment's j != i, ascending, of ``w^2 (y_i - y_j)``
+        (words 0, 1) and ``w`` (word 2), ``w = 1 / (1 + |y_i - y_j|^2)``; word 3 is 0.  ``y``: fp32 ``[N, 2]``.  The words depend on the
+        segment length and on nothing else about the launch or N.  ``out``: a buffer of that shape to write into (every word is
+        written).  No host synchronisation."""
+        N = _tsne.check_embedding(y)
+        self._ready_device()
+        yd = self._on_device(y)
+        shape = (_tsne.n_segments(N, _lib.load().keep_tsne_segment()), N, 4)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self._device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self._device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous fp32 {shape} on {self._device}")
+        self._call("tsne_repulsion", _ptr(yd), N, _ptr(out))
+        return out
+
+    def _tsne_step(self, st, graph, exaggeration: float, momentum: float, lr: float, sums: torch.Tensor, stats: bool, move: bool) -> None:
+        self._call("tsne_repulsion", _ptr(st.y), st.n, _ptr(st.partials))
+        self._call("tsne_step", _ptr(st.y), st.n, _ptr(st.partials), _ptr(graph.row_ptr), _ptr(graph.col), _ptr(graph.val), graph.nnz,
+                   exaggeration, momentum, lr, 1 if stats else 0, _ptr(sums), _ptr(st.rz), _ptr(st.grad), _ptr(st.update if move else None),
+                   _ptr(st.gains if move else None), _ptr(st.spare if move else None))
+        if move:
+            st.y, st.spare = st.spare, st.y
+
+    @staticmethod
+    def _tsne_words(sums: torch.Tensor) -> Tuple[float, float, float]:
+        """int64 [3] -> (Z, KL, squared gradient norm) as floats (reads them back)."""
+        z, kl, g2 = (int(v) for v in sums.cpu())
+        return z / _tsne.Z_ONE, kl / _tsne.KL_ONE, g2 / _tsne.G2_ONE
+
+    @torch.no_grad()
+    def tsne_step(self, state, graph, exaggeration: float, momentum: float, learning_rate: float, stats: bool = False):
+        """One iteration on a ``keep_amd.tsne.TsneState``: the repulsion, Z, the attraction over ``graph``, the
+        gradient ``4 (exaggeration A - R / Z)`` (left in ``state.grad``) and van der Maaten's update of ``state.update`` / ``gains`` / ``y``
+        -> int64 ``[3]`` on the device: ``Z 2^22``, and with ``stats`` ``KL 2^40`` and ``|g|^2 2^50`` (of the embedding before the update).
+        No host synchronisation."""
+        if not isinstance(state, _tsne.TsneState):
+            raise ValueError(f"state must be a TsneState, got {type(state).__name__}")
+        self._ready_device()
+        if state.y.device != self._device:
+            raise ValueError(f"the state lives on {state.y.device}, this engine on {self._device}")
+        self._tsne_graph_here(graph, state.n)
+        sums = torch.zeros(3, dtype=torch.int64, device=self._device)
+        self._tsne_step(state, graph, float(exaggeration), float(momentum), float(learning_rate), sums, bool(stats), True)
+        return sums
+
+    @torch.no_grad()
+    def tsne_gradient(self, y, graph, exaggeration: float = 1.0, state=None):
+        """One evaluation at an embedding -> ``(grad fp32 [N, 2] on the device, KL, Z)``: the kernels of an
+        iteration without the update.  ``y``: fp32 ``[N, 2]``; ``graph``: :meth:`tsne_graph`'s.  KL is that of the plain P whatever the
+        ``exaggeration``; Z is the exact value of its fixed-point word (``Z 2^22`` is an integer).  ``state``: a ``TsneState`` of N rows
+        whose scratch is used (and whose ``y`` is overwritten by ``y``); one is made otherwise.  One read-back of three words."""
+        N = _tsne.check_embedding(y)
+        self._ready_device()
+        yd = self._on_device(y)
+        self._tsne_graph_here(graph, N)
+        if state is None:
+            state = _tsne.TsneState(yd)
+        elif not isinstance(state, _tsne.TsneState) or state.n != N or state.y.device != self._device:
+            raise ValueError(f"state must be a TsneState of {N} rows on {self._device}")
+        else:
+            state.y.copy_(yd)
+        sums = torch.zeros(3, dtype=torch.int64, device=self._device)
+        self._tsne_step(state, graph, float(exaggeration), 0.0, 0.0, sums, True, False)
+        Z, kl, _ = self._tsne_words(sums)
+        return state.grad.clone(), kl, Z
+
+    @torch.no_grad()
+    def tsne_fit(self, features=None, perplexity=20, n_iter=1000, neighbours=None, n_neighbors=None, init="pca", early_exaggeration=12.0,
+                 exaggeration_iter=250, learning_rate="auto", min_grad_norm=1e-7, n_iter_without_progress=300, check_every=50, seed=0,
+                 normalize=True):
+        """The exact t-SNE embedding of a slide's tiles -> ``keep_amd.tsne.TileEmbedding``.
+
+        ``features``: fp32 ``[N, D]`` as in :meth:`topk`; their ``3 perplexity`` (or ``n_neighbors``) nearest neighbours by cosine are
+        taken with ``topk(..., exclude_self=True)`` unless ``neighbours`` (a ``Neighbours`` of the tiles against themselves, from
+        :meth:`topk_batches` with ``self_first=0`` for features that are never resident) is given.  ``2 <= perplexity``, ``3 perplexity
+        <= 64`` or ``perplexity <= n_neighbors / 2``, and below the neighbours every kept tile has.  ``init``: ``"pca"`` (``pca_fit(k=2)``
+        and ``pca_transform``, scaled to a standard deviation of 1e-4 in the first column; needs ``features``), ``"random"`` (1e-4 x
+        normal, counter-based from ``seed``) or an fp32 ``[N, 2]`` array.  ``early_exaggeration`` multiplies P for the first
+        ``exaggeration_iter`` iterations at momentum 0.5; then momentum 0.8 with update and gains started again.  ``learning_rate="auto"``:
+        ``max(N' / early_exaggeration / 4, 50)``.  Every ``check_every`` iterations the host reads the divergence and the gradient's
+        norm (the only synchronisations of the descent) and, after the exaggeration, stops when the norm is at most ``min_grad_norm``
+        or the divergence has not improved for ``n_iter_without_progress`` iterations.  Tiles the skip rule leaves out are compacted out
+        before the fit and come back as NaN rows.  Every sum has a fixed order or is an integer: two fits give the same bits."""
+        n_iter, ex_iter, every, patience = _tsne.check_iterations(n_iter, exaggeration_iter, check_every, n_iter_without_progress)
+        ex0 = _tsne.check_exaggeration(early_exaggeration, "early_exaggeration")
+        gmin = _tsne.check_min_grad_norm(min_grad_norm)
+        seed = _tsne._boot.check_seed(seed)
+        if neighbours is None:
+            if features is None:
+                raise ValueError("give features= or neighbours=")
+            perp, k = _tsne.check_perplexity(perplexity, n_neighbors)
+            N = _tsne.check_rows(check_features(features)[0])
+            x = self._cluster_features(features, normalize)
+            neighbours = self.topk(x, x, k, normalize=False, exclude_self=True)
+        else:
+            self._tsne_neighbours(neighbours)
+            if n_neighbors is not None and n_neighbors != neighbours.k:
+                raise ValueError(f"n_neighbors = {n_neighbors}, the lists hold {neighbours.k}")
+            perp, k = _tsne.check_perplexity(perplexity, neighbours.k)
+            N = _tsne.check_rows(neighbours.index.shape[0])
+            if features is not None and check_features(features)[0] != N:
+                raise ValueError(f"features has {features.shape[0]} rows, the lists {N}")
+            x = None if features is None else self._cluster_features(features, normalize)
+        start = _tsne.check_init(init, N)
+        if isinstance(start, str) and start == "pca" and x is None:
+            raise ValueError('init="pca" needs features= (give them beside neighbours=, or another init)')
+        p = self.tsne_affinities(neighbours, perp)
+        graph, kept = self.tsne_graph(neighbours, p)
+        m = graph.n
+        fewest = int(neighbours.count[kept].min())
+        if perp >= fewest:
+            raise ValueError(f"perplexity {perp:g} must be below the {fewest} neighbours the sparsest kept tile has")
+        lr = _tsne.check_learning_rate(learning_rate, m, ex0)
+        if isinstance(start, str) and start == "pca":
+            pca = self.pca_fit(x[kept], 2, normalize=False)
+            y0 = _tsne.pca_init(self.pca_transform(pca, x[kept], 2, normalize=False)[0].cpu().numpy())
+        elif isinstance(start, str):
+            y0 = _tsne.random_init(m, seed)
+        else:
+            y0 = start[kept.cpu().numpy()]
+        if not np.isfinite(y0).all():
+            raise ValueError("the initial embedding holds a non-finite value")
+        st = _tsne.TsneState(self._on_device(y0))
+        sums = torch.zeros((n_iter + 1, 3), dtype=torch.int64, device=self._device)      # a row per iteration: nothing to zero on the way
+        prog = _tsne.Progress(ex_iter, patience, gmin)
+        reason, done = "n_iter", n_iter
+        for it in range(n_iter):
+            ex, mom = _tsne.phase(it, ex_iter, ex0)
+            if it == ex_iter:
+                st.restart()
+            check = (it + 1) % every == 0
+            self._tsne_step(st, graph, ex, mom, lr, sums[it], check, True)
+            if check:
+                _, kl, g2 = self._tsne_words(sums[it])
+                stop = prog.check(it, kl, float(np.sqrt(g2)))
+                if stop is not None:
+                    reason, done = stop, it + 1
+                    break
+        self._tsne_step(st, graph, 1.0, 0.0, 0.0, sums[n_iter], True, False)
+        kl = self._tsne_words(sums[n_iter])[1]
+        emb = torch.full((N, 2), float("nan"), dtype=torch.float32, device=self._device)
+        emb[kept] = st.y
+        return _tsne.TileEmbedding(emb, kept, np.asarray(prog.iters, np.int64), np.asarray(prog.kls, np.float64), kl, done, reason, perp, k, lr,
+                                   ex0, ex_iter, start if isinstance(start, str) else "array", seed, m, graph)
 
     # ------------------------------------------------------------------ region table (DESIGN.md section 13)
     @torch.no_grad()

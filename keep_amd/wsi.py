@@ -691,6 +691,69 @@ def pca_map(tile_features, tile_coords, k_or_pca, downsample, shape, patch_size=
     return raster, pca
 
 
+def tsne_map(tile_features, tile_coords, downsample, shape, patch_size=256, origin=(0, 0), model=None, **fit):
+    """The t-SNE colour map of a slide: the geography of the tiles' 2-D embedding painted back onto the slide ->
+    ``(keep_amd.classmap.ClassRaster, keep_amd.tsne.TileEmbedding)``.  ``KEEPModel.tsne_fit(tile_features, **fit)`` embeds the slide's own
+    tiles; each embedding coordinate is ranked among them (``KEEPModel.percentiles``, as ``pca_map`` ranks a component) into planes 0 and
+    1, and plane 2 is ``1 - (p0 + p1) / 2``: tiles that lie together in the embedding share a colour under ``KEEPModel.render_rgb_map``.
+    Skipped tiles (a non-finite feature) are in no plane."""
+    from .cluster import check_features
+    from .heatmap import check_raster_args
+    check_raster_args(patch_size, downsample, shape, origin)
+    f = tile_features.squeeze(0) if isinstance(tile_features, torch.Tensor) and tile_features.dim() == 3 else tile_features
+    N, _ = check_features(f)
+    coords = tile_coords if isinstance(tile_coords, torch.Tensor) else torch.as_tensor(np.asarray(tile_coords))
+    if tuple(coords.shape) != (N, 2):
+        raise ValueError(f"tile_coords must be [{N}, 2] beside {N} feature rows, got shape {tuple(coords.shape)}")
+    m = _engine(model, tile_features)
+    emb = m.tsne_fit(f, **fit)
+    p0, p1 = m.percentiles(emb.embedding[:, 0].contiguous()), m.percentiles(emb.embedding[:, 1].contiguous())   # a NaN stays NaN
+    values = torch.stack([p0, p1, 1.0 - (p0 + p1) / 2.0], dim=1)
+    raster = m.class_raster(coords.to(m._device), values, patch_size, downsample, shape, origin, classes=["tSNE1", "tSNE2", "rest"])
+    return raster, emb
+
+
+def tsne_scatter(embedding, labels, n_classes, size=(512, 512), point=3, model=None):
+    """The scatter plot of an embedding on the device -> ``keep_amd.classmap.ClassRaster`` of ``size`` pixels with
+    a ``point`` x ``point`` square per tile in its label's plane; ``KEEPModel.class_map`` and ``render_class_map(thumbnail=None)`` paint it.
+    ``embedding``: a ``TileEmbedding`` or fp32 ``[N, 2]``; ``labels``: integers ``[N]`` in ``0 .. n_classes - 1`` (class, cluster or slide;
+    -1 leaves a tile out).  Each column is scaled affinely from its minimum and maximum (one read-back) onto ``0 .. size - point``,
+    column 0 along the width and column 1 down the height (``keep_amd.tsne.scatter_coords_numpy``); NaN rows are not drawn.  Pure
+    composition: ``class_raster(coords, onehot, patch_size=point, downsample=1, shape=size)``."""
+    from .classmap import check_classes
+    from .heatmap import check_raster_args
+    from .tsne import TileEmbedding, check_embedding
+    y = embedding.embedding if isinstance(embedding, TileEmbedding) else embedding
+    y = y if isinstance(y, torch.Tensor) else torch.as_tensor(np.asarray(y))
+    N = check_embedding(y)
+    C = check_classes(n_classes)
+    point, _, (h, w), _ = check_raster_args(point, 1, size)
+    if point > min(h, w):
+        raise ValueError(f"a point of {point} pixels does not fit a canvas of {h}x{w}")
+    lab = labels if isinstance(labels, torch.Tensor) else torch.as_tensor(np.asarray(labels))
+    if tuple(lab.shape) != (N,) or lab.dtype.is_floating_point or lab.dtype == torch.bool:
+        raise ValueError(f"labels must be integers [{N}], got {lab.dtype} {tuple(lab.shape)}")
+    m = _engine(model, y)
+    y, lab = y.to(m._device), lab.to(m._device, torch.int64)
+    shown = ~torch.isnan(y).any(dim=1)
+    coords = torch.zeros((N, 2), dtype=torch.int64, device=m._device)
+    lo_hi = torch.stack([torch.where(shown[:, None], y, torch.full_like(y, float("inf"))).amin(dim=0),
+                         torch.where(shown[:, None], y, torch.full_like(y, float("-inf"))).amax(dim=0),
+                         torch.stack([lab.min(), lab.max()]).to(torch.float32)]).cpu().numpy()
+    if lo_hi[2, 0] < -1 or lo_hi[2, 1] >= C:
+        raise ValueError(f"labels must lie in -1 .. {C - 1}, got {int(lo_hi[2, 0])} .. {int(lo_hi[2, 1])}")
+    if np.isfinite(lo_hi[:2]).all():
+        for c, span in ((0, w - point), (1, h - point)):
+            lo, hi = float(lo_hi[0, c]), float(lo_hi[1, c])
+            scale = max(hi - lo, float(np.finfo(np.float32).tiny))
+            v = torch.where(shown, y[:, c], torch.full_like(y[:, c], lo)).double()
+            coords[:, c] = torch.floor((v - lo) / scale * float(span) + 0.5).to(torch.int64)
+    onehot = torch.zeros((N, C), dtype=torch.float32, device=m._device)
+    onehot.scatter_(1, lab.clamp(min=0).reshape(N, 1), 1.0)
+    onehot[~(shown & (lab >= 0))] = float("nan")                        # class_raster leaves a row with a NaN out of every plane
+    return m.class_raster(coords, onehot, point, 1, (h, w))
+
+
 def probe_map(probe, tile_features, tile_coords, downsample, shape, patch_size=256, origin=(0, 0), vote=False, classes=None, model=None):
     """The supervised morphology map: a fitted linear probe's probabilities of every tile rasterised in slide
     geometry -> ``keep_amd.classmap.ClassRaster``.  ``probe``: a ``keep_amd.probe.LinearProbe`` (of ``KEEPModel.probe_fit``) or a
