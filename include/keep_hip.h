@@ -699,6 +699,53 @@ int keep_tsne_step(keep_handle* h, const float* y, int64_t N, const float* parti
                    const float* val, int64_t nnz, float exaggeration, float momentum, float lr, int stats, int64_t* sums, float* rz,
                    float* grad_out, float* update, float* gains, float* y_out, void* stream);
 
+/* ---- few-shot prototypes: SimpleShot episodes -------------------------------------
+ * Replaces: nothing in the reference; on this engine, per episode, a torch loop of centre, normalise and x @ P.T over the whole test set
+ * (E reads of the features, an [N,C] matrix per episode, a summation order the library picks).  2 <= C <= 63 classes, D a multiple of
+ * 16 in 16 .. 1024, 1 <= E <= 2^16 episodes per call, 1 <= N, M <= 2^22 rows per call; features are fp32 row-major unit rows, 16-byte
+ * aligned, under keep_cluster_assign's skip rule (a row holding a non-finite value or an element with |x| > 1 is skipped).  Anything
+ * else is KEEP_EINVAL and nothing is launched.  No host synchronisation.
+ *
+ * keep_fewshot_sample: the support sets.  class_rows int32 [M'] (the labelled training rows grouped by class) and class_offsets int64
+ * [C + 1] (class c is class_rows[class_offsets[c] .. class_offsets[c + 1]), n_c its size, at most 2^22) are the caller's and are
+ * trusted.  With the bootstrap's generator (section 24), for GLOBAL episode g = first_episode + e and class c: key = key(seed, 64 g +
+ * c), r_j = (mix64(key + j G) n_c) >> 64 for j = 0, 1, 2, ..; the support is the first `shots` DISTINCT values of r_j in order of first
+ * appearance, each mapped through class_rows[class_offsets[c] + r].  n_c <= shots: all of the class's rows in stored order.  At most
+ * KEEP_FEWSHOT_MAX_DRAWS draws are made (never reached in practice: the slots left are unused).  support_out int32 [E,C,shots], unused
+ * slots -1.  Episode g is the same list whatever E, first_episode or the grid.  1 <= shots <= KEEP_FEWSHOT_MAX_SHOTS, 0 <=
+ * first_episode <= 2^40.
+ * keep_fewshot_prototypes: train fp32 [M,D]; support int32 [E,C,shots] as above, but any 1 <= shots <= 2^22 (a slot outside 0 .. M - 1
+ * is unused).  One workgroup per episode walks the slots in (class, slot) order; every sum below is a sequential fp32 sum in that
+ * order per column.  A sampled row the skip rule drops is left out and one is ADDED to *support_skipped (int64, may be NULL).  mu = the
+ * sum of the kept rows / their number (one fp32 division per column), 0 with centre = 0 or no kept row; per kept row v = s - mu (one
+ * fp32 subtraction per element), n = sqrtf(the chain of v_d^2: lane l of a wave adds d = l, l + 64, .. ascending by fmaf from 0, the
+ * 64 partial sums are added by the xor butterfly 32, 16, .. 1), z = v / n (a zero row when n = 0); p_c = the sum of class c's z / their
+ * number.  bank_out fp32 [E,C + 1,D]: p_0 .. p_{C-1}, then mu; the row of a class without a kept row is zero and valid_out uint8 [E,C]
+ * is 0 for it, 1 otherwise.  consts_out fp32 [E,2 C + 1]: mu . p_c (C words), h_c = fp32(0.5 |p_c|^2) (C words), |mu|^2; each dot by
+ * the lane chain above.  An episode's words depend on train and that episode's support list alone.
+ * keep_fewshot_classify: feats fp32 [N,D]; bank / consts / valid as written above.  For row x and episode e the C + 1 dots x . p_c and
+ * x . mu are keep_cluster_assign's k-ordered fma chain from 0 on v_mfma_f32_16x16x4_f32, K never split (dots_out[:, j] is the `best` of
+ * keep_cluster_assign against the one-row bank j bit for bit).  Then, each a single fp32 operation in this order: r = sqrtf(max(0,
+ * fma(-2, x.mu, 1) + |mu|^2)); t_c = ((x.p_c - mu.p_c) - h_c * r); label = the first valid c with the largest t_c (the nearest
+ * prototype of q = (x - mu) / |x - mu|, since t_c / r = q.p_c - h_c); -1 when r = 0, when no class is valid, or for a skipped row.
+ * labels_out int32 [N,E] (may be NULL).  truth int32 [N] with confusion int64 [E,C,C] (both or neither): confusion[e, truth, label] is
+ * ADDED into for every labelled pair whose truth lies in 0 .. C - 1 (anything else, such as -1, leaves the row out); integer counts,
+ * gathered per workgroup and tile in LDS and flushed by one no-return 64-bit atomic per non-zero bin.  E == 1 only (NULL otherwise):
+ * scores_out fp32 [N,C] = t_c / r (-inf for an invalid class; a zero row with label -1), margin_out fp32 [N] = (t_best - t_second) / r
+ * (0 with fewer than two valid classes or label -1), dots_out fp32 [N,C + 1] the raw dots.  *skipped (int64, may be NULL) is ADDED
+ * into once per skipped test row.  At least one of labels_out / confusion / scores_out / margin_out / dots_out.  segments: 0 (chosen
+ * here) or 1 .. 1024 cuts of the episodes run by different workgroups (any value gives the same words; for measurement). */
+#define KEEP_FEWSHOT_MAX_SHOTS 256
+#define KEEP_FEWSHOT_MAX_DRAWS (1 << 20)
+int keep_fewshot_sample(keep_handle* h, const int32_t* class_rows, const int64_t* class_offsets, int64_t C, int64_t shots, uint64_t seed,
+                        int64_t first_episode, int64_t E, int32_t* support_out, void* stream);
+int keep_fewshot_prototypes(keep_handle* h, const float* train, int64_t M, int64_t D, const int32_t* support, int64_t E, int64_t C,
+                            int64_t shots, int centre, float* bank_out, float* consts_out, unsigned char* valid_out,
+                            int64_t* support_skipped, void* stream);
+int keep_fewshot_classify(keep_handle* h, const float* feats, int64_t N, int64_t D, const float* bank, const float* consts,
+                          const unsigned char* valid, int64_t E, int64_t C, const int32_t* truth, int64_t* confusion, int32_t* labels_out,
+                          float* scores_out, float* margin_out, float* dots_out, int64_t* skipped, int segments, void* stream);
+
 /* Region outlines: the boundary rings of a label image, with holes, and an outline drawn into an image.
  * Replaces: the contour polygons with a hole list per contour that CLAM's segmentTissue hands back (cv2.findContours with
  * RETR_CCOMP; the step of README.md:74) and the polygon annotation a viewer takes a lesion of WSI_evaluation/segment_utils.py's

@@ -82,6 +82,9 @@ SIGNATURES = {
     "keep_topk_merge": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "keep_topk_unpack": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "keep_knn_vote": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "keep_fewshot_sample": (_i32, [_vp, _vp, _vp, _i64, _i64, C.c_uint64, _i64, _i64, _vp, _vp]),
+    "keep_fewshot_prototypes": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "keep_fewshot_classify": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "keep_pca_chunk": (_i32, []),
     "keep_pca_moments": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "keep_pca_project": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -18,7 +18,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libkeep_hip.so")
-SOURCES = ["gemm_f16.hip", "gemm_f16_v2.hip", "gemm_f16_skinny.hip", "attention.hip", "attention_rollout.hip", "rowops.hip", "sgemm_f32.hip", "wsi.hip", "region.hip", "tissue.hip", "stain.hip", "quality.hip", "heatmap.hip", "classmap.hip", "cluster.hip", "probe.hip", "mil.hip", "neighbours.hip", "pca.hip", "tsne.hip", "rank.hip", "components.hip", "shape.hip", "outline.hip", "annotation.hip", "eval.hip", "bootstrap.hip", "lesion.hip", "launch_util.hip", "engine.hip", "weights.hip", "op_api.hip", "slide_api.hip"]
+SOURCES = ["gemm_f16.hip", "gemm_f16_v2.hip", "gemm_f16_skinny.hip", "attention.hip", "attention_rollout.hip", "rowops.hip", "sgemm_f32.hip", "wsi.hip", "region.hip", "tissue.hip", "stain.hip", "quality.hip", "heatmap.hip", "classmap.hip", "cluster.hip", "probe.hip", "mil.hip", "neighbours.hip", "fewshot.hip", "pca.hip", "tsne.hip", "rank.hip", "components.hip", "shape.hip", "outline.hip", "annotation.hip", "eval.hip", "bootstrap.hip", "lesion.hip", "launch_util.hip", "engine.hip", "weights.hip", "op_api.hip", "slide_api.hip"]
 # -falign-loops=64: the hot loops start on an instruction-cache line.  Without it a functionally identical edit elsewhere in a kernel moved the
 # K loop of the GEMM by a few dwords and the whole encoder by up to 3 % (measured: DESIGN.md section 4); with it +0.5 % and reproducible.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-falign-loops=64", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-value",

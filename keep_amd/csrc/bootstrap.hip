@@ -23,6 +23,7 @@
 //
 // Wave64; integer atomics only, none with a used result.
 #include "common.h"
+#include "boot_rng.h"
 #include "../../include/keep_hip.h"
 
 namespace keepk {
@@ -31,22 +32,6 @@ static_assert(BOOT_LDS_GROUPS == KEEP_BOOT_LDS_GROUPS, "the cap the header expor
 constexpr int BOOT_THREADS = 1024;
 constexpr int BOOT_WAVES = BOOT_THREADS / 64;
 constexpr int BOOT_SCAN_CHUNK = 2048;
-constexpr unsigned long long BOOT_G = 0x9E3779B97F4A7C15ull;
-
-__device__ __forceinline__ unsigned long long boot_mix64(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ unsigned long long boot_key(unsigned long long seed, long long b) {
-    return boot_mix64(seed ^ boot_mix64((unsigned long long)(b + 1) * BOOT_G));
-}
-
-// 0 <= result < n
-__device__ __forceinline__ unsigned boot_draw(unsigned long long key, unsigned j, unsigned n) {
-    return (unsigned)__umul64hi(boot_mix64(key + (unsigned long long)j * BOOT_G), (unsigned long long)n);
-}
 
 __device__ __forceinline__ int boot_count(const int64_t* dev, int N) {     // whatever the word holds, the indices stay inside [0, N)
     const int64_t v = *dev;

@@ -480,6 +480,22 @@ void launch_knn_check(const uint64_t* keys, int Nq, int k, int64_t n_bank, int* 
 void launch_knn_vote(const uint64_t* keys, int Nq, int k, const int32_t* bank_labels, int C, int mode, float T, float* probs, int32_t* label,
                      float* margin, int64_t* skipped, hipStream_t s);
 
+// Few-shot prototypes (fewshot.hip).  Feature rows with the limits of the clustering above.
+constexpr int FEWSHOT_MAX_C = 63;                       // an episode's C + 1 bank rows fit one tile of 64
+constexpr int64_t FEWSHOT_MAX_EPISODES = (int64_t)1 << 16;
+// support: int32 [E][C][shots], shots <= KEEP_FEWSHOT_MAX_SHOTS
+void launch_fewshot_sample(const int32_t* class_rows, const int64_t* class_offsets, int C, int shots, uint64_t seed, int64_t first_episode,
+                           int E, int32_t* support, hipStream_t s);
+// bank fp32 [E][C + 1][D], consts fp32 [E][2 C + 1], valid uint8 [E][C]; skipped may be null and is ADDED into
+void launch_fewshot_prototypes(const float* train, int M, int D, const int32_t* support, int E, int C, int shots, int centre, float* bank,
+                               float* consts, unsigned char* valid, int64_t* skipped, hipStream_t s);
+int fewshot_segments(int N, int E, int C, int cus);
+// S segments of the episodes' tiles; truth / confusion both or neither; confusion and skipped are ADDED into; scores / margin / dots with
+// E == 1 only; every output may be null
+void launch_fewshot_classify(const float* x, int N, int D, const float* bank, const float* consts, const unsigned char* valid, int E, int C,
+                             const int32_t* truth, int64_t* confusion, int32_t* labels, float* scores, float* margin, float* dots,
+                             int64_t* skipped, int S, hipStream_t s);
+
 // Sorted score population and rank percentiles (rank.hip)
 constexpr int SORT_TILE = 4096;                         // keys per block; up to this many are sorted by one block in LDS
 constexpr int SORT_SCAN_CHUNK = 2048;                   // entries of the digit table per block of the scan

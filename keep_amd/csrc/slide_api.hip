@@ -1068,6 +1068,78 @@ int keep_knn_vote(keep_handle* h, const uint64_t* keys, int64_t Nq, int k, const
     return check_launch(h, "knn_vote");
 }
 
+// Few-shot prototypes (fewshot.hip)
+static int fewshot_shape_check(keep_handle* h, const char* who, int64_t E, int64_t C) {
+    if (C < 2 || C > FEWSHOT_MAX_C) return h->fail(KEEP_EINVAL, "%s: C = %lld (2 .. 63)", who, (long long)C);
+    if (E < 1 || E > FEWSHOT_MAX_EPISODES) return h->fail(KEEP_EINVAL, "%s: %lld episodes (1 .. 2^16 per call)", who, (long long)E);
+    return KEEP_OK;
+}
+
+int keep_fewshot_sample(keep_handle* h, const int32_t* class_rows, const int64_t* class_offsets, int64_t C, int64_t shots, uint64_t seed,
+                        int64_t first_episode, int64_t E, int32_t* support_out, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = fewshot_shape_check(h, "fewshot_sample", E, C)) return rc;
+    if (shots < 1 || shots > KEEP_FEWSHOT_MAX_SHOTS) return h->fail(KEEP_EINVAL, "fewshot_sample: shots = %lld (1 .. 256)", (long long)shots);
+    if (first_episode < 0 || first_episode > ((int64_t)1 << 40))
+        return h->fail(KEEP_EINVAL, "fewshot_sample: first_episode %lld (0 .. 2^40)", (long long)first_episode);
+    if (!class_rows || !class_offsets || !support_out) return h->fail(KEEP_EINVAL, "fewshot_sample: null class_rows, class_offsets or support_out");
+    if (((uintptr_t)class_rows & 3) || ((uintptr_t)class_offsets & 7) || ((uintptr_t)support_out & 3))
+        return h->fail(KEEP_EINVAL, "fewshot_sample: a pointer is not aligned to its element size");
+    KEEP_ON_DEVICE(h);
+    launch_fewshot_sample(class_rows, class_offsets, (int)C, (int)shots, seed, first_episode, (int)E, support_out, (hipStream_t)stream);
+    return check_launch(h, "fewshot_sample");
+}
+
+int keep_fewshot_prototypes(keep_handle* h, const float* train, int64_t M, int64_t D, const int32_t* support, int64_t E, int64_t C,
+                            int64_t shots, int centre, float* bank_out, float* consts_out, unsigned char* valid_out,
+                            int64_t* support_skipped, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = fewshot_shape_check(h, "fewshot_prototypes", E, C)) return rc;
+    if (int rc = cluster_shape_check(h, "fewshot_prototypes", M, D, 1)) return rc;
+    if (shots < 1 || shots > CLUSTER_MAX_ROWS) return h->fail(KEEP_EINVAL, "fewshot_prototypes: shots = %lld (1 .. 2^22)", (long long)shots);
+    if (E * C * shots > ((int64_t)1 << 31) - 1) return h->fail(KEEP_EINVAL, "fewshot_prototypes: E C shots = %lld slots (below 2^31)", (long long)(E * C * shots));
+    if (centre != 0 && centre != 1) return h->fail(KEEP_EINVAL, "fewshot_prototypes: centre %d (0 or 1)", centre);
+    if (!train || !support || !bank_out || !consts_out || !valid_out)
+        return h->fail(KEEP_EINVAL, "fewshot_prototypes: null train, support, bank_out, consts_out or valid_out");
+    if (((uintptr_t)train & 15) || ((uintptr_t)bank_out & 15)) return h->fail(KEEP_EINVAL, "fewshot_prototypes: train / bank_out not 16-byte aligned");
+    if (((uintptr_t)support & 3) || ((uintptr_t)consts_out & 3) || ((uintptr_t)support_skipped & 7))
+        return h->fail(KEEP_EINVAL, "fewshot_prototypes: a pointer is not aligned to its element size");
+    KEEP_ON_DEVICE(h);
+    launch_fewshot_prototypes(train, (int)M, (int)D, support, (int)E, (int)C, (int)shots, centre, bank_out, consts_out, valid_out, support_skipped,
+                              (hipStream_t)stream);
+    return check_launch(h, "fewshot_prototypes");
+}
+
+int keep_fewshot_classify(keep_handle* h, const float* feats, int64_t N, int64_t D, const float* bank, const float* consts,
+                          const unsigned char* valid, int64_t E, int64_t C, const int32_t* truth, int64_t* confusion, int32_t* labels_out,
+                          float* scores_out, float* margin_out, float* dots_out, int64_t* skipped, int segments, void* stream) {
+    if (!h) return KEEP_EINVAL;
+    if (int rc = fewshot_shape_check(h, "fewshot_classify", E, C)) return rc;
+    if (int rc = cluster_shape_check(h, "fewshot_classify", N, D, 1)) return rc;
+    if (!feats || !bank || !consts || !valid) return h->fail(KEEP_EINVAL, "fewshot_classify: null feats, bank, consts or valid");
+    if (((uintptr_t)feats & 15) || ((uintptr_t)bank & 15)) return h->fail(KEEP_EINVAL, "fewshot_classify: feats / bank not 16-byte aligned");
+    if ((truth != nullptr) != (confusion != nullptr)) return h->fail(KEEP_EINVAL, "fewshot_classify: truth and confusion go together");
+    if (E != 1 && (scores_out || margin_out || dots_out))
+        return h->fail(KEEP_EINVAL, "fewshot_classify: scores_out, margin_out and dots_out take one episode, E = %lld", (long long)E);
+    if (!confusion && !labels_out && !scores_out && !margin_out && !dots_out) return h->fail(KEEP_EINVAL, "fewshot_classify: no output (every pointer is null)");
+    if (N * E > ((int64_t)1 << 40)) return h->fail(KEEP_EINVAL, "fewshot_classify: N E = %lld pairs (at most 2^40)", (long long)(N * E));
+    if (((uintptr_t)consts & 3) || ((uintptr_t)truth & 3) || ((uintptr_t)confusion & 7) || ((uintptr_t)labels_out & 3) || ((uintptr_t)scores_out & 3) ||
+        ((uintptr_t)margin_out & 3) || ((uintptr_t)dots_out & 3) || ((uintptr_t)skipped & 7))
+        return h->fail(KEEP_EINVAL, "fewshot_classify: a pointer is not aligned to its element size");
+    if (segments < 0 || segments > TOPK_MAX_SEGMENTS)
+        return h->fail(KEEP_EINVAL, "fewshot_classify: segments %d (0 = chosen here, 1 .. %d)", segments, TOPK_MAX_SEGMENTS);
+    KEEP_ON_DEVICE(h);
+    int S = segments;
+    if (S == 0) {
+        int cus = 0;
+        HIPCHK(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+        S = fewshot_segments((int)N, (int)E, (int)C, cus);
+    }
+    launch_fewshot_classify(feats, (int)N, (int)D, bank, consts, valid, (int)E, (int)C, truth, confusion, labels_out, scores_out, margin_out, dots_out,
+                            skipped, S, (hipStream_t)stream);
+    return check_launch(h, "fewshot_classify");
+}
+
 // the image, mask and od table that the three fit passes of the stain normalisation share
 static int stain_view_check(keep_handle* h, const char* who, const unsigned char* image, int64_t H, int64_t W, int64_t row_stride_bytes,
                             int pix_stride, const unsigned char* mask, int64_t mh, int64_t mw, int64_t downsample, const int32_t* od_q) {

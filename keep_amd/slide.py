@@ -27,6 +27,7 @@ from .morphometry import DEFAULT_MAX_PAIRS, RegionShape, check_shape_args
 from .outline import NCOLS as RING_COLS, RegionOutlines, check_draw_args, check_outline_args, check_ring_count, regions_labels, rgb_tensor
 from .region import (MASK_MODES, TILE, TissueMask, TissueSegmentation, check_downsample, check_grid_args, grid_shape, otsu_threshold, region_layout,
                      resize_tables, thumbnail_layout, tissue_params)
+from . import fewshot as _fs
 from . import mil as _mil
 from . import neighbours as _nb
 from . import pca as _pca
@@ -1333,6 +1334,148 @@ class SlideOps:
         self._call("knn_vote", _ptr(neighbours.keys.contiguous()), Nq, neighbours.k, _ptr(y), n, C_, mode, t, _ptr(probs), _ptr(labels),
                    _ptr(margin), _ptr(skipped))
         return labels, probs, margin, skipped
+
+    # ------------------------------------------------------------------ few-shot prototypes
+    @torch.no_grad()
+    def fewshot_sample(self, labels, n_classes: int, shots: int, n_episodes: int, seed: int = 0, first_episode: int = 0):
+        """Random support sets on the device -> ``keep_amd.fewshot.SupportSets``: for each of ``n_episodes``
+        episodes (at most 2^16 per call) and each class, ``shots`` distinct training rows of that class, uniformly, or the whole class
+        when it has no more than ``shots`` rows.  ``labels``: integers ``[M]``, a label outside ``0 .. n_classes - 1`` (such as -1)
+        leaves the row out; the grouping by class is a stable sort on the host.  The draws come from the bootstrap's counter-based
+        generator: global episode ``first_episode + i`` is the same support set whatever ``n_episodes`` or the split over calls, and
+        ``support`` equals ``keep_amd.fewshot.sample_numpy`` exactly.  No host synchronisation after the upload."""
+        C_, k = _fs.check_classes(n_classes), _fs.check_shots(shots)
+        E, first = _fs.check_episodes(n_episodes, first_episode)
+        if E > _fs.MAX_EPISODES:
+            raise ValueError(f"at most 2^16 episodes per call, got {E}")
+        seed = bootstrap.check_seed(seed)
+        rows, offsets = _fs.class_groups(labels, C_)
+        if len(rows) == 0:
+            raise ValueError("no labelled training row")
+        self._ready_device()
+        support = torch.empty((E, C_, k), dtype=torch.int32, device=self._device)
+        rows_d, offsets_d = self._on_device(rows), self._on_device(offsets)          # both alive until the launch is queued
+        self._call("fewshot_sample", _ptr(rows_d), _ptr(offsets_d), C_, k, C.c_uint64(seed), first, E, _ptr(support))
+        return _fs.SupportSets(support, C_, k, seed, first, rows, offsets)
+
+    @torch.no_grad()
+    def fewshot_prototypes(self, train_x, support, centre: bool = True, normalize: bool = True):
+        """The class prototypes of every episode -> ``keep_amd.fewshot.Prototypes``: SimpleShot's CL2N -- the mean
+        ``mu`` of an episode's support rows is subtracted, the rows are L2-normalised, and ``p_c`` is the mean of class c's rows.
+        ``train_x`` fp32 ``[M, D]`` as the features of :meth:`cluster_assign`; ``support``: a ``SupportSets`` or int32 ``[E, C, shots]``
+        row indices (-1 = unused slot; any ``shots`` up to 2^22 here).  A support row with a non-finite value or an element beyond 1
+        is left out and counted in ``support_skipped``; a class without a kept row is invalid and never predicted.  One workgroup per
+        episode adds the rows in (class, slot) order, so an episode's words depend on its own support list alone.  No host
+        synchronisation."""
+        M, D = check_features(train_x, "train_x")
+        sup = support.support if isinstance(support, _fs.SupportSets) else support
+        if not isinstance(sup, torch.Tensor) or sup.dim() != 3 or sup.dtype != torch.int32:
+            raise ValueError("support must be a SupportSets or an int32 tensor [E, C, shots]")
+        E, C_, k = int(sup.shape[0]), _fs.check_classes(int(sup.shape[1])), _fs.check_shots(int(sup.shape[2]), _fs.MAX_ROWS)
+        if not 1 <= E <= _fs.MAX_EPISODES:
+            raise ValueError(f"1..2^16 episodes per call, got {E}")
+        x = self._cluster_features(train_x, normalize)
+        sup = sup.to(self._device).contiguous()
+        dev = self._device
+        protos = _fs.Prototypes(torch.empty((E, C_ + 1, D), dtype=torch.float32, device=dev), torch.empty((E, 2 * C_ + 1), dtype=torch.float32, device=dev),
+                                torch.empty((E, C_), dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int64, device=dev), bool(centre))
+        self._call("fewshot_prototypes", _ptr(x), M, D, _ptr(sup), E, C_, k, 1 if centre else 0, _ptr(protos.bank), _ptr(protos.consts),
+                   _ptr(protos.valid), _ptr(protos.support_skipped))
+        return protos
+
+    def _fewshot_protos(self, protos, D: int):
+        E, C_, _ = _fs.check_prototypes(protos, D)
+        if E > _fs.MAX_EPISODES:
+            raise ValueError(f"at most 2^16 episodes per call, got {E}")
+        if protos.bank.device != self._device:
+            raise ValueError(f"the prototypes live on {protos.bank.device}, this engine on {self._device}")
+        return E, C_, protos.bank.contiguous(), protos.consts.contiguous(), protos.valid.contiguous()
+
+    @torch.no_grad()
+    def fewshot_classify(self, protos, x, truth=None, return_labels: bool = False, normalize: bool = True, segments: int = 0):
+        """Every test row against every episode's prototypes in one fused launch -> ``(confusion, labels,
+        skipped)``: int64 ``[E, C, C]`` (``confusion[e, truth, label]``; None without ``truth``), int32 ``[N, E]`` (None unless
+        ``return_labels``) and an int64 ``[1]`` count of skipped test rows.  ``x`` fp32 ``[N, D]`` as the features of
+        :meth:`cluster_assign`; ``truth``: integers ``[N]``, -1 leaves a row out of the counts.  The label is the nearest prototype of
+        the centred, normalised row among the valid classes, the first of equal ones; -1 for a skipped row or one equal to ``mu``.
+        The products are f32 MFMA chains of one fixed order and the counts integers: the words do not depend on N, the grid,
+        ``segments`` (0, or 1..1024 cuts of the episodes; for measurement) or the split over calls.  No ``[N, E C]`` matrix is
+        written.  No host synchronisation."""
+        N, D = check_features(x, "x")
+        self._ready_device()
+        E, C_, bank, consts, valid = self._fewshot_protos(protos, D)
+        segments = _nb.check_segments(segments)
+        if truth is None and not return_labels:
+            raise ValueError("nothing to return: give truth, return_labels=True or both")
+        f = self._cluster_features(x, normalize)
+        t = None if truth is None else self._probe_labels(truth, N)
+        conf = None if truth is None else torch.zeros((E, C_, C_), dtype=torch.int64, device=self._device)
+        labels = torch.empty((N, E), dtype=torch.int32, device=self._device) if return_labels else None
+        skipped = torch.zeros(1, dtype=torch.int64, device=self._device)
+        self._call("fewshot_classify", _ptr(f), N, D, _ptr(bank), _ptr(consts), _ptr(valid), E, C_, _ptr(t), _ptr(conf), _ptr(labels), _ptr(None),
+                   _ptr(None), _ptr(None), _ptr(skipped), segments)
+        return conf, labels, skipped
+
+    @torch.no_grad()
+    def fewshot_fit(self, train_x, train_y, n_classes: int, shots=None, seed: int = 0, centre: bool = True):
+        """A one-episode ``Prototypes``: the nearest-centroid classifier on centred, normalised features.
+        ``shots=None``: every labelled row of every class (the builder walks a class's list in chunks, so no limit of 256 applies;
+        one workgroup adds all rows in order); otherwise one sampled episode of ``shots`` rows per class."""
+        M, _ = check_features(train_x, "train_x")
+        if shots is not None:
+            return self.fewshot_prototypes(train_x, self.fewshot_sample(train_y, n_classes, shots, 1, seed), centre)
+        rows, offsets = _fs.class_groups(train_y, n_classes)
+        if len(train_y) != M:
+            raise ValueError(f"train_y has {len(train_y)} entries, train_x {M} rows")
+        if len(rows) == 0:
+            raise ValueError("no labelled training row")
+        sizes = np.diff(offsets)
+        sup = np.full((1, len(sizes), int(sizes.max())), -1, np.int32)
+        for c, n in enumerate(sizes):
+            sup[0, c, :n] = rows[offsets[c]:offsets[c + 1]]
+        self._ready_device()
+        return self.fewshot_prototypes(train_x, self._on_device(sup), centre)
+
+    @torch.no_grad()
+    def fewshot_predict(self, protos, x, normalize: bool = True):
+        """A one-episode ``Prototypes`` applied to tiles -> ``(labels, scores, margin, skipped)`` as
+        :meth:`probe_predict` returns them: int32 ``[N]`` (-1 for a skipped tile), fp32 ``[N, C]`` (``s_c = q . p_c - |p_c|^2 / 2 = 1/2 - |q -
+        p_c|^2 / 2`` of the centred, normalised tile ``q``; -inf for an invalid class, a zero row for a skipped tile), fp32 ``[N]`` (the
+        winner's score minus the runner-up's) and an int64 ``[1]`` count of skipped tiles."""
+        N, D = check_features(x, "x")
+        self._ready_device()
+        E, C_, bank, consts, valid = self._fewshot_protos(protos, D)
+        if E != 1:
+            raise ValueError(f"fewshot_predict takes the prototypes of one episode, got {E}")
+        f = self._cluster_features(x, normalize)
+        labels = torch.empty((N, 1), dtype=torch.int32, device=self._device)
+        scores = torch.empty((N, C_), dtype=torch.float32, device=self._device)
+        margin = torch.empty(N, dtype=torch.float32, device=self._device)
+        skipped = torch.zeros(1, dtype=torch.int64, device=self._device)
+        self._call("fewshot_classify", _ptr(f), N, D, _ptr(bank), _ptr(consts), _ptr(valid), 1, C_, _ptr(None), _ptr(None), _ptr(labels), _ptr(scores),
+                   _ptr(margin), _ptr(None), _ptr(skipped), 0)
+        return labels.reshape(N), scores, margin, skipped
+
+    @torch.no_grad()
+    def fewshot_episodes(self, train_x, train_y, test_x, test_y, n_classes: int, shots: int, n_episodes: int = 1000, seed: int = 0,
+                         first_episode: int = 0, episode_chunk=None) -> torch.Tensor:
+        """The few-shot protocol -> int64 ``[E, C, C]`` on the device, the confusion of the test set under each of
+        ``n_episodes`` random support sets of ``shots`` rows per class: :meth:`fewshot_sample`, :meth:`fewshot_prototypes` and
+        :meth:`fewshot_classify` over chunks of ``episode_chunk`` episodes (None: 4096).  Episode e is global episode ``first_episode +
+        e`` of ``seed``: the words are the same whatever ``episode_chunk``."""
+        E, first = _fs.check_episodes(n_episodes, first_episode)
+        C_ = _fs.check_classes(n_classes)
+        chunk = 4096 if episode_chunk is None else _fs._index(episode_chunk, "episode_chunk")
+        if not 1 <= chunk <= _fs.MAX_EPISODES:
+            raise ValueError(f"episode_chunk must be in 1..2^16, got {chunk}")
+        tx, qx = self._cluster_features(train_x, True), self._cluster_features(test_x, True)
+        truth = self._probe_labels(test_y, int(qx.shape[0]))
+        out = []
+        for e0 in range(0, E, chunk):
+            sup = self.fewshot_sample(train_y, C_, shots, min(chunk, E - e0), seed, first + e0)
+            protos = self.fewshot_prototypes(tx, sup, True, normalize=False)
+            out.append(self.fewshot_classify(protos, qx, truth, normalize=False)[0])
+        return torch.cat(out)
 
     # ------------------------------------------------------------------ t-SNE tile embedding (DESIGN.md section 32)
     def _tsne_neighbours(self, neighbours):

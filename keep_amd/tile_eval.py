@@ -206,6 +206,27 @@ def knn_probe(model, train_x, train_y, test_x, test_y, n_classes: int, k: int = 
     return out
 
 
+def few_shot(model, train_x, train_y, test_x, test_y, n_classes: int, shots: Sequence[int] = (1, 2, 4, 8, 16, 32), n_episodes: int = 1000,
+             seed: int = 0) -> dict:
+    """The few-shot prototype protocol on frozen features: SimpleShot with centring and L2 normalisation over
+    ``n_episodes`` random support sets per shot count (``KEEPModel.fewshot_episodes``) -> ``{k: dict}`` for every ``k`` of ``shots``, each
+    with ``confusions`` (int64 ``[E, C, C]`` on the host), ``balanced_accuracy`` and ``weighted_f1`` (float64 ``[E]``, one value per
+    episode) and, for either metric, ``<metric>_median`` / ``_q1`` / ``_q3`` / ``_mean`` over the episodes: the statistics the 50-round
+    zero-shot protocol reports.  Every shot count draws from the same ``seed``; a class smaller than ``k`` gives all its rows."""
+    from . import bootstrap
+    m = _engine(model)
+    out = {}
+    for k in shots:
+        conf = m.fewshot_episodes(train_x, train_y, test_x, test_y, n_classes, k, n_episodes, seed).cpu().numpy()
+        res = dict(confusions=conf)
+        for name, fn in (("balanced_accuracy", bootstrap.balanced_accuracy), ("weighted_f1", bootstrap.weighted_f1)):
+            v = np.asarray(fn(conf), np.float64)
+            q1, med, q3 = np.percentile(v, [25, 50, 75])
+            res.update({name: v, name + "_median": float(med), name + "_q1": float(q1), name + "_q3": float(q3), name + "_mean": float(v.mean())})
+        out[int(k)] = res
+    return out
+
+
 def retrieval_ranks(model, image_embeddings: torch.Tensor, text_embeddings: torch.Tensor,
                     targets: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Position of each caption's target image in its descending similarity list (int32 [P] on the device)."""

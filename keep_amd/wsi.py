@@ -834,6 +834,44 @@ def knn_map(train_features, train_labels, n_classes, tile_features, tile_coords,
     return m.class_raster(coords, probs[keep], patch_size, downsample, shape, origin, classes=classes)
 
 
+def prototype_map(protos, feats, coords, downsample, shape, patch_size=256, origin=(0, 0), classes=None, model=None):
+    """The few-shot morphology map: every tile's nearest class prototype (``KEEPModel.fewshot_predict`` with a
+    one-episode ``keep_amd.fewshot.Prototypes``, say of ``KEEPModel.fewshot_fit``) rasterised as votes in slide geometry ->
+    ``keep_amd.classmap.ClassRaster``, as :func:`knn_map` and :func:`cluster_map` build one.  Tiles without a label (a non-finite
+    feature, or a tile equal to the support mean) are in no plane.  ``KEEPModel.class_map``, ``render_class_map`` and
+    :func:`subtype_regions` take the raster from there."""
+    from .cluster import check_features
+    from .heatmap import check_raster_args
+    check_raster_args(patch_size, downsample, shape, origin)
+    f = feats.squeeze(0) if isinstance(feats, torch.Tensor) and feats.dim() == 3 else feats
+    N, _ = check_features(f)
+    xy = coords if isinstance(coords, torch.Tensor) else torch.as_tensor(np.asarray(coords))
+    if tuple(xy.shape) != (N, 2):
+        raise ValueError(f"coords must be [{N}, 2] beside {N} feature rows, got shape {tuple(xy.shape)}")
+    m = _engine(model, feats, protos.bank)
+    labels, scores, _, _ = m.fewshot_predict(protos, f)
+    keep = labels >= 0
+    return m.class_raster(xy.to(m._device)[keep], None, patch_size, downsample, shape, origin, labels=labels[keep], n_classes=int(scores.shape[1]),
+                          classes=classes)
+
+
+def prototype_slide_call(protos, feats, top=5, model=None):
+    """The multiple-instance SimpleShot call of a slide -> ``(label, pooled fp32 [C])``: a slide's score for class
+    c is the mean of its ``top`` largest tile scores ``s_c`` (``KEEPModel.fewshot_predict``; all kept tiles when the slide has fewer),
+    the label the first maximum of the pooled scores; ``(-1, zeros)`` when no tile is kept.  The pooling is ``torch.topk`` on the ``[N,
+    C]`` score matrix and a mean: plumbing on the device, not a kernel of this engine."""
+    if isinstance(top, bool) or not isinstance(top, (int, np.integer)) or int(top) < 1:
+        raise ValueError(f"top must be an integer >= 1, got {top!r}")
+    f = feats.squeeze(0) if isinstance(feats, torch.Tensor) and feats.dim() == 3 else feats
+    m = _engine(model, feats, protos.bank)
+    labels, scores, _, _ = m.fewshot_predict(protos, f)
+    s = scores[labels >= 0]
+    if s.shape[0] == 0:
+        return -1, torch.zeros(scores.shape[1], dtype=torch.float32, device=scores.device)
+    pooled = torch.topk(s, min(int(top), int(s.shape[0])), dim=0).values.mean(0)
+    return int(pooled.argmax()), pooled
+
+
 def search_tiles(query_features, tile_features, k, tile_coords=None, exclude_self=False, model=None):
     """Tile search: the ``k`` tiles most like every query by cosine -> ``(index int64 [Q, k], score fp32 [Q, k],
     coords [Q, k, 2] or None)`` on the device, best first, of equal scores the lower tile first; -1 / 0 / (-1, -1) in an empty slot
